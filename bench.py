@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the Grouped Gibbs sweep on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one full sweep of BASELINE.json's configs[1]: synthetic LDA corpus D=100k,
 V=50k, mean 200 tokens/doc (~20M tokens), K=100, alpha=0.1, beta=0.01 -- theta draw +
@@ -9,16 +9,24 @@ z draw + count merge (+ the exchange when N>1) + Phi re-draw, i.e. what
 UncollapsedParallelLDA.sample does between preZ() and postPhi() (UPLDA:659-687).
 Inputs are resident in HBM before the timed region; rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: corpus and z0 (seeded: the same arguments give the same inputs), --warmup
+sweeps, --steps timed sweeps, the outputs if --dump-outputs is given, the line.  --dump-outputs DIR writes what the last
+timed sweep left (rank 0's share at N>1) as DIR/<name>.npy in float64: z, theta, phi, type_topic_counts, topic_totals,
+each flattened and, above 2^20 elements, a fixed seeded sample of 2^20 of them (40 MB at most in all).
+
 N>1 shards the documents across the ranks, one process per GPU, joined by the library's NATIVE exchange
 (ggs_attach_rccl: RCCL reduce-scatter of the int32 counts by topic slice, Phi drawn for the rank's own topics,
 all-gather of the fp64 Phi slices; torch.distributed only carries the unique id, the barrier and the max over
 ranks).  Default `--scaling strong`, BASELINE.json's reading ("... at 1, 2, 4 and 8 GPUs ... >=6x strong scaling"):
-the N=1 corpus is split across the ranks, `value` = its tokens / time.  The same run then measures the weak-scaling
-regime (every rank brings a configs[1]-sized shard, rank r generated with seed+r) and reports it as "weak_scaling"
-(--no-weak-leg skips it); `--scaling weak` makes that the headline instead.
+the N=1 corpus is split across the ranks, `value` = its tokens / time; `--scaling weak` makes the weak-scaling regime
+(every rank brings a configs[1]-sized shard, rank r generated with seed+r) the headline instead.
 
-At N=1 the line also carries `extra_configs` (BASELINE configs 3 and the config-4 stand-in: ms per sweep, phase times,
-row-byte accounting) and `cpu_baseline` (the CPU restatement in three variants, on a bounded sample).
+--full adds everything else the benchmark measures and checks.  At N>1: the other scaling regime ("weak_scaling", or
+"strong_scaling"; --no-weak-leg skips it), the strong split of a larger corpus (--no-large-leg) and the comparison of
+the end state with one handle over the whole corpus (parity_vs_one_gpu; --no-verify).  At N=1: `extra_configs`
+(BASELINE configs 3 and the config-4 stand-in: ms per sweep, phase times, row-byte accounting; --no-extra-configs) and
+`cpu_baseline` (the CPU restatement in three variants, on a bounded sample; --no-cpu-baseline).  Both: the handle's
+invariant check after the timed region.
 
 N>1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -276,6 +284,26 @@ def state_digests(h, z_local=None):
     return {"z": sha256_of(z), "phi": sha256_of(h.get_phi()), "n_k": sha256_of(h.get_topic_totals()), "theta": sha256_of(h.get_theta()), "tokens": int(z.size)}
 
 
+DUMP_SAMPLE = 1 << 20      # --dump-outputs: elements per array at most (a larger output is sampled)
+
+
+def dump_outputs(h, out_dir, write, counts=True):
+    """--dump-outputs: what the last sweep left in the handle, one DIR/<name>.npy per array (float64, flattened; above
+    DUMP_SAMPLE elements a sample drawn with a fixed seed per array, so that equal arguments pick equal elements).  The
+    count getters are COLLECTIVE with an exchange attached: every rank calls them in this order, `write` on rank 0 only;
+    `counts=False` (the null exchange of --simulate-world) leaves them out."""
+    import numpy as np
+    arrays = [("z", h.get_z), ("theta", h.get_theta), ("phi", h.get_phi)]
+    if counts:
+        arrays += [("type_topic_counts", h.get_type_topic_counts), ("topic_totals", h.get_topic_totals)]
+    for i, (name, get) in enumerate(arrays):
+        a = get().reshape(-1)
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(20190 + i).choice(a.size, DUMP_SAMPLE, replace=False))]
+        if write:
+            np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+
+
 def make_handle(native, K, V, args, local_rank):
     return native.GGSHandle(K, V, args.alpha, args.beta, args.seed, device_id=local_rank,
                             flags={"ggs": 0, "pcgs": native.FLAG_PCGS, "collapsed": native.FLAG_COLLAPSED}[args.scheme])
@@ -286,8 +314,9 @@ def phases(tm):
     return {k: round(tm[k] / n, 4) for k in ("theta_ms", "z_ms", "merge_ms", "phi_ms", "exchange_ms", "exchange_rs_ms", "exchange_ag_ms")}
 
 
-def run_single(native, corpus, z0, K, args, local_rank, steps, warmup, fence):
-    """One handle over the whole corpus: (seconds for `steps` sweeps, per-sweep phase ms, launch info)."""
+def run_single(native, corpus, z0, K, args, local_rank, steps, warmup, fence, check=True, dump_dir=None):
+    """One handle over the whole corpus: (seconds for `steps` sweeps, per-sweep phase ms, launch info).  `check`: the
+    handle's invariant check after the timed region; `dump_dir`: dump_outputs of the last sweep there."""
     h = make_handle(native, K, corpus.num_types, args, local_rank)
     if args.simulate_world > 1:
         h.attach_null_exchange(args.simulate_rank, args.simulate_world)
@@ -306,7 +335,9 @@ def run_single(native, corpus, z0, K, args, local_rank, steps, warmup, fence):
     fence()
     dt = time.perf_counter() - t0
     tm = h.get_timings()
-    if args.simulate_world <= 1:
+    if dump_dir is not None:
+        dump_outputs(h, dump_dir, True, counts=args.simulate_world <= 1)
+    if check and args.simulate_world <= 1:
         h.check_invariants()
     info = h.launch_info()
     h.close()
@@ -352,9 +383,14 @@ def main():
     ap.add_argument("--alpha", type=float, default=0.1)
     ap.add_argument("--beta", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=2019)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: extra_configs + cpu_baseline (N=1), the other scaling leg, the large-corpus leg and "
+                         "parity_vs_one_gpu (N>1), the handle's invariant check; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed sweep computed as DIR/<name>.npy (float64; arrays above 2^20 elements as a fixed seeded sample)")
     ap.add_argument("--cpu-sample-docs", type=int, default=100000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="skip the extra_configs legs (configs 3 and 4 stand-in) of the default N=1 run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra-configs", action="store_true", help="--full: skip the extra_configs legs (configs 3 and 4 stand-in) of the N=1 run")
     ap.add_argument("--scheme", default="ggs", choices=["ggs", "pcgs", "collapsed"],
                     help="ggs = the headline path; pcgs = the partially collapsed z loop (SURVEY 8f-1); collapsed = the count-form conditional, parallel schedule (SURVEY 8f-4)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
@@ -381,6 +417,8 @@ def main():
                     help="N=1 only, a TIMING AID: run as rank --simulate-rank of this many with the peers missing (ggs_attach_null_exchange) on that "
                          "rank's share of the corpus; the sampler's results are wrong by construction, the per-rank phase times are what is read")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch  # device plumbing + torch.distributed (barrier, max over ranks, the unique id); imported before libggs_hip so both share one HIP runtime and one RCCL
 
@@ -400,6 +438,8 @@ def main():
         sys.exit("no GPU visible: the HIP path has no CPU fallback")
     if args.single_device:
         local_rank = 0
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
     torch.cuda.set_device(local_rank)
     dist = None
     sharded = world > 1 or args.force_sharded
@@ -433,12 +473,13 @@ def main():
 
     K = args.topics
 
-    def run_sharded(weak, docs=None):
-        """One measurement over `world` ranks: dict(dt, phases, docs, tokens, n_local, V, info, local corpus)"""
+    def run_sharded(weak, docs=None, headline=False):
+        """One measurement over `world` ranks: dict(dt, phases, docs, tokens, n_local, V, info, local corpus); the headline
+        leg writes --dump-outputs"""
         corpus = synthetic_lda_corpus(docs or args.docs, args.types, args.mean_len, true_topics=100, seed=args.seed + (rank if weak else 0))
         h = make_handle(native, K, corpus.num_types, args, local_rank)
         try:
-            return run_sharded_on(h, corpus, weak)
+            return run_sharded_on(h, corpus, weak, headline)
         except Exception:
             try:
                 h.close()
@@ -446,7 +487,7 @@ def main():
                 pass
             raise
 
-    def run_sharded_on(h, corpus, weak):
+    def run_sharded_on(h, corpus, weak, headline):
         stage(rank, "%s leg: corpus built (D=%d, N=%d), attaching the exchange" % ("weak" if weak else "strong", corpus.num_docs, corpus.num_tokens))
         if weak:
             sizes = gather_shard_sizes(corpus, rank, world, device="cuda" if args.backend == "nccl" else None)
@@ -477,12 +518,15 @@ def main():
         dt = max_over_ranks(time.perf_counter() - t0)
         stage(rank, "timed region done: %d sweeps in %.2f ms (max over ranks)" % (args.steps, dt * 1e3))
         tm = h.get_timings()
-        h.check_invariants()            # with the native exchange: a collective call (gathers the corpus-wide counts)
+        if headline and args.dump_outputs:
+            dump_outputs(h, args.dump_outputs, rank == 0)      # collective getters: every rank takes part, rank 0 writes
+        if args.full:
+            h.check_invariants()        # with the native exchange: a collective call (gathers the corpus-wide counts)
         if args.exchange == "native":
             xinfo = dict(xinfo, count_exchange=h.count_exchange())     # dense reduce-scatter or (cell, count) pairs, and how many pairs the last sweep sent
         res = dict(dt=dt, phases=phases(tm), docs=total_docs, tokens=total_tokens, n_local=sh.local.num_tokens, V=corpus.num_types,
                    info=h.launch_info(), local=sh.local, exchange=xinfo)
-        if not weak and not args.no_verify:
+        if not weak and args.full and not args.no_verify:
             # what this rank ends with, for the comparison with ONE handle over the whole corpus (verify_against_one_gpu)
             res["digests"] = state_digests(h)
             res["tok_range"] = (int(sh.tok_base), int(sh.tok_base + sh.local.num_tokens))
@@ -549,14 +593,14 @@ def main():
 
     fallback = []
 
-    def run_sharded_or_fall_back(weak, docs=None):
+    def run_sharded_or_fall_back(weak, docs=None, headline=False):
         """A native exchange that cannot be set up on every rank (librccl not loadable, ncclCommInitRank refused) would cost
         the whole scaling record: all ranks then agree to repeat the leg over torch.distributed (round 1's form: dense
         count all-reduce, Phi re-drawn everywhere) and the line says so.  Only failures every rank sees before its first
         sweep are covered -- one rank failing inside a collective leaves the others waiting, as with any collective."""
         err = None
         try:
-            res = run_sharded(weak, docs)
+            res = run_sharded(weak, docs, headline)
         except Exception as e:      # noqa: BLE001 -- whatever it was, the other ranks must hear of it
             res, err = None, "%s: %s" % (type(e).__name__, e)
         bad = torch.tensor([0 if err is None else 1], dtype=torch.int32, device="cuda" if args.backend == "nccl" else "cpu")
@@ -568,7 +612,7 @@ def main():
         stage(rank, "native exchange failed (%s); falling back to --exchange torch" % (err or "on another rank"))
         fallback.append(err or "failed on another rank")
         args.exchange = "torch"
-        return run_sharded(weak, docs)
+        return run_sharded(weak, docs, headline)
 
     sha = csrc_sha16()
     other = None
@@ -577,9 +621,9 @@ def main():
     verification = None
     if sharded:
         weak_first = args.scaling == "weak"
-        r = run_sharded_or_fall_back(weak_first)
+        r = run_sharded_or_fall_back(weak_first, headline=True)
         r2 = None
-        if world > 1 and not args.no_weak_leg:
+        if world > 1 and args.full and not args.no_weak_leg:
             r2 = run_sharded_or_fall_back(not weak_first)
         strong_leg = r2 if weak_first else r
         if strong_leg is not None and "digests" in strong_leg:
@@ -588,7 +632,7 @@ def main():
         # The strong split of a corpus --large-factor times the headline's: where the per-rank budget of DESIGN.md section 6
         # puts 8 GPUs at >= 6x one (the headline corpus is 1.5 ms of work on ONE GPU: its split is bound by what does not
         # shrink -- the Phi slice's chain and the collectives).  Timed and verified against one handle like the headline leg.
-        if world > 1 and args.large_factor > 1 and not args.no_large_leg and not args.no_verify:
+        if world > 1 and args.full and args.large_factor > 1 and not args.no_large_leg and not args.no_verify:
             r3 = run_sharded_or_fall_back(False, docs=args.large_factor * args.docs)
             v3 = verify_against_one_gpu(r3)
             r3.pop("corpus", None)
@@ -612,7 +656,8 @@ def main():
             b = even_split(corpus.num_docs, args.simulate_world)
             run_corpus, _, tb = corpus.shard(b[args.simulate_rank], b[args.simulate_rank + 1])
             run_z0 = z0[tb:tb + run_corpus.num_tokens]
-        dt, ph, info = run_single(native, run_corpus, run_z0, K, args, local_rank, args.steps, args.warmup, fence)
+        dt, ph, info = run_single(native, run_corpus, run_z0, K, args, local_rank, args.steps, args.warmup, fence, check=args.full,
+                                  dump_dir=args.dump_outputs)
         r = dict(dt=dt, phases=ph, docs=run_corpus.num_docs, tokens=run_corpus.num_tokens, n_local=run_corpus.num_tokens, V=corpus.num_types,
                  info=info, local=run_corpus)
 
@@ -662,7 +707,7 @@ def main():
             line["weak_scaling" if args.scaling == "strong" else "strong_scaling"] = other
         if sharded and large is not None:
             line["strong_scaling_large_corpus"] = large
-        if not sharded and args.simulate_world <= 1:
+        if args.full and not sharded and args.simulate_world <= 1:
             if not args.no_extra_configs and args.scheme == "ggs" and K == 100 and args.docs == 100000:
                 line["extra_configs"] = extra_configs(native, corpus, args, local_rank, fence, sha)
             if not args.no_cpu_baseline:

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 out=$GRAFT_REPO_ROOT/gpurun_out/profiles_$tag
 rm -rf $out && mkdir -p $out
 cd $GRAFT_REPO_ROOT
-python3 bench.py --no-extra-configs "$@" > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+python3 bench.py --full --no-extra-configs "$@" > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
 tail -c 900 $out/bench.json; echo
 python3 - $out/bench.json > $out/pmc_counters.txt <<'PY'
 import json, sys

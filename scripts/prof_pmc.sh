@@ -9,7 +9,7 @@ cd $GRAFT_REPO_ROOT
 i=0
 for ctrs in "$@"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $out/p$i -- python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 > $out/p$i.log 2>&1
+  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $out/p$i -- python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 > $out/p$i.log 2>&1
   f=$(find $out/p$i -name "*counter_collection.csv" | head -1)
   python3 - "$f" <<'PY'
 import csv, sys, collections

@@ -29,6 +29,9 @@ def test_library_exports_every_declared_symbol():
     from ldagroupedgibbssampler_amd import _lib
     names = declared_functions()
     assert len(names) >= 30
+    # dlopen in _lib.load()'s order (torch's HIP runtime first): mapping ROCm's copy here would leave a process running the
+    # whole suite with two HIP runtimes, and the GPU tests after this one with a runtime that sees no device
+    _lib._share_hip_runtime_with_torch()
     lib = ctypes.CDLL(_lib.LIB_PATH) if os.path.exists(_lib.LIB_PATH) else None
     if lib is None:
         pytest.fail("libggs_hip.so is not built: run __graft_entry__.build()")
