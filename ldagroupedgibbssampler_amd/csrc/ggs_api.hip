@@ -67,6 +67,7 @@ struct ggs_handle {
   int32_t theta_lds_main = 0, theta_b_main = 0;       // the theta draw as the critical leg (theta_main): workgroup size and LDS request
   int32_t theta_docs_per_block = 0, theta_lds = 0, z_lds = 0, z_tile_tokens = 0, z_waves_per_cu = 0, num_cus = 0;
   bool z_sliced = false;   // scores-in-registers kernel (K <= kSlicedMaxTopics)
+  bool z_f32 = false;      // ... its cold chunks scored from phiT32 (GGS_DEBUG_PHI64=1: from phiT, the fp64 path)
   bool z_stream = false;   // streaming kernel (K > kSlicedMaxTopics): rows once (z_stream1_kernel) ...
   bool z_two_pass = false; // ... or twice (z_stream_kernel, GGS_DEBUG_ZKERNEL=3: the cross-check)
   bool z_regck = false;    // z_stream1_kernel keeps its checkpoints in registers (K <= 1024)
@@ -136,6 +137,10 @@ struct ggs_handle {
   std::vector<int64_t> part_doc, part_chunk;           // [z_parts + 1] boundaries
   hipEvent_t ev_part[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int64_t theta_ahead_iter = INT64_MIN;     // iteration the side-stream theta was drawn for, or none
+  float *d_phiT32 = nullptr;                           // the float32 shadow of phiT the cold chunks gather (z_f32)
+  int32_t Kp32 = 0;
+  unsigned long long *d_replays = nullptr;             // GGS_DEBUG_REPLAYS: tokens z_sliced_kernel<KMAX, true> replayed, and its launches
+  int64_t z_f32_launches = 0;
   double *d_alpha = nullptr, *d_theta = nullptr, *d_phiT = nullptr, *d_mag = nullptr, *d_tot = nullptr, *d_phi_mean = nullptr;
   int32_t *d_n_wk = nullptr, *d_n_k = nullptr;
   double *d_sum_pref = nullptr, *d_sum_fn = nullptr;   // work space of the exact parallel column sums (ggs_exact_sum.hpp)
@@ -573,7 +578,8 @@ int launch_phi_slice(ggs_handle *h, bool initial, const int32_t *cnt, int32_t cn
   if ((rc = launch_magnitude_on(h, cnt, cnt_pitch, Ks, mag, n_k)) || (rc = phi_slice_gamma(h, initial, cnt, cnt_pitch, Ks, k0, out, out_pitch, mag, 0, h->sum_nseg)) ||
       (rc = phi_slice_total(h, out, out_pitch, Ks, tot)))
     return rc;
-  hipLaunchKernelGGL(phi_normalise_kernel, dim3(grid_for((int64_t)Ks * h->V, 256, 2)), dim3(256), 0, h->stream, out, tot, Ks, out_pitch, h->V, phi_mean);
+  hipLaunchKernelGGL(phi_normalise_kernel, dim3(grid_for((int64_t)Ks * h->V, 256, 2)), dim3(256), 0, h->stream, out, tot, Ks, out_pitch, h->V, phi_mean,
+                     out == h->d_phiT ? h->d_phiT32 : nullptr, h->Kp32);
   HIP_TRY(h, hipGetLastError());
   return GGS_OK;
 }
@@ -632,6 +638,7 @@ int phi_step_c(ggs_handle *h, bool accumulate_mean) {
   rp.all0 = h->d_phi_all0; rp.all1 = h->d_phi_all1; rp.krank = h->d_krank; rp.kcol = h->d_kcol; rp.phiT = h->d_phiT;
   rp.phi_mean = accumulate_mean ? h->d_phi_mean : nullptr;
   rp.c0 = (int64_t)half0_elems(h); rp.c1 = (int64_t)half1_elems(h); rp.K = h->K; rp.Kp = h->Kp; rp.V = h->V; rp.Ksm = h->Ksm; rp.v_split = h->v_split;
+  rp.phiT32 = h->d_phiT32; rp.Kp32 = h->Kp32;
   hipLaunchKernelGGL(phi_repack_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   HIP_TRY(h, hipGetLastError());
   h->have_phi = true;
@@ -691,6 +698,8 @@ int launch_theta(ggs_handle *h, hipStream_t stream, double *dst, int32_t iterati
     case 23: return reinterpret_cast<const void *>(KERNEL<184>);   default: return reinterpret_cast<const void *>(KERNEL<192>);     \
   }
 const void *sliced_kernel_for(int K) { GGS_KMAX_SWITCH(z_sliced_kernel) }
+const void *sliced32_kernel_for(int K) { GGS_KMAX_SWITCH(z_sliced32_kernel) }
+
 const void *hot_kernel_for(int K) { GGS_KMAX_SWITCH(z_hot_kernel) }
 const void *warm_kernel_for(int K) { GGS_KMAX_SWITCH(z_warm_kernel) }
 const void *pcgs_kernel_for(int K) { GGS_KMAX_SWITCH(pcgs_sliced_kernel) }
@@ -801,6 +810,9 @@ int launch_z(ggs_handle *h, bool force_fused = false, int64_t c0 = 0, int64_t c1
   zp.ht_pack = reinterpret_cast<const int4 *>(h->d_ht_pack); zp.h_docs = h->d_h_docs;
   zp.wt_pack = reinterpret_cast<const int4 *>(h->d_wt_pack); zp.w_docs = h->d_w_docs; zp.warm_words = h->d_warm_words;
   zp.warm_meta = h->d_warm_meta; zp.warm_tiers = h->warm_tiers; zp.warm_rows = h->warm_cap;
+  zp.phiT32 = h->d_phiT32; zp.Kp32 = h->Kp32; zp.replays = h->d_replays;
+  const bool f32 = h->z_f32 && h->d_phiT32;
+  const void *cold_kernel = f32 ? sliced32_kernel_for(h->K) : sliced_kernel_for(h->K);
   if (!h->z_sliced) {                                  // a range of the chunk table (the one-document chunks are in document order)
     zp.chunk_start += c0; zp.chunk_doc += c0; zp.chunk_len += c0; zp.num_chunks = c1 - c0;
     if (zp.chunk_doc1) zp.chunk_doc1 += c0;
@@ -852,7 +864,8 @@ int launch_z(ggs_handle *h, bool force_fused = false, int64_t c0 = 0, int64_t c1
       }
       zp.num_chunks = h->Cc; zp.num_hot = 0;
       static const int only = debug_env("GGS_DEBUG_ONLY") ? std::atoi(debug_env("GGS_DEBUG_ONLY")) : 0;   // timing experiments: 1 cold only, 2 hot only
-      if (only != 2) HIP_TRY(h, hipLaunchKernel(sliced_kernel_for(h->K), grid_of(h->Cc), sblock, args, (size_t)(kSlicedWaves * h->wave_lds), h->stream));
+      if (only != 2) HIP_TRY(h, hipLaunchKernel(cold_kernel, grid_of(h->Cc), sblock, args, (size_t)(kSlicedWaves * h->wave_lds), h->stream));
+      if (only != 2 && f32) ++h->z_f32_launches;
       if (only != 1) HIP_TRY(h, hipLaunchKernel(hot_kernel_for(h->K), grid_of(h->Cs - h->Cc), sblock, hargs, (size_t)(hp.hot_off + h->num_hot * h->hot_pitch + kHotTailBytes), h->side_hot));
       if (only != 1) { const int rc = launch_warm(h->side_hot); if (rc) return rc; }
       if (defer_join && zp.cnt_send && only == 0) {
@@ -867,8 +880,9 @@ int launch_z(ggs_handle *h, bool force_fused = false, int64_t c0 = 0, int64_t c1
       if (defer_join) h->hot_join_pending = true;
       else HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_hot_join, 0));
     } else {
-      HIP_TRY(h, hipLaunchKernel(sliced_kernel_for(h->K), grid_of(std::max(h->Cc, h->Cs - h->Cc)), sblock, args,
+      HIP_TRY(h, hipLaunchKernel(cold_kernel, grid_of(std::max(h->Cc, h->Cs - h->Cc)), sblock, args,
                                  (size_t)(kSlicedWaves * h->wave_lds + h->num_hot * h->hot_pitch), h->stream));
+      if (f32) ++h->z_f32_launches;
       const int rc = launch_warm(h->stream);
       if (rc) return rc;
     }
@@ -1402,6 +1416,10 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
       // (the score registers take most of the 512-entry file)
       h->z_tile_tokens = 64;
       const int kmax = ((h->K + 7) / 8) * 8, ns = (kmax + kSliceTopics - 1) / kSliceTopics;
+      // the cold chunks from phiT32 (a 32-topic slice per 128 bytes); its wave LDS is the fp64 form's: the ring, then two
+      // float32 theta rows and the replay's KMAX products where the two fp64 theta rows were
+      h->z_f32 = !(debug_env("GGS_DEBUG_PHI64") && std::atoi(debug_env("GGS_DEBUG_PHI64")) == 1);
+      h->Kp32 = (h->K + kSlice32Topics - 1) / kSlice32Topics * kSlice32Topics;
       // per wave: the chunk's kChunkDocs theta rows (zero-padded to KMAX), then the ring; a DMA's immediate slice offset
       // (< ns*128) is subtracted from its LDS destination, so the ring must not start below that
       h->ring_base = (std::max(kChunkDocs * kmax * 8, ns * 128) + 255) / 256 * 256;
@@ -1484,6 +1502,7 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     h->cfg_parts.theta_lds = h->theta_lds; h->cfg_parts.theta_lds_beside_z = h->theta_lds_beside_z;
   }
   if (h->z_sliced && (hipFuncSetAttribute(sliced_kernel_for(h->K), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess ||
+                      hipFuncSetAttribute(sliced32_kernel_for(h->K), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess ||
                       hipFuncSetAttribute(hot_kernel_for(h->K), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess ||
                       hipFuncSetAttribute(warm_kernel_for(h->K), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess))
     return bail(GGS_ERR_HIP);
@@ -1508,6 +1527,14 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
       (rc = dev_alloc(h, &h->d_n_k, h->K)) || (rc = dev_alloc(h, &h->d_status, 4)))
     return bail(rc);
   if ((h->flags & GGS_FLAG_SAVE_PHI_MEAN) && (rc = dev_alloc(h, &h->d_phi_mean, kv))) return bail(rc);
+  if (h->z_sliced && h->z_f32) {
+    if ((rc = dev_alloc(h, &h->d_phiT32, (size_t)h->V * h->Kp32 + kPhiTailPadBytes / 4))) return bail(rc);
+    if (hipMemset(h->d_phiT32, 0, sizeof(float) * ((size_t)h->V * h->Kp32 + kPhiTailPadBytes / 4)) != hipSuccess) return bail(GGS_ERR_HIP);
+    if (debug_env("GGS_DEBUG_REPLAYS") && std::atoi(debug_env("GGS_DEBUG_REPLAYS")) == 1) {
+      if ((rc = dev_alloc(h, &h->d_replays, 1))) return bail(rc);
+      if (hipMemset(h->d_replays, 0, sizeof(unsigned long long)) != hipSuccess) return bail(GGS_ERR_HIP);
+    }
+  }
   if (const char *e = debug_env("GGS_DEBUG_CHAIN")) h->exact_sum = std::atoi(e) == 0;
   if (const char *e = debug_env("GGS_DEBUG_GUIDED")) h->sum_guided = std::atoi(e) != 0;
   h->sum_nseg = (h->V + kSumSegRows - 1) / kSumSegRows;
@@ -1591,13 +1618,19 @@ void ggs_destroy(ggs_handle *h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
+  if (h->d_replays) {                                  // GGS_DEBUG_REPLAYS: the undecided tokens of the float32 cold path, measured
+    unsigned long long n = 0;
+    if (hipMemcpy(&n, h->d_replays, sizeof(n), hipMemcpyDeviceToHost) == hipSuccess)
+      fprintf(stderr, "[ggs] z replays: %llu tokens in %lld launches of z_sliced32_kernel (%.2f per launch)\n", n, (long long)h->z_f32_launches,
+              h->z_f32_launches ? (double)n / (double)h->z_f32_launches : 0.0);
+  }
   void *bufs[] = {h->d_doc_ptr, h->d_chunk_start, h->d_tok, h->d_z, h->d_chunk_doc, h->d_chunk_len, h->d_alpha, h->d_theta, h->d_theta_next,
                   h->d_phiT, h->d_mag, h->d_tot, h->d_phi_mean, h->d_n_wk, h->d_n_k, h->d_perm, h->d_inv_perm, h->d_zw, h->d_seg_word, h->d_seg_begin,
                   h->d_status, h->d_scratch, h->d_sum_pref, h->d_sum_fn, h->d_ct_tok, h->d_ct_idx, h->d_ct_ip, h->d_c_docs, h->d_hot_words, h->d_order,
                   h->d_test_ptr, h->d_test_tok, h->d_test_ll, h->d_test_docs, h->d_koff, h->d_cnt_send, h->d_cnt_own, h->d_cnt_all, h->d_n_k_own,
                   h->d_heldout_spill, h->d_phi_own, h->d_phi_all0, h->d_phi_all1, h->d_mag_own, h->d_krank, h->d_kcol, h->d_lcg, h->d_chunk_doc1,
                   h->d_hseg_word, h->d_hseg_begin, h->d_hseg_end, h->d_sp_count, h->d_sp_cnt32, h->d_sp_all, h->d_sp_send, h->d_sp_recv, h->d_sp_wg_count,
-                  h->d_sp_wg_off, h->d_ht_pack, h->d_h_docs, h->d_wt_pack, h->d_w_docs, h->d_warm_words, h->d_warm_meta};
+                  h->d_sp_wg_off, h->d_ht_pack, h->d_h_docs, h->d_wt_pack, h->d_w_docs, h->d_warm_words, h->d_warm_meta, h->d_phiT32, h->d_replays};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   exchange_free(h->xg);
@@ -2473,7 +2506,7 @@ int ggs_set_phi(ggs_handle *h, const double *phi) {
   if ((rc = ensure_scratch(h, kv * sizeof(double)))) return rc;
   HIP_TRY(h, hipMemcpyAsync(h->d_scratch, phi, kv * sizeof(double), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(phi_to_phiT_kernel, dim3(grid_for((int64_t)kv, 256)), dim3(256), 0, h->stream, static_cast<const double *>(h->d_scratch),
-                     h->d_phiT, h->K, h->Kp, h->V);
+                     h->d_phiT, h->K, h->Kp, h->V, h->d_phiT32, h->Kp32);
   HIP_TRY(h, hipGetLastError());
   // UPLDA:1897-1902: `if (savePhiMeans()) phiMean = new double[numTopics][numTypes]` -- the running sum restarts, noSampledPhi keeps counting
   if (h->d_phi_mean) HIP_TRY(h, hipMemsetAsync(h->d_phi_mean, 0, kv * sizeof(double), h->stream));

@@ -544,8 +544,14 @@ __global__ __launch_bounds__(64) void phi_gamma_kernel(PhiGammaParams p) {
   }
 }
 
+// The float32 shadow phiT32 [V][Kp32] of phiT that z_sliced_kernel<KMAX, true> gathers (ggs_z_sliced.hpp): round to nearest of
+// a value in [0, 1], NaN for anything else -- the margin there is proved for operands in [0, 1] only, and a NaN score sends
+// every token of the word to the exact replay.  Written wherever phiT becomes final, in the same kernels; the pad columns
+// K..Kp32-1 stay the zeros of the allocation.
+__device__ __forceinline__ float phi32_of(const double x) { return (x >= 0.0 && x <= 1.0) ? (float)x : __builtin_nanf(""); }
+
 __global__ __launch_bounds__(256) void phi_normalise_kernel(double *phiT, const double *tot, int32_t K, int32_t Kp, int32_t V,
-                                                            double *phi_mean /* [V][K] or null */) {
+                                                            double *phi_mean /* [V][K] or null */, float *phiT32 /* or null */, int32_t Kp32) {
   __builtin_amdgcn_s_setprio(3);
   const int64_t n = (int64_t)V * K;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -558,6 +564,7 @@ __global__ __launch_bounds__(256) void phi_normalise_kernel(double *phiT, const 
       if (x <= 0) x = kJavaMinValue;
       phiT[(size_t)v * Kp + k] = x;
     }
+    if (phiT32) phiT32[(size_t)v * Kp32 + k] = phi32_of(x);
     if (phi_mean) phi_mean[i] += x;                                  // GGS:193-197
   }
 }
@@ -573,6 +580,8 @@ struct PhiRepackParams {
   double *phiT, *phi_mean;       // phi_mean [V][K] or null
   int64_t c0, c1;
   int32_t K, Kp, V, Ksm, v_split;
+  float *phiT32;                 // or null
+  int32_t Kp32;
 };
 __global__ __launch_bounds__(256) void phi_repack_kernel(PhiRepackParams p) {
   __builtin_amdgcn_s_setprio(3);
@@ -590,6 +599,7 @@ __global__ __launch_bounds__(256) void phi_repack_kernel(PhiRepackParams p) {
       if (x <= 0) x = kJavaMinValue;
     }
     p.phiT[(size_t)v * p.Kp + k] = x;
+    if (p.phiT32) p.phiT32[(size_t)v * p.Kp32 + k] = phi32_of(x);
     if (p.phi_mean) p.phi_mean[i] += x;
   }
 }
@@ -624,12 +634,14 @@ __global__ __launch_bounds__(256) void phiT_to_phi_kernel(const double *phiT, do
     phi[i] = (scale == 1.0) ? x : x / scale;
   }
 }
-__global__ __launch_bounds__(256) void phi_to_phiT_kernel(const double *phi, double *phiT, int32_t K, int32_t Kp, int32_t V) {
+__global__ __launch_bounds__(256) void phi_to_phiT_kernel(const double *phi, double *phiT, int32_t K, int32_t Kp, int32_t V, float *phiT32, int32_t Kp32) {
   const int64_t n = (int64_t)V * K;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const int v = (int)(i / K), k = (int)(i - (int64_t)v * K);
-    phiT[(size_t)v * Kp + k] = phi[(size_t)k * V + v];
+    const double x = phi[(size_t)k * V + v];
+    phiT[(size_t)v * Kp + k] = x;
+    if (phiT32) phiT32[(size_t)v * Kp32 + k] = phi32_of(x);
   }
 }
 

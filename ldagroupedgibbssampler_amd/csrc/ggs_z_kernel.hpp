@@ -96,6 +96,11 @@ struct ZParams {
   const int64_t *warm_meta;    // [warm_tiers + 1] first chunk of a tier, then [warm_tiers] rows of its table
   int32_t warm_tiers, warm_rows;
   long long *dbg;              // -DGGS_WARM_TRACE builds only: per wave, cycles by phase of z_warm_kernel's chunk loop
+  // z_sliced_kernel<KMAX, true> (ggs_z_sliced.hpp): the cold chunks scored from the float32 shadow of phiT and decided by
+  // the margin of its header; the tokens too close to call are replayed from phiT and theta
+  const float *phiT32;         // [V][Kp32], Kp32 = K rounded up to whole 32-topic slices, the pad columns zero
+  int32_t Kp32;
+  unsigned long long *replays; // null, or += the tokens replayed (GGS_DEBUG_REPLAYS)
 };
 
 struct alignas(16) D2 { double a, b; };

@@ -57,6 +57,7 @@ namespace ggs {
 
 constexpr int kSliceTopics = 16;
 constexpr int kSliceUnits = 8;            // 16-byte units per row per slice
+constexpr int kSlice32Topics = 32;        // ... a slice of phiT32 (z_sliced32_kernel): 32 float32 topics in the same 128 bytes
 constexpr int kSliceBytes = 64 * 128;     // 64 rows x 16 topics x 8 B
 // Two slots (one slice in flight beyond the one being scored) since round 4: the LDS a third slot takes is worth more as
 // hot-word table -- measured at BASELINE config 2, sweep / z step in ms: 2 slots 1.496 / 0.922 (96 hot rows), 3 slots
@@ -105,11 +106,258 @@ __device__ __forceinline__ void static_for(F &&f) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The cold chunks from the float32 shadow of phiT (z_sliced32_kernel, the default below K = kSlicedDefaultTopics).
+//
+// phiT32 [V][Kp32] (phi32_of, ggs_kernels.hpp): a row is Kp32 = K rounded up to 32 floats, a slice 32 topics in the same
+// 128 bytes per row, gathered by the same LDS-DMA ring (the per-lane rotation is by 16-byte units: unchanged).  K = 100:
+// 4 slices = 512 bytes and 32 DMA instructions per chunk instead of 7 slices = 896 bytes and 56.  Theta is staged to LDS
+// as float32 (phi32_of as well), and a lane keeps the float32 PREFIX sums a_j of its token in registers (KMAX of them,
+// half the fp64 form's score registers):
+//     q_j = fl32(theta'_j * phi'_j)  (v_pk_mul_f32),   a_j = fl32(a_{j-1} + q_j),  A = a_{KMAX-1},
+//     t0' = fl32(fl64(U * A)),       d_j = fl32(a_j - t0'),  cnt = #{j < KMAX : d_j < 0},  m = min(t0', min_j |d_j|).
+// The draw is DECIDED as cnt when  2^-60 <= A <= FLT_MAX,  m > delta = fl32(fl32((2K + 8) 2^-24 A) * margin_scale)  and
+// cnt < K;  every other token is replayed exactly (GGS:96-113 element by element from the fp64 phiT row and fp64 theta).
+//
+// Why that is the Java draw.  u = 2^-24.  Operands: theta_j (a probability, <= 1) and phi_j in [0, 1] (anything else is NaN
+// in the shadow / in LDS, and a NaN A is undecided).  With float32 denormals kept OR flushed (the bound holds for both),
+// every float32 rounding of a value x errs by at most u|x| + 2^-126.  Let P_j = theta_j phi_j exactly, E_j = P_0 + .. + P_j,
+// E = E_{K-1}.  The compiled arithmetic (-ffp-contract=off: no fused multiply-add) gives
+//   * |theta' - theta| <= u theta + 2^-126, the same for phi, theta', phi' <= 1, so |q_j - P_j| <= 3.001 u P_j + 3.01 * 2^-126;
+//   * the addends are >= 0, so a_j is non-decreasing and the recursive sum errs by <= j u E_j + j 2^-126:
+//     |a_j - E_j| <= (j + 3.01) u E_j + 4.1 (j + 1) 2^-126 <= (K + 2.01) u E + 2^-115   (padding topics add exact zeros);
+//   * |t0' - U E| <= u U A (1 + 2^-28) + 2^-126 + U |A - E| <= 1.0001 u A + (K + 2.01) u E + 2^-115;
+//   * Java: p_j = fl64(P_j), S = its fp64 sum, t_0 = fl64(U S), t_{j+1} = fl64(t_j - p_j): |t_{j+1} - (U E - E_j)| <= 2^-44 E.
+// With A >= 2^-60 (E <= 1.00002 A, the 2^-115 terms below 2^-31 u A) the distance of (a_j - t0') to the Java value
+// t_{j+1} ~ U E - E_j, sign reversed, is at most (2K + 6.2) u A; and |d_j| > delta >= (2K + 8)(1 - u) u A implies
+// |a_j - t0'| >= (|d_j| - 2^-126) / (1 + u) > (2K + 6.2) u A.  So m > delta gives, for every j < K at once,
+// sign(t_{j+1}) = sign(t0' - a_j) (and t_0 > 0 from t0' > delta); the walk is monotone, so Java's
+// newTopic = #{j < K : t_{j+1} > 0} = cnt, and cnt < K says the walk ends inside the row (a padding topic repeats
+// a_{K-1}: it is counted only when a_{K-1} < t0', i.e. cnt >= K).  tests/test_margin32_model.py restates this in numpy.
+//
+// The walk: d_j for two topics per v_pk_add_f32, the sign bits collected by a funnel shift as in the fp64 form, m by one
+// v_min_f32 with an |.| modifier; once every lane's d is >= 0 the rest of the row changes neither cnt nor m (d only grows),
+// so the walk stops a block of 16 after the wave's last crossing.  The replay is the wave's: the undecided lanes one
+// after the other, all 64 lanes computing the KMAX fp64 products of that token into LDS (where the fp64 form's second
+// theta row was), then the fp64 sum and the Java walk read back from there (every lane the same; the owner keeps it).
+typedef float f2_t __attribute__((ext_vector_type(2)));
+typedef float f4_t __attribute__((ext_vector_type(4)));
+template <int KMAX>
+__device__ __forceinline__ void cold_chunks32(const ZParams &p, unsigned char *thb, unsigned char *ring, const int64_t wid, const int64_t stride, const int lane) {
+  constexpr int NS = (KMAX + kSlice32Topics - 1) / kSlice32Topics;   // 32-topic slices per chunk
+  constexpr int kAhead = NS < kRingSlots - 1 ? NS : kRingSlots - 1;
+  constexpr int NT = (KMAX + 63) / 64;
+  constexpr int kThetaRow = KMAX * 4;                              // bytes of one float32 theta row in LDS
+  const int K = p.K;
+  const unsigned char *phib = reinterpret_cast<const unsigned char *>(p.phiT32);
+  const size_t rowbytes = (size_t)p.Kp32 * 4;
+  const const_i32_t *cdocs = (const const_i32_t *)p.c_docs;
+  double *prod = reinterpret_cast<double *>(thb + kChunkDocs * kThetaRow);   // the replay's products (KMAX doubles)
+  const int lrow = lane >> 3, lslot = lane & 7;
+  const unsigned char *my_row = ring + lane * 128;
+  const int rot = lane >> 1;
+  const float mscale = (float)p.margin_scale;
+
+  auto load_theta = [&](const int d0, const int d1, double (&tv)[kChunkDocs][NT]) {
+    const double *t0 = p.theta + (size_t)d0 * K, *t1 = p.theta + (size_t)d1 * K;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      tv[0][t] = (t * 64 + lane < K) ? t0[t * 64 + lane] : 0.0;
+      tv[1][t] = (t * 64 + lane < K) ? t1[t * 64 + lane] : 0.0;
+    }
+  };
+  auto stage_theta = [&](const double (&tv)[kChunkDocs][NT]) {
+#pragma unroll
+    for (int r = 0; r < kChunkDocs; ++r)
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+        if (t * 64 + lane < KMAX) reinterpret_cast<float *>(thb + r * kThetaRow)[t * 64 + lane] = phi32_of(tv[r][t]);
+  };
+  auto row_addresses = [&](const int w, const unsigned char *(&ra)[8]) {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+      const int row = 8 * m + lrow;
+      const int wm = __shfl(w, row) & ((1 << kSlotShift) - 1);     // 0 for rows past the chunk
+      ra[m] = phib + (size_t)wm * rowbytes + (size_t)(((lslot - (row >> 1)) & 7) << 4);
+    }
+  };
+  auto issue_slice = [&](auto sc, const int slot, const unsigned char *const (&ra)[8]) {
+    constexpr int s = decltype(sc)::value;
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+      __builtin_amdgcn_global_load_lds((glb_cvoid_t *)ra[m], (lds_void_t *)(ring + slot * kSliceBytes + m * 1024 - s * 128), 16, s * 128, 0);
+  };
+  // U, the decision, the replay and the stores of one chunk c
+  auto finish = [&](const float (&a)[KMAX], const int64_t c, const int idx, const int ip, const int w) {
+    const uint64_t gtok = (uint64_t)(p.tok_base + idx);
+    const U4 o = philox4x32_10((uint32_t)gtok, (uint32_t)(gtok >> 32), (uint32_t)GGS_PURPOSE_Z << 24, p.iteration,
+                               (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
+    const double U = u53(o.x, o.y);
+    const float A = a[KMAX - 1];
+    const float t0 = (float)(U * (double)A);
+    const float delta = ((float)(2 * K + 8) * 0x1p-24f * A) * mscale;
+    const f2_t nt0 = {-t0, -t0};
+    int cnt = 0;
+    float m = t0;
+    bool live = true;
+#pragma unroll
+    for (int kb = 0; kb < KMAX; kb += 16) {
+      if (live) {                                                  // wave-uniform
+        uint32_t bits = 0;
+        float dl = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 16; j += 2)
+          if (kb + j < KMAX) {
+            const f2_t d = f2_t{a[kb + j], a[kb + j + 1]} + nt0;
+            bits = __builtin_amdgcn_alignbit(bits, __float_as_uint(d.x), 31);
+            bits = __builtin_amdgcn_alignbit(bits, __float_as_uint(d.y), 31);
+            m = fminf(m, fminf(fabsf(d.x), fabsf(d.y)));
+            dl = d.y;
+          }
+        cnt += __popc(bits);
+        live = __any(dl < 0.0f);
+      }
+    }
+    int new_topic = cnt;
+    const bool undecided = idx >= 0 && !(A >= 0x1p-60f && A <= 0x1.fffffep127f && m > delta && cnt < K);
+    uint64_t pend = __ballot(undecided);
+    if (pend) {                                                    // wave-uniform
+      if (p.replays && lane == 0) atomicAdd(p.replays, (unsigned long long)__popcll(pend));
+      const int slot = (int)((unsigned)w >> kSlotShift);
+      const int d0 = cdocs[2 * c], d1 = cdocs[2 * c + 1];
+      while (pend) {
+        const int L = (int)__builtin_ctzll(pend);
+        pend &= pend - 1;
+        const int wl = __shfl(w, L) & ((1 << kSlotShift) - 1), dl = __shfl(slot, L) ? d1 : d0;
+        const double UL = __shfl(U, L);
+        const double *th = p.theta + (size_t)dl * K, *ph = p.phiT + (size_t)wl * p.Kp;
+        for (int k = lane; k < K; k += 64) prod[k] = th[k] * ph[k];   // GGS:96-101's products
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the wave's LDS operations complete in order
+        double sum = 0.0;
+        for (int k = 0; k < K; ++k) sum += prod[k];
+        double sample = UL * sum;                                  // GGS:107-113
+        int nt = -1;
+        while (sample > 0.0) {
+          ++nt;
+          if (nt >= K) break;
+          sample -= prod[nt];
+        }
+        if (nt < 0 || nt >= K) {                                   // GGS:116-118 (and the index past K Java would throw on)
+          if (lane == L) atomicOr(p.status, ST_INVALID_TOPIC);
+          nt = nt < 0 ? 0 : K - 1;
+        }
+        if (lane == L) new_topic = nt;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // every read of the products is done before the next token's writes
+      }
+    }
+    if (idx < 0) return;
+    p.z[idx] = new_topic;
+    p.zw[ip] = new_topic;
+    const int word = w & ((1 << kSlotShift) - 1);
+    if (p.cnt_send) __hip_atomic_fetch_add(&p.cnt_send[slice_cell(p.smap, new_topic, word)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+
+  // ---- the chunk loop of cold_chunks (z_sliced_body), 32 topics per slice
+  const int64_t C = p.num_cold;
+  int64_t c = wid;
+  if (c >= C) return;
+  int w0 = p.ct_tok[c * 64 + lane], id0 = p.ct_idx[c * 64 + lane], ip0 = p.ct_ip[c * 64 + lane];
+  int w1 = 0, id1 = -1, ip1 = 0, w2 = 0, id2 = -1, ip2 = 0;
+  double tv0[kChunkDocs][NT], tv1[kChunkDocs][NT], tv2[kChunkDocs][NT];
+  load_theta(cdocs[2 * c], cdocs[2 * c + 1], tv0);
+  if (c + stride < C) {
+    const int64_t c1 = c + stride;
+    w1 = p.ct_tok[c1 * 64 + lane]; id1 = p.ct_idx[c1 * 64 + lane]; ip1 = p.ct_ip[c1 * 64 + lane];
+    load_theta(cdocs[2 * c1], cdocs[2 * c1 + 1], tv1);
+  } else {
+    load_theta(0, 0, tv1);
+  }
+#pragma unroll
+  for (int r = 0; r < kChunkDocs; ++r)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) tv2[r][t] = 0.0;
+  const unsigned char *ra[8], *ran[8];
+  row_addresses(w0, ra);
+  row_addresses(w1, ran);
+  int g = 0;
+  static_for<0, kAhead>([&](auto sc) { issue_slice(sc, decltype(sc)::value % kRingSlots, ra); });
+
+  for (;;) {
+    const bool has1 = c + stride < C, has2 = c + 2 * stride < C;
+    g = __builtin_amdgcn_readfirstlane(g);
+    stage_theta(tv0);
+    const unsigned char *trow = thb + ((unsigned)w0 >> kSlotShift) * kThetaRow;
+
+    float a[KMAX];
+    float acc = 0.0f;
+    static_for<0, NS>([&](auto sidx) {
+      constexpr int s = decltype(sidx)::value;
+      const int cur = (g + s) % kRingSlots;
+      const int nxt = (g + s + kAhead) % kRingSlots;
+      if constexpr (s + kAhead < NS) issue_slice(std::integral_constant<int, s + kAhead>{}, nxt, ra);
+      else if (has1) issue_slice(std::integral_constant<int, s + kAhead - NS>{}, nxt, ran);
+      // as in cold_chunks: 8 DMAs per slice, issued in order
+      if (has1 || s + kAhead < NS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * kAhead) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * (NS - 1 - s)) : "memory");
+      {                                                            // every lane (an idle one reads finite bytes: it stores nothing)
+        const unsigned char *rb = my_row + cur * kSliceBytes;
+        f4_t ph[kSliceUnits], th[kSliceUnits];                     // unit u = topics 4u .. 4u + 3 of the slice
+#pragma unroll
+        for (int u = 0; u < kSliceUnits; ++u)
+          if (s * kSlice32Topics + 4 * u < KMAX) {                 // compile time (KMAX is a multiple of 8)
+            ph[u] = *reinterpret_cast<const f4_t *>(rb + (((u + rot) & 7) << 4));
+            th[u] = *reinterpret_cast<const f4_t *>(trow + s * (kSlice32Topics * 4) + u * 16);
+          }
+#pragma unroll
+        for (int u = 0; u < kSliceUnits; ++u) {
+          constexpr int k0 = s * kSlice32Topics;
+          const int k = k0 + 4 * u;
+          if (k < KMAX) {
+            const f2_t q0 = f2_t{th[u].x, th[u].y} * f2_t{ph[u].x, ph[u].y};
+            const f2_t q1 = f2_t{th[u].z, th[u].w} * f2_t{ph[u].z, ph[u].w};
+            acc += q0.x; a[k] = acc;
+            acc += q0.y; a[k + 1] = acc;
+            acc += q1.x; a[k + 2] = acc;
+            acc += q1.y; a[k + 3] = acc;
+          }
+        }
+      }
+      // every read of this ring slot has RETURNED before the next step's DMA may refill it: issued is not enough -- the
+      // scheduler may sink the arithmetic (and the compiler's wait for these reads) behind that DMA, and beside the table
+      // waves of the fused form the reads queue long enough for an L2 hit to overwrite the slot first (measured: wrong
+      // draws in the fused form only, without this wait)
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    });
+    g = (g + NS) % kRingSlots;
+
+    if (has2) {
+      const int64_t c2 = c + 2 * stride;
+      w2 = p.ct_tok[c2 * 64 + lane]; id2 = p.ct_idx[c2 * 64 + lane]; ip2 = p.ct_ip[c2 * 64 + lane];
+      load_theta(cdocs[2 * c2], cdocs[2 * c2 + 1], tv2);
+    } else {
+      w2 = 0; id2 = -1; ip2 = 0;
+    }
+
+    finish(a, c, id0, ip0, w0);
+    if (!has1) break;
+    c += stride;
+    w0 = w1; id0 = id1; ip0 = ip1;
+    w1 = w2; id1 = id2; ip1 = ip2;
+#pragma unroll
+    for (int r = 0; r < kChunkDocs; ++r)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) { tv0[r][t] = tv1[r][t]; tv1[r][t] = tv2[r][t]; }
+#pragma unroll
+    for (int m = 0; m < 8; ++m) ra[m] = ran[m];
+    row_addresses(w1, ran);
+  }
+}
+
 // KMAX = K rounded up to a multiple of 8: the size of the score register file.  Topics
 // K..KMAX-1 are scored too, with theta = 0 (the LDS theta rows are zero-padded) against finite
 // phi bytes, so they add +0.0 to the sum and subtract 0.0 in the walk: no per-topic guards.
-template <int KMAX>
-__global__ __launch_bounds__(kSlicedWaves * 64) void z_sliced_kernel(ZParams p) {
+template <int KMAX, bool F32>
+__device__ __forceinline__ void z_sliced_body(const ZParams &p) {
   constexpr int NS = (KMAX + kSliceTopics - 1) / kSliceTopics;     // slices per chunk
   constexpr int kAhead = NS < kRingSlots - 1 ? NS : kRingSlots - 1;   // slices in flight beyond the one being scored
   constexpr int NT = (KMAX + 63) / 64;                             // 64-topic pieces of a theta row
@@ -384,9 +632,15 @@ __global__ __launch_bounds__(kSlicedWaves * 64) void z_sliced_kernel(ZParams p) 
 #pragma unroll 1
   for (int phase = 0; phase < 2; ++phase) {
     if ((phase ^ wave) & 1) hot_chunks();
+    else if constexpr (F32) cold_chunks32<KMAX>(p, thb, ring, wid, stride, lane);
     else cold_chunks();
   }
 }
+
+template <int KMAX>
+__global__ __launch_bounds__(kSlicedWaves * 64) void z_sliced_kernel(ZParams p) { z_sliced_body<KMAX, false>(p); }
+template <int KMAX>
+__global__ __launch_bounds__(kSlicedWaves * 64) void z_sliced32_kernel(ZParams p) { z_sliced_body<KMAX, true>(p); }
 
 // The LDS table of z_hot_kernel / z_warm_kernel: `nrows` phiT rows (KMAX doubles each, plain unit order), a zeroed pad
 // unit behind each (hot_pitch) and kHotTailBytes of zeros behind the last.  A row per wave at a time, its word id a scalar
