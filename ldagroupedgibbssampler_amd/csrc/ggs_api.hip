@@ -74,7 +74,8 @@ struct ggs_handle {
   int32_t z_group = 4;     // ... one per z_group slices
   bool z_two_rows = false; // z_stream1_kernel with two theta rows per wave: chunks may run across one document boundary (K <= 512)
   int32_t *d_chunk_doc1 = nullptr;
-  double margin_scale = 1.0;   // GGS_DEBUG_MARGIN: scales z_stream1_kernel's certainty margin (tests force its exact replay)
+  double margin_scale = 1.0;   // GGS_DEBUG_MARGIN, clamped to >= 1: scales the fp64 certainty margins (tests force the exact replays)
+  double margin_scale32 = 1.0; // ... clamped to >= 0: z_sliced32_kernel's margin (below 1 only to show the tests can fail)
 
   hipStream_t stream = nullptr;
   // device buffers
@@ -810,7 +811,7 @@ int launch_z(ggs_handle *h, bool force_fused = false, int64_t c0 = 0, int64_t c1
   zp.ht_pack = reinterpret_cast<const int4 *>(h->d_ht_pack); zp.h_docs = h->d_h_docs;
   zp.wt_pack = reinterpret_cast<const int4 *>(h->d_wt_pack); zp.w_docs = h->d_w_docs; zp.warm_words = h->d_warm_words;
   zp.warm_meta = h->d_warm_meta; zp.warm_tiers = h->warm_tiers; zp.warm_rows = h->warm_cap;
-  zp.phiT32 = h->d_phiT32; zp.Kp32 = h->Kp32; zp.replays = h->d_replays;
+  zp.phiT32 = h->d_phiT32; zp.Kp32 = h->Kp32; zp.replays = h->d_replays; zp.margin_scale32 = h->margin_scale32;
   const bool f32 = h->z_f32 && h->d_phiT32;
   const void *cold_kernel = f32 ? sliced32_kernel_for(h->K) : sliced_kernel_for(h->K);
   if (!h->z_sliced) {                                  // a range of the chunk table (the one-document chunks are in document order)
@@ -1382,8 +1383,13 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
       h->z_two_pass = mode == 3;
       if (h->z_sliced) h->z_stream = false;
     }
-    // only values above 1 are meaningful (they force the exact replay in tests); anything below would void the proof
-    if (const char *e = debug_env("GGS_DEBUG_MARGIN")) h->margin_scale = std::max(1.0, std::atof(e));
+    // above 1 the margins force the exact replays in tests.  Below 1 voids the proof, so only the float32 cold kernel takes
+    // it (its decided draw is a count of partial sums, always a topic < K); the checkpoint-and-refine walks of the fp64
+    // margin kernels keep >= 1, where a wrong slice could walk them out of it
+    if (const char *e = debug_env("GGS_DEBUG_MARGIN")) {
+      h->margin_scale = std::max(1.0, std::atof(e));
+      h->margin_scale32 = std::max(0.0, std::atof(e));
+    }
     if (h->z_stream) {
       // 64-token chunks, a 2-slot slice ring + the theta row zero-padded to whole slices (one-pass kernel: to whole
       // checkpoint groups, plus a checkpoint per group and lane); no score registers, so 8 waves per CU fit the

@@ -73,7 +73,7 @@ struct ZParams {
   int32_t num_hot, hot_pitch;  // rows and row pitch (bytes) of the LDS table
   int32_t hot_off, wave_lds;   // LDS byte offset of the table; bytes of LDS per wave (theta rows + ring)
   int32_t ring_base;           // offset of the ring inside a wave's LDS
-  double margin_scale;         // z_stream1_kernel: 1.0; tests scale the certainty margin up to force its exact replay path
+  double margin_scale;         // the fp64 margin kernels (z_stream1, z_hot, z_warm): 1.0; tests scale it up (>= 1) to force their exact replays
   // z_stream1_kernel with two theta rows per wave (moderate K): a chunk may run across ONE document boundary;
   // chunk_len then carries len | split << 8 (split = tokens of the first document) and chunk_doc1 the second document
   const int32_t *chunk_doc1;
@@ -101,6 +101,8 @@ struct ZParams {
   const float *phiT32;         // [V][Kp32], Kp32 = K rounded up to whole 32-topic slices, the pad columns zero
   int32_t Kp32;
   unsigned long long *replays; // null, or += the tokens replayed (GGS_DEBUG_REPLAYS)
+  double margin_scale32;       // its margin's scale: 1.0; tests scale it up to force the replay, or down to [0, 1) to decide
+                               // tokens the proof leaves undecided (a decided draw is always a topic < K: no walk to leave the row)
 };
 
 struct alignas(16) D2 { double a, b; };

@@ -133,7 +133,10 @@ __device__ __forceinline__ void static_for(F &&f) {
 // |a_j - t0'| >= (|d_j| - 2^-126) / (1 + u) > (2K + 6.2) u A.  So m > delta gives, for every j < K at once,
 // sign(t_{j+1}) = sign(t0' - a_j) (and t_0 > 0 from t0' > delta); the walk is monotone, so Java's
 // newTopic = #{j < K : t_{j+1} > 0} = cnt, and cnt < K says the walk ends inside the row (a padding topic repeats
-// a_{K-1}: it is counted only when a_{K-1} < t0', i.e. cnt >= K).  tests/test_margin32_model.py restates this in numpy.
+// a_{K-1}: it is counted only when a_{K-1} < t0', i.e. cnt >= K).  tests/test_margin32_model.py restates this in numpy;
+// tests/test_knife_edge_gpu.py checks that the device computes that model (replay count, and margin_scale 0 -- the only
+// kernel that takes a scale below 1 (GGS_DEBUG_MARGIN): a decided draw is a count < K whatever the margin -- draws the
+// model's cnt), with float32 denormals kept, the mode these kernels are compiled in.
 //
 // The walk: d_j for two topics per v_pk_add_f32, the sign bits collected by a funnel shift as in the fp64 form, m by one
 // v_min_f32 with an |.| modifier; once every lane's d is >= 0 the rest of the row changes neither cnt nor m (d only grows),
@@ -156,7 +159,7 @@ __device__ __forceinline__ void cold_chunks32(const ZParams &p, unsigned char *t
   const int lrow = lane >> 3, lslot = lane & 7;
   const unsigned char *my_row = ring + lane * 128;
   const int rot = lane >> 1;
-  const float mscale = (float)p.margin_scale;
+  const float mscale = (float)p.margin_scale32;
 
   auto load_theta = [&](const int d0, const int d1, double (&tv)[kChunkDocs][NT]) {
     const double *t0 = p.theta + (size_t)d0 * K, *t1 = p.theta + (size_t)d1 * K;
