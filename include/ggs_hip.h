@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GGS_ABI_VERSION 5
+#define GGS_ABI_VERSION 6
 
 typedef struct ggs_handle ggs_handle;
 
@@ -69,13 +69,23 @@ enum {
                                      ggs_collapsed_serial_sweep runs the reference's own serial chain.  ggs_get_phi returns
                                      the point estimate (beta + n_wk)/(betaSum + n_k); ggs_get_theta, ggs_log_posterior and
                                      ggs_sample_z_given_phi do not apply.  K up to 4096, any document length (as pcgs). */
-  GGS_FLAG_PCGS = 1 << 2          /* scheme=pcgs (LDAPartiallyCollapsedGibbsSampler): the z step is UPLDA:1466-1544,
+  GGS_FLAG_PCGS = 1 << 2,         /* scheme=pcgs (LDAPartiallyCollapsedGibbsSampler): the z step is UPLDA:1466-1544,
                                      score = (n_dk + alpha_k)*phi[k][w], sequential inside a document; no theta draw;
                                      counts, Phi draw and exchange exactly as for ggs.  Any K up to 4096 and any
                                      document length: up to 176 topics (scheme collapsed: 96 -- the measured break-even
                                      points) one LANE owns a document (64 documents per wave, int16 counts in LDS); above
                                      that, or when a document has 32768 tokens or more, one WAVE owns a document (int32
                                      counts, the topics spread over the lanes). */
+  GGS_FLAG_POLYAURN = 1 << 4      /* scheme=polyaurn (PolyaUrnSpaliasLDA, ParallelLDA.java:444-447; ABI version 6): the z step of
+                                     pcgs (implied: GGS_FLAG_PCGS is set internally), except that a document of one token, or
+                                     a token whose scores sum to 0 (its word's Phi column is all zero), draws floor(U * K) with
+                                     the token's own uniform U (PolyaUrnSpaliasLDA.java:261-278).  Phi (initial and per sweep)
+                                     is drawn as Poisson counts X_kv ~ Poisson(beta + n_kv) normalised by their integer row sum,
+                                     a row of sum 0 all zero (PolyaUrnDirichletFixedCoeffPoisson.java:17-40; UPLDA:1287-1294 for
+                                     the initial draw): n_kv < alias_poisson_threshold by inverse CDF over the pmf truncated to
+                                     2 * threshold terms and renormalised, larger counts as max(0, floor(sqrt(l) * g + l + 0.5))
+                                     with l = beta + n_kv and the element's Gaussian g (PolyaUrnDirichlet.java:102-107, the
+                                     negative draw clamped to 0).  Phi has exact zeros.  With GGS_FLAG_COLLAPSED: GGS_ERR_BAD_ARG. */
 };
 
 /* RNG stream addressing.  The reference draws from ThreadLocalRandom and a
@@ -104,7 +114,10 @@ typedef struct ggs_config {
   int32_t flags;          /* GGS_FLAG_*                                                        */
   int32_t phi_burn_in;    /* iterations: (phi_mean_burnin/100)*iterations, UPLDA:206-207       */
   int32_t phi_mean_thin;  /* cfg key phi_mean_thin, UPLDA:208                                  */
-  int32_t reserved;
+  int32_t alias_poisson_threshold; /* cfg key alias_poisson_threshold (ParsedLDAConfiguration.java:480-482; default 100,
+                             LDAConfiguration.java:44): counts below it draw their Poisson variate from a table.  Read only
+                             under GGS_FLAG_POLYAURN: 0 means 100, 1..512 allowed, anything else GGS_ERR_BAD_ARG.  (The
+                             field was `reserved` before ABI version 6; layout and struct_size are unchanged.) */
 } ggs_config;
 
 typedef struct ggs_timings {
@@ -342,6 +355,11 @@ int ggs_debug_philox(int32_t device_id, int64_t n, const uint32_t *ctr /*n*4*/, 
 int ggs_debug_math(int32_t device_id, int32_t op /*0 log,1 pow,2 sqrt,3 div*/, int64_t n, const double *x, const double *y, double *out);
 int ggs_debug_draw(int32_t device_id, int32_t kind /*0 uniform,1 gaussian,2 gamma (general loops),3 gamma as the kernels draw it: first try then general,4 as 3 with first-try results negated*/, uint64_t seed, uint32_t iteration,
                    uint32_t purpose, uint64_t elem0, int64_t n, const double *shape, double *out, int32_t *status);
+/* scheme=polyaurn's Poisson draw (PoissonFixedCoeffSampler.java:31-50, PolyaUrnDirichlet.java:102-107; GGS_FLAG_POLYAURN):
+ * out[i] = X of element elem0 + i with count counts[i] >= 0, exactly as the Phi kernel draws it under (beta, threshold) --
+ * threshold 0 means 100, 1..512 allowed.  ABI version 6. */
+int ggs_debug_poisson(int32_t device_id, double beta, int32_t threshold, uint64_t seed, uint32_t iteration, uint32_t purpose, uint64_t elem0,
+                      int64_t n, const int32_t *counts, int32_t *out);
 /* replaces: modelLogLikelihood (UPLDA:1644-1758), the Dirichlet-multinomial log likelihood of the current topic
  * assignments, split where a doc-sharded run splits it: doc_side covers THIS handle's documents (sum_d [...] +
  * D*lgS(alphaSum), UPLDA:1674-1694) and topic_side the (replicated) type-topic counts (UPLDA:1701-1747); the model's

@@ -13,7 +13,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GGS_HIP_LIB") or os.path.join(CSRC, "libggs_hip.so")   # override: kernel experiments only
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ggs_hip.h")
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class GGSConfig(C.Structure):
@@ -29,7 +29,7 @@ class GGSConfig(C.Structure):
         ("flags", C.c_int32),
         ("phi_burn_in", C.c_int32),
         ("phi_mean_thin", C.c_int32),
-        ("reserved", C.c_int32),
+        ("alias_poisson_threshold", C.c_int32),
     ]
 
 
@@ -134,6 +134,7 @@ SIGNATURES = {
     "ggs_debug_math": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _dp, _dp, _dp]),
     "ggs_debug_draw": (C.c_int, [C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int64,
                                  _dp, _dp, _ip]),
+    "ggs_debug_poisson": (C.c_int, [C.c_int32, C.c_double, C.c_int32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int64, _ip, _ip]),
     "ggs_model_log_likelihood": (C.c_int, [_vp, _dp, _dp]),
     "ggs_log_posterior": (C.c_int, [_vp, _dp, _dp]),
     "ggs_set_test_corpus": (C.c_int, [_vp, C.c_int64, _lp, _ip, C.c_int64]),

@@ -19,6 +19,7 @@
 #include "ggs_z_pcgs.hpp"
 #include "ggs_z_pcgs_wave.hpp"
 #include "ggs_z_collapsed.hpp"
+#include "ggs_phi_poisson.hpp"
 #include "ggs_loglik.hpp"
 #include "ggs_heldout.hpp"
 #include "ggs_exchange.hpp"
@@ -92,6 +93,12 @@ struct ggs_handle {
   bool pcgs_wave_forced = false;                       // ... because of K; otherwise decided per corpus (a document of 32 768 tokens or more)
   int32_t pcgs_wave_nb = 0, pcgs_wave_lds = 0, pcgs_wave_waves_per_cu = 0;
   bool collapsed = false;                              // scheme=collapsed: the pcgs machinery over psi = (beta + n_wk)/(betaSum + n_k)
+  // scheme=polyaurn (ggs_phi_poisson.hpp): the pcgs z loop with its two uniform-draw rules, Phi drawn as Poisson counts
+  bool polyaurn = false;
+  int32_t pa_L = 0;                                    // alias_poisson_threshold
+  double pa_t00 = 0;                                   // T_0[0]
+  double *d_pa_table = nullptr;                        // [L][2L]
+  unsigned long long *d_pa_acc = nullptr;              // [K][kPoissonAccStride]: the draw's integer totals
   uint64_t *d_lcg = nullptr;                           // ggs_collapsed_serial_sweep: the java.util.Random state
   bool lcg_ready = false;
   int32_t hot_cap = 0, num_hot = 0, hot_pitch = 0, wave_lds = 0, ring_base = 0;
@@ -241,6 +248,26 @@ int dev_alloc(ggs_handle *h, T **p, size_t count) {
   if (*p) { (void)hipFree(*p); *p = nullptr; }
   HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)));
   return GGS_OK;
+}
+
+// scheme=polyaurn: the inverse-CDF tables of the Poisson draws with c < L (ggs_phi_poisson.hpp), row c for lambda = beta + c:
+// p_0 = exp(-lambda), p_j = p_{j-1} * lambda / j for j < 2L (PoissonFixedCoeffSampler.java:31-50 keeps the same 2L terms),
+// S_j = p_0 + ... + p_j left to right, T_c[j] = S_j / S_{2L-1} and T_c[2L-1] = 1.  fp64, in this order: the tests restate it.
+void build_poisson_table(double beta, int32_t L, std::vector<double> &T) {
+  const int n = 2 * L;
+  T.assign((size_t)L * n, 0.0);
+  std::vector<double> S((size_t)n);
+  for (int32_t c = 0; c < L; ++c) {
+    const double lambda = beta + (double)c;
+    double pj = std::exp(-lambda), acc = 0.0;
+    for (int j = 0; j < n; ++j) {
+      if (j > 0) pj = pj * lambda / (double)j;
+      acc += pj;
+      S[(size_t)j] = acc;
+    }
+    for (int j = 0; j < n - 1; ++j) T[(size_t)c * n + j] = S[(size_t)j] / S[(size_t)n - 1];
+    T[(size_t)c * n + n - 1] = 1.0;
+  }
 }
 
 int ensure_scratch(ggs_handle *h, size_t bytes) {
@@ -572,10 +599,48 @@ int phi_slice_total(ggs_handle *h, const double *out, int32_t out_pitch, int32_t
   HIP_TRY(h, hipGetLastError());
   return GGS_OK;
 }
+// scheme=polyaurn: the Poisson draws of the rows [seg0, seg1) * 64 (ggs_phi_poisson.hpp) into out, their integer totals
+// into d_pa_acc -- zeroed first by the draw's first launch (`first`), so the two halves of an exchange's draw add up
+int phi_slice_poisson(ggs_handle *h, bool initial, const int32_t *cnt, int32_t cnt_pitch, int32_t Ks, int32_t k0, double *out, int32_t out_pitch,
+                      int32_t seg0, int32_t seg1, bool first) {
+  if (Ks <= 0) return GGS_OK;
+  if (first) HIP_TRY(h, hipMemsetAsync(h->d_pa_acc, 0, sizeof(unsigned long long) * kPoissonAccStride * (size_t)Ks, h->stream));
+  if (seg1 <= seg0) return GGS_OK;
+  PhiPoissonParams pp{};
+  pp.cnt = cnt; pp.out = out; pp.table = h->d_pa_table; pp.acc = h->d_pa_acc; pp.status = h->d_status;
+  pp.seed = h->seed; pp.iteration = (uint32_t)h->iteration; pp.purpose = initial ? GGS_PURPOSE_INIT_PHI : GGS_PURPOSE_PHI;
+  pp.Ks = Ks; pp.out_pitch = out_pitch; pp.cnt_pitch = cnt_pitch; pp.k0 = k0; pp.V = h->V;
+  pp.row_begin = seg0 * kSumSegRows; pp.row_end = std::min(h->V, seg1 * kSumSegRows);
+  pp.L = h->pa_L; pp.beta = h->beta; pp.t00 = h->pa_t00;
+  // tiles sized by the launch's work, as phi_slice_gamma sizes its own: about eight per CU, at least one cell per thread (a
+  // narrow slice -- one rank in eight draws 13 topics -- gets many short tiles); two workgroups per CU take them by grid
+  // stride, so the totals cost 2 * Ks atomics per workgroup whatever the tile count
+  const int64_t rows = pp.row_end - pp.row_begin, cells = rows * Ks;
+  const int64_t want = std::max<int64_t>(kPoissonThreads, cells / ((int64_t)h->num_cus * 8));
+  pp.rows_per_tile = (int32_t)std::max<int64_t>(1, std::min<int64_t>(rows, (want + Ks - 1) / Ks));
+  const int64_t tiles = (rows + pp.rows_per_tile - 1) / pp.rows_per_tile;
+  hipLaunchKernelGGL(phi_poisson_kernel, dim3((unsigned)std::min<int64_t>(tiles, (int64_t)h->num_cus * 2)), dim3(kPoissonThreads), (size_t)Ks * 12, h->stream, pp);
+  HIP_TRY(h, hipGetLastError());
+  return GGS_OK;
+}
+int phi_slice_poisson_totals(ggs_handle *h, int32_t Ks, double *tot, int32_t *n_k) {
+  if (Ks <= 0) return GGS_OK;
+  hipLaunchKernelGGL(phi_poisson_totals_kernel, dim3((unsigned)((Ks + 255) / 256)), dim3(256), 0, h->stream, h->d_pa_acc, Ks, tot, n_k);
+  HIP_TRY(h, hipGetLastError());
+  return GGS_OK;
+}
 int launch_phi_slice(ggs_handle *h, bool initial, const int32_t *cnt, int32_t cnt_pitch, int32_t Ks, int32_t k0, double *out, int32_t out_pitch,
                      double *mag, double *tot, int32_t *n_k, double *phi_mean) {
   if (Ks <= 0) return GGS_OK;
   int rc;
+  if (h->polyaurn) {                                   // no magnitudes, no gammas, no exact-sum walk: the totals are integers
+    if ((rc = phi_slice_poisson(h, initial, cnt, cnt_pitch, Ks, k0, out, out_pitch, 0, h->sum_nseg, true)) || (rc = phi_slice_poisson_totals(h, Ks, tot, n_k)))
+      return rc;
+    hipLaunchKernelGGL(phi_normalise_polyaurn_kernel, dim3(grid_for((int64_t)Ks * h->V, 256, 2)), dim3(256), 0, h->stream, out, tot, Ks, out_pitch, h->V,
+                       phi_mean, out == h->d_phiT ? h->d_phiT32 : nullptr, h->Kp32);
+    HIP_TRY(h, hipGetLastError());
+    return GGS_OK;
+  }
   if ((rc = launch_magnitude_on(h, cnt, cnt_pitch, Ks, mag, n_k)) || (rc = phi_slice_gamma(h, initial, cnt, cnt_pitch, Ks, k0, out, out_pitch, mag, 0, h->sum_nseg)) ||
       (rc = phi_slice_total(h, out, out_pitch, Ks, tot)))
     return rc;
@@ -604,9 +669,13 @@ int phi_step_a(ggs_handle *h) { return exchange_reduce_scatter(h); }
 int phi_step_a_clear(ggs_handle *h) { return h->seg_split > 0 ? GGS_OK : clear_send_buffer_if_dead(h, h->stream); }
 int phi_step_b1(ggs_handle *h, bool initial) {
   int rc;
-  if ((rc = launch_magnitude_on(h, h->d_cnt_own, h->Ksm, h->Ks, h->d_mag_own, h->d_n_k_own))) return rc;
+  if (h->polyaurn) {                                   // the Poisson draws of the first half (and the totals' zero fill)
+    if ((rc = phi_slice_poisson(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, 0, h->seg_split, true))) return rc;
+  } else if ((rc = launch_magnitude_on(h, h->d_cnt_own, h->Ksm, h->Ks, h->d_mag_own, h->d_n_k_own))) {
+    return rc;
+  }
   if (h->seg_split > 0) {
-    if ((rc = phi_slice_gamma(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, h->d_mag_own, 0, h->seg_split))) return rc;
+    if (!h->polyaurn && (rc = phi_slice_gamma(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, h->d_mag_own, 0, h->seg_split))) return rc;
     HIP_TRY(h, hipEventRecord(h->ev_half_drawn, h->stream));
     HIP_TRY(h, hipStreamWaitEvent(h->comm_stream, h->ev_half_drawn, 0));
   }
@@ -624,6 +693,10 @@ int phi_step_b2(ggs_handle *h, bool initial) {
     if ((rc = clear_send_buffer_if_dead(h, h->comm_stream))) return rc;
     HIP_TRY(h, hipEventRecord(h->ev_half_gathered, h->comm_stream));
   }
+  if (h->polyaurn) {                                   // the second half, then the integer totals into the slot behind the slice
+    if ((rc = phi_slice_poisson(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, h->seg_split, h->sum_nseg, false))) return rc;
+    return phi_slice_poisson_totals(h, h->Ks, h->d_phi_own + (size_t)h->V * h->Ksm, h->d_n_k_own);
+  }
   if ((rc = phi_slice_gamma(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, h->d_mag_own, h->seg_split, h->sum_nseg))) return rc;
   return phi_slice_total(h, h->d_phi_own, h->Ksm, h->Ks, h->d_phi_own + (size_t)h->V * h->Ksm);
 }
@@ -640,7 +713,8 @@ int phi_step_c(ggs_handle *h, bool accumulate_mean) {
   rp.phi_mean = accumulate_mean ? h->d_phi_mean : nullptr;
   rp.c0 = (int64_t)half0_elems(h); rp.c1 = (int64_t)half1_elems(h); rp.K = h->K; rp.Kp = h->Kp; rp.V = h->V; rp.Ksm = h->Ksm; rp.v_split = h->v_split;
   rp.phiT32 = h->d_phiT32; rp.Kp32 = h->Kp32;
-  hipLaunchKernelGGL(phi_repack_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
+  if (h->polyaurn) hipLaunchKernelGGL(phi_repack_polyaurn_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
+  else hipLaunchKernelGGL(phi_repack_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   HIP_TRY(h, hipGetLastError());
   h->have_phi = true;
   return GGS_OK;
@@ -704,6 +778,7 @@ const void *sliced32_kernel_for(int K) { GGS_KMAX_SWITCH(z_sliced32_kernel) }
 const void *hot_kernel_for(int K) { GGS_KMAX_SWITCH(z_hot_kernel) }
 const void *warm_kernel_for(int K) { GGS_KMAX_SWITCH(z_warm_kernel) }
 const void *pcgs_kernel_for(int K) { GGS_KMAX_SWITCH(pcgs_sliced_kernel) }
+const void *polyaurn_kernel_for(int K) { GGS_KMAX_SWITCH(polyaurn_sliced_kernel) }
 const void *collapsed_kernel_for(int K) {
   switch ((K + 7) / 8) {
 #define GGS_CK(N) case N: return reinterpret_cast<const void *>(pcgs_sliced_kernel<8 * N, true>);
@@ -714,12 +789,13 @@ const void *collapsed_kernel_for(int K) {
   }
 }
 
-// pcgs_wave_kernel<NB, COLLAPSED> for NB = blocks of 128 topics, rounded up to a power of two
-const void *pcgs_wave_kernel_for(int nb, bool collapsed) {
-#define GGS_WK(N) if (nb <= N) return collapsed ? reinterpret_cast<const void *>(pcgs_wave_kernel<N, true>) : reinterpret_cast<const void *>(pcgs_wave_kernel<N, false>);
+// pcgs_wave_kernel<NB, COLLAPSED> (scheme polyaurn: polyaurn_wave_kernel<NB>) for NB = blocks of 128 topics, rounded up to a
+// power of two
+const void *pcgs_wave_kernel_for(int nb, bool collapsed, bool polyaurn) {
+#define GGS_WK(N) if (nb <= N) return polyaurn ? reinterpret_cast<const void *>(polyaurn_wave_kernel<N>) : collapsed ? reinterpret_cast<const void *>(pcgs_wave_kernel<N, true>) : reinterpret_cast<const void *>(pcgs_wave_kernel<N, false>);
   GGS_WK(1) GGS_WK(2) GGS_WK(4) GGS_WK(8) GGS_WK(16)
 #undef GGS_WK
-  return collapsed ? reinterpret_cast<const void *>(pcgs_wave_kernel<32, true>) : reinterpret_cast<const void *>(pcgs_wave_kernel<32, false>);
+  return polyaurn ? reinterpret_cast<const void *>(polyaurn_wave_kernel<32>) : collapsed ? reinterpret_cast<const void *>(pcgs_wave_kernel<32, true>) : reinterpret_cast<const void *>(pcgs_wave_kernel<32, false>);
 }
 constexpr int kPcgsWaveMaxTopics = 32 * 128;          // 4096: two rows of K/64 doubles per lane in registers
 // Where the wave-per-document kernel takes over from the lane-per-document score-register kernels (which exist up to 192
@@ -729,6 +805,9 @@ constexpr int kPcgsWaveMaxTopics = 32 * 128;          // 4096: two rows of K/64 
 //   pcgs       K = 100: 2.51 / 3.33, 128: 3.69 / 3.3, 144: 4.02 / 4.9, 160: 4.28 / 4.9, 176: 4.69 / 4.9, 192: 6.04 / 5.0
 //   collapsed  K = 100: 3.60 / 3.74, 128: 6.31 / 3.71, 144: 6.96 / 5.6, 160: 7.63 / 5.6, 176: 8.62 / 5.6, 192: 11.4 / 5.6
 constexpr int kPcgsWaveFromTopics = 176, kCollapsedWaveFromTopics = 96;
+// scheme polyaurn: the lane-per-document kernels up to 168 topics -- polyaurn_sliced_kernel<176> spills to scratch where
+// pcgs_sliced_kernel<176> spills less, and the two kernels' times are within 10 % of each other there (pcgs above)
+constexpr int kPolyaurnWaveFromTopics = 168;
 
 int launch_pcgs_z(ggs_handle *h) {
   if (h->N == 0) return GGS_OK;
@@ -750,7 +829,7 @@ int launch_pcgs_z(ggs_handle *h) {
     }
     const dim3 wgrid((unsigned)std::min<int64_t>(h->pcgs_order_len, (int64_t)h->num_cus * h->pcgs_wave_waves_per_cu));
     void *args[] = {&pp, &h->margin_scale};
-    HIP_TRY(h, hipLaunchKernel(pcgs_wave_kernel_for(h->pcgs_wave_nb, h->collapsed), wgrid, block, args, (size_t)h->pcgs_wave_lds, h->stream));
+    HIP_TRY(h, hipLaunchKernel(pcgs_wave_kernel_for(h->pcgs_wave_nb, h->collapsed, h->polyaurn), wgrid, block, args, (size_t)h->pcgs_wave_lds, h->stream));
     return GGS_OK;
   }
   if (h->collapsed) {
@@ -768,7 +847,9 @@ int launch_pcgs_z(ggs_handle *h) {
     }
   } else if (h->pcgs_sliced) {
     void *args[] = {&pp};
-    HIP_TRY(h, hipLaunchKernel(pcgs_kernel_for(h->K), grid, block, args, (size_t)h->pcgs_lds, h->stream));
+    HIP_TRY(h, hipLaunchKernel(h->polyaurn ? polyaurn_kernel_for(h->K) : pcgs_kernel_for(h->K), grid, block, args, (size_t)h->pcgs_lds, h->stream));
+  } else if (h->polyaurn) {
+    hipLaunchKernelGGL(polyaurn_z_kernel, grid, block, (size_t)h->pcgs_lds, h->stream, pp);
   } else {
     hipLaunchKernelGGL(pcgs_z_kernel<false>, grid, block, (size_t)h->pcgs_lds, h->stream, pp);
   }
@@ -1341,6 +1422,11 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
   h->pitch16 = (h->Kp / 2) | 1;             // odd number of 16-byte units per LDS row
   h->beta = cfg->beta; h->seed = cfg->seed; h->flags = cfg->flags;
   if (h->flags & GGS_FLAG_COLLAPSED) { h->collapsed = true; h->flags |= GGS_FLAG_PCGS; }   // the lane-per-document z loop, a different matrix
+  if (h->flags & GGS_FLAG_POLYAURN) {                 // the pcgs z loop (two rules of its own) over a Poisson-drawn Phi
+    const int32_t L = cfg->alias_poisson_threshold == 0 ? 100 : cfg->alias_poisson_threshold;   // LDAConfiguration.java:44
+    if (h->collapsed || L < 1 || L > kPoissonMaxThreshold) { delete h; return GGS_ERR_BAD_ARG; }
+    h->polyaurn = true; h->flags |= GGS_FLAG_PCGS; h->pa_L = L;
+  }
   h->phi_burn_in = cfg->phi_burn_in; h->phi_thin = cfg->phi_mean_thin > 0 ? cfg->phi_mean_thin : 1;
   if (const char *ab = debug_env("GGS_DEBUG_ABLATE")) h->ablate = std::atoi(ab);
   h->alpha.assign(h->K, cfg->alpha_scalar);
@@ -1553,6 +1639,13 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
       hipMemset(h->d_n_k, 0, sizeof(int32_t) * h->K) != hipSuccess || hipMemset(h->d_status, 0, 16) != hipSuccess ||
       (h->d_phi_mean && hipMemset(h->d_phi_mean, 0, sizeof(double) * kv) != hipSuccess))
     return bail(GGS_ERR_HIP);
+  if (h->polyaurn) {
+    std::vector<double> T;
+    build_poisson_table(h->beta, h->pa_L, T);
+    h->pa_t00 = T[0];
+    if ((rc = dev_alloc(h, &h->d_pa_table, T.size())) || (rc = dev_alloc(h, &h->d_pa_acc, (size_t)h->K * kPoissonAccStride))) return bail(rc);
+    if (hipMemcpy(h->d_pa_table, T.data(), sizeof(double) * T.size(), hipMemcpyHostToDevice) != hipSuccess) return bail(GGS_ERR_HIP);
+  }
   if (h->flags & GGS_FLAG_PCGS) {
     // the wave-per-document kernel: any K up to 4096, any document length
     if (h->K <= kPcgsWaveMaxTopics) {
@@ -1563,13 +1656,13 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
       // waves per CU (the grid is persistent: exactly what is resident): what the kernel's registers allow (asked of the
       // runtime) and what LDS allows (computed here: the runtime's answer ignores the 2 KiB allocation granule)
       int by_regs = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, pcgs_wave_kernel_for(nb, h->collapsed), 64, (size_t)h->pcgs_wave_lds) != hipSuccess || by_regs < 1) by_regs = 1;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, pcgs_wave_kernel_for(nb, h->collapsed, h->polyaurn), 64, (size_t)h->pcgs_wave_lds) != hipSuccess || by_regs < 1) by_regs = 1;
       h->pcgs_wave_waves_per_cu = std::max(1, std::min(std::min(by_regs, 32), (kMaxLdsBytes - 2048) / ((h->pcgs_wave_lds + 2047) / 2048 * 2048)));
     }
-    h->pcgs_wave_forced = h->K > (h->collapsed ? kCollapsedWaveFromTopics : kPcgsWaveFromTopics);
+    h->pcgs_wave_forced = h->K > (h->collapsed ? kCollapsedWaveFromTopics : h->polyaurn ? kPolyaurnWaveFromTopics : kPcgsWaveFromTopics);
     if (const char *e = debug_env("GGS_DEBUG_PCGS_WAVE")) h->pcgs_wave_forced = std::atoi(e) != 0;
     if (h->pcgs_wave_forced && !h->pcgs_wave_nb) return bail(GGS_ERR_UNSUPPORTED);   // more than 4096 topics
-    if (h->pcgs_wave_nb && hipFuncSetAttribute(pcgs_wave_kernel_for(h->pcgs_wave_nb, h->collapsed), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess)
+    if (h->pcgs_wave_nb && hipFuncSetAttribute(pcgs_wave_kernel_for(h->pcgs_wave_nb, h->collapsed, h->polyaurn), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess)
       return bail(GGS_ERR_HIP);
     // pcgs_z_kernel: slice ring + alpha row + int16 [KT][64] document counts per single-wave workgroup
     const int ns = std::max(kPcgsRingSlots - 1, (h->K + kSliceTopics - 1) / kSliceTopics), kt = ns * kSliceTopics;
@@ -1584,8 +1677,9 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     if (h->pcgs_lds > kMaxLdsBytes && !h->pcgs_wave_forced) return bail(GGS_ERR_UNSUPPORTED);
     h->pcgs_waves_per_cu = std::max(1, std::min(8, (kMaxLdsBytes - 2048) / ((h->pcgs_lds + 2047) / 2048 * 2048)));   // never a CU filled to the last granule (see z_waves_per_cu)
     if (!h->pcgs_wave_forced &&
-        hipFuncSetAttribute(h->pcgs_sliced ? (h->collapsed ? collapsed_kernel_for(h->K) : pcgs_kernel_for(h->K))
-                                           : h->collapsed ? reinterpret_cast<const void *>(pcgs_z_kernel<true>) : reinterpret_cast<const void *>(pcgs_z_kernel<false>),
+        hipFuncSetAttribute(h->pcgs_sliced ? (h->collapsed ? collapsed_kernel_for(h->K) : h->polyaurn ? polyaurn_kernel_for(h->K) : pcgs_kernel_for(h->K))
+                            : h->collapsed ? reinterpret_cast<const void *>(pcgs_z_kernel<true>)
+                            : h->polyaurn  ? reinterpret_cast<const void *>(polyaurn_z_kernel) : reinterpret_cast<const void *>(pcgs_z_kernel<false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess)
       return bail(GGS_ERR_HIP);
     if (h->collapsed && ((rc = dev_alloc(h, &h->d_lcg, 2)) ||
@@ -1636,7 +1730,8 @@ void ggs_destroy(ggs_handle *h) {
                   h->d_test_ptr, h->d_test_tok, h->d_test_ll, h->d_test_docs, h->d_koff, h->d_cnt_send, h->d_cnt_own, h->d_cnt_all, h->d_n_k_own,
                   h->d_heldout_spill, h->d_phi_own, h->d_phi_all0, h->d_phi_all1, h->d_mag_own, h->d_krank, h->d_kcol, h->d_lcg, h->d_chunk_doc1,
                   h->d_hseg_word, h->d_hseg_begin, h->d_hseg_end, h->d_sp_count, h->d_sp_cnt32, h->d_sp_all, h->d_sp_send, h->d_sp_recv, h->d_sp_wg_count,
-                  h->d_sp_wg_off, h->d_ht_pack, h->d_h_docs, h->d_wt_pack, h->d_w_docs, h->d_warm_words, h->d_warm_meta, h->d_phiT32, h->d_replays};
+                  h->d_sp_wg_off, h->d_ht_pack, h->d_h_docs, h->d_wt_pack, h->d_w_docs, h->d_warm_words, h->d_warm_meta, h->d_phiT32, h->d_replays,
+                  h->d_pa_table, h->d_pa_acc};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   exchange_free(h->xg);
@@ -2883,6 +2978,29 @@ int ggs_debug_draw(int32_t device_id, int32_t kind, uint64_t seed, uint32_t iter
   if (hipMemcpy(out, dou, n * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&st, dst, 4, hipMemcpyDeviceToHost) != hipSuccess) return GGS_ERR_HIP;
   if (status) *status = (int32_t)st;
   return GGS_OK;
+}
+
+int ggs_debug_poisson(int32_t device_id, double beta, int32_t threshold, uint64_t seed, uint32_t iteration, uint32_t purpose, uint64_t elem0, int64_t n,
+                      const int32_t *counts, int32_t *out) {
+  const int32_t L = threshold == 0 ? 100 : threshold;
+  if (n <= 0 || !counts || !out || !(beta > 0) || L < 1 || L > kPoissonMaxThreshold || hipSetDevice(device_id) != hipSuccess) return GGS_ERR_BAD_ARG;
+  for (int64_t i = 0; i < n; ++i)
+    if (counts[i] < 0) return GGS_ERR_BAD_ARG;
+  std::vector<double> T;
+  build_poisson_table(beta, L, T);
+  TmpDev t;
+  auto *dt = static_cast<double *>(t.get(T.size() * 8)); auto *dc = static_cast<int32_t *>(t.get(n * 4));
+  auto *dou = static_cast<int32_t *>(t.get(n * 4)); auto *dst = static_cast<uint32_t *>(t.get(16));
+  if (!dt || !dc || !dou || !dst) return GGS_ERR_HIP;
+  if (hipMemcpy(dt, T.data(), T.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dc, counts, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(dst, 0, 16) != hipSuccess)
+    return GGS_ERR_HIP;
+  hipLaunchKernelGGL(debug_poisson_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, seed, iteration, purpose, elem0, n, dc, L, beta, dt, T[0],
+                     dou, dst);
+  uint32_t st = 0;
+  if (hipGetLastError() != hipSuccess || hipMemcpy(out, dou, n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&st, dst, 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return GGS_ERR_HIP;
+  return st ? GGS_ERR_RNG_EXHAUSTED : GGS_OK;
 }
 
 int ggs_debug_column_sum_guided(int32_t device_id, int32_t V, int32_t K, const double *x, const int32_t *counts, double beta, const double *guess,

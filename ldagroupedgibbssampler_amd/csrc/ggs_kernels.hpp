@@ -550,8 +550,11 @@ __global__ __launch_bounds__(64) void phi_gamma_kernel(PhiGammaParams p) {
 // K..Kp32-1 stay the zeros of the allocation.
 __device__ __forceinline__ float phi32_of(const double x) { return (x >= 0.0 && x <= 1.0) ? (float)x : __builtin_nanf(""); }
 
-__global__ __launch_bounds__(256) void phi_normalise_kernel(double *phiT, const double *tot, int32_t K, int32_t Kp, int32_t V,
-                                                            double *phi_mean /* [V][K] or null */, float *phiT32 /* or null */, int32_t Kp32) {
+// POLYAURN (scheme polyaurn, PolyaUrnDirichletFixedCoeffPoisson.java:33-40): tot is an integer count of the row's Poisson
+// draws; exact zeros stay zero (no clamp), and a row whose total is 0 becomes all zero (the draws are all 0 there anyway).
+template <bool POLYAURN>
+__device__ __forceinline__ void phi_normalise_body(double *phiT, const double *tot, int32_t K, int32_t Kp, int32_t V, double *phi_mean, float *phiT32,
+                                                   int32_t Kp32) {
   __builtin_amdgcn_s_setprio(3);
   const int64_t n = (int64_t)V * K;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -559,7 +562,10 @@ __global__ __launch_bounds__(256) void phi_normalise_kernel(double *phiT, const 
     const int v = (int)(i / K), k = (int)(i - (int64_t)v * K);
     double x = phiT[(size_t)v * Kp + k];
     const double s = tot[k];
-    if (s != 0) {
+    if constexpr (POLYAURN) {
+      x = s > 0 ? x / s : 0.0;
+      phiT[(size_t)v * Kp + k] = x;
+    } else if (s != 0) {
       x = x / s;
       if (x <= 0) x = kJavaMinValue;
       phiT[(size_t)v * Kp + k] = x;
@@ -567,6 +573,14 @@ __global__ __launch_bounds__(256) void phi_normalise_kernel(double *phiT, const 
     if (phiT32) phiT32[(size_t)v * Kp32 + k] = phi32_of(x);
     if (phi_mean) phi_mean[i] += x;                                  // GGS:193-197
   }
+}
+__global__ __launch_bounds__(256) void phi_normalise_kernel(double *phiT, const double *tot, int32_t K, int32_t Kp, int32_t V,
+                                                            double *phi_mean /* [V][K] or null */, float *phiT32 /* or null */, int32_t Kp32) {
+  phi_normalise_body<false>(phiT, tot, K, Kp, V, phi_mean, phiT32, Kp32);
+}
+__global__ __launch_bounds__(256) void phi_normalise_polyaurn_kernel(double *phiT, const double *tot, int32_t K, int32_t Kp, int32_t V, double *phi_mean,
+                                                                     float *phiT32, int32_t Kp32) {
+  phi_normalise_body<true>(phiT, tot, K, Kp, V, phi_mean, phiT32, Kp32);
 }
 
 // ---- exchange layout <-> device layout (one GPU of several; see include/ggs_hip.h, "multi-GPU") ----
@@ -583,7 +597,8 @@ struct PhiRepackParams {
   float *phiT32;                 // or null
   int32_t Kp32;
 };
-__global__ __launch_bounds__(256) void phi_repack_kernel(PhiRepackParams p) {
+template <bool POLYAURN>
+__device__ __forceinline__ void phi_repack_body(const PhiRepackParams &p) {
   __builtin_amdgcn_s_setprio(3);
   const int64_t n = (int64_t)p.V * p.K;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -594,7 +609,9 @@ __global__ __launch_bounds__(256) void phi_repack_kernel(PhiRepackParams p) {
     const double *h1 = p.all1 + (int64_t)r * p.c1;
     double x = v < p.v_split ? p.all0[(int64_t)r * p.c0 + (int64_t)v * p.Ksm + j] : h1[(int64_t)(v - p.v_split) * p.Ksm + j];
     const double s = h1[tot_off + j];
-    if (s != 0) {
+    if constexpr (POLYAURN) {                                        // as phi_normalise_body<true>
+      x = s > 0 ? x / s : 0.0;
+    } else if (s != 0) {
       x = x / s;
       if (x <= 0) x = kJavaMinValue;
     }
@@ -603,6 +620,8 @@ __global__ __launch_bounds__(256) void phi_repack_kernel(PhiRepackParams p) {
     if (p.phi_mean) p.phi_mean[i] += x;
   }
 }
+__global__ __launch_bounds__(256) void phi_repack_kernel(PhiRepackParams p) { phi_repack_body<false>(p); }
+__global__ __launch_bounds__(256) void phi_repack_polyaurn_kernel(PhiRepackParams p) { phi_repack_body<true>(p); }
 // cnt_all [nranks][V][Ksm] (the all-gathered count slices) -> n_wk [V][K]
 __global__ __launch_bounds__(256) void counts_unslice_kernel(const int32_t *cnt_all, const int64_t *koff, int32_t Ksm, int32_t *n_wk, int32_t K,
                                                              int32_t V) {

@@ -63,8 +63,8 @@ constexpr int pcgs_wave_depth() { return NB < 8 ? 2 : NB == 8 ? GGS_PCGS_WAVE_DE
 template <int NB>
 constexpr int pcgs_wave_min_waves() { return NB == 8 ? 3 : 1; }
 
-template <int NB, bool COLLAPSED>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pcgs_wave_min_waves<NB>()))) void pcgs_wave_kernel(PcgsParams p, double margin_scale) {
+template <int NB, bool COLLAPSED, bool POLYAURN>
+__device__ __forceinline__ void pcgs_wave_body(PcgsParams &p, const double margin_scale) {
   constexpr int KT = NB * 128;
   constexpr int kDepth = pcgs_wave_depth<NB, COLLAPSED>(), kSets = kDepth + 1;
   constexpr int kNG = NB < GGS_PCGS_WAVE_GROUPS ? NB : GGS_PCGS_WAVE_GROUPS, kG = NB / kNG;   // groups of the block search, blocks per group
@@ -189,7 +189,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pcgs_wave_mi
         const double s_hat = NB == 2 ? tot[0] + tot[NB - 1] : tot[0];
         const double T = U * s_hat;
         const double delta = ((double)(K + 16) * s_hat) * 0x1p-51 * margin_scale;
-        if (T > delta && s_hat < __builtin_huge_val()) {
+        bool uniform = false;                                              // POLYAURN (pcgs_z_body): before the margin logic;
+        if constexpr (POLYAURN) uniform = len == 1 || s_hat == 0.0;        // scores are >= 0, so s_hat == 0 iff Java's sum == 0
+        if (uniform) new_topic = polyaurn_uniform_topic(U, K);
+        if (!uniform && T > delta && s_hat < __builtin_huge_val()) {
           const bool second = NB == 2 && !(T - tot[0] <= delta);           // wave-uniform
           decide(second ? 1 : 0, second ? tot[0] : 0.0, second ? qa[NB - 1] : qa[0], second ? qb[NB - 1] : qb[0], second ? sc[NB - 1] : sc[0], T, delta);
         }
@@ -230,8 +233,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pcgs_wave_mi
 
       const double T = U * s_hat;
       const double delta = ((double)(K + 16) * s_hat) * 0x1p-51 * margin_scale;
+      bool uniform = false;                                                // POLYAURN, as above
+      if constexpr (POLYAURN) uniform = len == 1 || s_hat == 0.0;
+      if (uniform) new_topic = polyaurn_uniform_topic(U, K);
 
-      if (T > delta && s_hat < __builtin_huge_val()) {
+      if (!uniform && T > delta && s_hat < __builtin_huge_val()) {
         // descend: at a node covering groups [lo, lo + width) with C' = `before` at its start, the crossing is in the left
         // half iff the prefix at the left half's end is past T or too close to call; inside the group, block by block
         double before = 0.0;
@@ -330,6 +336,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pcgs_wave_mi
         if (t0 + u < len) step(t0 + u, rows[u], rows[(u + kDepth) % kSets]);
       });
   }
+}
+template <int NB, bool COLLAPSED>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pcgs_wave_min_waves<NB>()))) void pcgs_wave_kernel(PcgsParams p, double margin_scale) {
+  pcgs_wave_body<NB, COLLAPSED, false>(p, margin_scale);
+}
+template <int NB>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(pcgs_wave_min_waves<NB>()))) void polyaurn_wave_kernel(PcgsParams p, double margin_scale) {
+  pcgs_wave_body<NB, false, true>(p, margin_scale);
 }
 
 }  // namespace ggs

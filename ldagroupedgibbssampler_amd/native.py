@@ -8,7 +8,7 @@ from . import _lib
 OK = 0
 ERR_NEGATIVE_COUNT, ERR_INVALID_TOPIC, ERR_RNG_EXHAUSTED, ERR_BAD_ARG = 1, 2, 3, 4
 ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_INVARIANT = 5, 6, 7, 8
-FLAG_PARANOID, FLAG_SAVE_PHI_MEAN, FLAG_PCGS, FLAG_COLLAPSED = 1, 2, 4, 8
+FLAG_PARANOID, FLAG_SAVE_PHI_MEAN, FLAG_PCGS, FLAG_COLLAPSED, FLAG_POLYAURN = 1, 2, 4, 8, 16
 PURPOSE_Z, PURPOSE_THETA, PURPOSE_PHI, PURPOSE_INIT_PHI = 1, 2, 3, 4
 
 
@@ -34,7 +34,7 @@ def _lp(a):
     return a.ctypes.data_as(C.POINTER(C.c_int64))
 
 
-def _make_config(num_topics, num_types, alpha, beta, seed, device_id, flags, phi_burn_in, phi_mean_thin):
+def _make_config(num_topics, num_types, alpha, beta, seed, device_id, flags, phi_burn_in, phi_mean_thin, alias_poisson_threshold=0):
     """(ggs_config, the alpha array it points into -- keep it alive for the duration of the call)"""
     cfg = _lib.GGSConfig()
     cfg.struct_size = C.sizeof(_lib.GGSConfig)
@@ -52,6 +52,7 @@ def _make_config(num_topics, num_types, alpha, beta, seed, device_id, flags, phi
     cfg.beta = float(beta)
     cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     cfg.flags, cfg.phi_burn_in, cfg.phi_mean_thin = int(flags), int(phi_burn_in), int(phi_mean_thin)
+    cfg.alias_poisson_threshold = int(alias_poisson_threshold)      # FLAG_POLYAURN only; 0 = the default 100
     return cfg, keep
 
 
@@ -66,7 +67,8 @@ def rccl_unique_id():
 
 
 class GGSHandle:
-    def __init__(self, num_topics, num_types, alpha, beta, seed, device_id=0, flags=0, phi_burn_in=0, phi_mean_thin=1, _adopt=None):
+    def __init__(self, num_topics, num_types, alpha, beta, seed, device_id=0, flags=0, phi_burn_in=0, phi_mean_thin=1, _adopt=None,
+                 alias_poisson_threshold=0):
         self._L = _lib.load()
         self.K, self.V = int(num_topics), int(num_types)
         self.D = self.N = 0
@@ -75,7 +77,8 @@ class GGSHandle:
         if _adopt is not None:             # a handle created by ggs_group_create
             self._h = _adopt
             return
-        cfg, self._alpha = _make_config(num_topics, num_types, alpha, beta, seed, device_id, flags, phi_burn_in, phi_mean_thin)
+        cfg, self._alpha = _make_config(num_topics, num_types, alpha, beta, seed, device_id, flags, phi_burn_in, phi_mean_thin,
+                                        alias_poisson_threshold)
         h = C.c_void_p()
         rc = self._L.ggs_create(C.byref(cfg), C.byref(h))
         if rc:
@@ -338,11 +341,11 @@ class GGSGroup:
         self._chk(self._L.ggs_group_adopt(self._arr, n))
         return self
 
-    def __init__(self, num_topics, num_types, alpha, beta, seed, device_ids, flags=0, phi_burn_in=0, phi_mean_thin=1):
+    def __init__(self, num_topics, num_types, alpha, beta, seed, device_ids, flags=0, phi_burn_in=0, phi_mean_thin=1, alias_poisson_threshold=0):
         self._L = _lib.load()
         self._owns = True
         _lib.share_rccl_with_torch()
-        cfg, keep = _make_config(num_topics, num_types, alpha, beta, seed, 0, flags, phi_burn_in, phi_mean_thin)
+        cfg, keep = _make_config(num_topics, num_types, alpha, beta, seed, 0, flags, phi_burn_in, phi_mean_thin, alias_poisson_threshold)
         n = len(device_ids)
         devs = (C.c_int32 * n)(*[int(d) for d in device_ids])
         self._arr = (C.c_void_p * n)()
@@ -419,6 +422,17 @@ def debug_draw(kind, seed, iteration, purpose, elem0, n=None, shape=None, device
     if rc:
         raise GGSError(rc, "ggs_debug_draw")
     return out, st.value
+
+
+def debug_poisson(counts, beta, threshold, seed, iteration, purpose, elem0, device_id=0):
+    """scheme=polyaurn's Poisson variates X of elements elem0 + i with counts[i], as the Phi kernel draws them (int32)."""
+    L = _lib.load()
+    counts = np.ascontiguousarray(counts, np.int32)
+    out = np.empty(counts.size, np.int32)
+    rc = L.ggs_debug_poisson(device_id, float(beta), int(threshold), seed, iteration, purpose, elem0, counts.size, _ip(counts), _ip(out))
+    if rc:
+        raise GGSError(rc, "ggs_debug_poisson")
+    return out
 
 
 def debug_column_sum(x=None, counts=None, beta=0.0, device_id=0):

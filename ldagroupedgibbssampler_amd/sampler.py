@@ -37,6 +37,7 @@ class SimpleLDAConfiguration:
         self.save_phi_mean = bool(kw.pop("save_phi_mean", False))    # SAVE_PHI_MEAN_DEFAULT
         self.phi_mean_burnin = int(kw.pop("phi_mean_burnin", 0))     # percent of iterations, PHI_BURN_IN_DEFAULT
         self.phi_mean_thin = int(kw.pop("phi_mean_thin", 1))         # PHI_THIN_DEFAULT
+        self.alias_poisson_threshold = int(kw.pop("alias_poisson_threshold", 100))   # ALIAS_POISSON_DEFAULT_THRESHOLD; scheme=polyaurn only
         self.paranoid = bool(kw.pop("paranoid", False))              # run the UPLDA:299-338 invariants every sweep
         self.device_id = int(kw.pop("device_id", 0))                 # optional gpu_* key; default first visible GPU
         # the diagnostics of the sampling loop (UPLDA:695-905), computed on the device and written in the Java driver's formats
@@ -145,7 +146,8 @@ class LDAGroupedGibbsSampler:
         flags = (native.FLAG_PARANOID if cfg.paranoid else 0) | (native.FLAG_SAVE_PHI_MEAN if cfg.save_phi_mean else 0) | self._scheme_flags
         burn_in = int((cfg.phi_mean_burnin / 100.0) * cfg.iterations)        # UPLDA:206-207
         self._h = native.GGSHandle(self.numTopics, training.num_types, self.alpha, self.beta, self.startSeed,
-                                   device_id=cfg.device_id, flags=flags, phi_burn_in=burn_in, phi_mean_thin=cfg.phi_mean_thin)
+                                   device_id=cfg.device_id, flags=flags, phi_burn_in=burn_in, phi_mean_thin=cfg.phi_mean_thin,
+                                   alias_poisson_threshold=getattr(cfg, "alias_poisson_threshold", 100))
         self._corpus = training
         self._h.set_corpus(training.doc_ptr, training.tokens)
         self._h.init_z_java_lcg(self.startSeed)          # initialDrawTopicIndicator, UPLDA:458-460
@@ -390,6 +392,17 @@ class LDAPartiallyCollapsedGibbsSampler(LDAGroupedGibbsSampler):
         raise NotImplementedError("scheme=pcgs never draws theta; use getThetaEstimate() (UPLDA:716-720 does the same)")
 
 
+class PolyaUrnSpaliasLDA(LDAPartiallyCollapsedGibbsSampler):
+    """scheme=polyaurn (topics/PolyaUrnSpaliasLDA.java, ParallelLDA.java:444-447): the pcgs driver and z step, with Phi drawn
+    as Poisson counts normalised by their integer row sums (exact zeros) and a uniform topic for one-token documents and
+    all-zero score rows (PolyaUrnSpaliasLDA.java:261-278).  Config key alias_poisson_threshold (default 100): counts below it
+    draw from a table, larger ones from the normal approximation."""
+    _scheme_flags = native.FLAG_POLYAURN
+
+    def getTheta(self):
+        raise NotImplementedError("scheme=polyaurn never draws theta; use getThetaEstimate() (UPLDA:716-720 does the same)")
+
+
 class SerialCollapsedLDA(LDAGroupedGibbsSampler):
     """scheme=collapsed (topics/SerialCollapsedLDA.java; the conditional it samples from is sampleTopicsForOneDoc,
     MSLDA:158-226).  `schedule`:
@@ -425,7 +438,8 @@ class SerialCollapsedLDA(LDAGroupedGibbsSampler):
 
 
 def create_model(config, scheme=None):
-    """The `case "ggs"` / `case "pcgs"` / `case "collapsed"` of tui/ParallelLDA.createModel (ParallelLDA.java:401-490)."""
+    """The `case "ggs"` / `case "pcgs"` / `case "collapsed"` / `case "polyaurn"` of tui/ParallelLDA.createModel
+    (ParallelLDA.java:401-490)."""
     scheme = scheme or config.scheme
     if scheme == "ggs":
         return LDAGroupedGibbsSampler(config)
@@ -433,4 +447,6 @@ def create_model(config, scheme=None):
         return LDAPartiallyCollapsedGibbsSampler(config)
     if scheme == "collapsed":
         return SerialCollapsedLDA(config)
-    raise ValueError("scheme %r is not provided by this build (only the ggs, pcgs and collapsed z loops are in scope)" % scheme)
+    if scheme == "polyaurn":
+        return PolyaUrnSpaliasLDA(config)
+    raise ValueError("scheme %r is not provided by this build (only the ggs, pcgs, collapsed and polyaurn z loops are in scope)" % scheme)
