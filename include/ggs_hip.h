@@ -76,7 +76,7 @@ enum {
                                      points) one LANE owns a document (64 documents per wave, int16 counts in LDS); above
                                      that, or when a document has 32768 tokens or more, one WAVE owns a document (int32
                                      counts, the topics spread over the lanes). */
-  GGS_FLAG_POLYAURN = 1 << 4      /* scheme=polyaurn (PolyaUrnSpaliasLDA, ParallelLDA.java:444-447; ABI version 6): the z step of
+  GGS_FLAG_POLYAURN = 1 << 4,     /* scheme=polyaurn (PolyaUrnSpaliasLDA, ParallelLDA.java:444-447; ABI version 6): the z step of
                                      pcgs (implied: GGS_FLAG_PCGS is set internally), except that a document of one token, or
                                      a token whose scores sum to 0 (its word's Phi column is all zero), draws floor(U * K) with
                                      the token's own uniform U (PolyaUrnSpaliasLDA.java:261-278).  Phi (initial and per sweep)
@@ -86,6 +86,14 @@ enum {
                                      2 * threshold terms and renormalised, larger counts as max(0, floor(sqrt(l) * g + l + 0.5))
                                      with l = beta + n_kv and the element's Gaussian g (PolyaUrnDirichlet.java:102-107, the
                                      negative draw clamped to 0).  Phi has exact zeros.  With GGS_FLAG_COLLAPSED: GGS_ERR_BAD_ARG. */
+  GGS_FLAG_SPALIAS = 1 << 5       /* scheme=spalias (SpaliasUncollapsedParallelLDA, ParallelLDA.java:439-442): the pcgs model
+                                     (implied: GGS_FLAG_PCGS is set internally; Phi, counts, phi mean and exchange exactly as pcgs)
+                                     with the z step's conditional split into alpha_k * phi[k][w], drawn in O(1) from a Walker alias
+                                     table per word, and n_dk * phi[k][w], walked over the document's non-zero topics only: the
+                                     same distribution, O(nnz_d) per token, a different draw from the same uniform.  The tables are
+                                     rebuilt whenever Phi changes (ggs_init_phi, every sweep, ggs_set_phi); ggs_get_alias_tables
+                                     reads them back.  K up to 4096, any document length.  With GGS_FLAG_COLLAPSED or
+                                     GGS_FLAG_POLYAURN: GGS_ERR_BAD_ARG.  A new bit, not a new ABI version. */
 };
 
 /* RNG stream addressing.  The reference draws from ThreadLocalRandom and a
@@ -360,6 +368,13 @@ int ggs_debug_draw(int32_t device_id, int32_t kind /*0 uniform,1 gaussian,2 gamm
  * threshold 0 means 100, 1..512 allowed.  ABI version 6. */
 int ggs_debug_poisson(int32_t device_id, double beta, int32_t threshold, uint64_t seed, uint32_t iteration, uint32_t purpose, uint64_t elem0,
                       int64_t n, const int32_t *counts, int32_t *out);
+/* scheme=spalias's alias tables (reGenerateAliasTable, util/OptimizedGentleAliasMethod.java; GGS_FLAG_SPALIAS), built by the
+ * product kernel from phi [K][V] and alpha [K]: ps [V][K], a [V][K] and type_norm [V] = the k-order sum of phi[k][w] * alpha[k].
+ * A draw x in [0, 1) from word w's table: ups = x * K, i = (int)ups, topic = (ups - i) > ps[w][i] ? a[w][i] : i.  K up to 4096. */
+int ggs_debug_alias(int32_t device_id, int32_t V, int32_t K, const double *phi, const double *alpha, double *ps, int32_t *a, double *type_norm);
+/* the tables of the handle's current Phi (GGS_FLAG_SPALIAS; GGS_ERR_STATE otherwise or before the first Phi); any of the
+ * three outputs may be null */
+int ggs_get_alias_tables(ggs_handle *h, double *ps /*[V][K]*/, int32_t *a /*[V][K]*/, double *type_norm /*[V]*/);
 /* replaces: modelLogLikelihood (UPLDA:1644-1758), the Dirichlet-multinomial log likelihood of the current topic
  * assignments, split where a doc-sharded run splits it: doc_side covers THIS handle's documents (sum_d [...] +
  * D*lgS(alphaSum), UPLDA:1674-1694) and topic_side the (replicated) type-topic counts (UPLDA:1701-1747); the model's

@@ -1,0 +1,111 @@
+// ggs_alias.hpp -- scheme=spalias: the per-word Walker alias tables of the conditional's "prior" part,
+// pi[k] = phi[k][w] * alpha[k] (SpaliasUncollapsedParallelLDA.java:39-60; the build is reGenerateAliasTable of
+// util/OptimizedGentleAliasMethod.java).  Rebuilt whenever Phi changes, read by the z step of ggs_z_spalias.hpp.
+//
+// Per word: typeNorm = the k-order sum of pi from 0.0; bs[k] = pi[k] / typeNorm - 1.0 / K; k goes on the `lows` stack
+// if bs[k] < 0.0, else on `highs`, both in k order; then, while both stacks hold something: pop l from lows, peek h on
+// highs, c = bs[l], d = bs[h], bs[h] = c + d, pop highs if bs[h] <= 0, push h on lows if bs[h] < 0, a[l] = h,
+// ps[l] = 1.0 + (double)K * c.  Every entry the loop never pairs keeps a[k] = k, ps[k] = 1.0 (ours: Java leaves ps[k]
+// stale there; such an entry has a[k] = k, so no draw can tell).  A column that underflowed as a whole (typeNorm == 0)
+// makes every bs NaN: all k land on highs, the table is the identity, and the z step never reads it.
+//
+// The pairing loop is a serial chain of at most K steps per word in which every step depends on the one before (bs[h]
+// carries over), and the words are independent: V chains.  A chain runs on ONE LANE, out of LDS:
+//   bs   fp64 [K]   -- pi, then bs in place; the slot of a popped l is dead (l never returns to a stack) and takes ps[l]
+//   al   u16  [K]   -- the alias, preset to k
+//   st   u16  [K]   -- BOTH stacks: lows grow up from 0, highs down from K (they hold K entries at the start and never
+//                      more: a push on lows only ever follows a pop of highs)
+// 12 bytes per topic and word.  A single-wave workgroup takes `wpb` words at a time (as many as fit 48 KiB, at most 64):
+// all 64 lanes fill pi (coalesced: consecutive words' phiT rows), lanes 0..wpb-1 each sum their word's column in k order,
+// all lanes form bs, lanes 0..wpb-1 fill the stacks and run the chains, all lanes write ps / a out (coalesced).  At
+// K = 1024 four chains run per wave and thirteen waves fit a CU; at K = 4096 one chain per wave, three waves per CU.
+// The chain is LDS-latency bound: three dependent LDS operations per step (the stack entry, bs of it, the store).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace ggs {
+
+struct AliasParams {
+  const double *phiT;          // [V][Kp]
+  const double *alpha;         // [K]
+  double *ps;                  // [V][K]
+  int32_t *a;                  // [V][K]
+  double *type_norm;           // [V]
+  int32_t V, K, Kp, wpb;
+};
+
+constexpr int kAliasLdsBudget = 48 * 1024;
+inline int alias_words_per_block(int K) { return std::max(1, std::min(64, kAliasLdsBudget / (12 * K))); }
+inline size_t alias_lds_bytes(int K, int wpb) { return (size_t)wpb * K * 12 + 64 * sizeof(double); }
+
+__global__ __launch_bounds__(64) void alias_build_kernel(AliasParams p) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int K = p.K, wpb = p.wpb, lane = threadIdx.x;
+  double *bs = reinterpret_cast<double *>(smem);                                   // [wpb][K]
+  double *tnl = bs + (size_t)wpb * K;                                              // [64]
+  uint16_t *al = reinterpret_cast<uint16_t *>(tnl + 64);                           // [wpb][K]
+  uint16_t *st = al + (size_t)wpb * K;                                             // [wpb][K]
+  const double inv_k = 1.0 / (double)K;
+
+  for (int w0 = blockIdx.x * wpb; w0 < p.V; w0 += gridDim.x * wpb) {
+    const int nw = min(wpb, p.V - w0), cells = nw * K;
+    __syncthreads();
+    for (int idx = lane; idx < cells; idx += 64) {
+      const int wi = idx / K, k = idx - wi * K;
+      bs[idx] = p.phiT[(size_t)(w0 + wi) * p.Kp + k] * p.alpha[k];
+      al[idx] = (uint16_t)k;
+    }
+    __syncthreads();
+    if (lane < nw) {
+      const double *b = bs + (size_t)lane * K;
+      double tn = 0.0;
+      for (int k = 0; k < K; ++k) tn += b[k];
+      tnl[lane] = tn;
+      p.type_norm[w0 + lane] = tn;
+    }
+    __syncthreads();
+    for (int idx = lane; idx < cells; idx += 64) bs[idx] = bs[idx] / tnl[idx / K] - inv_k;
+    __syncthreads();
+    if (lane < nw) {
+      double *b = bs + (size_t)lane * K;
+      uint16_t *s = st + (size_t)lane * K, *aw = al + (size_t)lane * K;
+      int nl = 0, hp = K;                                                          // lows: s[0, nl), top s[nl - 1]; highs: s[hp, K), top s[hp]
+      for (int k = 0; k < K; ++k) {
+        if (b[k] < 0.0) s[nl++] = (uint16_t)k;
+        else s[--hp] = (uint16_t)k;
+      }
+      if (nl > 0 && hp < K) {
+        int h = s[hp];
+        double d = b[h];
+        while (true) {
+          const int l = s[--nl];
+          const double c = b[l];
+          b[l] = 1.0 + (double)K * c;                                              // ps[l]
+          aw[l] = (uint16_t)h;
+          d = c + d;
+          if (d <= 0.0) {                                                          // highs loses h ...
+            ++hp;
+            if (d < 0.0) s[nl++] = (uint16_t)h;                                    // ... and lows takes it
+            b[h] = d;
+            if (nl == 0 || hp == K) break;
+            h = s[hp];
+            d = b[h];
+          } else if (nl == 0) {
+            b[h] = d;
+            break;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    for (int idx = lane; idx < cells; idx += 64) {
+      const int wi = idx / K, k = idx - wi * K, av = al[idx];
+      const size_t o = (size_t)w0 * K + idx;
+      p.ps[o] = av == k ? 1.0 : bs[idx];
+      p.a[o] = av;
+    }
+  }
+}
+
+}  // namespace ggs

@@ -20,6 +20,8 @@
 #include "ggs_z_pcgs_wave.hpp"
 #include "ggs_z_collapsed.hpp"
 #include "ggs_phi_poisson.hpp"
+#include "ggs_alias.hpp"
+#include "ggs_z_spalias.hpp"
 #include "ggs_loglik.hpp"
 #include "ggs_heldout.hpp"
 #include "ggs_exchange.hpp"
@@ -99,6 +101,13 @@ struct ggs_handle {
   double pa_t00 = 0;                                   // T_0[0]
   double *d_pa_table = nullptr;                        // [L][2L]
   unsigned long long *d_pa_acc = nullptr;              // [K][kPoissonAccStride]: the draw's integer totals
+  // scheme=spalias (ggs_alias.hpp, ggs_z_spalias.hpp): the pcgs model, the z step split into an alias draw and a sparse walk
+  bool spalias = false;
+  bool alias_stale = true;                             // Phi has changed since the tables were built
+  double *d_alias_ps = nullptr, *d_alias_tn = nullptr; // [V][K], [V]
+  int32_t *d_alias_a = nullptr;                        // [V][K]
+  int32_t alias_wpb = 0, alias_lds = 0, alias_blocks_per_cu = 0;
+  int32_t sp_cap = 0, sp_lds = 0, sp_waves_per_cu = 0;
   uint64_t *d_lcg = nullptr;                           // ggs_collapsed_serial_sweep: the java.util.Random state
   bool lcg_ready = false;
   int32_t hot_cap = 0, num_hot = 0, hot_pitch = 0, wave_lds = 0, ring_base = 0;
@@ -717,6 +726,24 @@ int phi_step_c(ggs_handle *h, bool accumulate_mean) {
   else hipLaunchKernelGGL(phi_repack_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   HIP_TRY(h, hipGetLastError());
   h->have_phi = true;
+  h->alias_stale = true;
+  return GGS_OK;
+}
+
+// scheme=spalias: the alias tables of the Phi now in d_phiT (ggs_alias.hpp), on the handle's stream.  Called wherever Phi
+// changes (the draws below, ggs_set_phi), inside the span ggs_get_timings counts as phi_ms.  With an exchange every rank
+// holds the whole Phi after the all-gather and builds all V words for itself: what a rank's shard contains changes
+// with the corpus, the tables' layout does not.
+int launch_alias_build(ggs_handle *h) {
+  if (!h->spalias) return GGS_OK;
+  AliasParams ap{};
+  ap.phiT = h->d_phiT; ap.alpha = h->d_alpha; ap.ps = h->d_alias_ps; ap.a = h->d_alias_a; ap.type_norm = h->d_alias_tn;
+  ap.V = h->V; ap.K = h->K; ap.Kp = h->Kp; ap.wpb = h->alias_wpb;
+  const int64_t groups = ((int64_t)h->V + h->alias_wpb - 1) / h->alias_wpb;
+  hipLaunchKernelGGL(alias_build_kernel, dim3((unsigned)std::min<int64_t>(groups, (int64_t)h->num_cus * h->alias_blocks_per_cu)), dim3(64), (size_t)h->alias_lds,
+                     h->stream, ap);
+  HIP_TRY(h, hipGetLastError());
+  h->alias_stale = false;
   return GGS_OK;
 }
 
@@ -733,13 +760,14 @@ int launch_phi(ggs_handle *h, bool initial, bool accumulate_mean, Events *E = nu
     // on different streams at once (they could not share the links anyway), whatever the transport does about that itself
     if ((rc = phi_join_halves(h)) || (rc = phi_step_g1(h))) return rc;
     if (E) HIP_TRY(h, hipEventRecord(E->x[2], h->stream));
-    return phi_step_c(h, accumulate_mean);
+    if ((rc = phi_step_c(h, accumulate_mean))) return rc;
+    return launch_alias_build(h);
   }
   if ((rc = launch_phi_slice(h, initial, h->d_n_wk, h->K, h->K, 0, h->d_phiT, h->Kp, h->d_mag, h->d_tot, h->d_n_k, accumulate_mean ? h->d_phi_mean : nullptr)))
     return rc;
   h->n_k_valid = true;
   h->have_phi = true;
-  return GGS_OK;
+  return launch_alias_build(h);
 }
 
 int launch_theta(ggs_handle *h, hipStream_t stream, double *dst, int32_t iteration, int64_t d0 = 0, int64_t d1 = -1, int32_t lds = 0, int32_t docs_per_block = 0) {
@@ -816,6 +844,16 @@ int launch_pcgs_z(ggs_handle *h) {
   pp.alpha = h->d_alpha; pp.phiT = h->d_phiT; pp.status = h->d_status;
   pp.num_docs = h->pcgs_order_len; pp.tok_base = h->tok_base; pp.seed = h->seed; pp.iteration = (uint32_t)h->iteration;   // the length of the (padded) order list
   pp.K = h->K; pp.Kp = h->Kp;
+  if (h->spalias) {                                    // one wave per document over the non-zero topics (ggs_z_spalias.hpp)
+    int rc;
+    if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
+    SpaliasParams sp{};
+    sp.b = pp; sp.ps = h->d_alias_ps; sp.a = h->d_alias_a; sp.type_norm = h->d_alias_tn; sp.cap = h->sp_cap; sp.margin_scale = h->margin_scale;
+    hipLaunchKernelGGL(spalias_wave_kernel, dim3((unsigned)std::min<int64_t>(h->pcgs_order_len, (int64_t)h->num_cus * h->sp_waves_per_cu)), dim3(64), (size_t)h->sp_lds,
+                       h->stream, sp);
+    HIP_TRY(h, hipGetLastError());
+    return GGS_OK;
+  }
   const int64_t groups = (h->pcgs_order_len + 63) / 64;
   const dim3 grid((unsigned)std::min<int64_t>(groups, (int64_t)h->num_cus * h->pcgs_waves_per_cu)), block(64);
   if (h->pcgs_wave) {
@@ -1412,6 +1450,9 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
   *out = nullptr;
   if (cfg->struct_size != (int32_t)sizeof(ggs_config)) return GGS_ERR_BAD_ARG;
   if (cfg->num_topics <= 0 || cfg->num_types <= 0 || !(cfg->beta > 0)) return GGS_ERR_BAD_ARG;
+  // scheme=spalias runs over the pcgs model only (polyaurn over the sparse z step is not provided): an argument error,
+  // answered before any device is asked for
+  if ((cfg->flags & GGS_FLAG_SPALIAS) && (cfg->flags & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN))) return GGS_ERR_BAD_ARG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device_id < 0 || cfg->device_id >= ndev) return GGS_ERR_HIP;
   ggs_handle *h = new (std::nothrow) ggs_handle();
@@ -1426,6 +1467,10 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     const int32_t L = cfg->alias_poisson_threshold == 0 ? 100 : cfg->alias_poisson_threshold;   // LDAConfiguration.java:44
     if (h->collapsed || L < 1 || L > kPoissonMaxThreshold) { delete h; return GGS_ERR_BAD_ARG; }
     h->polyaurn = true; h->flags |= GGS_FLAG_PCGS; h->pa_L = L;
+  }
+  if (h->flags & GGS_FLAG_SPALIAS) {                  // the pcgs model; the z step draws from the same conditional another way
+    if (h->K > kPcgsWaveMaxTopics) { delete h; return GGS_ERR_UNSUPPORTED; }
+    h->spalias = true; h->flags |= GGS_FLAG_PCGS;
   }
   h->phi_burn_in = cfg->phi_burn_in; h->phi_thin = cfg->phi_mean_thin > 0 ? cfg->phi_mean_thin : 1;
   if (const char *ab = debug_env("GGS_DEBUG_ABLATE")) h->ablate = std::atoi(ab);
@@ -1639,6 +1684,15 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
       hipMemset(h->d_n_k, 0, sizeof(int32_t) * h->K) != hipSuccess || hipMemset(h->d_status, 0, 16) != hipSuccess ||
       (h->d_phi_mean && hipMemset(h->d_phi_mean, 0, sizeof(double) * kv) != hipSuccess))
     return bail(GGS_ERR_HIP);
+  if (h->spalias) {
+    if ((rc = dev_alloc(h, &h->d_alias_ps, kv)) || (rc = dev_alloc(h, &h->d_alias_a, kv)) || (rc = dev_alloc(h, &h->d_alias_tn, (size_t)h->V))) return bail(rc);
+    h->alias_wpb = alias_words_per_block(h->K);
+    h->alias_lds = (int32_t)alias_lds_bytes(h->K, h->alias_wpb);
+    h->alias_blocks_per_cu = std::max(1, std::min(16, (kMaxLdsBytes - 2048) / ((h->alias_lds + 2047) / 2048 * 2048)));
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(alias_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(spalias_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess)
+      return bail(GGS_ERR_HIP);
+  }
   if (h->polyaurn) {
     std::vector<double> T;
     build_poisson_table(h->beta, h->pa_L, T);
@@ -1731,7 +1785,7 @@ void ggs_destroy(ggs_handle *h) {
                   h->d_heldout_spill, h->d_phi_own, h->d_phi_all0, h->d_phi_all1, h->d_mag_own, h->d_krank, h->d_kcol, h->d_lcg, h->d_chunk_doc1,
                   h->d_hseg_word, h->d_hseg_begin, h->d_hseg_end, h->d_sp_count, h->d_sp_cnt32, h->d_sp_all, h->d_sp_send, h->d_sp_recv, h->d_sp_wg_count,
                   h->d_sp_wg_off, h->d_ht_pack, h->d_h_docs, h->d_wt_pack, h->d_w_docs, h->d_warm_words, h->d_warm_meta, h->d_phiT32, h->d_replays,
-                  h->d_pa_table, h->d_pa_acc};
+                  h->d_pa_table, h->d_pa_acc, h->d_alias_ps, h->d_alias_a, h->d_alias_tn};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   exchange_free(h->xg);
@@ -1858,6 +1912,14 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
     // the lane-per-document kernels keep the counts as int16: a longer document sends the corpus to the wave-per-document kernel
     h->pcgs_wave = h->pcgs_wave_forced || longest > kPcgsMaxDocLen;
     if (h->pcgs_wave && !h->pcgs_wave_nb) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=pcgs: a document of 32768 tokens or more with more than 4096 topics");
+    if (h->spalias) {
+      // the list of a document's non-zero topics holds at most min(K, its length) entries; the resident waves are what LDS allows,
+      // at most the CU's 32
+      h->sp_cap = (int32_t)std::max<int64_t>(1, std::min<int64_t>(h->K, longest));
+      h->sp_lds = (int32_t)spalias_lds_bytes(h->K, h->sp_cap);
+      h->sp_waves_per_cu = std::max(1, std::min(32, (kMaxLdsBytes - 2048) / ((h->sp_lds + 2047) / 2048 * 2048)));
+      if (const char *e = debug_env("GGS_DEBUG_SPALIAS_WPC")) h->sp_waves_per_cu = std::max(1, std::min(h->sp_waves_per_cu, std::atoi(e)));
+    }
     std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return doc_ptr[a + 1] - doc_ptr[a] > doc_ptr[b + 1] - doc_ptr[b]; });
     // A wave takes the groups w, w + W, ... of this list (W = the resident waves).  With between one and two rounds of
     // groups (the benchmark corpus: 1 563 groups for 1 024 waves) the plain order would give the waves of the 539
@@ -2414,7 +2476,7 @@ int group_phi(ggs_handle **hs, int32_t n, bool initial, bool in_sweep) {
     return rc;
   for (int32_t i = 0; i < n; ++i) {
     ggs_handle *h = hs[i];
-    if ((rc = bind_device(h)) || (rc = phi_step_c(h, acc[(size_t)i] != 0))) return rc;
+    if ((rc = bind_device(h)) || (rc = phi_step_c(h, acc[(size_t)i] != 0)) || (rc = launch_alias_build(h))) return rc;
     if (in_sweep) {
       HIP_TRY(h, hipEventRecord(h->evs[h->ev_head].e[5], h->stream));
       if (acc[(size_t)i]) h->n_sampled_phi++;
@@ -2611,8 +2673,25 @@ int ggs_set_phi(ggs_handle *h, const double *phi) {
   HIP_TRY(h, hipGetLastError());
   // UPLDA:1897-1902: `if (savePhiMeans()) phiMean = new double[numTopics][numTypes]` -- the running sum restarts, noSampledPhi keeps counting
   if (h->d_phi_mean) HIP_TRY(h, hipMemsetAsync(h->d_phi_mean, 0, kv * sizeof(double), h->stream));
+  h->alias_stale = true;
+  if ((rc = launch_alias_build(h))) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->have_phi = true;
+  return GGS_OK;
+}
+
+int ggs_get_alias_tables(ggs_handle *h, double *ps, int32_t *a, double *type_norm) {
+  if (!h) return GGS_ERR_BAD_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (!h->spalias) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS");
+  if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
+  if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
+  const size_t kv = (size_t)h->K * h->V;
+  if (ps) HIP_TRY(h, hipMemcpyAsync(ps, h->d_alias_ps, kv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (a) HIP_TRY(h, hipMemcpyAsync(a, h->d_alias_a, kv * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (type_norm) HIP_TRY(h, hipMemcpyAsync(type_norm, h->d_alias_tn, (size_t)h->V * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
   return GGS_OK;
 }
 int ggs_get_phi_mean(ggs_handle *h, double *phi_mean, int32_t *n_sampled) {
@@ -2921,7 +3000,7 @@ int ggs_get_z_form(ggs_handle *h, int32_t *kernel, int32_t *form, int32_t *calib
   if (!h) return GGS_ERR_BAD_ARG;
   const bool pcgs = (h->flags & GGS_FLAG_PCGS) != 0;
   const bool splittable = !pcgs && h->z_sliced && h->Cs > h->Cc && h->Cc > 0;
-  if (kernel) *kernel = pcgs ? (h->pcgs_wave ? 5 : 4) : h->z_sliced ? 1 : h->z_stream ? (h->z_two_pass ? 3 : 2) : 0;
+  if (kernel) *kernel = h->spalias ? 6 : pcgs ? (h->pcgs_wave ? 5 : 4) : h->z_sliced ? 1 : h->z_stream ? (h->z_two_pass ? 3 : 2) : 0;
   if (form) *form = (!pcgs && h->z_sliced) ? (splittable && h->z_split ? 1 : 2) : 0;
   if (calibrated) *calibrated = (splittable && h->z_split_tried && !h->z_split_forced && h->z_split_allowed) ? 1 : 0;
   return GGS_OK;
@@ -3001,6 +3080,28 @@ int ggs_debug_poisson(int32_t device_id, double beta, int32_t threshold, uint64_
   if (hipGetLastError() != hipSuccess || hipMemcpy(out, dou, n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&st, dst, 4, hipMemcpyDeviceToHost) != hipSuccess)
     return GGS_ERR_HIP;
   return st ? GGS_ERR_RNG_EXHAUSTED : GGS_OK;
+}
+
+int ggs_debug_alias(int32_t device_id, int32_t V, int32_t K, const double *phi, const double *alpha, double *ps, int32_t *a, double *type_norm) {
+  if (V <= 0 || K <= 0 || K > kPcgsWaveMaxTopics || !phi || !alpha || !ps || !a || !type_norm || hipSetDevice(device_id) != hipSuccess) return GGS_ERR_BAD_ARG;
+  const size_t kv = (size_t)K * V;
+  std::vector<double> phiT(kv);                         // [V][K], as the handle keeps it (pitch K here)
+  for (int32_t k = 0; k < K; ++k)
+    for (int32_t v = 0; v < V; ++v) phiT[(size_t)v * K + k] = phi[(size_t)k * V + v];
+  TmpDev t;
+  auto *dphi = static_cast<double *>(t.get(kv * 8)); auto *dal = static_cast<double *>(t.get((size_t)K * 8));
+  auto *dps = static_cast<double *>(t.get(kv * 8)); auto *da = static_cast<int32_t *>(t.get(kv * 4)); auto *dtn = static_cast<double *>(t.get((size_t)V * 8));
+  if (!dphi || !dal || !dps || !da || !dtn) return GGS_ERR_HIP;
+  if (hipMemcpy(dphi, phiT.data(), kv * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dal, alpha, (size_t)K * 8, hipMemcpyHostToDevice) != hipSuccess)
+    return GGS_ERR_HIP;
+  AliasParams ap{};
+  ap.phiT = dphi; ap.alpha = dal; ap.ps = dps; ap.a = da; ap.type_norm = dtn; ap.V = V; ap.K = K; ap.Kp = K; ap.wpb = alias_words_per_block(K);
+  if (hipFuncSetAttribute(reinterpret_cast<const void *>(alias_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess) return GGS_ERR_HIP;
+  hipLaunchKernelGGL(alias_build_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)V + ap.wpb - 1) / ap.wpb, 4096)), dim3(64), alias_lds_bytes(K, ap.wpb), nullptr, ap);
+  if (hipGetLastError() != hipSuccess || hipMemcpy(ps, dps, kv * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(a, da, kv * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(type_norm, dtn, (size_t)V * 8, hipMemcpyDeviceToHost) != hipSuccess)
+    return GGS_ERR_HIP;
+  return GGS_OK;
 }
 
 int ggs_debug_column_sum_guided(int32_t device_id, int32_t V, int32_t K, const double *x, const int32_t *counts, double beta, const double *guess,

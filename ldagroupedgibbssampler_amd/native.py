@@ -8,7 +8,7 @@ from . import _lib
 OK = 0
 ERR_NEGATIVE_COUNT, ERR_INVALID_TOPIC, ERR_RNG_EXHAUSTED, ERR_BAD_ARG = 1, 2, 3, 4
 ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_INVARIANT = 5, 6, 7, 8
-FLAG_PARANOID, FLAG_SAVE_PHI_MEAN, FLAG_PCGS, FLAG_COLLAPSED, FLAG_POLYAURN = 1, 2, 4, 8, 16
+FLAG_PARANOID, FLAG_SAVE_PHI_MEAN, FLAG_PCGS, FLAG_COLLAPSED, FLAG_POLYAURN, FLAG_SPALIAS = 1, 2, 4, 8, 16, 32
 PURPOSE_Z, PURPOSE_THETA, PURPOSE_PHI, PURPOSE_INIT_PHI = 1, 2, 3, 4
 
 
@@ -255,6 +255,12 @@ class GGSHandle:
         self._chk(self._L.ggs_get_phi_mean(self._h, _dp(out), C.byref(n)))
         return (out, n.value) if n.value else (None, 0)
 
+    def alias_tables(self):
+        """scheme=spalias: the alias tables of the current Phi, (ps [V][K], a [V][K], type_norm [V])."""
+        ps, a, tn = np.empty((self.V, self.K), np.float64), np.empty((self.V, self.K), np.int32), np.empty(self.V, np.float64)
+        self._chk(self._L.ggs_get_alias_tables(self._h, _dp(ps), _ip(a), _dp(tn)))
+        return ps, a, tn
+
     def get_theta(self, doc_begin=0, doc_end=None):
         doc_end = self.D if doc_end is None else doc_end
         out = np.empty((doc_end - doc_begin, self.K), np.float64)
@@ -322,7 +328,8 @@ class GGSHandle:
 
 
 Z_KERNEL_NAMES = {0: "z_kernel (whole-row tiles)", 1: "z_sliced_kernel + z_hot_kernel (score registers)", 2: "z_stream1_kernel (one pass)",
-                  3: "z_stream_kernel (two passes)", 4: "pcgs_sliced_kernel (lane per document)", 5: "pcgs_wave_kernel (wave per document)"}
+                  3: "z_stream_kernel (two passes)", 4: "pcgs_sliced_kernel (lane per document)", 5: "pcgs_wave_kernel (wave per document)",
+                  6: "spalias_wave_kernel (wave per document)"}
 
 
 class GGSGroup:
@@ -433,6 +440,19 @@ def debug_poisson(counts, beta, threshold, seed, iteration, purpose, elem0, devi
     if rc:
         raise GGSError(rc, "ggs_debug_poisson")
     return out
+
+
+def debug_alias(phi, alpha, device_id=0):
+    """scheme=spalias's alias tables of phi [K][V] under alpha, built by the product kernel: (ps [V][K], a [V][K], type_norm [V])."""
+    L = _lib.load()
+    phi = np.ascontiguousarray(phi, np.float64)
+    K, V = phi.shape
+    alpha = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, np.float64), (K,)))
+    ps, a, tn = np.empty((V, K), np.float64), np.empty((V, K), np.int32), np.empty(V, np.float64)
+    rc = L.ggs_debug_alias(device_id, V, K, _dp(phi), _dp(alpha), _dp(ps), _ip(a), _dp(tn))
+    if rc:
+        raise GGSError(rc, "ggs_debug_alias")
+    return ps, a, tn
 
 
 def debug_column_sum(x=None, counts=None, beta=0.0, device_id=0):

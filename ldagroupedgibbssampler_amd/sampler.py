@@ -403,6 +403,20 @@ class PolyaUrnSpaliasLDA(LDAPartiallyCollapsedGibbsSampler):
         raise NotImplementedError("scheme=polyaurn never draws theta; use getThetaEstimate() (UPLDA:716-720 does the same)")
 
 
+class SpaliasUncollapsedParallelLDA(LDAPartiallyCollapsedGibbsSampler):
+    """scheme=spalias (topics/SpaliasUncollapsedParallelLDA.java, ParallelLDA.java:439-442): the pcgs model and driver; the z
+    step draws from the pcgs conditional split into alpha_k * phi[k][w] (a Walker alias table per word, rebuilt with every
+    Phi) and n_dk * phi[k][w] (a walk over the document's non-zero topics): O(nnz_d) per token instead of O(K)."""
+    _scheme_flags = native.FLAG_SPALIAS
+
+    def getTheta(self):
+        raise NotImplementedError("scheme=spalias never draws theta; use getThetaEstimate() (UPLDA:716-720 does the same)")
+
+    def getAliasTables(self):
+        """(ps [V][K], a [V][K], typeNorm [V]) of the current Phi"""
+        return self._h.alias_tables()
+
+
 class SerialCollapsedLDA(LDAGroupedGibbsSampler):
     """scheme=collapsed (topics/SerialCollapsedLDA.java; the conditional it samples from is sampleTopicsForOneDoc,
     MSLDA:158-226).  `schedule`:
@@ -438,7 +452,7 @@ class SerialCollapsedLDA(LDAGroupedGibbsSampler):
 
 
 def create_model(config, scheme=None):
-    """The `case "ggs"` / `case "pcgs"` / `case "collapsed"` / `case "polyaurn"` of tui/ParallelLDA.createModel
+    """The `case "ggs"` / `case "pcgs"` / `case "collapsed"` / `case "polyaurn"` / `case "spalias"` of tui/ParallelLDA.createModel
     (ParallelLDA.java:401-490)."""
     scheme = scheme or config.scheme
     if scheme == "ggs":
@@ -449,4 +463,6 @@ def create_model(config, scheme=None):
         return SerialCollapsedLDA(config)
     if scheme == "polyaurn":
         return PolyaUrnSpaliasLDA(config)
-    raise ValueError("scheme %r is not provided by this build (only the ggs, pcgs, collapsed and polyaurn z loops are in scope)" % scheme)
+    if scheme == "spalias":
+        return SpaliasUncollapsedParallelLDA(config)
+    raise ValueError("scheme %r is not provided by this build (only the ggs, pcgs, collapsed, polyaurn and spalias z loops are in scope)" % scheme)
