@@ -1,6 +1,6 @@
 // ggs_api.hip -- host side of libggs_hip.so: handle, launches, C-ABI (include/ggs_hip.h).
 //
-// Build (see build.py): hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -shared
+// Build (see Makefile): hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -shared
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +25,7 @@
 #include "ggs_loglik.hpp"
 #include "ggs_heldout.hpp"
 #include "ggs_exchange.hpp"
+#include "ggs_corpus_lists.hpp"
 
 using namespace ggs;
 
@@ -32,13 +33,75 @@ namespace {
 
 // The GGS_DEBUG_* variables select kernels, scale proof margins and switch overlaps off: experiments and tests.  A
 // production process must not pick one up by accident, so they are only read when GGS_DEBUG=1 is set as well.
+// DESIGN.md section 8 lists them all.
 const char *debug_env(const char *name) {
   static const bool enabled = [] { const char *e = std::getenv("GGS_DEBUG"); return e && std::atoi(e) == 1; }();
   return enabled ? std::getenv(name) : nullptr;
 }
 
+// The knobs ggs_create reads, all at its top: what the launch planner takes instead of an environment, and the handle's
+// own switches.  (The knobs of other entry points are read there: the exchange's at its set-up, GGS_DEBUG_SPALIAS_WPC at
+// ggs_set_corpus, GGS_DEBUG_PHICOLS at a Phi draw, GGS_DEBUG_HELDOUT_CELLS at every held-out call.)
+struct Knob {
+  bool set = false;
+  int v = 0;
+  double f = 0;
+  explicit Knob(const char *name) { if (const char *e = debug_env(name)) { set = true; v = std::atoi(e); f = std::atof(e); } }
+  bool is(int x) const { return set && v == x; }
+};
+struct Knobs {
+  // the planner's
+  Knob zkernel{"GGS_DEBUG_ZKERNEL"}, group{"GGS_DEBUG_GROUP"}, regck{"GGS_DEBUG_REGCK"}, tworows{"GGS_DEBUG_TWOROWS"}, wpc{"GGS_DEBUG_WPC"};
+  Knob phi64{"GGS_DEBUG_PHI64"}, split{"GGS_DEBUG_SPLIT"}, hot{"GGS_DEBUG_HOT"}, tile{"GGS_DEBUG_TILE"};
+  Knob warm{"GGS_DEBUG_WARM"}, warm_rows{"GGS_DEBUG_WARM_ROWS"}, warm_fill{"GGS_DEBUG_WARM_FILL"}, warm_cpw{"GGS_DEBUG_WARM_CPW"};
+  Knob theta_b{"GGS_DEBUG_THETA_B"}, theta_wgs{"GGS_DEBUG_THETA_WGS"}, zparts{"GGS_DEBUG_ZPARTS"}, beside{"GGS_DEBUG_BESIDE"};
+  Knob pcgs_wave{"GGS_DEBUG_PCGS_WAVE"}, pcgs_stream{"GGS_DEBUG_PCGS_STREAM"};
+  // the handle's
+  Knob margin{"GGS_DEBUG_MARGIN"}, replays{"GGS_DEBUG_REPLAYS"}, chain{"GGS_DEBUG_CHAIN"}, guided{"GGS_DEBUG_GUIDED"};
+  Knob no_overlap{"GGS_DEBUG_NO_OVERLAP"}, theta_main{"GGS_DEBUG_THETA_MAIN"}, gamma_queue{"GGS_DEBUG_GAMMA_QUEUE"};
+};
+
 constexpr int kThetaBlock = 256;
-constexpr int kMaxLdsBytes = 160 * 1024;
+
+// One kernel as a handle launches it: the function, its workgroup, its dynamic LDS and the workgroups per CU of its
+// persistent grid.  The table kernels' LDS is given without table rows (they differ by corpus).
+struct KernelLaunch {
+  const void *fn = nullptr;
+  int block = 64, lds = 0, per_cu = 0;
+};
+// The launches a handle can make and the few numbers the corpus step needs: decided once, by plan_launches() from
+// (K, V, flags, CUs, knobs).  What depends on the corpus (a long document, D against V, the timed split) chooses
+// BETWEEN these entries.
+struct LaunchPlan {
+  int32_t kernel = 0;                  // the ggs z kernel, as ggs_get_z_form numbers it: 0 whole-row tiles, 1 score registers (sliced), 2 streaming in one pass, 3 in two
+  bool sliced() const { return kernel == 1; }
+  bool stream() const { return kernel >= 2; }
+  KernelLaunch z;                      // the tile kernel or the streaming kernel
+  int32_t tile_tokens = 64;            // tokens of a chunk of its table at most
+  bool two_rows = false;               // streaming: two theta rows per wave, chunks may run across one document boundary (K <= 512)
+  // sliced: the cold chunks' kernel (from phiT32 unless GGS_DEBUG_PHI64=1; in the fused form it takes the hot chunks too, the
+  // table behind its rings), the hot chunks' and the warm tiers' table kernels
+  KernelLaunch cold, hot, warm;
+  bool f32 = false;
+  bool split = true, split_forced = false;   // GGS_DEBUG_SPLIT=0: the fused form only; 2: the split form without the timed comparison
+  int32_t wave_lds = 0, ring_base = 0, hot_wave_lds = 0, warm_wave_lds = 0, hot_pitch = 0, Kp32 = 0;   // ZParams of the three
+  int32_t hot_cap = 0, warm_cap = 0, warm_docs = 0;   // rows of the hot table, of a warm tier's table; documents per warm chunk
+  // What a tier must bring (measured on the benchmark corpus and its halves, ggs_corpus_lists.hpp): chunks at least 40 % full, at
+  // least 3 of them per resident wave, three tiers at most -- GGS_DEBUG_WARM / GGS_DEBUG_WARM_FILL / GGS_DEBUG_WARM_CPW
+  int32_t warm_tiers_max = 3, warm_min_fill_pct = 40, warm_min_chunks_per_wave = 3;
+  // The theta draw and the z waves beside it, in the two configurations of the K > 192 path: with the z step cut into
+  // parts of consecutive documents (the NEXT theta of a part is drawn on the side stream while the following parts are
+  // sampled: the streaming z kernel waits on memory, the theta draw on the VALU) or in one piece.  Chosen per corpus.
+  struct ZCfg { int32_t parts = 1, z_per_cu = 0, theta_docs = 0, theta_lds = 0, theta_lds_beside_z = 0; } cfg_plain, cfg_parts;
+  bool parts_forced = false;
+  KernelLaunch theta;                  // its LDS and documents per workgroup: the configuration's, or ...
+  int32_t theta_docs_main = 0, theta_lds_main = 0;   // ... where the theta draw is the critical leg (theta_main)
+  // scheme pcgs / collapsed / polyaurn: a lane or a wave per document; spalias: the table build and the sparse walk (LDS per corpus)
+  KernelLaunch lane, wave, alias, spalias, serial;
+  bool wave_forced = false;            // ... because of K; otherwise per corpus (a document of 32 768 tokens or more)
+  int32_t alias_wpb = 0;
+  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &serial}; }
+};
 
 // The phase events of one sweep.  Sweeps are settled (waited for, checked, timed) in batches, so a ring of them:
 // sweep i records into slot i % kEvRing; the theta drawn ahead for sweep i + 1 records th0/th1 of THAT slot.
@@ -63,19 +126,12 @@ struct ggs_handle {
   int32_t flags = 0, phi_burn_in = 0, phi_thin = 1;
   int32_t iteration = 0;
   int32_t n_sampled_phi = 0;
-  int32_t ablate = 0;   // GGS_DEBUG_ABLATE: timing-only experiments, results are wrong on purpose
 
   int64_t D = 0, N = 0, C = 0, S = 0, doc_base = 0, tok_base = 0, global_tokens = -1;
   bool have_corpus = false, have_phi = false, in_sweep = false;
-  int32_t theta_lds_main = 0, theta_b_main = 0;       // the theta draw as the critical leg (theta_main): workgroup size and LDS request
-  int32_t theta_docs_per_block = 0, theta_lds = 0, z_lds = 0, z_tile_tokens = 0, z_waves_per_cu = 0, num_cus = 0;
-  bool z_sliced = false;   // scores-in-registers kernel (K <= kSlicedMaxTopics)
-  bool z_f32 = false;      // ... its cold chunks scored from phiT32 (GGS_DEBUG_PHI64=1: from phiT, the fp64 path)
-  bool z_stream = false;   // streaming kernel (K > kSlicedMaxTopics): rows once (z_stream1_kernel) ...
-  bool z_two_pass = false; // ... or twice (z_stream_kernel, GGS_DEBUG_ZKERNEL=3: the cross-check)
-  bool z_regck = false;    // z_stream1_kernel keeps its checkpoints in registers (K <= 1024)
-  int32_t z_group = 4;     // ... one per z_group slices
-  bool z_two_rows = false; // z_stream1_kernel with two theta rows per wave: chunks may run across one document boundary (K <= 512)
+  int32_t num_cus = 0;
+  LaunchPlan plan;                                     // every launch this handle can make (plan_launches, at ggs_create)
+  const LaunchPlan::ZCfg *cfg = nullptr;               // of the current corpus: plan.cfg_parts or plan.cfg_plain
   int32_t *d_chunk_doc1 = nullptr;
   double margin_scale = 1.0;   // GGS_DEBUG_MARGIN, clamped to >= 1: scales the fp64 certainty margins (tests force the exact replays)
   double margin_scale32 = 1.0; // ... clamped to >= 0: z_sliced32_kernel's margin (below 1 only to show the tests can fail)
@@ -84,16 +140,12 @@ struct ggs_handle {
   // device buffers
   int64_t *d_doc_ptr = nullptr, *d_chunk_start = nullptr;
   int32_t *d_tok = nullptr, *d_z = nullptr, *d_chunk_doc = nullptr, *d_chunk_len = nullptr;
-  // sliced z kernel (ggs_z_sliced.hpp): its chunk lists (cold chunks first), the hot-word table's word ids, LDS layout
+  // sliced z kernel (ggs_z_sliced.hpp): its chunk lists (cold chunks first), the hot-word table's word ids
   int32_t *d_ct_tok = nullptr, *d_ct_idx = nullptr, *d_ct_ip = nullptr, *d_c_docs = nullptr, *d_hot_words = nullptr;
   int64_t Cs = 0, Cc = 0;                              // sliced chunks in all, cold ones
   int32_t *d_order = nullptr;                          // scheme=pcgs: local documents, longest first
-  int32_t pcgs_lds = 0, pcgs_waves_per_cu = 0, max_doc_len = 0;
   int64_t pcgs_order_len = 0;                          // entries of d_order (documents, or the padded two-round list)
-  bool pcgs_sliced = false;                            // K <= 192: scores in registers, one pass over the rows per step
-  bool pcgs_wave = false;                              // wide rows or long documents: one wave per document (ggs_z_pcgs_wave.hpp)
-  bool pcgs_wave_forced = false;                       // ... because of K; otherwise decided per corpus (a document of 32 768 tokens or more)
-  int32_t pcgs_wave_nb = 0, pcgs_wave_lds = 0, pcgs_wave_waves_per_cu = 0;
+  bool pcgs_wave = false;                              // of the current corpus: plan.wave (wide rows, or a document of 32 768 tokens or more) instead of plan.lane
   bool collapsed = false;                              // scheme=collapsed: the pcgs machinery over psi = (beta + n_wk)/(betaSum + n_k)
   // scheme=polyaurn (ggs_phi_poisson.hpp): the pcgs z loop with its two uniform-draw rules, Phi drawn as Poisson counts
   bool polyaurn = false;
@@ -106,11 +158,11 @@ struct ggs_handle {
   bool alias_stale = true;                             // Phi has changed since the tables were built
   double *d_alias_ps = nullptr, *d_alias_tn = nullptr; // [V][K], [V]
   int32_t *d_alias_a = nullptr;                        // [V][K]
-  int32_t alias_wpb = 0, alias_lds = 0, alias_blocks_per_cu = 0;
-  int32_t sp_cap = 0, sp_lds = 0, sp_waves_per_cu = 0;
+  KernelLaunch sp_z;                                   // of the current corpus: plan.spalias with the LDS of lists of sp_cap entries
+  int32_t sp_cap = 0;
   uint64_t *d_lcg = nullptr;                           // ggs_collapsed_serial_sweep: the java.util.Random state
   bool lcg_ready = false;
-  int32_t hot_cap = 0, num_hot = 0, hot_pitch = 0, wave_lds = 0, ring_base = 0;
+  int32_t num_hot = 0;
   int32_t *d_perm = nullptr, *d_inv_perm = nullptr, *d_zw = nullptr, *d_seg_word = nullptr, *d_seg_begin = nullptr;
   // theta of the current / last z step, and the buffer the next iteration's theta is drawn into
   // on the side stream while this iteration's counts and Phi are computed (theta_{t+1} depends
@@ -119,7 +171,6 @@ struct ggs_handle {
   hipStream_t side = nullptr;
   hipStream_t side_hot = nullptr;                      // z_hot_kernel runs here, beside z_sliced_kernel on the main stream
   hipEvent_t ev_hot_fork = nullptr, ev_hot_join = nullptr;
-  hipEvent_t ev_theta_tail = nullptr;                  // GGS_DEBUG_THETA_TAIL_PCT (timing experiment), created on first use
   // Whole sweeps on one GPU (ggs_sweep, K <= 160): the next theta is the LONGER of the two legs behind the z step (0.61 ms
   // against 0.50 for the counts and the Phi chain), and a dependency across streams takes 10-25 us to resolve -- so the
   // long leg stays on the handle's stream, directly between two z steps, and the short one (count rebuild + Phi chain)
@@ -128,34 +179,19 @@ struct ggs_handle {
   bool whole_sweep = false;                            // inside ggs_sweep: z phase and Phi phase are enqueued back to back
   hipEvent_t hot_fork_from = nullptr;                  // an event already on the handle's stream that the hot kernel's stream may wait for instead of a fork event of its own
   hipEvent_t ev_chain_done = nullptr;
-  bool z_split = true;                                 // GGS_DEBUG_SPLIT=0: one kernel takes cold and hot chunks in turn
-  bool z_split_allowed = true, z_split_forced = false, z_split_tried = false;  // the first z step of a corpus times both forms and keeps the faster
-  int32_t hot_wave_lds = 0;
-  // the warm tiers (z_warm_kernel): tables of the words next in frequency after the hot table's, chunks of up to warm_docs documents
-  int32_t warm_docs = 0, warm_wave_lds = 0, warm_cap = 0;   // LDS layout: theta rows per wave; rows a tier's table may have
-  // What a tier must bring (measured on the benchmark corpus and its halves, ggs_set_corpus): chunks at least 40 % full, at
-  // least 3 of them per resident wave, three tiers at most -- GGS_DEBUG_WARM / GGS_DEBUG_WARM_FILL / GGS_DEBUG_WARM_CPW
-  int32_t warm_tiers_max = 3, warm_min_fill_pct = 40, warm_min_chunks_per_wave = 3;
+  bool z_split = true, z_split_tried = false;          // of the current corpus: cold and hot chunks beside each other; the first z step times both forms and keeps the faster
+  // the warm tiers (z_warm_kernel): tables of the words next in frequency after the hot table's, chunks of up to plan.warm_docs documents
   int32_t warm_tiers = 0, num_warm = 0, warm_rows_max = 0;  // of the current corpus: tiers kept, their words in all, the largest table
   int64_t Cw = 0, warm_chunks_max = 0;                      // warm chunks in all, of the largest tier
   int32_t *d_wt_pack = nullptr, *d_w_docs = nullptr, *d_warm_words = nullptr;   // d_wt_pack: four int32 per lane (ZParams::wt_pack)
   int32_t *d_ht_pack = nullptr, *d_h_docs = nullptr;        // the hot chunks in the same packed form (z_hot_kernel)
   int64_t *d_warm_meta = nullptr;
   bool overlap_theta = true;
-  // K > 192: the z step is cut into parts of consecutive documents and the NEXT iteration's theta of a part is drawn
-  // (side stream) while the following parts are still being sampled: the streaming z kernel waits on memory, the theta
-  // draw on the VALU.  The last part's theta runs beside the Phi phase as before.
-  int32_t z_parts = 1, theta_lds_beside_z = 0;
-  // the two launch configurations of the K > 192 path, chosen per corpus (ggs_set_corpus): with the z step cut into parts
-  // (theta workgroups beside the z waves) or in one piece
-  struct ZCfg { int32_t parts = 1, z_waves_per_cu = 0, theta_docs_per_block = 0, theta_lds = 0, theta_lds_beside_z = 0; } cfg_plain, cfg_parts;
-  bool z_parts_forced = false;
   int32_t gamma_queue_cap = 1 << 20;   // GGS_DEBUG_GAMMA_QUEUE: a tiny queue sends the leftovers of the first try down the on-the-spot path
-  std::vector<int64_t> part_doc, part_chunk;           // [z_parts + 1] boundaries
+  std::vector<int64_t> part_doc, part_chunk;           // [parts + 1] boundaries of the z step's parts (plan.cfg_parts; the last part's theta runs beside the Phi phase)
   hipEvent_t ev_part[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int64_t theta_ahead_iter = INT64_MIN;     // iteration the side-stream theta was drawn for, or none
-  float *d_phiT32 = nullptr;                           // the float32 shadow of phiT the cold chunks gather (z_f32)
-  int32_t Kp32 = 0;
+  float *d_phiT32 = nullptr;                           // the float32 shadow of phiT the cold chunks gather (plan.f32), rows of plan.Kp32
   unsigned long long *d_replays = nullptr;             // GGS_DEBUG_REPLAYS: tokens z_sliced_kernel<KMAX, true> replayed, and its launches
   int64_t z_f32_launches = 0;
   double *d_alpha = nullptr, *d_theta = nullptr, *d_phiT = nullptr, *d_mag = nullptr, *d_tot = nullptr, *d_phi_mean = nullptr;
@@ -227,6 +263,7 @@ struct ggs_handle {
   bool n_k_valid = false;                              // d_n_k follows d_n_wk
   std::vector<ggs_handle *> group;                     // ggs_group_create: the handles of the group, in rank order (rank 0 only)
 
+  std::vector<void **> owned;                          // every device buffer dev_alloc has filled: what ggs_destroy frees
   Events evs[kEvRing];
   int ev_head = 0, ev_pending = 0;                     // slot of the sweep in progress; sweeps enqueued but not settled
   ggs_timings tm{};
@@ -252,11 +289,32 @@ int bind_device(ggs_handle *h) {
   return GGS_OK;
 }
 
+// Every device buffer of a handle is allocated here and recorded, so that ggs_destroy frees it without a list of its own.
 template <typename T>
 int dev_alloc(ggs_handle *h, T **p, size_t count) {
+  void **slot = reinterpret_cast<void **>(p);
+  if (std::find(h->owned.begin(), h->owned.end(), slot) == h->owned.end()) h->owned.push_back(slot);
   if (*p) { (void)hipFree(*p); *p = nullptr; }
-  HIP_TRY(h, hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)));
+  HIP_TRY(h, hipMalloc(slot, std::max<size_t>(count, 1) * sizeof(T)));
   return GGS_OK;
+}
+// ... and filled from the host (on the null stream)
+template <typename T>
+int upload(ggs_handle *h, T **p, const T *src, size_t count) {
+  const int rc = dev_alloc(h, p, count);
+  if (rc) return rc;
+  if (count) HIP_TRY(h, hipMemcpy(*p, src, sizeof(T) * count, hipMemcpyHostToDevice));
+  return GGS_OK;
+}
+template <typename T>
+int upload(ggs_handle *h, T **p, const std::vector<T> &v) { return upload(h, p, v.data(), v.size()); }
+
+// A plan entry on `st` over `items` work items, one per wave: the grid is persistent -- the workgroups that stay resident
+// (CUs x per_cu), fewer where the items do not fill them -- and strides the rest.  `table_lds`: the rows of a Phi table.
+hipError_t launch(const ggs_handle *h, const KernelLaunch &l, int64_t items, void **args, hipStream_t st, int table_lds = 0) {
+  const int waves = l.block / 64;
+  const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((items + waves - 1) / waves, (int64_t)h->num_cus * l.per_cu));
+  return hipLaunchKernel(l.fn, dim3((unsigned)grid), dim3((unsigned)l.block), args, (size_t)(l.lds + table_lds), st);
 }
 
 // scheme=polyaurn: the inverse-CDF tables of the Poisson draws with c < L (ggs_phi_poisson.hpp), row c for lambda = beta + c:
@@ -646,7 +704,7 @@ int launch_phi_slice(ggs_handle *h, bool initial, const int32_t *cnt, int32_t cn
     if ((rc = phi_slice_poisson(h, initial, cnt, cnt_pitch, Ks, k0, out, out_pitch, 0, h->sum_nseg, true)) || (rc = phi_slice_poisson_totals(h, Ks, tot, n_k)))
       return rc;
     hipLaunchKernelGGL(phi_normalise_polyaurn_kernel, dim3(grid_for((int64_t)Ks * h->V, 256, 2)), dim3(256), 0, h->stream, out, tot, Ks, out_pitch, h->V,
-                       phi_mean, out == h->d_phiT ? h->d_phiT32 : nullptr, h->Kp32);
+                       phi_mean, out == h->d_phiT ? h->d_phiT32 : nullptr, h->plan.Kp32);
     HIP_TRY(h, hipGetLastError());
     return GGS_OK;
   }
@@ -654,7 +712,7 @@ int launch_phi_slice(ggs_handle *h, bool initial, const int32_t *cnt, int32_t cn
       (rc = phi_slice_total(h, out, out_pitch, Ks, tot)))
     return rc;
   hipLaunchKernelGGL(phi_normalise_kernel, dim3(grid_for((int64_t)Ks * h->V, 256, 2)), dim3(256), 0, h->stream, out, tot, Ks, out_pitch, h->V, phi_mean,
-                     out == h->d_phiT ? h->d_phiT32 : nullptr, h->Kp32);
+                     out == h->d_phiT ? h->d_phiT32 : nullptr, h->plan.Kp32);
   HIP_TRY(h, hipGetLastError());
   return GGS_OK;
 }
@@ -721,7 +779,7 @@ int phi_step_c(ggs_handle *h, bool accumulate_mean) {
   rp.all0 = h->d_phi_all0; rp.all1 = h->d_phi_all1; rp.krank = h->d_krank; rp.kcol = h->d_kcol; rp.phiT = h->d_phiT;
   rp.phi_mean = accumulate_mean ? h->d_phi_mean : nullptr;
   rp.c0 = (int64_t)half0_elems(h); rp.c1 = (int64_t)half1_elems(h); rp.K = h->K; rp.Kp = h->Kp; rp.V = h->V; rp.Ksm = h->Ksm; rp.v_split = h->v_split;
-  rp.phiT32 = h->d_phiT32; rp.Kp32 = h->Kp32;
+  rp.phiT32 = h->d_phiT32; rp.Kp32 = h->plan.Kp32;
   if (h->polyaurn) hipLaunchKernelGGL(phi_repack_polyaurn_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   else hipLaunchKernelGGL(phi_repack_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   HIP_TRY(h, hipGetLastError());
@@ -738,11 +796,9 @@ int launch_alias_build(ggs_handle *h) {
   if (!h->spalias) return GGS_OK;
   AliasParams ap{};
   ap.phiT = h->d_phiT; ap.alpha = h->d_alpha; ap.ps = h->d_alias_ps; ap.a = h->d_alias_a; ap.type_norm = h->d_alias_tn;
-  ap.V = h->V; ap.K = h->K; ap.Kp = h->Kp; ap.wpb = h->alias_wpb;
-  const int64_t groups = ((int64_t)h->V + h->alias_wpb - 1) / h->alias_wpb;
-  hipLaunchKernelGGL(alias_build_kernel, dim3((unsigned)std::min<int64_t>(groups, (int64_t)h->num_cus * h->alias_blocks_per_cu)), dim3(64), (size_t)h->alias_lds,
-                     h->stream, ap);
-  HIP_TRY(h, hipGetLastError());
+  ap.V = h->V; ap.K = h->K; ap.Kp = h->Kp; ap.wpb = h->plan.alias_wpb;
+  void *args[] = {&ap};
+  HIP_TRY(h, launch(h, h->plan.alias, ((int64_t)h->V + ap.wpb - 1) / ap.wpb, args, h->stream));
   h->alias_stale = false;
   return GGS_OK;
 }
@@ -770,17 +826,18 @@ int launch_phi(ggs_handle *h, bool initial, bool accumulate_mean, Events *E = nu
   return launch_alias_build(h);
 }
 
+// `lds`, `docs_per_block`: 0 = those of the corpus' configuration (plan.cfg_plain / cfg_parts)
 int launch_theta(ggs_handle *h, hipStream_t stream, double *dst, int32_t iteration, int64_t d0 = 0, int64_t d1 = -1, int32_t lds = 0, int32_t docs_per_block = 0) {
   if (d1 < 0) d1 = h->D;
   if (d1 <= d0) return GGS_OK;
-  if (docs_per_block <= 0) docs_per_block = h->theta_docs_per_block;
+  if (docs_per_block <= 0) docs_per_block = h->cfg->theta_docs;
   ThetaParams tp{};
   tp.doc_ptr = h->d_doc_ptr + d0; tp.z = h->d_z; tp.alpha = h->d_alpha; tp.theta = dst + (size_t)d0 * h->K; tp.status = h->d_status;
   tp.num_docs = d1 - d0; tp.doc_base = h->doc_base + d0; tp.seed = h->seed; tp.iteration = (uint32_t)iteration;
   tp.K = h->K; tp.docs_per_block = docs_per_block; tp.queue_cap = std::min(kGammaQueue, h->gamma_queue_cap);
   const int64_t grid = (d1 - d0 + docs_per_block - 1) / docs_per_block;
-  hipLaunchKernelGGL(theta_kernel<kThetaBlock>, dim3((unsigned)grid), dim3(kThetaBlock), lds ? lds : h->theta_lds, stream, tp);
-  HIP_TRY(h, hipGetLastError());
+  void *args[] = {&tp};
+  HIP_TRY(h, hipLaunchKernel(h->plan.theta.fn, dim3((unsigned)grid), dim3(kThetaBlock), args, (size_t)(lds ? lds : h->cfg->theta_lds), stream));
   return GGS_OK;
 }
 
@@ -837,6 +894,174 @@ constexpr int kPcgsWaveFromTopics = 176, kCollapsedWaveFromTopics = 96;
 // pcgs_sliced_kernel<176> spills less, and the two kernels' times are within 10 % of each other there (pcgs above)
 constexpr int kPolyaurnWaveFromTopics = 168;
 
+const void *tile_kernel_for(int K) {
+  const int nt = (K + 63) / 64;
+  return nt <= 1 ? reinterpret_cast<const void *>(z_kernel<1>) : nt <= 2 ? reinterpret_cast<const void *>(z_kernel<2>)
+       : nt <= 4 ? reinterpret_cast<const void *>(z_kernel<4>) : nt <= 8 ? reinterpret_cast<const void *>(z_kernel<8>)
+       : nt <= 16 ? reinterpret_cast<const void *>(z_kernel<16>) : reinterpret_cast<const void *>(z_kernel<20>);
+}
+const void *stream_kernel_for(bool two_pass, bool regck, int group) {
+  if (two_pass) return reinterpret_cast<const void *>(z_stream_kernel);
+  if (!regck) return reinterpret_cast<const void *>(z_stream1_kernel<false, 4>);
+  return group == 1 ? reinterpret_cast<const void *>(z_stream1_kernel<true, 1>) : group == 2 ? reinterpret_cast<const void *>(z_stream1_kernel<true, 2>)
+                                                                                             : reinterpret_cast<const void *>(z_stream1_kernel<true, 4>);
+}
+// the lane-per-document kernel of a scheme: scores in registers (K <= 192), or streamed
+const void *pcgs_lane_kernel_for(int K, bool sliced, bool collapsed, bool polyaurn) {
+  if (sliced) return collapsed ? collapsed_kernel_for(K) : polyaurn ? polyaurn_kernel_for(K) : pcgs_kernel_for(K);
+  return collapsed ? reinterpret_cast<const void *>(pcgs_z_kernel<true>) : polyaurn ? reinterpret_cast<const void *>(polyaurn_z_kernel) : reinterpret_cast<const void *>(pcgs_z_kernel<false>);
+}
+
+// Every launch a handle of (K, V, flags) can make on the device: which kernel, how much LDS (the layout
+// functions beside the kernels), how many workgroups per CU.  `flags` with GGS_FLAG_PCGS set for every scheme that runs the
+// pcgs machinery.  No environment, no handle; the one HIP call is the occupancy query of the wave-per-document kernel.
+int plan_launches(const int K, const int V, const int32_t flags, const Knobs &kn, LaunchPlan &pl) {
+  const bool pcgs = (flags & GGS_FLAG_PCGS) != 0, collapsed = (flags & GGS_FLAG_COLLAPSED) != 0, polyaurn = (flags & GGS_FLAG_POLYAURN) != 0;
+  const int Kp = (K + 1) & ~1, pitch16 = (Kp / 2) | 1;
+  // score-register kernels up to K = 160: measured on the benchmark corpus (sweep, ms; round 3) K=136: 2.13 sliced / 2.40
+  // streaming, 152: 2.33 / 2.56, 160: 2.40 / 2.50, 164: 3.06 / 2.83, 168: 3.06 / 2.75, 184: 3.24 / 2.94 (round 2: 184: 3.55 /
+  // 3.64, 192: 4.22 / 3.59) -- from KMAX = 168 on the cold kernel fills the whole register file (256 + 256) and the one-pass
+  // streaming kernel with the next theta drawn beside it wins (the sliced kernels can take K up to kSlicedMaxTopics = 192:
+  // GGS_DEBUG_ZKERNEL=1).  The sliced kernel tags chunk tokens (word ids) in bit 30.
+  const bool sliced_ok = K <= kSlicedMaxTopics && V < (1 << kSlotShift);
+  bool sliced = sliced_ok && K <= kSlicedDefaultTopics, stream = !sliced && K > 2 * kSliceTopics, two_pass = false;
+  if (kn.zkernel.set) {          // 0: whole-row tile kernel, 1: sliced where possible, 2: streaming kernel where it applies, 3: its two-pass form
+    const int mode = kn.zkernel.v;
+    sliced = sliced_ok && mode == 1;
+    stream = (mode == 2 || mode == 3) ? K > 2 * kSliceTopics : (stream && mode != 0);
+    two_pass = mode == 3;
+    if (sliced) stream = false;
+  }
+  pl.kernel = sliced ? 1 : stream ? (two_pass ? 3 : 2) : 0;
+  // The z waves are persistent and stride the chunk table statically, so a grid is what is truly co-resident
+  // (lds_workgroups_per_cu); the passes are latency chains, so waves in flight matter more than lanes in use.
+  if (stream) {
+    // 64-token chunks, a 2-slot slice ring + the theta row zero-padded to whole slices (one-pass kernel: to whole
+    // checkpoint groups, plus a checkpoint per group and lane); no score registers, so 8 waves per CU fit the
+    // register file and LDS bounds the residency
+    const int ns = stream_slices(K);
+    // checkpoint group: the smallest that keeps the checkpoints in registers (K <= 256: one slice, <= 512: two, <= 1024: four); beyond, four slices and LDS
+    int group = ns <= kRegCheckpoints ? 1 : ns <= 2 * kRegCheckpoints ? 2 : 4;
+    if (kn.group.set && (kn.group.v == 1 || kn.group.v == 2 || kn.group.v == 4)) group = kn.group.v;
+    bool regck = !two_pass && z_stream1_groups(K, group) <= kRegCheckpoints;          // checkpoints in registers or in LDS
+    if (kn.regck.set) regck = regck && kn.regck.v != 0;
+    if (!regck) group = 4;                               // the LDS-checkpoint kernel is instantiated for groups of four
+    // Chunks of 64 consecutive tokens across ONE document boundary (two theta rows per wave) instead of near-equal
+    // cuts of single documents: 98 % of the lanes busy instead of 78 % at 200-token documents.  Where the second row
+    // would cost resident waves (K > 512: 8 KiB at K = 1024) the single-document chunks stay.
+    pl.two_rows = !two_pass && (kn.tworows.set ? kn.tworows.v != 0 : K <= 512);
+    pl.z.fn = stream_kernel_for(two_pass, regck, group);
+    pl.z.lds = two_pass ? z_stream_lds_bytes(K) : z_stream1_lds_bytes(K, group, pl.two_rows, regck);
+    if (pl.z.lds > kMaxLdsBytes) return GGS_ERR_UNSUPPORTED;   // K > ~16000: the theta row itself would need slicing
+  } else if (sliced) {
+    // 64-token chunks; one 4-wave workgroup per CU (a wave per SIMD: the score registers take most of the 512-entry file),
+    // per wave the two theta rows and the slice ring, per workgroup the hot-word table.  The cold chunks from phiT32 (a
+    // 32-topic slice per 128 bytes); its wave LDS is the fp64 form's: the ring, then two float32 theta rows and the
+    // replay's KMAX products where the two fp64 theta rows were
+    pl.f32 = !kn.phi64.is(1);
+    pl.Kp32 = round_up(K, kSlice32Topics);
+    pl.ring_base = sliced_ring_base(K); pl.wave_lds = sliced_wave_lds(K); pl.hot_pitch = table_row_pitch(K);
+    pl.hot_wave_lds = hot_wave_lds(K); pl.warm_wave_lds = warm_wave_lds(K);
+    if (kn.split.set) { pl.split = kn.split.v != 0; pl.split_forced = kn.split.v == 2; }
+    // split: the two workgroups must fit one CU together
+    pl.hot_cap = pl.split ? table_rows_beside_cold(K, pl.hot_wave_lds) : table_rows_fused(K);
+    if (kn.hot.set) pl.hot_cap = std::max(0, std::min(pl.hot_cap, kn.hot.v));
+    pl.cold = {pl.f32 ? sliced32_kernel_for(K) : sliced_kernel_for(K), kSlicedWaves * 64, sliced_cold_lds(K), 1};
+    pl.hot = {hot_kernel_for(K), kSlicedWaves * 64, table_lds(K, pl.hot_wave_lds, 0), 1};
+    // the warm tiers: the same LDS beside the cold kernel's workgroup, more of it for theta rows (warm_docs per wave), the rest a table
+    pl.warm = {warm_kernel_for(K), kSlicedWaves * 64, table_lds(K, pl.warm_wave_lds, 0), 1};
+    pl.warm_docs = warm_docs_for(sliced_kmax(K));
+    pl.warm_cap = table_rows_beside_cold(K, pl.warm_wave_lds);
+    if (pl.warm_cap < 16) pl.warm_cap = 0;               // the table loads and barriers of a tier want tokens to pay them
+    if (kn.warm.set) pl.warm_tiers_max = std::max(0, std::min(kWarmMaxTiers, kn.warm.v));
+    if (kn.warm_rows.set) pl.warm_cap = std::max(0, std::min(pl.warm_cap, kn.warm_rows.v));
+    if (kn.warm_fill.set) pl.warm_min_fill_pct = std::max(1, std::min(100, kn.warm_fill.v));
+    if (kn.warm_cpw.set) pl.warm_min_chunks_per_wave = std::max(0, kn.warm_cpw.v);
+  } else {
+    // a tile of T token rows + one theta row per wave: the largest tile that still lets 6 single-wave workgroups share a
+    // CU, but at least 8 rows
+    int T = z_tile_rows_in(kMaxLdsBytes / 6 / kLdsGranule * kLdsGranule, Kp, pitch16);
+    if (kn.tile.set) T = kn.tile.v;
+    pl.tile_tokens = std::max(8, std::min(64, T));
+    pl.z.fn = tile_kernel_for(K);
+    pl.z.lds = z_tile_lds_bytes(Kp, pitch16, pl.tile_tokens);
+    if (pl.z.lds > kMaxLdsBytes) return GGS_ERR_UNSUPPORTED;   // K > ~2400 needs a K-sliced kernel
+  }
+  if (!sliced) {
+    pl.z.per_cu = lds_workgroups_per_cu(pl.z.lds, 8);
+    if (kn.wpc.set) pl.z.per_cu = std::max(1, kn.wpc.v);
+  }
+
+  // ---- the theta draw
+  int B = 64;
+  while (B > 1 && theta_lds_bytes(K, B) > 32 * 1024) B >>= 1;
+  if (theta_lds_bytes(K, B) > kMaxLdsBytes) return GGS_ERR_UNSUPPORTED;
+  pl.theta.fn = reinterpret_cast<const void *>(theta_kernel<kThetaBlock>); pl.theta.block = kThetaBlock;
+  // The request is padded to a quarter of the CU's LDS: at most 4 workgroups (16 waves) of the theta draw per CU.
+  // It runs on the side stream beside the Phi phase, which is the critical path; stream priority orders dispatch,
+  // not running waves, and measured with 5-6 resident workgroups theta finishes early (0.53 ms instead of 0.75)
+  // while the Phi phase it starves gets longer (0.67 -> 0.72 ms).
+  // ... and 24 KiB of every CU stay free for the main stream's own LDS users (the walk of the exact column sums,
+  // 14.5 KiB per workgroup: with the CU's LDS handed out to theta workgroups to the last granule it waited for the
+  // theta draw to END -- 5 ms at K = 1024).
+  const int theta_quarter = (kMaxLdsBytes - 24 * 1024) / 4;
+  pl.cfg_plain = {1, pl.z.per_cu, B, std::max(theta_lds_bytes(K, B), theta_quarter), 0};
+  // ... unless the theta draw is the critical leg itself (theta_main): then five workgroups per CU, of 16 documents
+  // each.  Measured at K = 100 on one box, ms per sweep (documents per workgroup x workgroups per CU): 32x4 1.60-1.61,
+  // 32x5 1.598-1.62, 24x5 1.593, 16x4 1.614, 16x5 1.568-1.587, 16x6 1.58, 16x8 1.598, 12x5 1.609, 8x8 1.635 -- the smaller
+  // workgroups leave the Phi chain beside them its pace (0.39 ms against 0.44), so that it ends before the theta draw does.
+  pl.theta_docs_main = kn.theta_b.set ? std::max(1, std::min(B, kn.theta_b.v)) : std::min(B, 16);
+  pl.theta_lds_main = std::max(theta_lds_bytes(K, pl.theta_docs_main), (kMaxLdsBytes - 24 * 1024) / (kn.theta_wgs.set ? std::max(1, kn.theta_wgs.v) : 5));
+  // K > 192 (one-pass streaming z kernel): theta workgroups small enough to sit BESIDE the z waves -- on the LDS the z
+  // waves give up -- so that the next theta of a part of the documents is drawn while the following parts are sampled
+  // (z_phase).  The padded request caps them at kBeside per CU while z runs.
+  pl.parts_forced = kn.zparts.set;
+  int parts = kn.zparts.set ? std::max(1, std::min(8, kn.zparts.v)) : (stream && !two_pass && !pcgs) ? 8 : 1;   // measured at K = 1024: 1 part 18.4 ms per sweep, 2: 18.1, 4: 16.5, 8: 15.9
+  pl.cfg_parts = pl.cfg_plain;
+  if (parts > 1 && stream && !two_pass) {
+    const int kBeside = kn.beside.set ? std::max(1, kn.beside.v) : 4;   // measured at K = 1024 (sweep): 2 -> 16.9 ms, 3 -> 16.1, 4 -> 15.0, 5 -> 15.0
+    int Bt = 64;
+    while (Bt > 1 && theta_lds_bytes(K, Bt) > 10 * 1024) Bt >>= 1;
+    const int t_lds = theta_lds_bytes(K, Bt), z_alloc = lds_alloc_of(pl.z.lds);
+    const int zw = std::min(pl.z.per_cu, (kMaxLdsBytes - kLdsGranule - kBeside * lds_alloc_of(t_lds)) / z_alloc);
+    if (t_lds <= 12 * 1024 && zw >= 2)
+      pl.cfg_parts = {parts, zw, Bt, std::max(t_lds, theta_quarter), std::max(t_lds, (kMaxLdsBytes - kLdsGranule - zw * z_alloc) / kBeside / kLdsGranule * kLdsGranule)};
+    else
+      parts = 1;
+  }
+  pl.cfg_parts.parts = parts;
+  if (!pcgs) return GGS_OK;
+
+  // ---- scheme pcgs / collapsed / polyaurn / spalias
+  // the wave-per-document kernel: any K up to 4096, any document length.  Waves per CU (the grid is persistent: exactly what
+  // is resident): what the kernel's registers allow (asked of the runtime) and what LDS allows (the runtime's answer
+  // ignores the allocation granule)
+  if (K <= kPcgsWaveMaxTopics) {
+    const int nb = pcgs_wave_blocks(Kp);
+    pl.wave.fn = pcgs_wave_kernel_for(nb, collapsed, polyaurn);
+    pl.wave.lds = pcgs_wave_lds_bytes(nb);
+    int by_regs = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, pl.wave.fn, 64, (size_t)pl.wave.lds) != hipSuccess || by_regs < 1) by_regs = 1;
+    pl.wave.per_cu = lds_workgroups_per_cu(pl.wave.lds, std::min(by_regs, 32));
+  }
+  pl.wave_forced = kn.pcgs_wave.set ? kn.pcgs_wave.v != 0 : K > (collapsed ? kCollapsedWaveFromTopics : polyaurn ? kPolyaurnWaveFromTopics : kPcgsWaveFromTopics);
+  if (pl.wave_forced && !pl.wave.fn) return GGS_ERR_UNSUPPORTED;   // more than 4096 topics
+  // the lane-per-document kernel: its waves per CU also size the padded document order, whichever kernel runs
+  const bool lane_sliced = K <= kSlicedMaxTopics && !(kn.pcgs_stream.set && kn.pcgs_stream.v != 0);
+  pl.lane.lds = lane_sliced ? pcgs_sliced_lds_bytes(K) : pcgs_z_lds_bytes(K);
+  if (pl.lane.lds > kMaxLdsBytes && !pl.wave_forced) return GGS_ERR_UNSUPPORTED;
+  pl.lane.per_cu = lds_workgroups_per_cu(pl.lane.lds, 8);
+  if (!pl.wave_forced) pl.lane.fn = pcgs_lane_kernel_for(K, lane_sliced, collapsed, polyaurn);
+  if (collapsed) pl.serial.fn = reinterpret_cast<const void *>(collapsed_serial_kernel);
+  if (flags & GGS_FLAG_SPALIAS) {
+    pl.alias_wpb = alias_words_per_block(K);
+    pl.alias = {reinterpret_cast<const void *>(alias_build_kernel), 64, (int)alias_lds_bytes(K, pl.alias_wpb), 0};
+    pl.alias.per_cu = lds_workgroups_per_cu(pl.alias.lds, 16);
+    pl.spalias.fn = reinterpret_cast<const void *>(spalias_wave_kernel);
+  }
+  return GGS_OK;
+}
+
 int launch_pcgs_z(ggs_handle *h) {
   if (h->N == 0) return GGS_OK;
   PcgsParams pp{};
@@ -844,54 +1069,28 @@ int launch_pcgs_z(ggs_handle *h) {
   pp.alpha = h->d_alpha; pp.phiT = h->d_phiT; pp.status = h->d_status;
   pp.num_docs = h->pcgs_order_len; pp.tok_base = h->tok_base; pp.seed = h->seed; pp.iteration = (uint32_t)h->iteration;   // the length of the (padded) order list
   pp.K = h->K; pp.Kp = h->Kp;
+  int rc;
   if (h->spalias) {                                    // one wave per document over the non-zero topics (ggs_z_spalias.hpp)
-    int rc;
     if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
     SpaliasParams sp{};
     sp.b = pp; sp.ps = h->d_alias_ps; sp.a = h->d_alias_a; sp.type_norm = h->d_alias_tn; sp.cap = h->sp_cap; sp.margin_scale = h->margin_scale;
-    hipLaunchKernelGGL(spalias_wave_kernel, dim3((unsigned)std::min<int64_t>(h->pcgs_order_len, (int64_t)h->num_cus * h->sp_waves_per_cu)), dim3(64), (size_t)h->sp_lds,
-                       h->stream, sp);
-    HIP_TRY(h, hipGetLastError());
-    return GGS_OK;
-  }
-  const int64_t groups = (h->pcgs_order_len + 63) / 64;
-  const dim3 grid((unsigned)std::min<int64_t>(groups, (int64_t)h->num_cus * h->pcgs_waves_per_cu)), block(64);
-  if (h->pcgs_wave) {
-    // one wave per document: wide topic rows, or a document the lane-per-document kernels' int16 counts cannot hold
-    if (h->collapsed) {
-      int rc = launch_magnitude(h);
-      if (rc) return rc;
-      pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;
-      hipLaunchKernelGGL(psi_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, h->d_n_wk, h->d_n_k, pp.beta, pp.beta_sum, h->d_phiT,
-                         h->K, h->Kp, h->V);
-    }
-    const dim3 wgrid((unsigned)std::min<int64_t>(h->pcgs_order_len, (int64_t)h->num_cus * h->pcgs_wave_waves_per_cu));
-    void *args[] = {&pp, &h->margin_scale};
-    HIP_TRY(h, hipLaunchKernel(pcgs_wave_kernel_for(h->pcgs_wave_nb, h->collapsed, h->polyaurn), wgrid, block, args, (size_t)h->pcgs_wave_lds, h->stream));
+    void *args[] = {&sp};
+    HIP_TRY(h, launch(h, h->sp_z, h->pcgs_order_len, args, h->stream));
     return GGS_OK;
   }
   if (h->collapsed) {
     // the sweep-start ratios (beta + n_wk)/(betaSum + n_k) of the corpus-wide counts, then the pcgs loop over them
-    int rc = launch_magnitude(h);
-    if (rc) return rc;
+    if ((rc = launch_magnitude(h))) return rc;
     pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;   // betaSum = beta * numTypes, MSLDA:136
     hipLaunchKernelGGL(psi_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, h->d_n_wk, h->d_n_k, pp.beta, pp.beta_sum, h->d_phiT,
                        h->K, h->Kp, h->V);
-    if (h->pcgs_sliced) {
-      void *args[] = {&pp};
-      HIP_TRY(h, hipLaunchKernel(collapsed_kernel_for(h->K), grid, block, args, (size_t)h->pcgs_lds, h->stream));
-    } else {
-      hipLaunchKernelGGL(pcgs_z_kernel<true>, grid, block, (size_t)h->pcgs_lds, h->stream, pp);
-    }
-  } else if (h->pcgs_sliced) {
-    void *args[] = {&pp};
-    HIP_TRY(h, hipLaunchKernel(h->polyaurn ? polyaurn_kernel_for(h->K) : pcgs_kernel_for(h->K), grid, block, args, (size_t)h->pcgs_lds, h->stream));
-  } else if (h->polyaurn) {
-    hipLaunchKernelGGL(polyaurn_z_kernel, grid, block, (size_t)h->pcgs_lds, h->stream, pp);
-  } else {
-    hipLaunchKernelGGL(pcgs_z_kernel<false>, grid, block, (size_t)h->pcgs_lds, h->stream, pp);
+    HIP_TRY(h, hipGetLastError());
   }
-  HIP_TRY(h, hipGetLastError());
+  // one wave per document (wide topic rows, or a document the lane-per-document kernels' int16 counts cannot hold), or
+  // one lane: 64 documents of the order list per wave
+  void *wave_args[] = {&pp, &h->margin_scale}, *lane_args[] = {&pp};
+  if (h->pcgs_wave) HIP_TRY(h, launch(h, h->plan.wave, h->pcgs_order_len, wave_args, h->stream));
+  else HIP_TRY(h, launch(h, h->plan.lane, (h->pcgs_order_len + 63) / 64, lane_args, h->stream));
   return GGS_OK;
 }
 
@@ -902,7 +1101,7 @@ int launch_pcgs_z(ggs_handle *h) {
 // on the rank) 0.139 / 0.132 ms against 0.040 of count kernel; N = 4 (100) 0.290 / 0.26 against 0.05; N = 2 (200) 0.627 / 0.52
 // against 0.07 -- they pay up to about 64 tokens per word (GGS_DEBUG_ZCOUNTS=2 forces them).
 bool z_counts_itself(const ggs_handle *h) {
-  return h->xg && h->z_counts && h->z_sliced && !(h->flags & GGS_FLAG_PCGS) && (h->z_counts_forced || h->N <= (int64_t)64 * h->V) && !use_sparse(h);
+  return h->xg && h->z_counts && h->plan.sliced() && !(h->flags & GGS_FLAG_PCGS) && (h->z_counts_forced || h->N <= (int64_t)64 * h->V) && !use_sparse(h);
 }
 // `defer_join` (with `count`, split form): the hot words' count launch follows the hot kernel on ITS stream and the
 // handle's stream is not made to wait for that stream here -- the caller does (join_hot_stream), behind the z step's end
@@ -913,111 +1112,73 @@ int launch_z(ggs_handle *h, bool force_fused = false, int64_t c0 = 0, int64_t c1
   if (h->C == 0) return GGS_OK;
   if (c1 < 0) c1 = h->C;
   if (c1 <= c0) return GGS_OK;
+  const LaunchPlan &pl = h->plan;
   ZParams zp{};
   zp.tok = h->d_tok; zp.inv_perm = h->d_inv_perm; zp.z = h->d_z; zp.zw = h->d_zw; zp.chunk_start = h->d_chunk_start; zp.chunk_doc = h->d_chunk_doc; zp.chunk_len = h->d_chunk_len;
   zp.theta = h->d_theta; zp.phiT = h->d_phiT; zp.status = h->d_status;
   zp.tok_base = h->tok_base; zp.seed = h->seed; zp.iteration = (uint32_t)h->iteration;
-  zp.K = h->K; zp.Kp = h->Kp; zp.pitch16 = h->pitch16; zp.tile_tokens = h->z_tile_tokens;
+  zp.K = h->K; zp.Kp = h->Kp; zp.pitch16 = h->pitch16; zp.tile_tokens = pl.tile_tokens;
   zp.num_chunks = h->C;
-  zp.ablate = h->ablate;
   zp.margin_scale = h->margin_scale;
-  zp.chunk_doc1 = h->d_chunk_doc1; zp.two_rows = (h->z_stream && h->z_two_rows && h->d_chunk_doc1) ? 1 : 0;
+  zp.chunk_doc1 = h->d_chunk_doc1; zp.two_rows = (pl.two_rows && h->d_chunk_doc1) ? 1 : 0;
   zp.ct_tok = h->d_ct_tok; zp.ct_idx = h->d_ct_idx; zp.ct_ip = h->d_ct_ip; zp.c_docs = h->d_c_docs; zp.num_cold = h->Cc;
-  zp.hot_words = h->d_hot_words; zp.num_hot = h->num_hot; zp.hot_pitch = h->hot_pitch;
-  zp.wave_lds = h->wave_lds; zp.hot_off = kSlicedWaves * h->wave_lds; zp.ring_base = h->ring_base;
+  zp.hot_words = h->d_hot_words; zp.num_hot = h->num_hot; zp.hot_pitch = pl.hot_pitch;
+  zp.wave_lds = pl.wave_lds; zp.hot_off = kSlicedWaves * pl.wave_lds; zp.ring_base = pl.ring_base;
   zp.cnt_send = (count && z_counts_itself(h)) ? h->d_cnt_send : nullptr;
   zp.smap = h->smap;
   zp.ht_pack = reinterpret_cast<const int4 *>(h->d_ht_pack); zp.h_docs = h->d_h_docs;
   zp.wt_pack = reinterpret_cast<const int4 *>(h->d_wt_pack); zp.w_docs = h->d_w_docs; zp.warm_words = h->d_warm_words;
-  zp.warm_meta = h->d_warm_meta; zp.warm_tiers = h->warm_tiers; zp.warm_rows = h->warm_cap;
-  zp.phiT32 = h->d_phiT32; zp.Kp32 = h->Kp32; zp.replays = h->d_replays; zp.margin_scale32 = h->margin_scale32;
-  const bool f32 = h->z_f32 && h->d_phiT32;
-  const void *cold_kernel = f32 ? sliced32_kernel_for(h->K) : sliced_kernel_for(h->K);
-  if (!h->z_sliced) {                                  // a range of the chunk table (the one-document chunks are in document order)
+  zp.warm_meta = h->d_warm_meta; zp.warm_tiers = h->warm_tiers; zp.warm_rows = pl.warm_cap;
+  zp.phiT32 = h->d_phiT32; zp.Kp32 = pl.Kp32; zp.replays = h->d_replays; zp.margin_scale32 = h->margin_scale32;
+  void *args[] = {&zp};
+  if (!pl.sliced()) {
+    // a range of the chunk table (the one-document chunks are in document order); persistent single-wave workgroups stride it
     zp.chunk_start += c0; zp.chunk_doc += c0; zp.chunk_len += c0; zp.num_chunks = c1 - c0;
     if (zp.chunk_doc1) zp.chunk_doc1 += c0;
+    KernelLaunch z = pl.z;
+    z.per_cu = h->cfg->z_per_cu;
+    HIP_TRY(h, launch(h, z, zp.num_chunks, args, h->stream));
+    return GGS_OK;
   }
-  // persistent waves: as many single-wave workgroups as stay resident, each strides the chunk table
-  const dim3 grid((unsigned)std::min<int64_t>(zp.num_chunks, (int64_t)h->num_cus * h->z_waves_per_cu)), block(64);
-  const int nt = (h->K + 63) / 64;
-  if (h->z_sliced) {
-    // one 4-wave workgroup per CU (a wave per SIMD), persistent; the hot-word table fills the LDS the rings leave
-    zp.num_chunks = h->Cs;
-    void *args[] = {&zp};
-    const dim3 sblock(kSlicedWaves * 64);
-    auto grid_of = [&](int64_t chunks) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((chunks + kSlicedWaves - 1) / kSlicedWaves, (int64_t)h->num_cus))); };
-    // the warm tiers (z_warm_kernel): behind the hot chunks on their stream, or behind the one kernel of the fused form
-    ZParams wp = zp;
-    wp.wave_lds = h->warm_wave_lds; wp.hot_off = kSlicedWaves * h->warm_wave_lds;
-    void *wargs[] = {&wp};
-    auto launch_warm = [&](hipStream_t st) -> int {
-      if (h->Cw == 0) return GGS_OK;
-#ifdef GGS_WARM_TRACE
-      static long long *dbg = nullptr;
-      static int launches = 0;
-      if (!dbg) HIP_TRY(h, hipMalloc(&dbg, sizeof(long long) * 8 * 1024 * 4));
-      wp.dbg = dbg;
-#endif
-      HIP_TRY(h, hipLaunchKernel(warm_kernel_for(h->K), grid_of(h->warm_chunks_max), sblock, wargs, (size_t)(wp.hot_off + h->warm_rows_max * h->hot_pitch + kHotTailBytes), st));
-#ifdef GGS_WARM_TRACE
-      if (++launches == 12) {                                        // a steady-state sweep: print the phase averages once
-        HIP_TRY(h, hipDeviceSynchronize());
-        std::vector<long long> v(8 * 1024);
-        HIP_TRY(h, hipMemcpy(v.data(), dbg, sizeof(long long) * v.size(), hipMemcpyDeviceToHost));
-        double a[7] = {0, 0, 0, 0, 0, 0, 0};
-        for (int w = 0; w < 1024; ++w) for (int i = 0; i < 7; ++i) a[i] += (double)v[(size_t)w * 8 + i] / 1024;
-        fprintf(stderr, "[warm trace] cycles per wave: wait %.0f stage %.0f issue %.0f arithmetic %.0f stores %.0f rest %.0f | kernel %.0f\n", a[0], a[1], a[2], a[3], a[4], a[5], a[6]);
-      }
-#endif
-      return GGS_OK;
-    };
-    if (h->z_split && !force_fused && h->Cs > h->Cc && h->Cc > 0) {
-      // cold chunks on the main stream, hot chunks beside them (z_hot_kernel): two waves per SIMD
-      ZParams hp = zp;
-      hp.wave_lds = h->hot_wave_lds; hp.hot_off = kSlicedWaves * h->hot_wave_lds;
-      void *hargs[] = {&hp};
-      if (h->hot_fork_from) {
-        HIP_TRY(h, hipStreamWaitEvent(h->side_hot, h->hot_fork_from, 0));
-      } else {
-        HIP_TRY(h, hipEventRecord(h->ev_hot_fork, h->stream));
-        HIP_TRY(h, hipStreamWaitEvent(h->side_hot, h->ev_hot_fork, 0));
-      }
-      zp.num_chunks = h->Cc; zp.num_hot = 0;
-      static const int only = debug_env("GGS_DEBUG_ONLY") ? std::atoi(debug_env("GGS_DEBUG_ONLY")) : 0;   // timing experiments: 1 cold only, 2 hot only
-      if (only != 2) HIP_TRY(h, hipLaunchKernel(cold_kernel, grid_of(h->Cc), sblock, args, (size_t)(kSlicedWaves * h->wave_lds), h->stream));
-      if (only != 2 && f32) ++h->z_f32_launches;
-      if (only != 1) HIP_TRY(h, hipLaunchKernel(hot_kernel_for(h->K), grid_of(h->Cs - h->Cc), sblock, hargs, (size_t)(hp.hot_off + h->num_hot * h->hot_pitch + kHotTailBytes), h->side_hot));
-      if (only != 1) { const int rc = launch_warm(h->side_hot); if (rc) return rc; }
-      if (defer_join && zp.cnt_send && only == 0) {
-        hipStream_t main_stream = h->stream;
-        h->stream = h->side_hot;
-        const int rc = launch_count_hot(h);
-        h->stream = main_stream;
-        if (rc) return rc;
-        h->hot_counted = true;
-      }
-      HIP_TRY(h, hipEventRecord(h->ev_hot_join, h->side_hot));
-      if (defer_join) h->hot_join_pending = true;
-      else HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_hot_join, 0));
+  // one 4-wave workgroup per CU (a wave per SIMD), persistent; the hot-word table fills the LDS the rings leave
+  zp.num_chunks = h->Cs;
+  const int hot_rows_lds = h->num_hot * pl.hot_pitch;
+  // the warm tiers (z_warm_kernel): behind the hot chunks on their stream, or behind the one kernel of the fused form
+  ZParams wp = zp;
+  wp.wave_lds = pl.warm_wave_lds; wp.hot_off = kSlicedWaves * pl.warm_wave_lds;
+  void *wargs[] = {&wp};
+  auto launch_warm = [&](hipStream_t st) { return h->Cw == 0 ? hipSuccess : launch(h, pl.warm, h->warm_chunks_max, wargs, st, h->warm_rows_max * pl.hot_pitch); };
+  if (h->z_split && !force_fused && h->Cs > h->Cc && h->Cc > 0) {
+    // cold chunks on the main stream, hot chunks beside them (z_hot_kernel): two waves per SIMD
+    ZParams hp = zp;
+    hp.wave_lds = pl.hot_wave_lds; hp.hot_off = kSlicedWaves * pl.hot_wave_lds;
+    void *hargs[] = {&hp};
+    if (h->hot_fork_from) {
+      HIP_TRY(h, hipStreamWaitEvent(h->side_hot, h->hot_fork_from, 0));
     } else {
-      HIP_TRY(h, hipLaunchKernel(cold_kernel, grid_of(std::max(h->Cc, h->Cs - h->Cc)), sblock, args,
-                                 (size_t)(kSlicedWaves * h->wave_lds + h->num_hot * h->hot_pitch), h->stream));
-      if (f32) ++h->z_f32_launches;
-      const int rc = launch_warm(h->stream);
-      if (rc) return rc;
+      HIP_TRY(h, hipEventRecord(h->ev_hot_fork, h->stream));
+      HIP_TRY(h, hipStreamWaitEvent(h->side_hot, h->ev_hot_fork, 0));
     }
-  } else if (h->z_stream && h->z_two_pass) hipLaunchKernelGGL(z_stream_kernel, grid, block, h->z_lds, h->stream, zp);
-  else if (h->z_stream && h->z_regck && h->z_group == 1) hipLaunchKernelGGL((z_stream1_kernel<true, 1>), grid, block, h->z_lds, h->stream, zp);
-  else if (h->z_stream && h->z_regck && h->z_group == 2) hipLaunchKernelGGL((z_stream1_kernel<true, 2>), grid, block, h->z_lds, h->stream, zp);
-  else if (h->z_stream && h->z_regck) hipLaunchKernelGGL((z_stream1_kernel<true, 4>), grid, block, h->z_lds, h->stream, zp);
-  else if (h->z_stream) hipLaunchKernelGGL((z_stream1_kernel<false, 4>), grid, block, h->z_lds, h->stream, zp);
-  else if (nt <= 1) hipLaunchKernelGGL(z_kernel<1>, grid, block, h->z_lds, h->stream, zp);
-  else if (nt <= 2) hipLaunchKernelGGL(z_kernel<2>, grid, block, h->z_lds, h->stream, zp);
-  else if (nt <= 4) hipLaunchKernelGGL(z_kernel<4>, grid, block, h->z_lds, h->stream, zp);
-  else if (nt <= 8) hipLaunchKernelGGL(z_kernel<8>, grid, block, h->z_lds, h->stream, zp);
-  else if (nt <= 16) hipLaunchKernelGGL(z_kernel<16>, grid, block, h->z_lds, h->stream, zp);
-  else hipLaunchKernelGGL(z_kernel<20>, grid, block, h->z_lds, h->stream, zp);
-  HIP_TRY(h, hipGetLastError());
+    zp.num_chunks = h->Cc; zp.num_hot = 0;
+    HIP_TRY(h, launch(h, pl.cold, h->Cc, args, h->stream));
+    HIP_TRY(h, launch(h, pl.hot, h->Cs - h->Cc, hargs, h->side_hot, hot_rows_lds));
+    HIP_TRY(h, launch_warm(h->side_hot));
+    if (defer_join && zp.cnt_send) {
+      hipStream_t main_stream = h->stream;
+      h->stream = h->side_hot;
+      const int rc = launch_count_hot(h);
+      h->stream = main_stream;
+      if (rc) return rc;
+      h->hot_counted = true;
+    }
+    HIP_TRY(h, hipEventRecord(h->ev_hot_join, h->side_hot));
+    if (defer_join) h->hot_join_pending = true;
+    else HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_hot_join, 0));
+  } else {
+    HIP_TRY(h, launch(h, pl.cold, std::max(h->Cc, h->Cs - h->Cc), args, h->stream, hot_rows_lds));
+    HIP_TRY(h, launch_warm(h->stream));
+  }
+  if (pl.f32) ++h->z_f32_launches;
   return GGS_OK;
 }
 
@@ -1147,7 +1308,7 @@ int z_phase(ggs_handle *h) {
     if ((rc = launch_theta(h, h->stream, h->d_theta, h->iteration))) return rc;
   }
   HIP_TRY(h, hipEventRecord(E.e[1], h->stream));
-  if (h->z_sliced && h->z_split && !h->z_split_tried && h->Cs > h->Cc && h->Cc > 0) {
+  if (h->plan.sliced() && h->z_split && !h->z_split_tried && h->Cs > h->Cc && h->Cc > 0) {
     // Whether the guest kernel really runs beside the cold one depends on how the runtime maps streams to hardware
     // queues (measured: beside each other in a plain process, one after the other under torchrun + RCCL).  Both forms
     // write the same z, so the first z step of a corpus simply runs twice, timed, and the slower form is dropped.
@@ -1172,7 +1333,7 @@ int z_phase(ggs_handle *h) {
   h->theta_ahead_iter = INT64_MIN;
   const bool ahead = h->overlap_theta && h->side && h->D > 0;
   const int32_t P = (int32_t)h->part_doc.size() - 1;   // 1 for a small corpus
-  if (ahead && P > 1 && h->z_stream) {
+  if (ahead && P > 1 && h->plan.stream()) {
     // part by part: z of part p on the main stream, then -- beside z of part p + 1 -- theta of iteration t+1 for the
     // documents of part p on the side stream; the last part's theta runs beside the counts and the Phi draw
     Events &N = h->evs[(h->ev_head + 1) % kEvRing];
@@ -1182,34 +1343,13 @@ int z_phase(ggs_handle *h) {
       HIP_TRY(h, hipStreamWaitEvent(h->side, h->ev_part[p], 0));
       if (p == 0) { N.theta_on_main = false; HIP_TRY(h, hipEventRecord(N.th0, h->side)); }
       if ((rc = launch_theta(h, h->side, h->d_theta_next, h->iteration + 1, h->part_doc[(size_t)p], h->part_doc[(size_t)p + 1],
-                             p + 1 < P ? h->theta_lds_beside_z : 0)))
+                             p + 1 < P ? h->cfg->theta_lds_beside_z : 0)))
         return rc;
     }
     HIP_TRY(h, hipEventRecord(N.th1, h->side));
     HIP_TRY(h, hipEventRecord(E.e[2], h->stream));
     h->theta_ahead_iter = (int64_t)h->iteration + 1;
   } else {
-    // TIMING EXPERIMENT (GGS_DEBUG_THETA_EARLY=1; results are WRONG on purpose): the next theta is launched BESIDE the z
-    // step instead of behind it -- drawn from the z the step is still writing.  What it measures is the best case of
-    // "theta_{t+1} of document part p beside the z step of part p + 1"  without the parts' own costs
-    // (an event packet, a launch and the drain of the persistent z waves each): the z step with a theta workgroup as the
-    // SIMDs' guest, and the counts + Phi chain alone behind it.  Needs LDS beside the z kernels: GGS_DEBUG_HOT shrinks
-    // the hot-word table.  DESIGN.md section 5 has the numbers.
-    static const int theta_early = debug_env("GGS_DEBUG_THETA_EARLY") ? std::atoi(debug_env("GGS_DEBUG_THETA_EARLY")) : 0;
-    bool early = false;
-    if (theta_early && ahead && !h->xg && h->z_sliced) {
-      Events &N = h->evs[(h->ev_head + 1) % kEvRing];
-      h->chain_on_side = false;
-      N.theta_on_main = false;
-      HIP_TRY(h, hipStreamWaitEvent(h->side, E.e[1], 0));
-      HIP_TRY(h, hipEventRecord(N.th0, h->side));
-      const int b = std::max(1, std::min(h->theta_docs_per_block, theta_early > 1 ? theta_early : 16));
-      const int bp = b | 1;
-      if ((rc = launch_theta(h, h->side, h->d_theta_next, h->iteration + 1, 0, -1, (int32_t)((size_t)h->K * bp * 8 + (size_t)b * 20 + kThetaQueueBytes), b))) return rc;
-      HIP_TRY(h, hipEventRecord(N.th1, h->side));
-      h->theta_ahead_iter = (int64_t)h->iteration + 1;
-      early = true;
-    }
     const bool counting = z_counts_itself(h) && h->C > 0;
     if (counting && !h->cnt_send_zeroed && (rc = clear_send_buffer(h, h->stream))) return rc;   // nobody cleared it behind the last reduce-scatter (or none came): counts no z step asked for are overwritten, as a count rebuild overwrites them
     h->hot_counted = false;
@@ -1217,25 +1357,7 @@ int z_phase(ggs_handle *h) {
     if (counting) { h->z_counted = true; h->cnt_send_zeroed = false; h->counted_sparse = false; }
     HIP_TRY(h, hipEventRecord(E.e[2], h->stream));      // the cold kernel's end; the hot chunks' stream is joined below, and by the theta draw's stream
     h->chain_on_side = h->chain_on_side && ahead;
-    // TIMING EXPERIMENT (GGS_DEBUG_THETA_TAIL_PCT=p; results are WRONG on purpose): the table kernels' stream ends ~0.2 ms
-    // before the cold kernel does, and their LDS is free from then on.  What would the next theta of the first p % of the
-    // documents cost and save if it ran THERE (behind z_warm_kernel, beside the cold kernel's tail), the rest behind the z
-    // step as always?  Drawn from the z the cold kernel is still writing -- the real thing needs the z step cut into two
-    // document parts whose first is complete by then.  DESIGN.md section 5 has the numbers.
-    static const int theta_tail_pct = debug_env("GGS_DEBUG_THETA_TAIL_PCT") ? std::max(0, std::min(100, std::atoi(debug_env("GGS_DEBUG_THETA_TAIL_PCT")))) : 0;
-    int64_t d_tail = 0;
-    if (theta_tail_pct && ahead && !early && !h->xg && h->z_sliced && h->z_split && h->chain_on_side && h->side_hot) {
-      if (!h->ev_theta_tail) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_theta_tail, hipEventDisableTiming));
-      d_tail = h->D * theta_tail_pct / 100;
-      // GGS_DEBUG_THETA_TAIL_STREAM=1: on a stream of its own behind the table kernels (the count + Phi chain, which runs on
-      // their stream, then starts when the cold kernel ends and not behind this draw)
-      static const bool own = debug_env("GGS_DEBUG_THETA_TAIL_STREAM") && std::atoi(debug_env("GGS_DEBUG_THETA_TAIL_STREAM")) == 1;
-      hipStream_t tail_on = own ? h->side : h->side_hot;
-      if (own) HIP_TRY(h, hipStreamWaitEvent(h->side, h->ev_hot_join, 0));
-      if ((rc = launch_theta(h, tail_on, h->d_theta_next, h->iteration + 1, 0, d_tail, h->theta_lds_main, h->theta_b_main))) return rc;
-      HIP_TRY(h, hipEventRecord(h->ev_theta_tail, tail_on));
-    }
-    if (ahead && !early) {
+    if (ahead) {
       // theta of iteration t+1 from the z just drawn, concurrent with the counts and the Phi draw
       Events &N = h->evs[(h->ev_head + 1) % kEvRing];
       hipStream_t ts = h->chain_on_side ? h->stream : h->side;
@@ -1243,8 +1365,7 @@ int z_phase(ggs_handle *h) {
       if (h->hot_join_pending) HIP_TRY(h, hipStreamWaitEvent(ts, h->ev_hot_join, 0));   // the theta draw reads the hot chunks' z as well
       N.theta_on_main = h->chain_on_side;
       if (!h->chain_on_side) HIP_TRY(h, hipEventRecord(N.th0, ts));
-      if ((rc = launch_theta(h, ts, h->d_theta_next, h->iteration + 1, d_tail, -1, h->chain_on_side ? h->theta_lds_main : 0, h->chain_on_side ? h->theta_b_main : 0))) return rc;
-      if (d_tail) HIP_TRY(h, hipStreamWaitEvent(ts, h->ev_theta_tail, 0));
+      if ((rc = launch_theta(h, ts, h->d_theta_next, h->iteration + 1, 0, -1, h->chain_on_side ? h->plan.theta_lds_main : 0, h->chain_on_side ? h->plan.theta_docs_main : 0))) return rc;
       HIP_TRY(h, hipEventRecord(N.th1, ts));
       h->theta_ahead_iter = (int64_t)h->iteration + 1;
     }
@@ -1394,8 +1515,7 @@ int setup_exchange(ggs_handle *h, Exchange *x) {
     // other libraries' blocking streams is exactly the convention not to rely on.  HIGH priority: measured with RCCL
     // and a torch process group in the process, a normal-priority stream shares its hardware queue with theirs and the
     // sweep's phases stretch (one rank: 2.59 ms per sweep against 1.93 on a high-priority stream or the null stream).
-    static const bool stay = debug_env("GGS_DEBUG_OWN_STREAM") && std::atoi(debug_env("GGS_DEBUG_OWN_STREAM")) == 0;   // experiments
-    if (!stay) {
+    if (!(debug_env("GGS_DEBUG_OWN_STREAM") && std::atoi(debug_env("GGS_DEBUG_OWN_STREAM")) == 0)) {   // 0: experiments
       int lo = 0, hi = 0;
       (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
       HIP_TRY(h, hipStreamCreateWithPriority(&h->own_stream, hipStreamNonBlocking, hi));
@@ -1457,6 +1577,8 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device_id < 0 || cfg->device_id >= ndev) return GGS_ERR_HIP;
   ggs_handle *h = new (std::nothrow) ggs_handle();
   if (!h) return GGS_ERR_HIP;
+  const Knobs kn;                                      // every GGS_DEBUG_* variable this call reads
+  // 1. the model
   h->K = cfg->num_topics; h->V = cfg->num_types; h->device = cfg->device_id;
   h->Ks = h->Ksm = h->K; h->k0 = 0;
   h->Kp = (h->K + 1) & ~1;
@@ -1473,273 +1595,72 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     h->spalias = true; h->flags |= GGS_FLAG_PCGS;
   }
   h->phi_burn_in = cfg->phi_burn_in; h->phi_thin = cfg->phi_mean_thin > 0 ? cfg->phi_mean_thin : 1;
-  if (const char *ab = debug_env("GGS_DEBUG_ABLATE")) h->ablate = std::atoi(ab);
   h->alpha.assign(h->K, cfg->alpha_scalar);
   if (cfg->alpha) std::copy(cfg->alpha, cfg->alpha + h->K, h->alpha.begin());
   for (double a : h->alpha)
     if (!(a > 0)) { delete h; return GGS_ERR_BAD_ARG; }
+  // 2. the handle's own switches
+  // GGS_DEBUG_MARGIN: above 1 the margins force the exact replays in tests.  Below 1 voids the proof, so only the float32 cold
+  // kernel takes it (its decided draw is a count of partial sums, always a topic < K); the checkpoint-and-refine walks of the
+  // fp64 margin kernels keep >= 1, where a wrong slice could walk them out of it
+  if (kn.margin.set) { h->margin_scale = std::max(1.0, kn.margin.f); h->margin_scale32 = std::max(0.0, kn.margin.f); }
+  if (kn.chain.set) h->exact_sum = kn.chain.v == 0;
+  if (kn.guided.set) h->sum_guided = kn.guided.v != 0;
+  if (kn.no_overlap.set) h->overlap_theta = kn.no_overlap.v == 0;
+  if (kn.theta_main.set) { h->theta_main = kn.theta_main.v != 0; h->theta_main_always = kn.theta_main.v == 2; }
+  if (kn.gamma_queue.set) h->gamma_queue_cap = std::max(0, kn.gamma_queue.v);
+  h->sum_nseg = (h->V + kSumSegRows - 1) / kSumSegRows;
 
   int rc = GGS_OK;
   auto bail = [&](int code) { ggs_destroy(h); return code; };
+  // 3. the device and the launches this handle can make on it
   if (hipSetDevice(h->device) != hipSuccess) return bail(GGS_ERR_HIP);
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) return bail(GGS_ERR_HIP);
     h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
-  // LDS budget of the z kernel: a tile of T token rows + one theta row per wave.  The waves
-  // are persistent and stride the chunk table statically, so the grid must not exceed what
-  // is truly co-resident: measured on MI355X, LDS is handed out in granules (6 x 26,912 B
-  // do not fit a CU although the occupancy API says they do), so residency is computed
-  // with the request rounded up to 2 KiB.  T is the largest tile that still lets 6
-  // single-wave workgroups share a CU -- the passes are latency chains, so waves in flight
-  // matter more than lanes in use -- but at least 8 rows.
-  {
-    constexpr int kGranule = 2048;
-    auto alloc_of = [&](int bytes) { return (bytes + kGranule - 1) / kGranule * kGranule; };
-    const int pitch = h->pitch16 * 16, thbytes = ((h->Kp * 8 + 15) / 16) * 16;
-    // the sliced kernel tags chunk tokens (word ids) in bit 30
-    // score-register kernels up to K = 160: measured on the benchmark corpus (sweep, ms; round 3) K=136: 2.13 sliced / 2.40
-    // streaming, 152: 2.33 / 2.56, 160: 2.40 / 2.50, 164: 3.06 / 2.83, 168: 3.06 / 2.75, 184: 3.24 / 2.94 (round 2: 184: 3.55 /
-    // 3.64, 192: 4.22 / 3.59) -- from KMAX = 168 on the cold kernel fills the whole register file (256 + 256) and the one-pass
-    // streaming kernel with the next theta drawn beside it wins (the sliced kernels can take K up to kSlicedMaxTopics = 192:
-    // GGS_DEBUG_ZKERNEL=1)
-    const bool sliced_ok = h->K <= kSlicedMaxTopics && h->V < (1 << kSlotShift);
-    h->z_sliced = sliced_ok && h->K <= kSlicedDefaultTopics;
-    h->z_stream = !h->z_sliced && h->K > 2 * kSliceTopics;
-    if (const char *e = debug_env("GGS_DEBUG_ZKERNEL")) {          // 0: whole-row tile kernel, 1: sliced where possible, 2: streaming kernel where it applies, 3: its two-pass form
-      const int mode = std::atoi(e);
-      h->z_sliced = sliced_ok && mode == 1;
-      h->z_stream = (mode == 2 || mode == 3) ? h->K > 2 * kSliceTopics : (h->z_stream && mode != 0);
-      h->z_two_pass = mode == 3;
-      if (h->z_sliced) h->z_stream = false;
-    }
-    // above 1 the margins force the exact replays in tests.  Below 1 voids the proof, so only the float32 cold kernel takes
-    // it (its decided draw is a count of partial sums, always a topic < K); the checkpoint-and-refine walks of the fp64
-    // margin kernels keep >= 1, where a wrong slice could walk them out of it
-    if (const char *e = debug_env("GGS_DEBUG_MARGIN")) {
-      h->margin_scale = std::max(1.0, std::atof(e));
-      h->margin_scale32 = std::max(0.0, std::atof(e));
-    }
-    if (h->z_stream) {
-      // 64-token chunks, a 2-slot slice ring + the theta row zero-padded to whole slices (one-pass kernel: to whole
-      // checkpoint groups, plus a checkpoint per group and lane); no score registers, so 8 waves per CU fit the
-      // register file and LDS bounds the residency
-      h->z_tile_tokens = 64;
-      const int ns = (h->K + kSliceTopics - 1) / kSliceTopics;
-      // checkpoint group: the smallest that keeps the checkpoints in registers (K <= 256: one slice, <= 512: two, <= 1024: four); beyond, four slices and LDS
-      h->z_group = ns <= kRegCheckpoints ? 1 : ns <= 2 * kRegCheckpoints ? 2 : 4;
-      if (const char *e = debug_env("GGS_DEBUG_GROUP")) { const int gq = std::atoi(e); if (gq == 1 || gq == 2 || gq == 4) h->z_group = gq; }
-      const int ng = (ns + h->z_group - 1) / h->z_group;
-      h->z_regck = !h->z_two_pass && ng <= kRegCheckpoints;          // checkpoints in registers or in LDS
-      if (const char *e = debug_env("GGS_DEBUG_REGCK")) h->z_regck = h->z_regck && std::atoi(e) != 0;
-      if (!h->z_regck) h->z_group = 4;                               // the LDS-checkpoint kernel is instantiated for groups of four
-      const int ngl = (ns + h->z_group - 1) / h->z_group;
-      // Chunks of 64 consecutive tokens across ONE document boundary (two theta rows per wave) instead of near-equal
-      // cuts of single documents: 98 % of the lanes busy instead of 78 % at 200-token documents.  Where the second row
-      // would cost resident waves (K > 512: 8 KiB at K = 1024) the single-document chunks stay.
-      h->z_two_rows = !h->z_two_pass && h->K <= 512;
-      if (const char *e = debug_env("GGS_DEBUG_TWOROWS")) h->z_two_rows = !h->z_two_pass && std::atoi(e) != 0;
-      h->z_lds = h->z_two_pass ? kStreamRingSlots * kSliceBytes + ns * kSliceTopics * 8
-                               : kStream1RingSlots * kSliceBytes + (h->z_two_rows ? 2 : 1) * ngl * h->z_group * kSliceTopics * 8 + (h->z_regck ? 0 : ngl * 64 * 8);
-      if (h->z_lds > kMaxLdsBytes) return bail(GGS_ERR_UNSUPPORTED);   // K > ~16000: the theta row itself would need slicing
-      // the waves are persistent, so the grid must be what is truly co-resident -- and a CU's 160 KiB cannot be filled
-      // to the last granule: measured, 5 x 32 KiB and 4 x 40 KiB leave one workgroup waiting for a second round
-      // (z at K = 1024: 18.6 ms with 5 waves of 32 KiB requested, 12.7 ms with 4)
-      h->z_waves_per_cu = std::max(1, std::min(8, (kMaxLdsBytes - kGranule) / alloc_of(h->z_lds)));
-      if (const char *e = debug_env("GGS_DEBUG_WPC")) h->z_waves_per_cu = std::max(1, std::atoi(e));
-    } else if (h->z_sliced) {
-      // 64-token chunks, per wave the two theta rows and the slice ring, per workgroup (4 waves, one per SIMD) the hot-word table
-      // (the score registers take most of the 512-entry file)
-      h->z_tile_tokens = 64;
-      const int kmax = ((h->K + 7) / 8) * 8, ns = (kmax + kSliceTopics - 1) / kSliceTopics;
-      // the cold chunks from phiT32 (a 32-topic slice per 128 bytes); its wave LDS is the fp64 form's: the ring, then two
-      // float32 theta rows and the replay's KMAX products where the two fp64 theta rows were
-      h->z_f32 = !(debug_env("GGS_DEBUG_PHI64") && std::atoi(debug_env("GGS_DEBUG_PHI64")) == 1);
-      h->Kp32 = (h->K + kSlice32Topics - 1) / kSlice32Topics * kSlice32Topics;
-      // per wave: the chunk's kChunkDocs theta rows (zero-padded to KMAX), then the ring; a DMA's immediate slice offset
-      // (< ns*128) is subtracted from its LDS destination, so the ring must not start below that
-      h->ring_base = (std::max(kChunkDocs * kmax * 8, ns * 128) + 255) / 256 * 256;
-      h->wave_lds = h->ring_base + kRingSlots * kSliceBytes;
-      h->hot_pitch = ((h->K + 7) / 8) * 64 + 16;                     // KMAX doubles + one unit: an odd number of 16-byte units
-      if (const char *e = debug_env("GGS_DEBUG_SPLIT")) { h->z_split = std::atoi(e) != 0; h->z_split_forced = std::atoi(e) == 2; }   // 2: the split form without the timed comparison
-      h->z_split_allowed = h->z_split;
-      h->hot_wave_lds = (kChunkDocs * ns * kSliceTopics * 8 + 255) / 256 * 256;   // z_hot_kernel: two theta rows per wave (whole slices), then the table and its zeroed tail
-      // split: the two workgroups must fit one CU together, each request rounded up to the LDS allocation granule
-      h->hot_cap = h->z_split ? ((kMaxLdsBytes - alloc_of(kSlicedWaves * h->wave_lds) - kSlicedWaves * h->hot_wave_lds) / kGranule * kGranule - kHotTailBytes) / h->hot_pitch
-                              : (kMaxLdsBytes - kSlicedWaves * h->wave_lds) / h->hot_pitch;
-      h->hot_cap = std::max(0, std::min(255, h->hot_cap));
-      if (const char *e = debug_env("GGS_DEBUG_HOT")) h->hot_cap = std::max(0, std::min(h->hot_cap, std::atoi(e)));
-      h->z_lds = kSlicedWaves * h->wave_lds + h->hot_cap * h->hot_pitch;
-      h->z_waves_per_cu = kSlicedWaves;
-      // the warm tiers: the same LDS beside the cold kernel's workgroup, more of it for theta rows (warm_docs per wave), the rest a table
-      h->warm_docs = warm_docs_for(kmax);
-      h->warm_wave_lds = (h->warm_docs * (ns * kSliceTopics * 8 + kWarmThetaPad) + 255) / 256 * 256;
-      h->warm_cap = ((kMaxLdsBytes - alloc_of(kSlicedWaves * h->wave_lds) - kSlicedWaves * h->warm_wave_lds) / kGranule * kGranule - kHotTailBytes) / h->hot_pitch;
-      h->warm_cap = std::max(0, std::min(255, h->warm_cap));
-      if (h->warm_cap < 16) h->warm_cap = 0;                           // the table loads and barriers of a tier want tokens to pay them
-      if (const char *e = debug_env("GGS_DEBUG_WARM")) h->warm_tiers_max = std::max(0, std::min(kWarmMaxTiers, std::atoi(e)));
-      if (const char *e = debug_env("GGS_DEBUG_WARM_ROWS")) h->warm_cap = std::max(0, std::min(h->warm_cap, std::atoi(e)));
-      if (const char *e = debug_env("GGS_DEBUG_WARM_FILL")) h->warm_min_fill_pct = std::max(1, std::min(100, std::atoi(e)));
-      if (const char *e = debug_env("GGS_DEBUG_WARM_CPW")) h->warm_min_chunks_per_wave = std::max(0, std::atoi(e));
-    } else {
-    int T = (kMaxLdsBytes / 6 / kGranule * kGranule - thbytes) / pitch;
-    if (const char *e = debug_env("GGS_DEBUG_TILE")) T = std::atoi(e);
-    T = std::max(8, std::min(64, T));
-    h->z_tile_tokens = T;
-    h->z_lds = T * pitch + thbytes;
-    if (h->z_lds > kMaxLdsBytes) return bail(GGS_ERR_UNSUPPORTED);   // K > ~2400 needs a K-sliced kernel (not in this round)
-    h->z_waves_per_cu = std::max(1, std::min(8, (kMaxLdsBytes - kGranule) / alloc_of(h->z_lds)));
-    if (const char *e = debug_env("GGS_DEBUG_WPC")) h->z_waves_per_cu = std::max(1, std::atoi(e));
-    }
-  }
-  {
-    int B = 64;
-    auto lds_of = [&](int b) { const int bp = b | 1; return (int)((size_t)h->K * bp * 8 + (size_t)b * 20 + kThetaQueueBytes); };
-    while (B > 1 && lds_of(B) > 32 * 1024) B >>= 1;
-    if (lds_of(B) > kMaxLdsBytes) return bail(GGS_ERR_UNSUPPORTED);
-    // The request is padded to a quarter of the CU's LDS: at most 4 workgroups (16 waves) of the theta draw per CU.
-    // It runs on the side stream beside the Phi phase, which is the critical path; stream priority orders dispatch,
-    // not running waves, and measured with 5-6 resident workgroups theta finishes early (0.53 ms instead of 0.75)
-    // while the Phi phase it starves gets longer (0.67 -> 0.72 ms).
-    // ... and 24 KiB of every CU stay free for the main stream's own LDS users (the walk of the exact column sums,
-    // 14.5 KiB per workgroup: with the CU's LDS handed out to theta workgroups to the last granule it waited for the
-    // theta draw to END -- 5 ms at K = 1024).
-    h->theta_docs_per_block = B; h->theta_lds = std::max(lds_of(B), (kMaxLdsBytes - 24 * 1024) / 4);
-    // ... unless the theta draw is the critical leg itself (theta_main, below): then five workgroups per CU, of 16 documents
-    // each.  Measured at K = 100 on one box, ms per sweep (documents per workgroup x workgroups per CU): 32x4 1.60-1.61,
-    // 32x5 1.598-1.62, 24x5 1.593, 16x4 1.614, 16x5 1.568-1.587, 16x6 1.58, 16x8 1.598, 12x5 1.609, 8x8 1.635 -- the smaller
-    // workgroups leave the Phi chain beside them its pace (0.39 ms against 0.44), so that it ends before the theta draw does.
-    h->theta_b_main = std::min(B, 16);
-    if (const char *e = debug_env("GGS_DEBUG_THETA_B")) h->theta_b_main = std::max(1, std::min(B, std::atoi(e)));
-    h->theta_lds_main = std::max(lds_of(h->theta_b_main), (kMaxLdsBytes - 24 * 1024) / (debug_env("GGS_DEBUG_THETA_WGS") ? std::max(1, std::atoi(debug_env("GGS_DEBUG_THETA_WGS"))) : 5));
-    // K > 192 (one-pass streaming z kernel): theta workgroups small enough to sit BESIDE the z waves -- three of
-    // them, on the LDS the z waves give up -- so that the next theta of a part of the documents is drawn while the
-    // following parts are sampled (z_phase).  The padded request caps them at three per CU while z runs.
-    h->cfg_plain.parts = 1; h->cfg_plain.z_waves_per_cu = h->z_waves_per_cu; h->cfg_plain.theta_docs_per_block = h->theta_docs_per_block; h->cfg_plain.theta_lds = h->theta_lds;
-    if (const char *e = debug_env("GGS_DEBUG_ZPARTS")) { h->z_parts = std::max(1, std::min(8, std::atoi(e))); h->z_parts_forced = true; }
-    else h->z_parts = (h->z_stream && !h->z_two_pass && !(h->flags & GGS_FLAG_PCGS)) ? 8 : 1;   // measured at K = 1024: 1 part 18.4 ms per sweep, 2: 18.1, 4: 16.5, 8: 15.9
-    if (h->z_parts > 1 && h->z_stream && !h->z_two_pass) {
-      constexpr int kGranule = 2048;
-      const int kBeside = debug_env("GGS_DEBUG_BESIDE") ? std::max(1, std::atoi(debug_env("GGS_DEBUG_BESIDE"))) : 4;   // measured at K = 1024 (sweep): 2 -> 16.9 ms, 3 -> 16.1, 4 -> 15.0, 5 -> 15.0
-      auto alloc_of = [&](int bytes) { return (bytes + kGranule - 1) / kGranule * kGranule; };
-      int Bt = 64;
-      while (Bt > 1 && lds_of(Bt) > 10 * 1024) Bt >>= 1;
-      const int z_alloc = alloc_of(h->z_lds), zw = std::min(h->z_waves_per_cu, (kMaxLdsBytes - kGranule - kBeside * alloc_of(lds_of(Bt))) / z_alloc);
-      if (lds_of(Bt) <= 12 * 1024 && zw >= 2) {
-        h->z_waves_per_cu = zw;
-        h->theta_docs_per_block = Bt;
-        h->theta_lds_beside_z = std::max(lds_of(Bt), (kMaxLdsBytes - kGranule - zw * z_alloc) / kBeside / kGranule * kGranule);
-        h->theta_lds = std::max(lds_of(Bt), (kMaxLdsBytes - 24 * 1024) / 4);
-      } else {
-        h->z_parts = 1;
-      }
-    }
-    h->cfg_parts.parts = h->z_parts; h->cfg_parts.z_waves_per_cu = h->z_waves_per_cu; h->cfg_parts.theta_docs_per_block = h->theta_docs_per_block;
-    h->cfg_parts.theta_lds = h->theta_lds; h->cfg_parts.theta_lds_beside_z = h->theta_lds_beside_z;
-  }
-  if (h->z_sliced && (hipFuncSetAttribute(sliced_kernel_for(h->K), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess ||
-                      hipFuncSetAttribute(sliced32_kernel_for(h->K), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess ||
-                      hipFuncSetAttribute(hot_kernel_for(h->K), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess ||
-                      hipFuncSetAttribute(warm_kernel_for(h->K), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess))
-    return bail(GGS_ERR_HIP);
-  const void *zk[] = {reinterpret_cast<const void *>(z_kernel<1>), reinterpret_cast<const void *>(z_kernel<2>),
-                      reinterpret_cast<const void *>(z_kernel<4>), reinterpret_cast<const void *>(z_kernel<8>),
-                      reinterpret_cast<const void *>(z_kernel<16>), reinterpret_cast<const void *>(z_kernel<20>)};
+  if ((rc = plan_launches(h->K, h->V, h->flags, kn, h->plan))) return bail(rc);
+  h->cfg = &h->plan.cfg_parts;
+  h->z_split = h->plan.split;
   // The attribute is process-global per kernel, not per handle: always the hardware maximum, so that a later handle
   // with a smaller K never lowers the cap under a live one.
-  if (h->z_stream && (hipFuncSetAttribute(reinterpret_cast<const void *>(z_stream_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess ||
-                      hipFuncSetAttribute(reinterpret_cast<const void *>(z_stream1_kernel<true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess ||
-                      hipFuncSetAttribute(reinterpret_cast<const void *>(z_stream1_kernel<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess ||
-                      hipFuncSetAttribute(reinterpret_cast<const void *>(z_stream1_kernel<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess ||
-                      hipFuncSetAttribute(reinterpret_cast<const void *>(z_stream1_kernel<false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess))
-    return bail(GGS_ERR_HIP);
-  for (const void *f : zk)
-    if (!h->z_sliced && !h->z_stream && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess) return bail(GGS_ERR_HIP);
-  if (hipFuncSetAttribute(reinterpret_cast<const void *>(theta_kernel<kThetaBlock>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess)
-    return bail(GGS_ERR_HIP);
-  const size_t kv = (size_t)h->K * h->V;
-  if ((rc = dev_alloc(h, &h->d_alpha, h->K)) || (rc = dev_alloc(h, &h->d_phiT, (size_t)h->V * h->Kp + kPhiTailPadBytes / 8)) ||
+  for (const KernelLaunch *l : h->plan.all())
+    if (l->fn && hipFuncSetAttribute(l->fn, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess) return bail(GGS_ERR_HIP);
+  // 4. the model's buffers
+  const size_t kv = (size_t)h->K * h->V, phi_elems = (size_t)h->V * h->Kp + kPhiTailPadBytes / 8;
+  if ((rc = dev_alloc(h, &h->d_alpha, h->K)) || (rc = dev_alloc(h, &h->d_phiT, phi_elems)) ||
       (rc = dev_alloc(h, &h->d_mag, h->K)) || (rc = dev_alloc(h, &h->d_tot, h->K)) || (rc = dev_alloc(h, &h->d_n_wk, kv)) ||
       (rc = dev_alloc(h, &h->d_n_k, h->K)) || (rc = dev_alloc(h, &h->d_status, 4)))
     return bail(rc);
   if ((h->flags & GGS_FLAG_SAVE_PHI_MEAN) && (rc = dev_alloc(h, &h->d_phi_mean, kv))) return bail(rc);
-  if (h->z_sliced && h->z_f32) {
-    if ((rc = dev_alloc(h, &h->d_phiT32, (size_t)h->V * h->Kp32 + kPhiTailPadBytes / 4))) return bail(rc);
-    if (hipMemset(h->d_phiT32, 0, sizeof(float) * ((size_t)h->V * h->Kp32 + kPhiTailPadBytes / 4)) != hipSuccess) return bail(GGS_ERR_HIP);
-    if (debug_env("GGS_DEBUG_REPLAYS") && std::atoi(debug_env("GGS_DEBUG_REPLAYS")) == 1) {
+  if (h->plan.sliced() && h->plan.f32) {
+    const size_t n32 = (size_t)h->V * h->plan.Kp32 + kPhiTailPadBytes / 4;
+    if ((rc = dev_alloc(h, &h->d_phiT32, n32))) return bail(rc);
+    if (hipMemset(h->d_phiT32, 0, sizeof(float) * n32) != hipSuccess) return bail(GGS_ERR_HIP);
+    if (kn.replays.is(1)) {
       if ((rc = dev_alloc(h, &h->d_replays, 1))) return bail(rc);
       if (hipMemset(h->d_replays, 0, sizeof(unsigned long long)) != hipSuccess) return bail(GGS_ERR_HIP);
     }
   }
-  if (const char *e = debug_env("GGS_DEBUG_CHAIN")) h->exact_sum = std::atoi(e) == 0;
-  if (const char *e = debug_env("GGS_DEBUG_GUIDED")) h->sum_guided = std::atoi(e) != 0;
-  h->sum_nseg = (h->V + kSumSegRows - 1) / kSumSegRows;
   if (h->exact_sum && ((rc = dev_alloc(h, &h->d_sum_pref, ((size_t)h->sum_nseg + 1) * h->K)) ||
                        (rc = dev_alloc(h, &h->d_sum_fn, (size_t)h->sum_nseg * h->K * 4))))
     return bail(rc);
   if (hipMemcpy(h->d_alpha, h->alpha.data(), sizeof(double) * h->K, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemset(h->d_phiT, 0, sizeof(double) * ((size_t)h->V * h->Kp + kPhiTailPadBytes / 8)) != hipSuccess ||
+      hipMemset(h->d_phiT, 0, sizeof(double) * phi_elems) != hipSuccess ||
       hipMemset(h->d_n_wk, 0, sizeof(int32_t) * kv) != hipSuccess ||
       hipMemset(h->d_n_k, 0, sizeof(int32_t) * h->K) != hipSuccess || hipMemset(h->d_status, 0, 16) != hipSuccess ||
       (h->d_phi_mean && hipMemset(h->d_phi_mean, 0, sizeof(double) * kv) != hipSuccess))
     return bail(GGS_ERR_HIP);
-  if (h->spalias) {
-    if ((rc = dev_alloc(h, &h->d_alias_ps, kv)) || (rc = dev_alloc(h, &h->d_alias_a, kv)) || (rc = dev_alloc(h, &h->d_alias_tn, (size_t)h->V))) return bail(rc);
-    h->alias_wpb = alias_words_per_block(h->K);
-    h->alias_lds = (int32_t)alias_lds_bytes(h->K, h->alias_wpb);
-    h->alias_blocks_per_cu = std::max(1, std::min(16, (kMaxLdsBytes - 2048) / ((h->alias_lds + 2047) / 2048 * 2048)));
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(alias_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(spalias_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess)
-      return bail(GGS_ERR_HIP);
-  }
+  if (h->spalias && ((rc = dev_alloc(h, &h->d_alias_ps, kv)) || (rc = dev_alloc(h, &h->d_alias_a, kv)) || (rc = dev_alloc(h, &h->d_alias_tn, (size_t)h->V)))) return bail(rc);
   if (h->polyaurn) {
     std::vector<double> T;
     build_poisson_table(h->beta, h->pa_L, T);
     h->pa_t00 = T[0];
-    if ((rc = dev_alloc(h, &h->d_pa_table, T.size())) || (rc = dev_alloc(h, &h->d_pa_acc, (size_t)h->K * kPoissonAccStride))) return bail(rc);
-    if (hipMemcpy(h->d_pa_table, T.data(), sizeof(double) * T.size(), hipMemcpyHostToDevice) != hipSuccess) return bail(GGS_ERR_HIP);
+    if ((rc = upload(h, &h->d_pa_table, T)) || (rc = dev_alloc(h, &h->d_pa_acc, (size_t)h->K * kPoissonAccStride))) return bail(rc);
   }
-  if (h->flags & GGS_FLAG_PCGS) {
-    // the wave-per-document kernel: any K up to 4096, any document length
-    if (h->K <= kPcgsWaveMaxTopics) {
-      int nb = 1;
-      while (nb * 128 < h->Kp) nb *= 2;
-      h->pcgs_wave_nb = nb;
-      h->pcgs_wave_lds = nb * 128 * 12;                        // counts int32 + alpha fp64
-      // waves per CU (the grid is persistent: exactly what is resident): what the kernel's registers allow (asked of the
-      // runtime) and what LDS allows (computed here: the runtime's answer ignores the 2 KiB allocation granule)
-      int by_regs = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, pcgs_wave_kernel_for(nb, h->collapsed, h->polyaurn), 64, (size_t)h->pcgs_wave_lds) != hipSuccess || by_regs < 1) by_regs = 1;
-      h->pcgs_wave_waves_per_cu = std::max(1, std::min(std::min(by_regs, 32), (kMaxLdsBytes - 2048) / ((h->pcgs_wave_lds + 2047) / 2048 * 2048)));
-    }
-    h->pcgs_wave_forced = h->K > (h->collapsed ? kCollapsedWaveFromTopics : h->polyaurn ? kPolyaurnWaveFromTopics : kPcgsWaveFromTopics);
-    if (const char *e = debug_env("GGS_DEBUG_PCGS_WAVE")) h->pcgs_wave_forced = std::atoi(e) != 0;
-    if (h->pcgs_wave_forced && !h->pcgs_wave_nb) return bail(GGS_ERR_UNSUPPORTED);   // more than 4096 topics
-    if (h->pcgs_wave_nb && hipFuncSetAttribute(pcgs_wave_kernel_for(h->pcgs_wave_nb, h->collapsed, h->polyaurn), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess)
-      return bail(GGS_ERR_HIP);
-    // pcgs_z_kernel: slice ring + alpha row + int16 [KT][64] document counts per single-wave workgroup
-    const int ns = std::max(kPcgsRingSlots - 1, (h->K + kSliceTopics - 1) / kSliceTopics), kt = ns * kSliceTopics;
-    h->pcgs_sliced = h->K <= kSlicedMaxTopics;
-    if (const char *e = debug_env("GGS_DEBUG_PCGS_STREAM")) h->pcgs_sliced = h->pcgs_sliced && std::atoi(e) == 0;
-    if (h->pcgs_sliced) {
-      const int kmax = ((h->K + 7) / 8) * 8;                       // alpha row + counts below the ring (pcgs_sliced_kernel's kHead)
-      h->pcgs_lds = (kmax * 8 + kmax * 128 + 255) / 256 * 256 + kPcgsRingSlots * kSliceBytes;
-    } else {
-      h->pcgs_lds = kPcgsRingSlots * kSliceBytes + kt * 8 + kt * 128;
-    }
-    if (h->pcgs_lds > kMaxLdsBytes && !h->pcgs_wave_forced) return bail(GGS_ERR_UNSUPPORTED);
-    h->pcgs_waves_per_cu = std::max(1, std::min(8, (kMaxLdsBytes - 2048) / ((h->pcgs_lds + 2047) / 2048 * 2048)));   // never a CU filled to the last granule (see z_waves_per_cu)
-    if (!h->pcgs_wave_forced &&
-        hipFuncSetAttribute(h->pcgs_sliced ? (h->collapsed ? collapsed_kernel_for(h->K) : h->polyaurn ? polyaurn_kernel_for(h->K) : pcgs_kernel_for(h->K))
-                            : h->collapsed ? reinterpret_cast<const void *>(pcgs_z_kernel<true>)
-                            : h->polyaurn  ? reinterpret_cast<const void *>(polyaurn_z_kernel) : reinterpret_cast<const void *>(pcgs_z_kernel<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess)
-      return bail(GGS_ERR_HIP);
-    if (h->collapsed && ((rc = dev_alloc(h, &h->d_lcg, 2)) ||
-                         hipFuncSetAttribute(reinterpret_cast<const void *>(collapsed_serial_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess))
-      return bail(rc ? rc : GGS_ERR_HIP);
-  }
+  if (h->collapsed && (rc = dev_alloc(h, &h->d_lcg, 2))) return bail(rc);
+  // 5. events and streams
   for (auto &e : h->ev_part)
     if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return bail(GGS_ERR_HIP);
   for (auto &E : h->evs) {
@@ -1749,9 +1670,6 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
       if (hipEventCreate(&e) != hipSuccess) return bail(GGS_ERR_HIP);
     if (hipEventCreate(&E.th0) != hipSuccess || hipEventCreate(&E.th1) != hipSuccess) return bail(GGS_ERR_HIP);
   }
-  if (const char *e = debug_env("GGS_DEBUG_NO_OVERLAP")) h->overlap_theta = std::atoi(e) == 0;
-  if (const char *e = debug_env("GGS_DEBUG_THETA_MAIN")) { h->theta_main = std::atoi(e) != 0; h->theta_main_always = std::atoi(e) == 2; }
-  if (const char *e = debug_env("GGS_DEBUG_GAMMA_QUEUE")) h->gamma_queue_cap = std::max(0, std::atoi(e));
   {
     // lowest priority: the theta draw fills whatever the Phi phase (on the caller's stream) leaves idle
     int lo = 0, hi = 0;
@@ -1778,20 +1696,13 @@ void ggs_destroy(ggs_handle *h) {
       fprintf(stderr, "[ggs] z replays: %llu tokens in %lld launches of z_sliced32_kernel (%.2f per launch)\n", n, (long long)h->z_f32_launches,
               h->z_f32_launches ? (double)n / (double)h->z_f32_launches : 0.0);
   }
-  void *bufs[] = {h->d_doc_ptr, h->d_chunk_start, h->d_tok, h->d_z, h->d_chunk_doc, h->d_chunk_len, h->d_alpha, h->d_theta, h->d_theta_next,
-                  h->d_phiT, h->d_mag, h->d_tot, h->d_phi_mean, h->d_n_wk, h->d_n_k, h->d_perm, h->d_inv_perm, h->d_zw, h->d_seg_word, h->d_seg_begin,
-                  h->d_status, h->d_scratch, h->d_sum_pref, h->d_sum_fn, h->d_ct_tok, h->d_ct_idx, h->d_ct_ip, h->d_c_docs, h->d_hot_words, h->d_order,
-                  h->d_test_ptr, h->d_test_tok, h->d_test_ll, h->d_test_docs, h->d_koff, h->d_cnt_send, h->d_cnt_own, h->d_cnt_all, h->d_n_k_own,
-                  h->d_heldout_spill, h->d_phi_own, h->d_phi_all0, h->d_phi_all1, h->d_mag_own, h->d_krank, h->d_kcol, h->d_lcg, h->d_chunk_doc1,
-                  h->d_hseg_word, h->d_hseg_begin, h->d_hseg_end, h->d_sp_count, h->d_sp_cnt32, h->d_sp_all, h->d_sp_send, h->d_sp_recv, h->d_sp_wg_count,
-                  h->d_sp_wg_off, h->d_ht_pack, h->d_h_docs, h->d_wt_pack, h->d_w_docs, h->d_warm_words, h->d_warm_meta, h->d_phiT32, h->d_replays,
-                  h->d_pa_table, h->d_pa_acc, h->d_alias_ps, h->d_alias_a, h->d_alias_tn};
-  for (void *b : bufs)
-    if (b) (void)hipFree(b);
+  for (void **slot : h->owned)
+    if (*slot) (void)hipFree(*slot);
+  if (h->d_scratch) (void)hipFree(h->d_scratch);
+  if (h->d_heldout_spill) (void)hipFree(h->d_heldout_spill);
   exchange_free(h->xg);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
-  if (h->ev_theta_tail) (void)hipEventDestroy(h->ev_theta_tail);
   if (h->ev_half_drawn) (void)hipEventDestroy(h->ev_half_drawn);
   if (h->ev_half_gathered) (void)hipEventDestroy(h->ev_half_gathered);
   for (auto &e : h->ev_part)
@@ -1824,6 +1735,7 @@ int ggs_set_stream(ggs_handle *h, void *hip_stream) {
 }
 
 int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32_t *tokens, int64_t doc_base, int64_t tok_base) {
+  // 1. validate, before the handle is touched
   if (!h || D < 0 || !doc_ptr || doc_base < 0 || tok_base < 0) return set_err(h, GGS_ERR_BAD_ARG, "bad corpus arguments");
   if (doc_ptr[0] != 0) return set_err(h, GGS_ERR_BAD_ARG, "doc_ptr[0] must be 0");
   for (int64_t d = 0; d < D; ++d)
@@ -1837,326 +1749,74 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   if (rc) return rc;
   if ((rc = drop_theta_ahead(h))) return rc;
 
-  // z-kernel work items: each document is cut into ceil(len/T) near-equal chunks of <= T tokens.
-  std::vector<int64_t> cstart;
-  std::vector<int32_t> cdoc, clen;
-  cstart.reserve((size_t)(N / 48 + D)); cdoc.reserve(cstart.capacity()); clen.reserve(cstart.capacity());
-  std::vector<int32_t> cdoc1;
-  const bool two_rows = h->z_stream && h->z_two_rows;
-  if (two_rows) {
-    // 64 consecutive tokens per chunk, across at most one document boundary; clen = tokens | tokens of the first document << 8
-    int64_t pos = 0;
-    int64_t d = 0;
-    while (pos < N) {
-      while (doc_ptr[d + 1] <= pos) ++d;                            // the document of token `pos` (empty documents hold none)
-      const int64_t take0 = std::min<int64_t>(64, doc_ptr[d + 1] - pos);
-      int64_t len = take0, d1 = d;
-      if (take0 < 64 && pos + take0 < N) {                          // room left: the next non-empty document joins
-        d1 = d + 1;
-        while (doc_ptr[d1 + 1] <= pos + take0) ++d1;
-        len += std::min<int64_t>(64 - take0, doc_ptr[d1 + 1] - (pos + take0));
-      }
-      cstart.push_back(pos); cdoc.push_back((int32_t)d); cdoc1.push_back((int32_t)d1);
-      clen.push_back((int32_t)(len | (take0 << 8)));
-      pos += len;
-    }
-  } else
-  for (int64_t d = 0; d < D; ++d) {
-    const int64_t len = doc_ptr[d + 1] - doc_ptr[d];
-    if (len == 0) continue;
-    const int64_t T = h->z_tile_tokens, n = (len + T - 1) / T, base = len / n, rem = len % n;
-    int64_t s = doc_ptr[d];
-    for (int64_t j = 0; j < n; ++j) {
-      const int64_t l = base + (j < rem ? 1 : 0);
-      cstart.push_back(s); cdoc.push_back((int32_t)d); clen.push_back((int32_t)l);
-      s += l;
-    }
-  }
-  // count-kernel work items: tokens sorted by word (counting sort, stable), each word's run
-  // cut into segments of at most kSegTokens entries.
-  constexpr int64_t kSegTokens = 4096;
-  std::vector<int32_t> perm((size_t)N), seg_word, seg_begin, hot_words, warm_cand, hseg_word, hseg_begin, hseg_end;
-  {
-    std::vector<int64_t> wptr((size_t)h->V + 1, 0);
-    for (int64_t i = 0; i < N; ++i) wptr[(size_t)tokens[i] + 1]++;
-    for (int32_t w = 0; w < h->V; ++w) wptr[(size_t)w + 1] += wptr[(size_t)w];
-    for (int32_t w = 0; w < h->V; ++w)
-      for (int64_t b = wptr[(size_t)w]; b < wptr[(size_t)w + 1]; b += kSegTokens) { seg_word.push_back(w); seg_begin.push_back((int32_t)b); }
-    seg_begin.push_back((int32_t)N);
-    std::vector<int64_t> cur(wptr.begin(), wptr.end() - 1);
-    for (int64_t i = 0; i < N; ++i) perm[(size_t)cur[(size_t)tokens[i]]++] = (int32_t)i;
-    // the hot-word table of the sliced z kernel: the hot_cap most frequent words of THIS handle's tokens
-    if (h->z_sliced && h->hot_cap > 0) {
-      std::vector<int32_t> order((size_t)h->V);
-      for (int32_t w = 0; w < h->V; ++w) order[(size_t)w] = w;
-      const size_t nh = (size_t)std::min<int32_t>(h->hot_cap, h->V);
-      // ... and, behind them, the candidates of the warm tiers (z_warm_kernel): the next warm_tiers_max x warm_cap words
-      const size_t nw = std::min<size_t>((size_t)h->V, nh + (size_t)h->warm_tiers_max * (size_t)h->warm_cap);
-      auto freq = [&](int32_t w) { return wptr[(size_t)w + 1] - wptr[(size_t)w]; };
-      std::partial_sort(order.begin(), order.begin() + nw, order.end(), [&](int32_t a, int32_t b) { return freq(a) != freq(b) ? freq(a) > freq(b) : a < b; });
-      for (size_t r = 0; r < nh && freq(order[r]) > 0; ++r) hot_words.push_back(order[r]);
-      for (size_t r = nh; r < nw && freq(order[r]) > 0; ++r) warm_cand.push_back(order[r]);
-      for (int32_t w : hot_words)
-        for (int64_t b = wptr[(size_t)w]; b < wptr[(size_t)w + 1]; b += kSegTokens) {
-          hseg_word.push_back(w); hseg_begin.push_back((int32_t)b); hseg_end.push_back((int32_t)std::min(b + kSegTokens, wptr[(size_t)w + 1]));
-        }
-    }
-    // a segment ends where the next begins, or at the end of its word's run
-    // (seg_begin[s+1] is the next segment's start, which is exactly that)
-  }
-  if (h->flags & GGS_FLAG_PCGS) {
-    // documents longest first: the 64 of a pcgs wave are then equally long
-    std::vector<int32_t> order((size_t)D);
-    int64_t longest = 0;
-    for (int64_t d = 0; d < D; ++d) { order[(size_t)d] = (int32_t)d; longest = std::max(longest, doc_ptr[d + 1] - doc_ptr[d]); }
+  // 2. what this corpus chooses between the plan's entries.  The parts of the z step pay where the theta draw (D x K
+  // gammas) is longer than the Phi chain it otherwise hides beside (V x K gammas): the excess is what is drawn beside
+  // the z parts.  Measured: D = 100 000, V = 50 000, K = 1 024: 1 part 18.4 ms per sweep, 2: 18.1, 4: 16.5, 8: 15.9;
+  // D = 18 846, V = 60 000, K = 200: 8 parts 1.112, 4: 1.071, 2: 1.019, 1: 1.006 (every part costs an event packet, a launch
+  // and the drain of the persistent z waves).
+  const LaunchPlan &pl = h->plan;
+  int32_t parts = pl.cfg_parts.parts;
+  if (!pl.parts_forced && parts > 1) parts = D <= (int64_t)h->V ? 1 : D < 2 * (int64_t)h->V ? std::min(parts, 4) : parts;
+  h->cfg = parts > 1 ? &pl.cfg_parts : &pl.cfg_plain;
+
+  // 3. the lists, on the host (ggs_corpus_lists.hpp)
+  CorpusShape shape;
+  shape.V = h->V; shape.pcgs = (h->flags & GGS_FLAG_PCGS) != 0; shape.sliced = pl.sliced(); shape.two_rows = pl.two_rows;
+  shape.tile_tokens = pl.tile_tokens; shape.z_parts = parts;
+  shape.hot_cap = pl.hot_cap; shape.warm_cap = pl.warm_cap; shape.warm_docs = pl.warm_docs;
+  shape.warm_tiers_max = pl.warm_tiers_max; shape.warm_min_fill_pct = pl.warm_min_fill_pct; shape.warm_min_chunks_per_wave = pl.warm_min_chunks_per_wave;
+  shape.sliced_waves = (int64_t)h->num_cus * kSlicedWaves; shape.pcgs_waves = (int64_t)h->num_cus * pl.lane.per_cu;
+  const CorpusLists L = build_corpus_lists(shape, D, doc_ptr, tokens);
+  if (shape.pcgs) {
     // the lane-per-document kernels keep the counts as int16: a longer document sends the corpus to the wave-per-document kernel
-    h->pcgs_wave = h->pcgs_wave_forced || longest > kPcgsMaxDocLen;
-    if (h->pcgs_wave && !h->pcgs_wave_nb) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=pcgs: a document of 32768 tokens or more with more than 4096 topics");
+    h->pcgs_wave = pl.wave_forced || L.longest > kPcgsMaxDocLen;
+    if (h->pcgs_wave && !pl.wave.fn) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=pcgs: a document of 32768 tokens or more with more than 4096 topics");
     if (h->spalias) {
       // the list of a document's non-zero topics holds at most min(K, its length) entries; the resident waves are what LDS allows,
       // at most the CU's 32
-      h->sp_cap = (int32_t)std::max<int64_t>(1, std::min<int64_t>(h->K, longest));
-      h->sp_lds = (int32_t)spalias_lds_bytes(h->K, h->sp_cap);
-      h->sp_waves_per_cu = std::max(1, std::min(32, (kMaxLdsBytes - 2048) / ((h->sp_lds + 2047) / 2048 * 2048)));
-      if (const char *e = debug_env("GGS_DEBUG_SPALIAS_WPC")) h->sp_waves_per_cu = std::max(1, std::min(h->sp_waves_per_cu, std::atoi(e)));
+      h->sp_cap = (int32_t)std::max<int64_t>(1, std::min<int64_t>(h->K, L.longest));
+      h->sp_z = pl.spalias;
+      h->sp_z.lds = (int)spalias_lds_bytes(h->K, h->sp_cap);
+      h->sp_z.per_cu = lds_workgroups_per_cu(h->sp_z.lds, 32);
+      if (const char *e = debug_env("GGS_DEBUG_SPALIAS_WPC")) h->sp_z.per_cu = std::max(1, std::min(h->sp_z.per_cu, std::atoi(e)));
     }
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return doc_ptr[a + 1] - doc_ptr[a] > doc_ptr[b + 1] - doc_ptr[b]; });
-    // A wave takes the groups w, w + W, ... of this list (W = the resident waves).  With between one and two rounds of
-    // groups (the benchmark corpus: 1 563 groups for 1 024 waves) the plain order would give the waves of the 539
-    // LONGEST groups a second one: 420 steps against 205 for the rest.  Instead the W - m longest groups run alone and
-    // the 2m shortest are paired long-with-short on the last m waves (-1 = no document): 360 steps at most.
-    const int64_t n_groups = (D + 63) / 64, W = (int64_t)h->num_cus * h->pcgs_waves_per_cu;
-    h->pcgs_order_len = D;
-    if (n_groups > W && n_groups <= 2 * W) {
-      const int64_t m = n_groups - W;
-      std::vector<int32_t> padded((size_t)(2 * W * 64), -1);
-      auto put = [&](int64_t position, int64_t group) {
-        for (int64_t j = 0; j < 64 && group * 64 + j < D; ++j) padded[(size_t)(position * 64 + j)] = order[(size_t)(group * 64 + j)];
-      };
-      for (int64_t g = 0; g < W; ++g) put(g, g);
-      for (int64_t j = 0; j < m; ++j) put(W + (W - m + j), n_groups - 1 - j);
-      order.swap(padded);
-      h->pcgs_order_len = (int64_t)order.size();
-    }
-    if ((rc = dev_alloc(h, &h->d_order, order.size()))) return rc;
-    if (!order.empty()) HIP_TRY(h, hipMemcpy(h->d_order, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice));
   }
-  h->D = D; h->N = N; h->C = (int64_t)cstart.size(); h->S = (int64_t)seg_word.size(); h->doc_base = doc_base; h->tok_base = tok_base;
-  {
-    // the parts of the z step (z_phase): consecutive documents with about equal token counts, and their chunk ranges
-    // Parts pay where the theta draw (D x K gammas) is longer than the Phi chain it otherwise hides beside (V x K gammas):
-    // the excess is what is drawn beside the z parts.  Measured: D = 100 000, V = 50 000, K = 1 024: 1 part 18.4 ms per
-    // sweep, 2: 18.1, 4: 16.5, 8: 15.9; D = 18 846, V = 60 000, K = 200: 8 parts 1.112, 4: 1.071, 2: 1.019, 1: 1.006 (every part
-    // costs an event packet, a launch and the drain of the persistent z waves).
-    {
-      int32_t want = h->cfg_parts.parts;
-      if (!h->z_parts_forced && want > 1) want = D <= (int64_t)h->V ? 1 : D < 2 * (int64_t)h->V ? std::min(want, 4) : want;
-      const ggs_handle::ZCfg &c = want > 1 ? h->cfg_parts : h->cfg_plain;
-      h->z_parts = want; h->z_waves_per_cu = c.z_waves_per_cu; h->theta_docs_per_block = c.theta_docs_per_block; h->theta_lds = c.theta_lds;
-      h->theta_lds_beside_z = c.theta_lds_beside_z;
-    }
-    const int32_t P = (h->z_parts > 1 && D >= 64 * h->z_parts) ? h->z_parts : 1;
-    h->part_doc.assign((size_t)P + 1, D); h->part_chunk.assign((size_t)P + 1, (int64_t)cstart.size());
-    h->part_doc[0] = 0; h->part_chunk[0] = 0;
-    int64_t d = 0;
-    size_t c = 0;
-    for (int32_t p = 1; p < P; ++p) {
-      const int64_t want = N * p / P;
-      while (d < D && doc_ptr[d] < want) ++d;
-      while (c < cdoc.size() && cdoc[c] < d) ++c;
-      h->part_doc[(size_t)p] = d; h->part_chunk[(size_t)p] = (int64_t)c;
-    }
-    if (P != h->z_parts) { h->part_doc.resize(2); h->part_chunk.resize(2); h->part_doc[1] = D; h->part_chunk[1] = (int64_t)cstart.size(); }
-  }
-  if ((rc = dev_alloc(h, &h->d_doc_ptr, (size_t)D + 1)) || (rc = dev_alloc(h, &h->d_tok, (size_t)N)) || (rc = dev_alloc(h, &h->d_z, (size_t)N)) ||
-      (rc = dev_alloc(h, &h->d_theta, (size_t)D * h->K + 2)) || (rc = dev_alloc(h, &h->d_theta_next, (size_t)D * h->K + 2)) || (rc = dev_alloc(h, &h->d_chunk_start, (size_t)h->C)) ||
-      (rc = dev_alloc(h, &h->d_chunk_doc, (size_t)h->C)) || (rc = dev_alloc(h, &h->d_chunk_len, (size_t)h->C)) ||
-      (rc = dev_alloc(h, &h->d_perm, (size_t)N)) || (rc = dev_alloc(h, &h->d_inv_perm, (size_t)N)) || (rc = dev_alloc(h, &h->d_zw, (size_t)N)) || (rc = dev_alloc(h, &h->d_seg_word, (size_t)h->S)) ||
-      (rc = dev_alloc(h, &h->d_seg_begin, (size_t)h->S + 1)))
+  h->D = D; h->N = N; h->C = (int64_t)L.cstart.size(); h->S = (int64_t)L.seg_word.size(); h->doc_base = doc_base; h->tok_base = tok_base;
+  h->part_doc = L.part_doc; h->part_chunk = L.part_chunk;
+  h->pcgs_order_len = (int64_t)L.order.size();
+  h->num_hot = (int32_t)L.hot_words.size(); h->HS = (int64_t)L.hseg_word.size();
+  h->Cc = L.Cc; h->Cs = L.Cs;
+  h->warm_tiers = L.warm_tiers; h->num_warm = L.num_warm; h->Cw = L.Cw; h->warm_chunks_max = L.warm_chunks_max; h->warm_rows_max = L.warm_rows_max;
+
+  // 4. upload (on the null stream), the state of the corpus zeroed
+  const size_t theta_elems = (size_t)D * h->K + 2;
+  if ((rc = upload(h, &h->d_doc_ptr, doc_ptr, (size_t)D + 1)) || (rc = upload(h, &h->d_tok, tokens, (size_t)N)) ||
+      (rc = upload(h, &h->d_chunk_start, L.cstart)) || (rc = upload(h, &h->d_chunk_doc, L.cdoc)) || (rc = upload(h, &h->d_chunk_len, L.clen)) ||
+      (pl.two_rows && h->C && (rc = upload(h, &h->d_chunk_doc1, L.cdoc1))) ||
+      (rc = upload(h, &h->d_perm, L.perm)) || (rc = upload(h, &h->d_inv_perm, L.inv)) ||
+      (rc = upload(h, &h->d_seg_word, L.seg_word)) || (rc = upload(h, &h->d_seg_begin, L.seg_begin)) ||
+      (rc = upload(h, &h->d_hseg_word, L.hseg_word)) || (rc = upload(h, &h->d_hseg_begin, L.hseg_begin)) || (rc = upload(h, &h->d_hseg_end, L.hseg_end)) ||
+      (shape.pcgs && (rc = upload(h, &h->d_order, L.order))))
     return rc;
-  std::vector<int32_t> inv((size_t)N);
-  if (N) {
-    HIP_TRY(h, hipMemcpy(h->d_perm, perm.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice));
-    for (int64_t i = 0; i < N; ++i) inv[(size_t)perm[(size_t)i]] = (int32_t)i;
-    HIP_TRY(h, hipMemcpy(h->d_inv_perm, inv.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice));
-  }
-  HIP_TRY(h, hipMemset(h->d_zw, 0, sizeof(int32_t) * std::max<size_t>((size_t)N, 1)));
-  if (h->S) HIP_TRY(h, hipMemcpy(h->d_seg_word, seg_word.data(), sizeof(int32_t) * seg_word.size(), hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(h->d_seg_begin, seg_begin.data(), sizeof(int32_t) * seg_begin.size(), hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(h->d_doc_ptr, doc_ptr, sizeof(int64_t) * ((size_t)D + 1), hipMemcpyHostToDevice));
-  if (N) HIP_TRY(h, hipMemcpy(h->d_tok, tokens, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice));
-  h->num_hot = (int32_t)hot_words.size();
-  h->HS = (int64_t)hseg_word.size();
-  if ((rc = dev_alloc(h, &h->d_hseg_word, hseg_word.size())) || (rc = dev_alloc(h, &h->d_hseg_begin, hseg_begin.size())) || (rc = dev_alloc(h, &h->d_hseg_end, hseg_end.size()))) return rc;
-  if (h->HS) {
-    HIP_TRY(h, hipMemcpy(h->d_hseg_word, hseg_word.data(), sizeof(int32_t) * hseg_word.size(), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_hseg_begin, hseg_begin.data(), sizeof(int32_t) * hseg_begin.size(), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_hseg_end, hseg_end.data(), sizeof(int32_t) * hseg_end.size(), hipMemcpyHostToDevice));
-  }
-  h->Cs = h->Cc = 0;
-  h->warm_tiers = 0; h->num_warm = 0; h->Cw = 0;
-  if (h->z_sliced) {
-    // Chunk lists of the sliced kernel: walk the documents in order and deal every token to the open
-    // cold chunk or the open hot chunk; a chunk closes at 64 tokens or when a third document would enter it.
-    // (documents are visited in order, so a token's document is always the chunk's newest: slot = documents so far - 1)
-    struct Builder {
-      int maxdocs = kChunkDocs, docslots = kChunkDocs, shift = kSlotShift;   // documents a chunk may draw from; ids stored per chunk
-      std::vector<int32_t> tok, idx, docs;
-      int fill = 64, ndocs = 0, last = -1;
-      int64_t tokens = 0;
-      void add(int32_t value, int32_t token, int32_t doc) {
-        if (fill == 64 || (doc != last && ndocs == maxdocs)) {
-          tok.resize(tok.size() + 64, 0); idx.resize(idx.size() + 64, -1);
-          docs.insert(docs.end(), (size_t)docslots, doc);
-          fill = 0; ndocs = 1; last = doc;
-        } else if (doc != last) {
-          docs[docs.size() - (size_t)docslots + (size_t)ndocs] = doc; ++ndocs; last = doc;
-        }
-        const size_t at = tok.size() - 64 + (size_t)fill;
-        tok[at] = value | ((ndocs - 1) << shift); idx[at] = token;
-        ++fill; ++tokens;
-      }
-      int64_t chunks() const { return (int64_t)(tok.size() / 64); }
-    } cold, hot;
-    std::vector<int32_t> row_of((size_t)h->V, -1);
-    for (size_t r = 0; r < hot_words.size(); ++r) row_of[(size_t)hot_words[r]] = (int32_t)r;
-    // The warm tiers: tier t = candidates [t*warm_cap, (t+1)*warm_cap).  A tier is kept while its chunks (64 lanes, up to
-    // warm_docs documents) are reasonably full -- a token in a half-empty chunk costs what two cost -- and numerous enough
-    // to pay for the tier's table load, its two barriers and the ragged end of its chunk list; tiers are kept in order: the
-    // first one that falls short ends the list, its words and all later ones stay cold.  Measured with the table kernels'
-    // hand-counted loads (profiles/r04_warm_tier_sweep.txt; before them a tier wanted 10 chunks per wave), sweep in ms with
-    // 0 / 1 / 2 / 3 tiers: the benchmark corpus (20 M tokens; 14.4, 11.7, 10.7 chunks per wave) 1.517 / 1.494 / 1.461 /
-    // 1.471 (4, 5, 6 tiers: 1.464 / 1.471 / 1.472, 8: 1.513); half of it (rank 0 of 2: 7 chunks per wave in the first tier)
-    // 0.887 / 0.873 / 0.870 / 0.864; a quarter 0.552 / 0.547 / 0.543 / 0.545; an eighth (under 2 chunks per wave) 0.376 /
-    // 0.378 / 0.380 / 0.394 -- there a tier's table load and barriers cost what its tokens save.
-    std::vector<Builder> warm;
-    int32_t tiers = 0;
-    if (h->warm_cap > 0 && hot_words.size() == (size_t)h->hot_cap && !warm_cand.empty()) {
-      const int32_t cand_tiers = (int32_t)((warm_cand.size() + (size_t)h->warm_cap - 1) / (size_t)h->warm_cap);
-      warm.resize((size_t)cand_tiers);
-      for (Builder &b : warm) { b.maxdocs = h->warm_docs; b.docslots = kWarmDocSlots; b.shift = kWarmSlotShift; }
-      std::vector<int32_t> warm_of((size_t)h->V, -1);
-      for (size_t r = 0; r < warm_cand.size(); ++r) warm_of[(size_t)warm_cand[r]] = (int32_t)r;
-      for (int64_t d = 0; d < D; ++d)
-        for (int64_t i = doc_ptr[d]; i < doc_ptr[d + 1]; ++i) {
-          const int32_t r = warm_of[(size_t)tokens[i]];
-          if (r >= 0) warm[(size_t)(r / h->warm_cap)].add(r % h->warm_cap, (int32_t)i, (int32_t)d);
-        }
-      const int64_t min_chunks = (int64_t)h->warm_min_chunks_per_wave * h->num_cus * kSlicedWaves;
-      while (tiers < cand_tiers && warm[(size_t)tiers].tokens > 0 && warm[(size_t)tiers].chunks() >= min_chunks &&
-             warm[(size_t)tiers].tokens * 100 >= warm[(size_t)tiers].chunks() * 64 * h->warm_min_fill_pct)
-        ++tiers;
-      warm.resize((size_t)tiers);
-      warm_cand.resize(std::min(warm_cand.size(), (size_t)tiers * (size_t)h->warm_cap));
-      for (int32_t w : warm_cand) row_of[(size_t)w] = -2;              // in a kept tier: neither cold nor hot
-    }
-    for (int64_t d = 0; d < D; ++d)
-      for (int64_t i = doc_ptr[d]; i < doc_ptr[d + 1]; ++i) {
-        const int32_t r = row_of[(size_t)tokens[i]];
-        if (r >= 0) hot.add(r, (int32_t)i, (int32_t)d);
-        else if (r == -1) cold.add(tokens[i], (int32_t)i, (int32_t)d);
-      }
-    // Lanes of a chunk in (document, row) order: the 16 lanes one LDS pass serves then mostly read the same theta row
-    // and, in hot chunks, few distinct table rows (tokens of one word share a row: a broadcast, not a bank conflict).
-    auto sort_lanes = [](Builder &b) {
-      std::vector<std::pair<uint32_t, int32_t>> tmp(64);
-      for (size_t c0 = 0; c0 < b.tok.size(); c0 += 64) {
-        int n = 0;
-        while (n < 64 && b.idx[c0 + (size_t)n] >= 0) ++n;                 // active lanes are a prefix
-        for (int j = 0; j < n; ++j) tmp[(size_t)j] = {(uint32_t)b.tok[c0 + (size_t)j], b.idx[c0 + (size_t)j]};
-        std::sort(tmp.begin(), tmp.begin() + n);
-        for (int j = 0; j < n; ++j) { b.tok[c0 + (size_t)j] = (int32_t)tmp[(size_t)j].first; b.idx[c0 + (size_t)j] = tmp[(size_t)j].second; }
-      }
-    };
-    sort_lanes(cold);
-    sort_lanes(hot);
-    for (Builder &b : warm) sort_lanes(b);
-    h->Cc = (int64_t)(cold.docs.size() / 2);
-    h->Cs = h->Cc + (int64_t)(hot.docs.size() / 2);
-    {
-      // z_hot_kernel reads its chunks in the packed form of the warm tiers: one 16-byte entry per lane, the chunk's
-      // documents in kWarmDocSlots slots, the document slot at kWarmSlotShift
-      const size_t nh64 = hot.tok.size(), nhc = nh64 / 64;
-      std::vector<int32_t> hpack(4 * nh64, 0), hdocs(nhc * (size_t)kWarmDocSlots, 0);
-      for (size_t j = 0; j < nh64; ++j) {
-        const uint32_t t = (uint32_t)hot.tok[j];
-        hpack[4 * j] = (int32_t)((t & ((1u << kSlotShift) - 1)) | ((t >> kSlotShift) << kWarmSlotShift));
-        hpack[4 * j + 1] = hot.idx[j];
-        if (hot.idx[j] >= 0) hpack[4 * j + 2] = inv[(size_t)hot.idx[j]];
-      }
-      for (size_t c = 0; c < nhc; ++c)
-        for (int r = 0; r < kWarmDocSlots; ++r) hdocs[c * (size_t)kWarmDocSlots + (size_t)r] = hot.docs[2 * c + (size_t)std::min(r, 1)];
-      if ((rc = dev_alloc(h, &h->d_ht_pack, hpack.size())) || (rc = dev_alloc(h, &h->d_h_docs, hdocs.size()))) return rc;
-      if (nh64) {
-        HIP_TRY(h, hipMemcpy(h->d_ht_pack, hpack.data(), sizeof(int32_t) * hpack.size(), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->d_h_docs, hdocs.data(), sizeof(int32_t) * hdocs.size(), hipMemcpyHostToDevice));
-      }
-    }
-    cold.tok.insert(cold.tok.end(), hot.tok.begin(), hot.tok.end());
-    cold.idx.insert(cold.idx.end(), hot.idx.begin(), hot.idx.end());
-    cold.docs.insert(cold.docs.end(), hot.docs.begin(), hot.docs.end());
-    std::vector<int32_t> ip(cold.idx.size(), 0);
-    for (size_t j = 0; j < ip.size(); ++j)
-      if (cold.idx[j] >= 0) ip[j] = inv[(size_t)cold.idx[j]];
-    const size_t n64 = cold.tok.size();
-    if ((rc = dev_alloc(h, &h->d_ct_tok, n64)) || (rc = dev_alloc(h, &h->d_ct_idx, n64)) || (rc = dev_alloc(h, &h->d_ct_ip, n64)) ||
-        (rc = dev_alloc(h, &h->d_c_docs, cold.docs.size())) || (rc = dev_alloc(h, &h->d_hot_words, hot_words.size())))
-      return rc;
-    if (n64) {
-      HIP_TRY(h, hipMemcpy(h->d_ct_tok, cold.tok.data(), sizeof(int32_t) * n64, hipMemcpyHostToDevice));
-      HIP_TRY(h, hipMemcpy(h->d_ct_idx, cold.idx.data(), sizeof(int32_t) * n64, hipMemcpyHostToDevice));
-      HIP_TRY(h, hipMemcpy(h->d_ct_ip, ip.data(), sizeof(int32_t) * n64, hipMemcpyHostToDevice));
-      HIP_TRY(h, hipMemcpy(h->d_c_docs, cold.docs.data(), sizeof(int32_t) * cold.docs.size(), hipMemcpyHostToDevice));
-    }
-    if (h->num_hot) HIP_TRY(h, hipMemcpy(h->d_hot_words, hot_words.data(), sizeof(int32_t) * hot_words.size(), hipMemcpyHostToDevice));
-    // the warm tiers' lists, tier after tier; meta = [tiers + 1] first chunk of a tier, then [tiers] rows of its table
-    h->warm_tiers = tiers; h->num_warm = (int32_t)warm_cand.size(); h->Cw = 0; h->warm_chunks_max = 0; h->warm_rows_max = 0;
-    if (tiers > 0) {
-      std::vector<int32_t> wtok, widx, wdocs, wwords((size_t)tiers * (size_t)h->warm_cap, 0);
-      std::vector<int64_t> meta((size_t)(2 * tiers + 1), 0);
-      for (int32_t t = 0; t < tiers; ++t) {
-        const Builder &b = warm[(size_t)t];
-        meta[(size_t)t] = (int64_t)(wtok.size() / 64);
-        const int32_t rows = (int32_t)std::min<size_t>((size_t)h->warm_cap, warm_cand.size() - (size_t)t * (size_t)h->warm_cap);
-        meta[(size_t)(tiers + 1 + t)] = rows;
-        h->warm_rows_max = std::max(h->warm_rows_max, rows);
-        h->warm_chunks_max = std::max(h->warm_chunks_max, b.chunks());
-        wtok.insert(wtok.end(), b.tok.begin(), b.tok.end());
-        widx.insert(widx.end(), b.idx.begin(), b.idx.end());
-        wdocs.insert(wdocs.end(), b.docs.begin(), b.docs.end());
-        for (int32_t r = 0; r < rows; ++r) wwords[(size_t)t * (size_t)h->warm_cap + (size_t)r] = warm_cand[(size_t)t * (size_t)h->warm_cap + (size_t)r];
-      }
-      meta[(size_t)tiers] = (int64_t)(wtok.size() / 64);
-      h->Cw = meta[(size_t)tiers];
-      std::vector<int32_t> wpack(4 * widx.size(), 0);
-      for (size_t j = 0; j < widx.size(); ++j) {
-        wpack[4 * j] = wtok[j]; wpack[4 * j + 1] = widx[j];
-        if (widx[j] >= 0) wpack[4 * j + 2] = inv[(size_t)widx[j]];
-      }
-      if ((rc = dev_alloc(h, &h->d_wt_pack, wpack.size())) ||
-          (rc = dev_alloc(h, &h->d_w_docs, wdocs.size())) || (rc = dev_alloc(h, &h->d_warm_words, wwords.size())) || (rc = dev_alloc(h, &h->d_warm_meta, meta.size())))
-        return rc;
-      HIP_TRY(h, hipMemcpy(h->d_wt_pack, wpack.data(), sizeof(int32_t) * wpack.size(), hipMemcpyHostToDevice));
-      HIP_TRY(h, hipMemcpy(h->d_w_docs, wdocs.data(), sizeof(int32_t) * wdocs.size(), hipMemcpyHostToDevice));
-      HIP_TRY(h, hipMemcpy(h->d_warm_words, wwords.data(), sizeof(int32_t) * wwords.size(), hipMemcpyHostToDevice));
-      HIP_TRY(h, hipMemcpy(h->d_warm_meta, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice));
-    }
-  }
+  if (pl.sliced() && ((rc = upload(h, &h->d_ct_tok, L.ct_tok)) || (rc = upload(h, &h->d_ct_idx, L.ct_idx)) || (rc = upload(h, &h->d_ct_ip, L.ct_ip)) ||
+                      (rc = upload(h, &h->d_c_docs, L.c_docs)) || (rc = upload(h, &h->d_hot_words, L.hot_words)) ||
+                      (rc = upload(h, &h->d_ht_pack, L.ht_pack)) || (rc = upload(h, &h->d_h_docs, L.h_docs))))
+    return rc;
+  if (L.warm_tiers > 0 && ((rc = upload(h, &h->d_wt_pack, L.wt_pack)) || (rc = upload(h, &h->d_w_docs, L.w_docs)) ||
+                           (rc = upload(h, &h->d_warm_words, L.warm_words)) || (rc = upload(h, &h->d_warm_meta, L.warm_meta))))
+    return rc;
+  if ((rc = dev_alloc(h, &h->d_z, (size_t)N)) || (rc = dev_alloc(h, &h->d_zw, (size_t)N)) ||
+      (rc = dev_alloc(h, &h->d_theta, theta_elems)) || (rc = dev_alloc(h, &h->d_theta_next, theta_elems)))
+    return rc;
   HIP_TRY(h, hipMemset(h->d_z, 0, sizeof(int32_t) * std::max<size_t>((size_t)N, 1)));
+  HIP_TRY(h, hipMemset(h->d_zw, 0, sizeof(int32_t) * std::max<size_t>((size_t)N, 1)));
   HIP_TRY(h, hipMemset(h->d_theta, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
   HIP_TRY(h, hipMemset(h->d_theta_next, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
-  if (h->C) {
-    HIP_TRY(h, hipMemcpy(h->d_chunk_start, cstart.data(), sizeof(int64_t) * cstart.size(), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_chunk_doc, cdoc.data(), sizeof(int32_t) * cdoc.size(), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_chunk_len, clen.data(), sizeof(int32_t) * clen.size(), hipMemcpyHostToDevice));
-    if (two_rows) {
-      if ((rc = dev_alloc(h, &h->d_chunk_doc1, cdoc1.size()))) return rc;
-      HIP_TRY(h, hipMemcpy(h->d_chunk_doc1, cdoc1.data(), sizeof(int32_t) * cdoc1.size(), hipMemcpyHostToDevice));
-    }
-  }
   HIP_TRY(h, hipDeviceSynchronize());   // the uploads and memsets above ran on the null stream; the handle's stream may not synchronise with it
+
+  // 5. a new corpus: no Phi, no sweep in progress, the z form to be timed again
   h->have_corpus = true; h->have_phi = false; h->in_sweep = false; h->global_tokens = -1; h->lcg_ready = false;
-  h->z_split = h->z_split_allowed; h->z_split_tried = h->z_split_forced;
+  h->z_split = pl.split; h->z_split_tried = pl.split_forced;
   h->counts_global = h->xg == nullptr; h->cnt_own_valid = false; h->n_k_valid = false;
   return GGS_OK;
 }
@@ -2216,7 +1876,7 @@ int ggs_get_iteration(const ggs_handle *h, int32_t *it) { if (!h || !it) return 
 // see theta_main: only where the z step is one launch pair (no parts), theta is drawn at all, no collective is in the chain, and
 // the theta draw (D x K gammas) is the longer leg (the Phi chain draws V x K)
 bool chain_on_side_ok(const ggs_handle *h) {
-  return h->theta_main && h->z_sliced && h->side_hot && h->ev_chain_done && !h->xg && !h->collapsed && !(h->flags & GGS_FLAG_PCGS) &&
+  return h->theta_main && h->plan.sliced() && h->side_hot && h->ev_chain_done && !h->xg && !h->collapsed && !(h->flags & GGS_FLAG_PCGS) &&
          (h->D >= (int64_t)h->V || h->theta_main_always);
 }
 
@@ -2669,7 +2329,7 @@ int ggs_set_phi(ggs_handle *h, const double *phi) {
   if ((rc = ensure_scratch(h, kv * sizeof(double)))) return rc;
   HIP_TRY(h, hipMemcpyAsync(h->d_scratch, phi, kv * sizeof(double), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(phi_to_phiT_kernel, dim3(grid_for((int64_t)kv, 256)), dim3(256), 0, h->stream, static_cast<const double *>(h->d_scratch),
-                     h->d_phiT, h->K, h->Kp, h->V, h->d_phiT32, h->Kp32);
+                     h->d_phiT, h->K, h->Kp, h->V, h->d_phiT32, h->plan.Kp32);
   HIP_TRY(h, hipGetLastError());
   // UPLDA:1897-1902: `if (savePhiMeans()) phiMean = new double[numTopics][numTypes]` -- the running sum restarts, noSampledPhi keeps counting
   if (h->d_phi_mean) HIP_TRY(h, hipMemsetAsync(h->d_phi_mean, 0, kv * sizeof(double), h->stream));
@@ -2968,41 +2628,42 @@ int ggs_check_invariants(ggs_handle *h) {
 
 int ggs_get_launch_info(ggs_handle *h, int64_t *num_chunks, int32_t *lds_bytes_z, int32_t *docs_per_block_theta) {
   if (!h) return GGS_ERR_BAD_ARG;
-  if (num_chunks) *num_chunks = h->z_sliced ? h->Cs + h->Cw : h->C;
-  if (lds_bytes_z) *lds_bytes_z = h->z_lds;
-  if (docs_per_block_theta) *docs_per_block_theta = h->theta_docs_per_block;
+  const LaunchPlan &pl = h->plan;
+  if (num_chunks) *num_chunks = pl.sliced() ? h->Cs + h->Cw : h->C;
+  if (lds_bytes_z) *lds_bytes_z = pl.sliced() ? sliced_fused_lds(h->K, pl.hot_cap) : pl.z.lds;
+  if (docs_per_block_theta) *docs_per_block_theta = h->cfg->theta_docs;
   return GGS_OK;
 }
 
 int ggs_get_num_hot_words(ggs_handle *h, int32_t *num_hot) {
   if (!h || !num_hot) return GGS_ERR_BAD_ARG;
-  *num_hot = (h->z_sliced && !(h->flags & GGS_FLAG_PCGS)) ? h->num_hot + h->num_warm : 0;
+  *num_hot = (h->plan.sliced() && !(h->flags & GGS_FLAG_PCGS)) ? h->num_hot + h->num_warm : 0;
   return GGS_OK;
 }
 
 int ggs_get_z_parts(ggs_handle *h, int32_t *parts) {
   if (!h || !parts) return GGS_ERR_BAD_ARG;
   const int32_t P = (int32_t)h->part_doc.size() - 1;
-  *parts = (h->z_stream && h->overlap_theta && P > 1 && !(h->flags & GGS_FLAG_PCGS)) ? P : 1;
+  *parts = (h->plan.stream() && h->overlap_theta && P > 1 && !(h->flags & GGS_FLAG_PCGS)) ? P : 1;
   return GGS_OK;
 }
 
 int ggs_get_warm_tiers(ggs_handle *h, int32_t *tiers, int32_t *warm_words, int32_t *docs_per_chunk) {
   if (!h) return GGS_ERR_BAD_ARG;
-  const bool on = h->have_corpus && h->z_sliced && !(h->flags & GGS_FLAG_PCGS);
+  const bool on = h->have_corpus && h->plan.sliced() && !(h->flags & GGS_FLAG_PCGS);
   if (tiers) *tiers = on ? h->warm_tiers : 0;
   if (warm_words) *warm_words = on ? h->num_warm : 0;
-  if (docs_per_chunk) *docs_per_chunk = on && h->warm_tiers ? h->warm_docs : 0;
+  if (docs_per_chunk) *docs_per_chunk = on && h->warm_tiers ? h->plan.warm_docs : 0;
   return GGS_OK;
 }
 
 int ggs_get_z_form(ggs_handle *h, int32_t *kernel, int32_t *form, int32_t *calibrated) {
   if (!h) return GGS_ERR_BAD_ARG;
   const bool pcgs = (h->flags & GGS_FLAG_PCGS) != 0;
-  const bool splittable = !pcgs && h->z_sliced && h->Cs > h->Cc && h->Cc > 0;
-  if (kernel) *kernel = h->spalias ? 6 : pcgs ? (h->pcgs_wave ? 5 : 4) : h->z_sliced ? 1 : h->z_stream ? (h->z_two_pass ? 3 : 2) : 0;
-  if (form) *form = (!pcgs && h->z_sliced) ? (splittable && h->z_split ? 1 : 2) : 0;
-  if (calibrated) *calibrated = (splittable && h->z_split_tried && !h->z_split_forced && h->z_split_allowed) ? 1 : 0;
+  const bool splittable = !pcgs && h->plan.sliced() && h->Cs > h->Cc && h->Cc > 0;
+  if (kernel) *kernel = h->spalias ? 6 : pcgs ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
+  if (form) *form = (!pcgs && h->plan.sliced()) ? (splittable && h->z_split ? 1 : 2) : 0;
+  if (calibrated) *calibrated = (splittable && h->z_split_tried && !h->plan.split_forced && h->plan.split) ? 1 : 0;
   return GGS_OK;
 }
 

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/ggs_hip.h"
+#include "ggs_layout.hpp"
 
 namespace ggs {
 

@@ -77,6 +77,9 @@ struct ThetaParams {
 
 constexpr int kGammaQueue = 768;             // uint16 element indices: a workgroup's cells number < 65536 (LDS / 8)
 constexpr int kThetaQueueBytes = 8 + 2 * kGammaQueue;
+// LDS of theta_kernel with b documents per workgroup: gam [K][b | 1] doubles, mag, tot [b] doubles, len [b] int32, the queue
+// (mirrors the carve-up at the top of the kernel, whose B is a run-time parameter)
+constexpr int theta_lds_bytes(const int K, const int b) { return (int)((size_t)K * (b | 1) * 8 + (size_t)b * 20 + kThetaQueueBytes); }
 
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void theta_kernel(ThetaParams p) {

@@ -61,7 +61,7 @@ struct ZParams {
   uint64_t seed;
   uint32_t iteration;
   int32_t K, Kp, pitch16, tile_tokens;
-  int32_t ablate;   // timing-only experiments (env GGS_DEBUG_ABLATE): 2 no walk, 4 no staging, 8 no sum pass
+  int32_t ablate;   // timing-only experiments, concluded: the host leaves it 0 (the kernels' branches go with the next change of device code)
   // z_sliced_kernel only (ggs_z_sliced.hpp): its own chunk lists -- cold chunks [0, num_cold), hot chunks
   // [num_cold, num_chunks) -- stored chunk-major, 64 entries per chunk
   const int32_t *ct_tok;       // cold: word id, hot: row of the LDS table; | (0 or 1: which of the chunk's documents) << 30
@@ -95,7 +95,7 @@ struct ZParams {
   const int32_t *warm_words;   // [warm_tiers][warm_rows] word ids of the tables' rows
   const int64_t *warm_meta;    // [warm_tiers + 1] first chunk of a tier, then [warm_tiers] rows of its table
   int32_t warm_tiers, warm_rows;
-  long long *dbg;              // -DGGS_WARM_TRACE builds only: per wave, cycles by phase of z_warm_kernel's chunk loop
+  long long *dbg;              // the phase trace of z_warm_kernel's chunk loop, concluded: the host leaves it null
   // z_sliced_kernel<KMAX, true> (ggs_z_sliced.hpp): the cold chunks scored from the float32 shadow of phiT and decided by
   // the margin of its header; the tokens too close to call are replayed from phiT and theta
   const float *phiT32;         // [V][Kp32], Kp32 = K rounded up to whole 32-topic slices, the pad columns zero
@@ -115,6 +115,12 @@ typedef __attribute__((address_space(4))) const int64_t const_i64_t;
 typedef __attribute__((address_space(4))) const int32_t const_i32_t;
 
 __device__ __forceinline__ D2 lds_d2(const unsigned char *p) { return *reinterpret_cast<const D2 *>(p); }
+
+// LDS of z_kernel: a tile of T token rows of pitch16 16-byte units, then the theta row (Kp doubles, whole units) -- mirrors
+// `thb = smem + tile_tokens * pitch` in the kernel, whose tile size and pitch are run-time parameters
+constexpr int z_tile_theta_bytes(const int Kp) { return (Kp * 8 + 15) / 16 * 16; }
+constexpr int z_tile_lds_bytes(const int Kp, const int pitch16, const int T) { return T * pitch16 * 16 + z_tile_theta_bytes(Kp); }
+constexpr int z_tile_rows_in(const int bytes, const int Kp, const int pitch16) { return (bytes - z_tile_theta_bytes(Kp)) / (pitch16 * 16); }
 
 // NT = number of 64-topic slices of a theta row; the launcher picks the smallest NT with 64*NT >= K.
 template <int NT>

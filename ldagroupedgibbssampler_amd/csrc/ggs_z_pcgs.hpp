@@ -39,8 +39,16 @@ struct PcgsParams {
   double beta, beta_sum;
 };
 
-constexpr int kPcgsMaxDocLen = 32767;  // counts are int16
+// (kPcgsMaxDocLen, the longest document the int16 counts hold: ggs_layout.hpp)
 constexpr int kPcgsRingSlots = 3;      // two slices ahead: 24 KiB of ring, so that four waves fit a CU at K = 100
+// LDS of pcgs_z_body (pcgs_z_kernel, polyaurn_z_kernel): the ring, the alpha row zero-padded to KT topics, the int16 document
+// counts [KT][64]; KT = whole slices, at least the ring's depth (mirrors NS / alb / cnt below, whose K is a run-time parameter)
+constexpr int pcgs_z_alpha_offset() { return kPcgsRingSlots * kSliceBytes; }
+constexpr int pcgs_z_slices(const int K) { return imax(kPcgsRingSlots - 1, (K + kSliceTopics - 1) / kSliceTopics); }
+constexpr int pcgs_z_lds_bytes(const int K) { return pcgs_z_alpha_offset() + pcgs_z_slices(K) * kSliceTopics * (8 + 128); }
+// LDS of the score-register kernels (ggs_z_pcgs_sliced_body.hpp): the alpha row and the counts, then the ring
+constexpr int pcgs_sliced_head_bytes(const int kmax) { return (kmax * 8 + kmax * 128 + 255) / 256 * 256; }
+constexpr int pcgs_sliced_lds_bytes(const int K) { return pcgs_sliced_head_bytes((K + 7) / 8 * 8) + kPcgsRingSlots * kSliceBytes; }
 
 // POLYAURN (scheme polyaurn, PolyaUrnSpaliasLDA.java:261-278): a document of one token, or a token whose scores sum to 0
 // (the word's Phi column is all zero), draws floor(U * K) -- the reference's candidate list is empty there.  Every other
@@ -55,7 +63,7 @@ __device__ __forceinline__ void pcgs_z_body(PcgsParams &p) {
   const int K = p.K;
   const int NS = max(kAhead, (K + kSliceTopics - 1) / kSliceTopics);   // slices per pass; at least kAhead (padding topics score 0)
   const int KT = NS * kSliceTopics;
-  double *alb = reinterpret_cast<double *>(smem + kPcgsRingSlots * kSliceBytes);   // alpha, zero padded to KT
+  double *alb = reinterpret_cast<double *>(smem + pcgs_z_alpha_offset());   // alpha, zero padded to KT
   int16_t *cnt = reinterpret_cast<int16_t *>(alb + KT);                              // [KT][64]
   const unsigned char *phib = reinterpret_cast<const unsigned char *>(p.phiT);
   const size_t rowbytes = (size_t)p.Kp * 8;

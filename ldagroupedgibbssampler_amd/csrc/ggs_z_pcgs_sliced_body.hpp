@@ -5,7 +5,7 @@
 // No include guard on purpose.
   constexpr int NS = (KMAX + kSliceTopics - 1) / kSliceTopics;
   constexpr int kAhead = NS < kPcgsRingSlots - 1 ? NS : kPcgsRingSlots - 1;
-  constexpr int kHead = (KMAX * 8 + KMAX * 128 + 255) / 256 * 256;  // alpha row + counts, below the ring (>= NS*128)
+  constexpr int kHead = pcgs_sliced_head_bytes(KMAX);              // alpha row + counts, below the ring (>= NS*128)
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = threadIdx.x;
   const int K = p.K;

@@ -63,6 +63,12 @@ constexpr int pcgs_wave_depth() { return NB < 8 ? 2 : NB == 8 ? GGS_PCGS_WAVE_DE
 template <int NB>
 constexpr int pcgs_wave_min_waves() { return NB == 8 ? 3 : 1; }
 
+// LDS of pcgs_wave_body: the document's counts [KT] int32, then alpha [KT] fp64 zero padded; KT = NB blocks of 128 topics,
+// NB the power of two that holds the padded row
+constexpr int pcgs_wave_blocks(const int Kp) { int nb = 1; while (nb * 128 < Kp) nb *= 2; return nb; }
+constexpr int pcgs_wave_alpha_offset(const int nb) { return nb * 128 * 4; }
+constexpr int pcgs_wave_lds_bytes(const int nb) { return pcgs_wave_alpha_offset(nb) + nb * 128 * 8; }
+
 template <int NB, bool COLLAPSED, bool POLYAURN>
 __device__ __forceinline__ void pcgs_wave_body(PcgsParams &p, const double margin_scale) {
   constexpr int KT = NB * 128;
@@ -70,7 +76,7 @@ __device__ __forceinline__ void pcgs_wave_body(PcgsParams &p, const double margi
   constexpr int kNG = NB < GGS_PCGS_WAVE_GROUPS ? NB : GGS_PCGS_WAVE_GROUPS, kG = NB / kNG;   // groups of the block search, blocks per group
   extern __shared__ __align__(16) unsigned char smem[];
   int32_t *cnt = reinterpret_cast<int32_t *>(smem);                        // [KT]
-  double *alb = reinterpret_cast<double *>(smem + (size_t)KT * 4);         // [KT] alpha, zero padded
+  double *alb = reinterpret_cast<double *>(smem + pcgs_wave_alpha_offset(NB));   // [KT] alpha, zero padded
   const int lane = threadIdx.x, K = p.K;
   const int units = p.Kp / 2;                                              // 16-byte units per phiT row (Kp is even; a padding column holds 0)
 

@@ -69,15 +69,11 @@ constexpr int kRingSlots = GGS_RING_SLOTS;
 constexpr int kSlicedMaxTopics = 192;     // 384 score registers (VGPR + AGPR) + working set < 512
 constexpr int kSlicedDefaultTopics = 160; // ... and the largest K the host gives to these kernels unasked (ggs_api.hip: measured break-even)
 constexpr int kPhiTailPadBytes = 1024;    // zeroed bytes after the last phiT row (see above; the pcgs kernel pads K to 48, the one-pass stream kernel to a multiple of 64)
-constexpr int kSlicedWaves = 4;           // waves per workgroup (one per SIMD), sharing the hot-word table
-constexpr int kChunkDocs = 2;             // documents a chunk may draw tokens from
 constexpr int kHotTailBytes = 64;          // zeroed bytes after z_hot_kernel's table: what a lane refining the last slice reads past the last row
-constexpr int kSlotShift = 30;            // chunk token word: value | (which of the chunk's documents) << 30
 
 // ---- the warm tiers (z_warm_kernel, below)
-constexpr int kWarmMaxTiers = 8;
-constexpr int kWarmSlotShift = 16;         // warm chunk token word: table row | (which of the chunk's documents) << 16
-constexpr int kWarmDocSlots = 8;           // document ids stored per warm chunk (one 32-byte scalar load), whatever warm_docs_for() says
+// (kSlicedWaves, kChunkDocs, kSlotShift, kWarmMaxTiers, kWarmSlotShift, kWarmDocSlots: ggs_layout.hpp, the host's list
+// builder packs with them)
 // LDS pitch of a warm chunk's theta rows = whole slices + 16 bytes: the rows are a multiple of 128 bytes, so without the pad
 // lanes of different documents reading the same topics hit the same banks (measured: 54 % of the warm kernel's LDS cycles
 // were bank conflicts against the hot kernel's 38 %); with it the 16-byte reads of 8 rows at one offset touch 8 disjoint
@@ -96,6 +92,33 @@ constexpr int warm_docs_for(const int kmax) {
   const int d = rowd <= 112 ? GGS_WARM_LANE_DOUBLES / 2 : rowd <= 128 ? GGS_WARM_LANE_DOUBLES / 2 - 1 : 2;
   return d < 2 ? 2 : d > 8 ? 8 : d;
 }
+
+// ---- LDS layout of the four kernels of this file, in bytes; K is the handle's, KMAX = sliced_kmax(K) the instance's.
+// The kernels take these offsets as parameters (ZParams::wave_lds, hot_off, ring_base, hot_pitch): the host calls the
+// functions, fills the parameters and sizes the launch with them.
+constexpr int sliced_kmax(const int K) { return (K + 7) / 8 * 8; }
+constexpr int sliced_slices(const int K) { return (sliced_kmax(K) + kSliceTopics - 1) / kSliceTopics; }
+// cold kernels, per wave: the chunk's kChunkDocs theta rows (zero-padded to KMAX), then the ring; a DMA's immediate slice
+// offset (< slices * 128) is subtracted from its LDS destination, so the ring must not start below that
+constexpr int sliced_ring_base(const int K) { return round_up(imax(kChunkDocs * sliced_kmax(K) * 8, sliced_slices(K) * 128), 256); }
+constexpr int sliced_wave_lds(const int K) { return sliced_ring_base(K) + kRingSlots * kSliceBytes; }
+constexpr int sliced_cold_lds(const int K) { return kSlicedWaves * sliced_wave_lds(K); }
+// a row of a Phi table (hot words, a warm tier): KMAX doubles + one unit, an odd number of 16-byte units
+constexpr int table_row_pitch(const int K) { return sliced_kmax(K) / 8 * 64 + 16; }
+// the fused form: the cold kernel takes the hot chunks too, the table behind its waves' rings
+constexpr int sliced_fused_lds(const int K, const int rows) { return sliced_cold_lds(K) + rows * table_row_pitch(K); }
+// table kernels, per wave: the theta rows of a chunk's documents in whole slices (z_hot_kernel: kChunkDocs rows;
+// z_warm_kernel: warm_docs_for(KMAX) rows, kWarmThetaPad apart); behind the waves the table and its zeroed tail
+constexpr int hot_wave_lds(const int K) { return round_up(kChunkDocs * sliced_slices(K) * kSliceTopics * 8, 256); }
+constexpr int warm_wave_lds(const int K) { return round_up(warm_docs_for(sliced_kmax(K)) * (sliced_slices(K) * kSliceTopics * 8 + kWarmThetaPad), 256); }
+constexpr int table_lds(const int K, const int wave_lds, const int rows) { return kSlicedWaves * wave_lds + rows * table_row_pitch(K) + kHotTailBytes; }
+// rows a table may have: beside the cold kernel's workgroup on the same CU (both requests rounded up to the allocation
+// granule), or in the fused form; a row index is 8 bits of the chunk token word
+constexpr int table_rows_beside_cold(const int K, const int wave_lds) {
+  return imax(0, imin(255, ((kMaxLdsBytes - lds_alloc_of(sliced_cold_lds(K)) - kSlicedWaves * wave_lds) / kLdsGranule * kLdsGranule - kHotTailBytes) / table_row_pitch(K)));
+}
+constexpr int table_rows_fused(const int K) { return imax(0, imin(255, (kMaxLdsBytes - sliced_cold_lds(K)) / table_row_pitch(K))); }
+
 struct alignas(8) D2u { double a, b; };    // two doubles at an 8-byte aligned address (a theta row starts at d*K*8)
 
 template <int S, int N, class F>

@@ -26,6 +26,10 @@ namespace ggs {
 #define GGS_STREAM_RING 2
 #endif
 constexpr int kStreamRingSlots = GGS_STREAM_RING;
+// LDS of z_stream_kernel: the ring, then the theta row zero-padded to whole slices
+constexpr int stream_slices(const int K) { return (K + kSliceTopics - 1) / kSliceTopics; }
+constexpr int z_stream_theta_offset() { return kStreamRingSlots * kSliceBytes; }
+constexpr int z_stream_lds_bytes(const int K) { return z_stream_theta_offset() + stream_slices(K) * kSliceTopics * 8; }
 
 __global__ __launch_bounds__(64) void z_stream_kernel(ZParams p) {
   constexpr int kAhead = kStreamRingSlots - 1;
@@ -34,7 +38,7 @@ __global__ __launch_bounds__(64) void z_stream_kernel(ZParams p) {
   const int K = p.K, Kp = p.Kp;
   const int NS = (K + kSliceTopics - 1) / kSliceTopics;            // slices per pass (host guarantees NS >= 3)
   const int KT = NS * kSliceTopics;                                // theta row in LDS, zero padded
-  double *thb = reinterpret_cast<double *>(smem + kStreamRingSlots * kSliceBytes);
+  double *thb = reinterpret_cast<double *>(smem + z_stream_theta_offset());
   const unsigned char *phib = reinterpret_cast<const unsigned char *>(p.phiT);
   const size_t rowbytes = (size_t)Kp * 8;
   const const_i64_t *cstart = (const const_i64_t *)p.chunk_start;
@@ -216,6 +220,15 @@ constexpr int kMaxGroupSlices = 4;
 constexpr int kStream1RingSlots = GGS_STREAM1_RING;                // measured at K = 1024 with 4 waves per CU: 2 slots 12.7 ms, 3 slots 12.9; waves per CU matter more
 constexpr int kRegCheckpoints = 16;                                // REGCK: checkpoints in registers for up to 16 groups (K <= 1024): 8 KiB less LDS per wave at K = 1024
 
+// LDS of z_stream1_kernel<REGCK, G>: the ring, the theta row(s) zero-padded to whole checkpoint groups (two rows: a chunk
+// may run across a document boundary), without REGCK the checkpoints [groups][64] (mirrors thb / ckb below, whose K and
+// two_rows are run-time parameters)
+constexpr int z_stream1_theta_offset() { return kStream1RingSlots * kSliceBytes; }
+constexpr int z_stream1_groups(const int K, const int G) { return (stream_slices(K) + G - 1) / G; }
+constexpr int z_stream1_lds_bytes(const int K, const int G, const bool two_rows, const bool regck) {
+  return z_stream1_theta_offset() + (two_rows ? 2 : 1) * z_stream1_groups(K, G) * G * kSliceTopics * 8 + (regck ? 0 : z_stream1_groups(K, G) * 64 * 8);
+}
+
 template <bool REGCK, int kGroupSlices>
 __global__ __launch_bounds__(64) void z_stream1_kernel(ZParams p) {
   constexpr int R = kStream1RingSlots, kAhead = R - 1;
@@ -227,7 +240,7 @@ __global__ __launch_bounds__(64) void z_stream1_kernel(ZParams p) {
   const int NS = (K + kSliceTopics - 1) / kSliceTopics;            // slices of pass 1
   const int NG = (NS + kGroupSlices - 1) / kGroupSlices;           // checkpoint groups
   const int KTG = NG * kGroupSlices * kSliceTopics;                // theta row in LDS, zero padded to whole groups
-  double *thb = reinterpret_cast<double *>(smem + R * kSliceBytes);   // theta row(s): one, or two with p.two_rows (a chunk across a document boundary)
+  double *thb = reinterpret_cast<double *>(smem + z_stream1_theta_offset());   // theta row(s): one, or two with p.two_rows (a chunk across a document boundary)
   double *ckb = thb + (p.two_rows ? 2 : 1) * KTG;                  // [NG][64] (!REGCK)
   double ck[REGCK ? kRegCheckpoints : 1];                           // REGCK: the lane's checkpoints
   const unsigned char *phib = reinterpret_cast<const unsigned char *>(p.phiT);
