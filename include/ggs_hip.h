@@ -379,9 +379,12 @@ int ggs_get_alias_tables(ggs_handle *h, double *ps /*[V][K]*/, int32_t *a /*[V][
  * assignments, split where a doc-sharded run splits it: doc_side covers THIS handle's documents (sum_d [...] +
  * D*lgS(alphaSum), UPLDA:1674-1694) and topic_side the (replicated) type-topic counts (UPLDA:1701-1747); the model's
  * value is the sum of every shard's doc_side plus one topic_side.  lgS = MALLET Dirichlet.logGammaStirling.  A
- * diagnostic: partial sums are reduced in a fixed tree, so the value is run-to-run identical and within ~1e-12 (measured: 8e-13 at K=100, 5e-11 at K=1024, 18 M tokens)
- * relative of the Java loop's running sum, not bit-equal to it.  Needs tokensPerTopic up to date (any completed sweep,
- * ggs_init_phi or ggs_set_z with redraw). */
+ * diagnostic: partial sums are reduced in a fixed tree, so the value is run-to-run identical and not bit-equal to the Java
+ * loop's running sum: each side lies within (c + 2) * 2^-53 * sum|term| of the exact sum of the Java loop's terms, c the
+ * longest chain of additions in the tree (a few dozen; csrc/ggs_loglik.hpp), where the running sum itself is only within
+ * (terms - 1) * 2^-53 * sum|term| of it.  Needs tokensPerTopic up to date (any completed sweep, ggs_init_phi or ggs_set_z
+ * with redraw).  GGS_ERR_UNSUPPORTED beyond 10238 topics (four documents' topic counts are kept in LDS); so for
+ * ggs_log_posterior. */
 int ggs_model_log_likelihood(ggs_handle *h, double *doc_side, double *topic_side);
 /* replaces: computeLogPosterior (UPLDA:1573-1634, the LDA log posterior of Doss and George 2025, logged every
  * diagnostic iteration, UPLDA:820-821) for scheme ggs: doc_side = sum over THIS handle's tokens of

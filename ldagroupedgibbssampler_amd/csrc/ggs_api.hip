@@ -1627,6 +1627,9 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
   // with a smaller K never lowers the cap under a live one.
   for (const KernelLaunch *l : h->plan.all())
     if (l->fn && hipFuncSetAttribute(l->fn, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess) return bail(GGS_ERR_HIP);
+  // the document kernels of the two diagnostics: four K-long histograms per block pass 64 KiB from K = 4095
+  for (const void *f : {reinterpret_cast<const void *>(ll_docs_kernel), reinterpret_cast<const void *>(lp_docs_kernel)})
+    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess) return bail(GGS_ERR_HIP);
   // 4. the model's buffers
   const size_t kv = (size_t)h->K * h->V, phi_elems = (size_t)h->V * h->Kp + kPhiTailPadBytes / 8;
   if ((rc = dev_alloc(h, &h->d_alpha, h->K)) || (rc = dev_alloc(h, &h->d_phiT, phi_elems)) ||
@@ -2382,12 +2385,20 @@ int ggs_get_doc_topic_counts(ggs_handle *h, int64_t doc_begin, int64_t doc_end, 
   HIP_TRY(h, hipGetLastError());
   return copy_out(h, n_dk, h->d_scratch, bytes);
 }
+// ll_docs_kernel and lp_docs_kernel keep four K-long histograms per block in LDS (ggs_loglik.hpp)
+static int ll_check_topics(ggs_handle *h) {
+  if (h->K > kLLMaxTopics)
+    return set_err(h, GGS_ERR_UNSUPPORTED, "the model log likelihood and the log posterior keep four documents' topic counts in LDS: at most " +
+                                               std::to_string(kLLMaxTopics) + " topics fit its 160 KiB, this model has " + std::to_string(h->K));
+  return GGS_OK;
+}
 int ggs_model_log_likelihood(ggs_handle *h, double *doc_side, double *topic_side) {
   int rc = require_ready(h, false);
   if (rc) return rc;
   if (!doc_side || !topic_side) return set_err(h, GGS_ERR_BAD_ARG, "null output");
   if ((rc = launch_magnitude(h))) return rc;       // corpus-wide counts gathered, tokensPerTopic in step with them
   const int K = h->K;
+  if ((rc = ll_check_topics(h))) return rc;
   const int64_t doc_blocks = (h->D + kLLBlock / 64 - 1) / (kLLBlock / 64), type_blocks = 1024;
   const size_t bytes = 32 + sizeof(double) * (size_t)(doc_blocks + type_blocks);
   if ((rc = ensure_scratch(h, bytes))) return rc;
@@ -2398,7 +2409,7 @@ int ggs_model_log_likelihood(ggs_handle *h, double *doc_side, double *topic_side
   double alpha_sum = 0;
   for (int k = 0; k < K; ++k) alpha_sum += h->alpha[k];
   if (doc_blocks)
-    hipLaunchKernelGGL(ll_docs_kernel, dim3((unsigned)doc_blocks), dim3(kLLBlock), (size_t)(kLLBlock / 64) * K * sizeof(int32_t), h->stream, h->d_doc_ptr,
+    hipLaunchKernelGGL(ll_docs_kernel, dim3((unsigned)doc_blocks), dim3(kLLBlock), ll_docs_lds_bytes(K), h->stream, h->d_doc_ptr,
                        h->d_z, h->d_alpha, alpha_sum, h->D, K, d_doc);
   hipLaunchKernelGGL(ll_types_kernel, dim3((unsigned)type_blocks), dim3(kLLBlock), 0, h->stream, h->d_n_wk, (int64_t)K * h->V, h->beta, d_type, d_nz);
   hipLaunchKernelGGL(ll_finish_kernel, dim3(1), dim3(kLLBlock), 0, h->stream, d_doc, doc_blocks, d_type, type_blocks, h->d_n_k, K, h->beta * h->V,
@@ -2414,6 +2425,7 @@ int ggs_log_posterior(ggs_handle *h, double *doc_side, double *topic_side) {
   if (rc) return rc;
   if (!doc_side || !topic_side) return set_err(h, GGS_ERR_BAD_ARG, "null output");
   if (h->collapsed) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed has no Phi: the log posterior of UPLDA:1573-1634 does not apply");
+  if ((rc = ll_check_topics(h))) return rc;
   if (h->flags & GGS_FLAG_PCGS) {
     // UPLDA:710-714: every scheme but ggs draws theta_d ~ Dir(n_d. + alpha) afresh for the diagnostics
     // (LDAUtils.drawDirichlets); here: the theta draw of GGS:57-72 under the stream GGS_PURPOSE_THETA at the current iteration
@@ -2426,7 +2438,7 @@ int ggs_log_posterior(ggs_handle *h, double *doc_side, double *topic_side) {
   auto *d_out = static_cast<double *>(h->d_scratch);
   double *d_doc = d_out + 4, *d_phi = d_doc + doc_blocks;
   if (doc_blocks)
-    hipLaunchKernelGGL(lp_docs_kernel, dim3((unsigned)doc_blocks), dim3(kLLBlock), (size_t)(kLLBlock / 64) * K * sizeof(int32_t), h->stream, h->d_doc_ptr,
+    hipLaunchKernelGGL(lp_docs_kernel, dim3((unsigned)doc_blocks), dim3(kLLBlock), ll_docs_lds_bytes(K), h->stream, h->d_doc_ptr,
                        h->d_tok, h->d_z, h->d_alpha, h->d_theta, h->d_phiT, h->D, K, h->Kp, d_doc);
   hipLaunchKernelGGL(lp_phi_kernel, dim3((unsigned)phi_blocks), dim3(kLLBlock), 0, h->stream, h->d_phiT, (int64_t)h->V, K, h->Kp, d_phi);
   hipLaunchKernelGGL(lp_finish_kernel, dim3(1), dim3(kLLBlock), 0, h->stream, d_doc, doc_blocks, d_phi, phi_blocks, h->beta, d_out);

@@ -11,9 +11,14 @@
 // its published source: shift z up to >= 2, Stirling series to 1/(1260 z^5), undo the shift).
 // A diagnostic, not sampler state: the reference adds ~15 M terms of mixed sign in one running
 // double; here partial sums are reduced in a FIXED tree (run-to-run identical, not order-identical
-// to Java), so against the oracle's sequential sum the result agrees to ~1e-12 relative (the sequential sum's own
-// rounding error grows with the number of terms: 5e-11 measured at K=1024 and 18 M tokens), and the
-// test states that tolerance.
+// to Java).  The terms themselves are the oracle's to the bit, so each side differs from the EXACT sum of
+// those terms by at most (c + 2) * 2^-53 * sum|term|, c the longest chain of additions an addend passes
+// through here: the per-thread strided loop, the lane tree (6), the wave partials (4), and the same again
+// in the finish kernel.  tests/diagnostics_cases.py derives c per launch shape, tests/test_diagnostics_gpu.py
+// asserts the bound for K = 1 ... 4096 under pcgs, spalias and polyaurn, to 2049 under ggs (DESIGN.md section 5 has the
+// largest ratios the MI355X showed).  Against the Java-order
+// running sum no such bound holds: that sum's own error grows with the number of terms, (n - 1) * 2^-53 *
+// sum|term| (5e-11 relative of the result measured at K=1024 and 18 M tokens).
 #pragma once
 #include "ggs_device_math.hpp"
 
@@ -29,6 +34,14 @@ __device__ __forceinline__ double log_gamma_stirling(double z) {
 }
 
 constexpr int kLLBlock = 256;
+
+// The two document kernels keep one K-long int32 histogram per document in LDS, a wave per document, four documents per
+// block, beside the block sum's four wave partials: that fits the 160 KiB up to kLLMaxTopics, beyond it the launchers
+// answer GGS_ERR_UNSUPPORTED.  All of it is dynamic LDS: the runtime refuses the 160 KiB cap on a kernel that also has
+// static LDS.
+constexpr int kLLWavePartBytes = (kLLBlock / 64) * (int)sizeof(double);
+constexpr int kLLMaxTopics = (kMaxLdsBytes - kLLWavePartBytes) / ((kLLBlock / 64) * (int)sizeof(int32_t));   // 10238
+inline size_t ll_docs_lds_bytes(int32_t K) { return (size_t)kLLWavePartBytes + (size_t)(kLLBlock / 64) * K * sizeof(int32_t); }
 
 // block-wide sum in a fixed order: lane tree, then wave 0 adds the wave partials in index order
 __device__ __forceinline__ double ll_block_sum(double v, double *wave_part) {
@@ -46,10 +59,10 @@ __device__ __forceinline__ double ll_block_sum(double v, double *wave_part) {
 // one wave per document (4 documents per block): LDS histogram of its z, then the document's term
 __global__ __launch_bounds__(kLLBlock) void ll_docs_kernel(const int64_t *doc_ptr, const int32_t *z, const double *alpha, double alpha_sum,
                                                             int64_t num_docs, int32_t K, double *block_out) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  __shared__ double wave_part[kLLBlock / 64];
+  extern __shared__ __align__(16) unsigned char smem[];       // all of the kernel's LDS is dynamic: the cap set on it is the hardware's
+  double *wave_part = reinterpret_cast<double *>(smem);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  int32_t *hist = reinterpret_cast<int32_t *>(smem) + (size_t)wave * K;
+  int32_t *hist = reinterpret_cast<int32_t *>(smem + kLLWavePartBytes) + (size_t)wave * K;
   const int64_t d = (int64_t)blockIdx.x * (kLLBlock / 64) + wave;
   double v = 0.0;
   if (d < num_docs) {
@@ -109,18 +122,19 @@ __global__ __launch_bounds__(kLLBlock) void ll_finish_kernel(const double *doc_p
 //   document side  sum_tokens log(phi[z][w] + EPS) + sum_d sum_k (n_dk + alpha_k - 1) * log(theta[d][k] + EPS)   :1604-1619
 //   topic side     (beta - 1) * sum_{k,v} log(phi[k][v] + EPS)                                                    :1622-1628
 //
-// with EPS = 1e-12 and theta = the rows the last z step used.  Same reduction as above: fixed tree, ~1e-12
-// relative against the Java-order loop.  Documents without tokens have no theta row in the reference either
+// with EPS = 1e-12 and theta = the rows the last z step used.  Same reduction as above: fixed tree, the same bound
+// against the exact sum of the Java loop's terms (the "+ 2": Java adds count * logPhi per cell and (beta - 1) * logPhi
+// per Phi entry, rounded products; here logPhi is added per token and the Phi sum multiplied once).  Documents without tokens have no theta row in the reference either
 // (GGS:52-53 leaves the row as allocated, zeros): their theta term uses log(0 + EPS), as in Java.
 constexpr double kLogPostEps = 1e-12;
 
 __global__ __launch_bounds__(kLLBlock) void lp_docs_kernel(const int64_t *doc_ptr, const int32_t *tok, const int32_t *z, const double *alpha,
                                                             const double *theta, const double *phiT, int64_t num_docs, int32_t K, int32_t Kp,
                                                             double *block_out) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  __shared__ double wave_part[kLLBlock / 64];
+  extern __shared__ __align__(16) unsigned char smem[];       // all of the kernel's LDS is dynamic: the cap set on it is the hardware's
+  double *wave_part = reinterpret_cast<double *>(smem);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  int32_t *hist = reinterpret_cast<int32_t *>(smem) + (size_t)wave * K;
+  int32_t *hist = reinterpret_cast<int32_t *>(smem + kLLWavePartBytes) + (size_t)wave * K;
   const int64_t d = (int64_t)blockIdx.x * (kLLBlock / 64) + wave;
   double v = 0.0;
   if (d < num_docs) {

@@ -1170,9 +1170,18 @@ static double log_gamma_stirling(double z) {
   return result;
 }
 
+/* The two diagnostics below add every term through acc_add(): the running double is what the Java loop keeps, and a
+ * caller that wants the terms themselves (orc_*_terms) gets each one as the double the running sum receives, in the
+ * order it receives them.  One implementation serves both, so the exported terms cannot drift from the sums. */
+typedef struct { double *buf; int64_t cap, n; } term_sink;
+static inline void acc_add(double *acc, double term, term_sink *sink) {
+  *acc += term;
+  if (sink) { if (sink->buf && sink->n < sink->cap) sink->buf[sink->n] = term; sink->n++; }
+}
+
 /* UPLDA:1644-1758 modelLogLikelihood, in the Java loop order (one running double), split into the part that
  * runs over this state's documents (:1674-1694) and the part that runs over the type-topic counts (:1701-1747). */
-void orc_model_log_likelihood(const orc_state *s, double *doc_side, double *topic_side) {
+static void model_log_likelihood_impl(const orc_state *s, double *doc_side, double *topic_side, term_sink *doc_sink, term_sink *topic_sink) {
   const int32_t K = s->K, V = s->V;
   double alphaSum = 0;
   for (int32_t k = 0; k < K; k++) alphaSum += s->alpha[k];
@@ -1184,11 +1193,11 @@ void orc_model_log_likelihood(const orc_state *s, double *doc_side, double *topi
     const int64_t b = s->doc_ptr[d], e = s->doc_ptr[d + 1];
     for (int64_t i = b; i < e; i++) topicCounts[s->z[i]]++;
     for (int32_t k = 0; k < K; k++)
-      if (topicCounts[k] > 0) ll += (log_gamma_stirling(s->alpha[k] + topicCounts[k]) - topicLogGammas[k]);
-    ll -= log_gamma_stirling(alphaSum + (double)(e - b));
+      if (topicCounts[k] > 0) acc_add(&ll, (log_gamma_stirling(s->alpha[k] + topicCounts[k]) - topicLogGammas[k]), doc_sink);
+    acc_add(&ll, -log_gamma_stirling(alphaSum + (double)(e - b)), doc_sink);
     memset(topicCounts, 0, sizeof(int32_t) * (size_t)K);
   }
-  ll += s->D * log_gamma_stirling(alphaSum);
+  acc_add(&ll, s->D * log_gamma_stirling(alphaSum), doc_sink);
   *doc_side = ll;
   ll = 0.0;
   int64_t nonZeroTypeTopics = 0;
@@ -1197,13 +1206,22 @@ void orc_model_log_likelihood(const orc_state *s, double *doc_side, double *topi
       int32_t c = s->n_wk[(size_t)w * K + k];
       if (c == 0) continue;
       nonZeroTypeTopics++;
-      ll += log_gamma_stirling(s->beta + c);
+      acc_add(&ll, log_gamma_stirling(s->beta + c), topic_sink);
     }
-  for (int32_t k = 0; k < K; k++) ll -= log_gamma_stirling((s->beta * V) + s->n_k[k]);
-  ll += log_gamma_stirling(s->beta * V) * K;
-  ll -= log_gamma_stirling(s->beta) * nonZeroTypeTopics;
+  for (int32_t k = 0; k < K; k++) acc_add(&ll, -log_gamma_stirling((s->beta * V) + s->n_k[k]), topic_sink);
+  acc_add(&ll, log_gamma_stirling(s->beta * V) * K, topic_sink);
+  acc_add(&ll, -(log_gamma_stirling(s->beta) * nonZeroTypeTopics), topic_sink);
   *topic_side = ll;
   free(topicCounts); free(topicLogGammas);
+}
+void orc_model_log_likelihood(const orc_state *s, double *doc_side, double *topic_side) {
+  model_log_likelihood_impl(s, doc_side, topic_side, NULL, NULL);
+}
+int64_t orc_model_log_likelihood_terms(const orc_state *s, int side, double *terms, int64_t cap) {
+  term_sink sink = { terms, terms ? cap : 0, 0 };
+  double a, b;
+  model_log_likelihood_impl(s, &a, &b, side == 0 ? &sink : NULL, side == 0 ? NULL : &sink);
+  return sink.n;
 }
 
 /* UPLDA:710-714: for every scheme but "ggs" the sampling loop draws a fresh theta for its diagnostics from the
@@ -1233,7 +1251,7 @@ int orc_draw_diagnostic_theta(orc_state *s) {
  * dense per-document K x V matrix m_djt is kept as the sorted list of the document's (topic, type) pairs: the Java
  * loop visits k then v ascending and adds count * logPhi for every non-zero cell, and so does this. */
 static int cmp_i64(const void *a, const void *b) { int64_t x = *(const int64_t *)a, y = *(const int64_t *)b; return (x > y) - (x < y); }
-void orc_log_posterior(const orc_state *s, double *doc_side, double *topic_side) {
+static void log_posterior_impl(const orc_state *s, double *doc_side, double *topic_side, term_sink *doc_sink, term_sink *topic_sink) {
   const double EPS = 1e-12;
   const int32_t K = s->K, V = s->V;
   double lp = 0.0;
@@ -1250,19 +1268,28 @@ void orc_log_posterior(const orc_state *s, double *doc_side, double *topic_side)
       int64_t j = i;
       while (j < e - b && cell[j] == cell[i]) j++;
       const int32_t k = (int32_t)(cell[i] / V), v = (int32_t)(cell[i] % V);
-      lp += (double)(j - i) * orc_log(s->phi[(size_t)k * V + v] + EPS);
+      acc_add(&lp, (double)(j - i) * orc_log(s->phi[(size_t)k * V + v] + EPS), doc_sink);
       i = j;
     }
     for (int32_t k = 0; k < K; k++)                          /* :1615-1618 */
-      lp += (n_dj[k] + s->alpha[k] - 1.0) * orc_log(s->theta[(size_t)d * K + k] + EPS);
+      acc_add(&lp, (n_dj[k] + s->alpha[k] - 1.0) * orc_log(s->theta[(size_t)d * K + k] + EPS), doc_sink);
   }
   *doc_side = lp;
   lp = 0.0;
   const double betaMinus1 = s->beta - 1.0;                   /* :1622-1628 */
   for (int32_t k = 0; k < K; k++)
-    for (int32_t v = 0; v < V; v++) lp += betaMinus1 * orc_log(s->phi[(size_t)k * V + v] + EPS);
+    for (int32_t v = 0; v < V; v++) acc_add(&lp, betaMinus1 * orc_log(s->phi[(size_t)k * V + v] + EPS), topic_sink);
   *topic_side = lp;
   free(n_dj); free(cell);
+}
+void orc_log_posterior(const orc_state *s, double *doc_side, double *topic_side) {
+  log_posterior_impl(s, doc_side, topic_side, NULL, NULL);
+}
+int64_t orc_log_posterior_terms(const orc_state *s, int side, double *terms, int64_t cap) {
+  term_sink sink = { terms, terms ? cap : 0, 0 };
+  double a, b;
+  log_posterior_impl(s, &a, &b, side == 0 ? &sink : NULL, side == 0 ? NULL : &sink);
+  return sink.n;
 }
 
 /* ------------------------------------------------------------------------ */

@@ -96,6 +96,12 @@ int orc_init_phi(orc_state *s);                        /* UPLDA:1287-1294       
 void orc_set_phi_mean_gating(orc_state *s, int save, int burn_in, int thin);
 /* UPLDA:1573-1634 computeLogPosterior in the Java loop order; the value is doc_side + topic_side */
 void orc_log_posterior(const orc_state *s, double *doc_side, double *topic_side);
+/* The terms of one side (0 = document side, 1 = topic side) of the two diagnostics, each as the double the running sum
+ * receives and in the order it receives them: orc_log_posterior / orc_model_log_likelihood return their running sum, a
+ * test takes the exact sum (math.fsum) of the same terms.  Writes at most cap terms, returns how many there are
+ * (terms == NULL: only counts). */
+int64_t orc_log_posterior_terms(const orc_state *s, int side, double *terms, int64_t cap);
+int64_t orc_model_log_likelihood_terms(const orc_state *s, int side, double *terms, int64_t cap);
 int orc_draw_diagnostic_theta(orc_state *s);   /* UPLDA:710-714, the non-ggs schemes' theta for the diagnostics */
 /* UPLDA:1644-1758 modelLogLikelihood in the Java loop order; the model's value is doc_side + topic_side */
 void orc_model_log_likelihood(const orc_state *s, double *doc_side, double *topic_side);

@@ -64,6 +64,8 @@ def lib():
         "orc_set_scheme": (None, [vp, C.c_int]),
         "orc_model_log_likelihood": (None, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "orc_log_posterior": (None, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "orc_model_log_likelihood_terms": (C.c_int64, [vp, C.c_int, dp, C.c_int64]),
+        "orc_log_posterior_terms": (C.c_int64, [vp, C.c_int, dp, C.c_int64]),
         "orc_draw_diagnostic_theta": (C.c_int, [vp]),
         "orc_heldout_log_likelihood": (C.c_int, [vp, C.c_int64, lp, ip, C.c_int64, C.c_int32, dp, C.POINTER(C.c_double)]),
         "orc_set_iteration": (None, [vp, C.c_int32]),
@@ -258,6 +260,23 @@ class OracleSampler:
         a, b = C.c_double(), C.c_double()
         lib().orc_log_posterior(self._h, C.byref(a), C.byref(b))
         return a.value, b.value
+
+    def _terms(self, fn):
+        sides = []
+        for side in (0, 1):
+            n = fn(self._h, side, None, 0)
+            out = np.empty(n, np.float64)
+            assert fn(self._h, side, _dp(out), n) == n
+            sides.append(out)
+        return tuple(sides)
+
+    def model_log_likelihood_terms(self):
+        """(document-side terms, topic-side terms): every double model_log_likelihood() adds to its running sum, in order."""
+        return self._terms(lib().orc_model_log_likelihood_terms)
+
+    def log_posterior_terms(self):
+        """(document-side terms, topic-side terms): every double log_posterior() adds to its running sum, in order."""
+        return self._terms(lib().orc_log_posterior_terms)
 
     def heldout_log_likelihood(self, doc_ptr, tokens, num_particles=100, doc_base=0):
         """MarginalProbEstimatorPlain.evaluateLeftToRight (MPE:85-121) on the current counts: (total, per-document)."""
