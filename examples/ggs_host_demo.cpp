@@ -2,7 +2,7 @@
 // tui/ParallelLDA.java:173-296 drives the Java sampler.  Reads an integer corpus
 //   line 1: D V      then D lines: len tok tok ...
 // runs `iterations` sweeps and prints z and tokensPerTopic so a test can compare it with the
-// ctypes path.   usage: ggs_host_demo corpus.txt K alpha beta seed iterations [log_dir [ggs|collapsed]]
+// ctypes path.   usage: ggs_host_demo corpus.txt K alpha beta seed iterations [log_dir [ggs|collapsed|lightpclda]]
 // With a log_dir the corpus doubles as the test set and the loop's diagnostics are on (compute_likelihood,
 // start_diagnostic = 1, log_topic_indicators): the files of the Java driver appear there (ggs_formats.hpp).
 #include <cstdio>
@@ -14,7 +14,7 @@
 #include "ggs_sampler.hpp"
 
 int main(int argc, char **argv) {
-  if (argc < 7 || argc > 9) { std::fprintf(stderr, "usage: %s corpus.txt K alpha beta seed iterations [log_dir [ggs|collapsed]]\n", argv[0]); return 2; }
+  if (argc < 7 || argc > 9) { std::fprintf(stderr, "usage: %s corpus.txt K alpha beta seed iterations [log_dir [ggs|collapsed|lightpclda]]\n", argv[0]); return 2; }
   std::ifstream in(argv[1]);
   ggs::InstanceList inst;
   int64_t D;
@@ -31,6 +31,7 @@ int main(int argc, char **argv) {
   const bool logging = argc >= 8;
   if (logging) { cfg.log_dir = argv[7]; cfg.compute_likelihood = true; cfg.start_diagnostic = 1; cfg.log_topic_indicators = true; }
   cfg.collapsed = argc >= 9 && std::string(argv[8]) == "collapsed";
+  cfg.lightpclda = argc >= 9 && std::string(argv[8]) == "lightpclda";
   struct Counting : ggs::LDAGroupedGibbsSampler {
     using LDAGroupedGibbsSampler::LDAGroupedGibbsSampler;
     int pre = 0, post = 0;

@@ -86,7 +86,7 @@ enum {
                                      2 * threshold terms and renormalised, larger counts as max(0, floor(sqrt(l) * g + l + 0.5))
                                      with l = beta + n_kv and the element's Gaussian g (PolyaUrnDirichlet.java:102-107, the
                                      negative draw clamped to 0).  Phi has exact zeros.  With GGS_FLAG_COLLAPSED: GGS_ERR_BAD_ARG. */
-  GGS_FLAG_SPALIAS = 1 << 5       /* scheme=spalias (SpaliasUncollapsedParallelLDA, ParallelLDA.java:439-442): the pcgs model
+  GGS_FLAG_SPALIAS = 1 << 5,      /* scheme=spalias (SpaliasUncollapsedParallelLDA, ParallelLDA.java:439-442): the pcgs model
                                      (implied: GGS_FLAG_PCGS is set internally; Phi, counts, phi mean and exchange exactly as pcgs)
                                      with the z step's conditional split into alpha_k * phi[k][w], drawn in O(1) from a Walker alias
                                      table per word, and n_dk * phi[k][w], walked over the document's non-zero topics only: the
@@ -94,6 +94,20 @@ enum {
                                      rebuilt whenever Phi changes (ggs_init_phi, every sweep, ggs_set_phi); ggs_get_alias_tables
                                      reads them back.  K up to 4096, any document length.  With GGS_FLAG_COLLAPSED or
                                      GGS_FLAG_POLYAURN: GGS_ERR_BAD_ARG.  A new bit, not a new ABI version. */
+  GGS_FLAG_LIGHTPCLDA = 1 << 6    /* scheme=lightpclda (LightPCLDA, ParallelLDA.java:469-473; LightPCLDA.java:86-221): the pcgs model
+                                     (implied: GGS_FLAG_PCGS is set internally; Phi, counts, phi mean and exchange exactly as pcgs)
+                                     with a Metropolis-Hastings z step, O(1) per token: a proposal from the word's alias table
+                                     and one from the document's own indicator array, each accepted on a ratio of a few numbers.
+                                     The tables are spalias's, pi[k] = phi[k][w] * alpha[k] (the reference's PhiTableBuilderFactory,
+                                     LightPCLDA.java:50-83, is never installed), rebuilt wherever spalias rebuilds them;
+                                     ggs_get_alias_tables reads them back, ggs_get_mh_stats the acceptance counters.  The four
+                                     uniforms of a token are the two doubles of Philox block 0 and the two of block 1 of its Z
+                                     stream, taken whether or not the branch that uses them runs.  When the document proposal
+                                     equals the current topic the new topic is the token's OLD one, as in the reference
+                                     (LightPCLDA.java:115, 175).  An alias draw or an alpha-branch topic equal to K is
+                                     GGS_ERR_INVALID_TOPIC.  The chain is approximate by design and is not repaired.
+                                     K up to 4096, any document length.  With GGS_FLAG_COLLAPSED, GGS_FLAG_POLYAURN or
+                                     GGS_FLAG_SPALIAS: GGS_ERR_BAD_ARG.  A new bit, not a new ABI version. */
 };
 
 /* RNG stream addressing.  The reference draws from ThreadLocalRandom and a
@@ -353,7 +367,8 @@ int ggs_get_warm_tiers(ggs_handle *h, int32_t *tiers, int32_t *warm_words, int32
 int ggs_get_z_parts(ggs_handle *h, int32_t *parts);
 /* Which z kernel(s) the sweeps of the current corpus run, so that a benchmark line can NAME what it timed instead of
  * assuming it: *kernel = 0 whole-row tile kernel, 1 score-register kernels (K <= 160), 2 one-pass streaming kernel,
- * 3 its two-pass cross-check, 4 pcgs lane-per-document, 5 pcgs wave-per-document; *form (kernel 1 only, else 0) =
+ * 3 its two-pass cross-check, 4 pcgs lane-per-document, 5 pcgs wave-per-document, 6 spalias wave-per-document,
+ * 7 lightpclda wave-per-document; *form (kernel 1 only, else 0) =
  * 1 split (cold chunks and hot chunks as two kernels side by side), 2 fused (one kernel takes both in turn);
  * *calibrated = 1 once the first z step of the corpus has timed both forms and kept the faster (0 before that, and
  * when a form is forced or there is nothing to split).  ABI version 4. */
@@ -372,9 +387,14 @@ int ggs_debug_poisson(int32_t device_id, double beta, int32_t threshold, uint64_
  * product kernel from phi [K][V] and alpha [K]: ps [V][K], a [V][K] and type_norm [V] = the k-order sum of phi[k][w] * alpha[k].
  * A draw x in [0, 1) from word w's table: ups = x * K, i = (int)ups, topic = (ups - i) > ps[w][i] ? a[w][i] : i.  K up to 4096. */
 int ggs_debug_alias(int32_t device_id, int32_t V, int32_t K, const double *phi, const double *alpha, double *ps, int32_t *a, double *type_norm);
-/* the tables of the handle's current Phi (GGS_FLAG_SPALIAS; GGS_ERR_STATE otherwise or before the first Phi); any of the
- * three outputs may be null */
+/* the tables of the handle's current Phi (GGS_FLAG_SPALIAS or GGS_FLAG_LIGHTPCLDA; GGS_ERR_STATE otherwise or before the
+ * first Phi); any of the three outputs may be null */
 int ggs_get_alias_tables(ggs_handle *h, double *ps /*[V][K]*/, int32_t *a /*[V][K]*/, double *type_norm /*[V]*/);
+/* scheme=lightpclda's Metropolis-Hastings counters, cumulative since ggs_set_corpus (the three the reference keeps
+ * commented out, LightPCLDA.java:28-44), every token in exactly one: out[0] tokens whose word proposal was accepted and
+ * kept, out[1] tokens whose document proposal was accepted, out[2] tokens left on their old topic.  GGS_ERR_STATE
+ * without GGS_FLAG_LIGHTPCLDA. */
+int ggs_get_mh_stats(ggs_handle *h, int64_t out[3]);
 /* replaces: modelLogLikelihood (UPLDA:1644-1758), the Dirichlet-multinomial log likelihood of the current topic
  * assignments, split where a doc-sharded run splits it: doc_side covers THIS handle's documents (sum_d [...] +
  * D*lgS(alphaSum), UPLDA:1674-1694) and topic_side the (replicated) type-topic counts (UPLDA:1701-1747); the model's

@@ -50,6 +50,7 @@ struct LDAConfiguration {
   bool collapsed = false;         // scheme=collapsed (ParallelLDA.java:424-428, SerialCollapsedLDA): the serial chain of MSLDA:158-226
   bool polyaurn = false;          // scheme=polyaurn (ParallelLDA.java:444-447, PolyaUrnSpaliasLDA): the pcgs z step over a Poisson-drawn Phi
   bool spalias = false;           // scheme=spalias (ParallelLDA.java:439-442, SpaliasUncollapsedParallelLDA): the pcgs model, a sparse z step over alias tables
+  bool lightpclda = false;        // scheme=lightpclda (ParallelLDA.java:469-473, LightPCLDA): the pcgs model, a Metropolis-Hastings z step over alias tables
   int alias_poisson_threshold = 100;   // ALIAS_POISSON_DEFAULT_THRESHOLD (LDAConfiguration.java:44); read under polyaurn only
   int device_id = 0;
   // the diagnostics of the sampling loop (UPLDA:695-905), computed on the device, written as the Java driver writes them
@@ -86,7 +87,7 @@ class LDAGroupedGibbsSampler {
     c.seed = (uint64_t)(int64_t)startSeed_;
     c.flags = (config_.paranoid ? GGS_FLAG_PARANOID : 0) | (config_.save_phi_mean ? GGS_FLAG_SAVE_PHI_MEAN : 0) |
               (config_.pcgs ? GGS_FLAG_PCGS : 0) | (config_.collapsed ? GGS_FLAG_COLLAPSED : 0) | (config_.polyaurn ? GGS_FLAG_POLYAURN : 0) |
-              (config_.spalias ? GGS_FLAG_SPALIAS : 0);
+              (config_.spalias ? GGS_FLAG_SPALIAS : 0) | (config_.lightpclda ? GGS_FLAG_LIGHTPCLDA : 0);
     c.alias_poisson_threshold = config_.alias_poisson_threshold;
     c.phi_burn_in = (int32_t)(((double)config_.phi_mean_burnin / 100) * config_.iterations);   // UPLDA:206-207
     c.phi_mean_thin = config_.phi_mean_thin;

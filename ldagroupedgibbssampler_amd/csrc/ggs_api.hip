@@ -22,6 +22,7 @@
 #include "ggs_phi_poisson.hpp"
 #include "ggs_alias.hpp"
 #include "ggs_z_spalias.hpp"
+#include "ggs_z_lightpc.hpp"
 #include "ggs_loglik.hpp"
 #include "ggs_heldout.hpp"
 #include "ggs_exchange.hpp"
@@ -96,11 +97,12 @@ struct LaunchPlan {
   bool parts_forced = false;
   KernelLaunch theta;                  // its LDS and documents per workgroup: the configuration's, or ...
   int32_t theta_docs_main = 0, theta_lds_main = 0;   // ... where the theta draw is the critical leg (theta_main)
-  // scheme pcgs / collapsed / polyaurn: a lane or a wave per document; spalias: the table build and the sparse walk (LDS per corpus)
-  KernelLaunch lane, wave, alias, spalias, serial;
+  // scheme pcgs / collapsed / polyaurn: a lane or a wave per document; spalias: the table build and the sparse walk (LDS per corpus);
+  // lightpclda: the same table build and the Metropolis-Hastings step
+  KernelLaunch lane, wave, alias, spalias, lightpc, serial;
   bool wave_forced = false;            // ... because of K; otherwise per corpus (a document of 32 768 tokens or more)
   int32_t alias_wpb = 0;
-  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &serial}; }
+  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial}; }
 };
 
 // The phase events of one sweep.  Sweeps are settled (waited for, checked, timed) in batches, so a ring of them:
@@ -160,6 +162,11 @@ struct ggs_handle {
   int32_t *d_alias_a = nullptr;                        // [V][K]
   KernelLaunch sp_z;                                   // of the current corpus: plan.spalias with the LDS of lists of sp_cap entries
   int32_t sp_cap = 0;
+  // scheme=lightpclda (ggs_z_lightpc.hpp): the pcgs model and spalias's tables, a Metropolis-Hastings z step
+  bool lightpc = false;
+  bool has_alias() const { return spalias || lightpc; }
+  double alpha_sum = 0;                                // the k-order sum of alpha
+  unsigned long long *d_mh = nullptr;                  // [3]: ggs_get_mh_stats, zeroed by ggs_set_corpus
   uint64_t *d_lcg = nullptr;                           // ggs_collapsed_serial_sweep: the java.util.Random state
   bool lcg_ready = false;
   int32_t num_hot = 0;
@@ -793,7 +800,7 @@ int phi_step_c(ggs_handle *h, bool accumulate_mean) {
 // holds the whole Phi after the all-gather and builds all V words for itself: what a rank's shard contains changes
 // with the corpus, the tables' layout does not.
 int launch_alias_build(ggs_handle *h) {
-  if (!h->spalias) return GGS_OK;
+  if (!h->has_alias()) return GGS_OK;
   AliasParams ap{};
   ap.phiT = h->d_phiT; ap.alpha = h->d_alpha; ap.ps = h->d_alias_ps; ap.a = h->d_alias_a; ap.type_norm = h->d_alias_tn;
   ap.V = h->V; ap.K = h->K; ap.Kp = h->Kp; ap.wpb = h->plan.alias_wpb;
@@ -1059,6 +1066,17 @@ int plan_launches(const int K, const int V, const int32_t flags, const Knobs &kn
     pl.alias.per_cu = lds_workgroups_per_cu(pl.alias.lds, 16);
     pl.spalias.fn = reinterpret_cast<const void *>(spalias_wave_kernel);
   }
+  if (flags & GGS_FLAG_LIGHTPCLDA) {
+    pl.alias_wpb = alias_words_per_block(K);
+    pl.alias = {reinterpret_cast<const void *>(alias_build_kernel), 64, (int)alias_lds_bytes(K, pl.alias_wpb), 0};
+    pl.alias.per_cu = lds_workgroups_per_cu(pl.alias.lds, 16);
+    // the resident single-wave workgroups: what the kernel's registers allow (asked of the runtime) and what LDS allows, at
+    // most the CU's 32 -- a lone wave issues at a fraction of a SIMD's rate, and the step is a chain of dependent operations
+    pl.lightpc = {reinterpret_cast<const void *>(lightpc_wave_kernel), 64, (int)lightpc_lds_bytes(K), 0};
+    int by_regs = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, pl.lightpc.fn, 64, (size_t)pl.lightpc.lds) != hipSuccess || by_regs < 1) by_regs = 1;
+    pl.lightpc.per_cu = lds_workgroups_per_cu(pl.lightpc.lds, std::min(by_regs, 32));
+  }
   return GGS_OK;
 }
 
@@ -1076,6 +1094,14 @@ int launch_pcgs_z(ggs_handle *h) {
     sp.b = pp; sp.ps = h->d_alias_ps; sp.a = h->d_alias_a; sp.type_norm = h->d_alias_tn; sp.cap = h->sp_cap; sp.margin_scale = h->margin_scale;
     void *args[] = {&sp};
     HIP_TRY(h, launch(h, h->sp_z, h->pcgs_order_len, args, h->stream));
+    return GGS_OK;
+  }
+  if (h->lightpc) {                                    // one wave per document, two proposals per token (ggs_z_lightpc.hpp)
+    if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
+    LightpcParams lp{};
+    lp.b = pp; lp.ps = h->d_alias_ps; lp.a = h->d_alias_a; lp.mh = h->d_mh; lp.alpha_sum = h->alpha_sum;
+    void *args[] = {&lp};
+    HIP_TRY(h, launch(h, h->plan.lightpc, h->pcgs_order_len, args, h->stream));
     return GGS_OK;
   }
   if (h->collapsed) {
@@ -1573,6 +1599,8 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
   // scheme=spalias runs over the pcgs model only (polyaurn over the sparse z step is not provided): an argument error,
   // answered before any device is asked for
   if ((cfg->flags & GGS_FLAG_SPALIAS) && (cfg->flags & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN))) return GGS_ERR_BAD_ARG;
+  // scheme=lightpclda likewise, and it is not spalias: one z step per handle
+  if ((cfg->flags & GGS_FLAG_LIGHTPCLDA) && (cfg->flags & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS))) return GGS_ERR_BAD_ARG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device_id < 0 || cfg->device_id >= ndev) return GGS_ERR_HIP;
   ggs_handle *h = new (std::nothrow) ggs_handle();
@@ -1594,11 +1622,16 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     if (h->K > kPcgsWaveMaxTopics) { delete h; return GGS_ERR_UNSUPPORTED; }
     h->spalias = true; h->flags |= GGS_FLAG_PCGS;
   }
+  if (h->flags & GGS_FLAG_LIGHTPCLDA) {               // the pcgs model and spalias's tables; a Metropolis-Hastings z step
+    if (h->K > kPcgsWaveMaxTopics) { delete h; return GGS_ERR_UNSUPPORTED; }
+    h->lightpc = true; h->flags |= GGS_FLAG_PCGS;
+  }
   h->phi_burn_in = cfg->phi_burn_in; h->phi_thin = cfg->phi_mean_thin > 0 ? cfg->phi_mean_thin : 1;
   h->alpha.assign(h->K, cfg->alpha_scalar);
   if (cfg->alpha) std::copy(cfg->alpha, cfg->alpha + h->K, h->alpha.begin());
   for (double a : h->alpha)
     if (!(a > 0)) { delete h; return GGS_ERR_BAD_ARG; }
+  for (double a : h->alpha) h->alpha_sum = h->alpha_sum + a;
   // 2. the handle's own switches
   // GGS_DEBUG_MARGIN: above 1 the margins force the exact replays in tests.  Below 1 voids the proof, so only the float32 cold
   // kernel takes it (its decided draw is a count of partial sums, always a topic < K); the checkpoint-and-refine walks of the
@@ -1655,7 +1688,8 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
       hipMemset(h->d_n_k, 0, sizeof(int32_t) * h->K) != hipSuccess || hipMemset(h->d_status, 0, 16) != hipSuccess ||
       (h->d_phi_mean && hipMemset(h->d_phi_mean, 0, sizeof(double) * kv) != hipSuccess))
     return bail(GGS_ERR_HIP);
-  if (h->spalias && ((rc = dev_alloc(h, &h->d_alias_ps, kv)) || (rc = dev_alloc(h, &h->d_alias_a, kv)) || (rc = dev_alloc(h, &h->d_alias_tn, (size_t)h->V)))) return bail(rc);
+  if (h->has_alias() && ((rc = dev_alloc(h, &h->d_alias_ps, kv)) || (rc = dev_alloc(h, &h->d_alias_a, kv)) || (rc = dev_alloc(h, &h->d_alias_tn, (size_t)h->V)))) return bail(rc);
+  if (h->lightpc && ((rc = dev_alloc(h, &h->d_mh, 3)) || hipMemset(h->d_mh, 0, 3 * sizeof(unsigned long long)) != hipSuccess)) return bail(rc ? rc : GGS_ERR_HIP);
   if (h->polyaurn) {
     std::vector<double> T;
     build_poisson_table(h->beta, h->pa_L, T);
@@ -1815,6 +1849,7 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   HIP_TRY(h, hipMemset(h->d_zw, 0, sizeof(int32_t) * std::max<size_t>((size_t)N, 1)));
   HIP_TRY(h, hipMemset(h->d_theta, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
   HIP_TRY(h, hipMemset(h->d_theta_next, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
+  if (h->d_mh) HIP_TRY(h, hipMemset(h->d_mh, 0, 3 * sizeof(unsigned long long)));
   HIP_TRY(h, hipDeviceSynchronize());   // the uploads and memsets above ran on the null stream; the handle's stream may not synchronise with it
 
   // 5. a new corpus: no Phi, no sweep in progress, the z form to be timed again
@@ -2347,7 +2382,7 @@ int ggs_get_alias_tables(ggs_handle *h, double *ps, int32_t *a, double *type_nor
   if (!h) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (!h->spalias) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS");
+  if (!h->has_alias()) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS or GGS_FLAG_LIGHTPCLDA");
   if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
   if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
   const size_t kv = (size_t)h->K * h->V;
@@ -2355,6 +2390,17 @@ int ggs_get_alias_tables(ggs_handle *h, double *ps, int32_t *a, double *type_nor
   if (a) HIP_TRY(h, hipMemcpyAsync(a, h->d_alias_a, kv * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   if (type_norm) HIP_TRY(h, hipMemcpyAsync(type_norm, h->d_alias_tn, (size_t)h->V * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return GGS_OK;
+}
+int ggs_get_mh_stats(ggs_handle *h, int64_t out[3]) {
+  if (!h || !out) return GGS_ERR_BAD_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (!h->lightpc) return set_err(h, GGS_ERR_STATE, "ggs_get_mh_stats needs GGS_FLAG_LIGHTPCLDA");
+  unsigned long long v[3];
+  HIP_TRY(h, hipMemcpyAsync(v, h->d_mh, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int i = 0; i < 3; ++i) out[i] = (int64_t)v[i];
   return GGS_OK;
 }
 int ggs_get_phi_mean(ggs_handle *h, double *phi_mean, int32_t *n_sampled) {
@@ -2673,7 +2719,7 @@ int ggs_get_z_form(ggs_handle *h, int32_t *kernel, int32_t *form, int32_t *calib
   if (!h) return GGS_ERR_BAD_ARG;
   const bool pcgs = (h->flags & GGS_FLAG_PCGS) != 0;
   const bool splittable = !pcgs && h->plan.sliced() && h->Cs > h->Cc && h->Cc > 0;
-  if (kernel) *kernel = h->spalias ? 6 : pcgs ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
+  if (kernel) *kernel = h->lightpc ? 7 : h->spalias ? 6 : pcgs ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
   if (form) *form = (!pcgs && h->plan.sliced()) ? (splittable && h->z_split ? 1 : 2) : 0;
   if (calibrated) *calibrated = (splittable && h->z_split_tried && !h->plan.split_forced && h->plan.split) ? 1 : 0;
   return GGS_OK;

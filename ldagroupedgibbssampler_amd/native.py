@@ -8,7 +8,7 @@ from . import _lib
 OK = 0
 ERR_NEGATIVE_COUNT, ERR_INVALID_TOPIC, ERR_RNG_EXHAUSTED, ERR_BAD_ARG = 1, 2, 3, 4
 ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_INVARIANT = 5, 6, 7, 8
-FLAG_PARANOID, FLAG_SAVE_PHI_MEAN, FLAG_PCGS, FLAG_COLLAPSED, FLAG_POLYAURN, FLAG_SPALIAS = 1, 2, 4, 8, 16, 32
+FLAG_PARANOID, FLAG_SAVE_PHI_MEAN, FLAG_PCGS, FLAG_COLLAPSED, FLAG_POLYAURN, FLAG_SPALIAS, FLAG_LIGHTPCLDA = 1, 2, 4, 8, 16, 32, 64
 PURPOSE_Z, PURPOSE_THETA, PURPOSE_PHI, PURPOSE_INIT_PHI = 1, 2, 3, 4
 
 
@@ -256,10 +256,17 @@ class GGSHandle:
         return (out, n.value) if n.value else (None, 0)
 
     def alias_tables(self):
-        """scheme=spalias: the alias tables of the current Phi, (ps [V][K], a [V][K], type_norm [V])."""
+        """scheme=spalias or lightpclda: the alias tables of the current Phi, (ps [V][K], a [V][K], type_norm [V])."""
         ps, a, tn = np.empty((self.V, self.K), np.float64), np.empty((self.V, self.K), np.int32), np.empty(self.V, np.float64)
         self._chk(self._L.ggs_get_alias_tables(self._h, _dp(ps), _ip(a), _dp(tn)))
         return ps, a, tn
+
+    def mh_stats(self):
+        """scheme=lightpclda: tokens whose word proposal was accepted and kept, whose document proposal was accepted, and
+        tokens left on their old topic, cumulative since set_corpus (int64 [3]; they sum to the tokens sampled)."""
+        out = np.zeros(3, np.int64)
+        self._chk(self._L.ggs_get_mh_stats(self._h, _lp(out)))
+        return out
 
     def get_theta(self, doc_begin=0, doc_end=None):
         doc_end = self.D if doc_end is None else doc_end
@@ -329,7 +336,7 @@ class GGSHandle:
 
 Z_KERNEL_NAMES = {0: "z_kernel (whole-row tiles)", 1: "z_sliced_kernel + z_hot_kernel (score registers)", 2: "z_stream1_kernel (one pass)",
                   3: "z_stream_kernel (two passes)", 4: "pcgs_sliced_kernel (lane per document)", 5: "pcgs_wave_kernel (wave per document)",
-                  6: "spalias_wave_kernel (wave per document)"}
+                  6: "spalias_wave_kernel (wave per document)", 7: "lightpc_wave_kernel (wave per document)"}
 
 
 class GGSGroup:

@@ -417,6 +417,24 @@ class SpaliasUncollapsedParallelLDA(LDAPartiallyCollapsedGibbsSampler):
         return self._h.alias_tables()
 
 
+class LightPCLDA(LDAPartiallyCollapsedGibbsSampler):
+    """scheme=lightpclda (topics/LightPCLDA.java, ParallelLDA.java:469-473): the pcgs model and driver and spalias's alias
+    tables; the z step makes two Metropolis-Hastings proposals per token, one from the word's table and one from the
+    document's own indicator array: O(1) per token.  The chain is approximate by design."""
+    _scheme_flags = native.FLAG_LIGHTPCLDA
+
+    def getTheta(self):
+        raise NotImplementedError("scheme=lightpclda never draws theta; use getThetaEstimate() (UPLDA:716-720 does the same)")
+
+    def getAliasTables(self):
+        """(ps [V][K], a [V][K], typeNorm [V]) of the current Phi"""
+        return self._h.alias_tables()
+
+    def getMHStats(self):
+        """tokens whose word proposal was kept, whose document proposal was accepted, left on their old topic (cumulative)"""
+        return self._h.mh_stats()
+
+
 class SerialCollapsedLDA(LDAGroupedGibbsSampler):
     """scheme=collapsed (topics/SerialCollapsedLDA.java; the conditional it samples from is sampleTopicsForOneDoc,
     MSLDA:158-226).  `schedule`:
@@ -452,7 +470,7 @@ class SerialCollapsedLDA(LDAGroupedGibbsSampler):
 
 
 def create_model(config, scheme=None):
-    """The `case "ggs"` / `case "pcgs"` / `case "collapsed"` / `case "polyaurn"` / `case "spalias"` of tui/ParallelLDA.createModel
+    """The `case "ggs"` / `case "pcgs"` / `case "collapsed"` / `case "polyaurn"` / `case "spalias"` / `case "lightpclda"` of tui/ParallelLDA.createModel
     (ParallelLDA.java:401-490)."""
     scheme = scheme or config.scheme
     if scheme == "ggs":
@@ -465,4 +483,6 @@ def create_model(config, scheme=None):
         return PolyaUrnSpaliasLDA(config)
     if scheme == "spalias":
         return SpaliasUncollapsedParallelLDA(config)
-    raise ValueError("scheme %r is not provided by this build (only the ggs, pcgs, collapsed, polyaurn and spalias z loops are in scope)" % scheme)
+    if scheme == "lightpclda":
+        return LightPCLDA(config)
+    raise ValueError("scheme %r is not provided by this build (only the ggs, pcgs, collapsed, polyaurn, spalias and lightpclda z loops are in scope)" % scheme)
