@@ -15,6 +15,7 @@ import pytest
 from ldagroupedgibbssampler_amd.corpus import Corpus, even_split, random_corpus, synthetic_lda_corpus
 from ldagroupedgibbssampler_amd.sharded import java_lcg_initial_z
 from tests import lda_posterior as LP
+from tests import lightpclda_knife_edge as KE
 from tests import lightpclda_restatement as R
 from tests.test_native_exchange_gpu import ThreadTransport, assert_bit_equal
 
@@ -87,14 +88,28 @@ def test_phi_mean_with_burn_in_and_thin(native, oracle, cats):
 def test_ragged_corpus(native, oracle):
     """Documents of 0 and 1 tokens (the one-token document: (int)ui can only be 0 or the alpha branch), 63, 64 and 65 (chunk
     boundaries), 130, and 700 tokens over V = 5, where most (int)ui land inside the current chunk, in an earlier chunk or
-    on the token itself."""
-    rng = np.random.default_rng(3)
-    lens = np.array([63, 0, 1, 64, 700, 65, 1, 130, 0, 2], np.int64)
-    tokens = rng.integers(0, 5, lens.sum()).astype(np.int32)
-    c = Corpus(np.concatenate(([0], np.cumsum(lens))).astype(np.int64), tokens, 5)
-    g, m = run_pair(native, c, 7, 0.3, 0.1, 3)
+    on the token itself -- counted: over the sweeps at least 20 tokens draw their document proposal from each of the
+    token's own position, a later one, an earlier one of the same 64-token chunk, an earlier chunk and the alpha branch,
+    both after an accepted word proposal and without (12 sweeps: the own position without an accepted word proposal, one
+    token in about len + alphaSum of those, is what needs them)."""
+    doc_ptr, tokens = KE.ragged_corpus()
+    c = Corpus(doc_ptr, tokens, KE.RAGGED["V"])
+    q = KE.RAGGED
+    assert SEED == q["seed"]
+    g, m = run_pair(native, c, q["K"], q["alpha"], q["beta"], q["sweeps"], zseed=q["zseed"])
     assert (m.stats > 0).all()
     g.close()
+    walk = KE.ragged_model(java_lcg_initial_z(c.num_tokens, q["K"], q["zseed"]))
+    counts = {}
+    for _ in range(q["sweeps"]):
+        z = KE.count_dt_sources(walk, counts)
+        walk.sweep(1)
+        assert (z == walk.z).all()
+    assert (walk.z == m.z).all()                                    # the walk counted the chain the device was compared with
+    print("document proposals by (source, after an accepted word proposal): %s" % sorted(counts.items()))
+    for src in KE.RAGGED_SOURCES:
+        for after in (False, True):
+            assert counts.get((src, after), 0) >= 20, (src, after, counts)
 
 
 @pytest.mark.parametrize("K", [1024, 4096])
