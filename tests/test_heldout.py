@@ -3,6 +3,13 @@
 The reference has no test and no golden output for this estimator and draws from a clock-seeded Randoms: parity
 unpinned against a JVM run.  What pins the oracle's restatement here: closed forms (one-token documents are exact;
 a two-token document's exact marginal against many particles), and what pins the device: the oracle, bit for bit.
+
+Those closed forms stop at the second token: the first draw happens with no counts and the second draw's result is never
+used.  Everything that happens from the third token on (the topic-beta bucket, the sorted localTopicIndex, the update of
+cachedCoefficients, topicBetaMass around a draw, tokensSoFar beyond 1) is pinned against the model in
+tests/test_heldout_model.py and tests/test_heldout_model_gpu.py (the enumerated sequential-proposal limit of
+tests/heldout_model.py, with its own variance), and the five comparisons of the particle pass at their exact edges in
+tests/test_heldout_knife_edge_model.py and tests/test_heldout_knife_edge_gpu.py (the rows of tests/heldout_knife_edge.py).
 """
 import numpy as np
 import pytest
