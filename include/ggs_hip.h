@@ -351,7 +351,11 @@ int ggs_reset_timings(ggs_handle *h);
  * deltas zero at postSample", ParanoidUncollapsedParallelLDA.java:42-55, has no device
  * counterpart: there is no delta matrix, the counts are rebuilt from z every sweep.) */
 int ggs_check_invariants(ggs_handle *h);
-/* Launch geometry of the z kernel, for bench.py's roofline accounting. */
+/* Launch geometry of the z kernel the handle launches (ggs_get_z_form names it), for bench.py's roofline accounting.
+ * lds_bytes_z: the dynamic LDS of that launch (score-register kernels: of the fused form with a full hot table; scheme
+ * spalias: of the current corpus, since its lists are sized by the longest document).  num_chunks: the work items the
+ * persistent grid strides -- chunks for scheme ggs; for the other schemes entries of the document order (wave per
+ * document) or groups of 64 of them (lane per document); 0 before ggs_set_corpus. */
 int ggs_get_launch_info(ggs_handle *h, int64_t *num_chunks, int32_t *lds_bytes_z, int32_t *docs_per_block_theta);
 /* Words whose phiT rows the z kernels keep in LDS tables for the current corpus -- the hot-word table plus the warm
  * tiers' tables (0 for K > 192 and scheme pcgs): tokens of these, the most frequent words of the handle's corpus, read

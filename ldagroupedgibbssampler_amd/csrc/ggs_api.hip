@@ -64,6 +64,12 @@ struct Knobs {
 
 constexpr int kThetaBlock = 256;
 
+// What a handle samples and how: derived once from ggs_config::flags (scheme_of).  Every scheme but ggs runs the pcgs
+// machinery: no theta in the chain, a document order instead of chunk lists, the plan's lane / wave / ... entries.
+enum class Scheme { ggs, pcgs, collapsed, polyaurn, spalias, lightpclda };
+constexpr bool pcgs_family(Scheme s) { return s != Scheme::ggs; }
+constexpr bool has_alias(Scheme s) { return s == Scheme::spalias || s == Scheme::lightpclda; }
+
 // One kernel as a handle launches it: the function, its workgroup, its dynamic LDS and the workgroups per CU of its
 // persistent grid.  The table kernels' LDS is given without table rows (they differ by corpus).
 struct KernelLaunch {
@@ -71,10 +77,10 @@ struct KernelLaunch {
   int block = 64, lds = 0, per_cu = 0;
 };
 // The launches a handle can make and the few numbers the corpus step needs: decided once, by plan_launches() from
-// (K, V, flags, CUs, knobs).  What depends on the corpus (a long document, D against V, the timed split) chooses
-// BETWEEN these entries.
+// (K, V, scheme, CUs, knobs): the ggs entries for scheme ggs only, the pcgs entries for the pcgs family only.  What
+// depends on the corpus (a long document, D against V, the timed split) chooses BETWEEN these entries.
 struct LaunchPlan {
-  int32_t kernel = 0;                  // the ggs z kernel, as ggs_get_z_form numbers it: 0 whole-row tiles, 1 score registers (sliced), 2 streaming in one pass, 3 in two
+  int32_t kernel = 0;                  // the ggs z kernel, as ggs_get_z_form numbers it: 0 whole-row tiles, 1 score registers (sliced), 2 streaming in one pass, 3 in two; the pcgs family leaves it 0
   bool sliced() const { return kernel == 1; }
   bool stream() const { return kernel >= 2; }
   KernelLaunch z;                      // the tile kernel or the streaming kernel
@@ -125,7 +131,8 @@ struct ggs_handle {
   double beta = 0;
   std::vector<double> alpha;
   uint64_t seed = 0;
-  int32_t flags = 0, phi_burn_in = 0, phi_thin = 1;
+  int32_t flags = 0, phi_burn_in = 0, phi_thin = 1;   // flags: as the caller passed them
+  Scheme scheme = Scheme::ggs;
   int32_t iteration = 0;
   int32_t n_sampled_phi = 0;
 
@@ -148,23 +155,19 @@ struct ggs_handle {
   int32_t *d_order = nullptr;                          // scheme=pcgs: local documents, longest first
   int64_t pcgs_order_len = 0;                          // entries of d_order (documents, or the padded two-round list)
   bool pcgs_wave = false;                              // of the current corpus: plan.wave (wide rows, or a document of 32 768 tokens or more) instead of plan.lane
-  bool collapsed = false;                              // scheme=collapsed: the pcgs machinery over psi = (beta + n_wk)/(betaSum + n_k)
+  KernelLaunch pcgs_z;                                 // the plan entry launch_pcgs_z launches (pcgs_entry; spalias: with the LDS of lists of sp_cap entries) ...
+  int64_t pcgs_items = 0;                              // ... over this many work items: entries of d_order, or groups of 64 of them (plan.lane)
   // scheme=polyaurn (ggs_phi_poisson.hpp): the pcgs z loop with its two uniform-draw rules, Phi drawn as Poisson counts
-  bool polyaurn = false;
   int32_t pa_L = 0;                                    // alias_poisson_threshold
   double pa_t00 = 0;                                   // T_0[0]
   double *d_pa_table = nullptr;                        // [L][2L]
   unsigned long long *d_pa_acc = nullptr;              // [K][kPoissonAccStride]: the draw's integer totals
   // scheme=spalias (ggs_alias.hpp, ggs_z_spalias.hpp): the pcgs model, the z step split into an alias draw and a sparse walk
-  bool spalias = false;
   bool alias_stale = true;                             // Phi has changed since the tables were built
   double *d_alias_ps = nullptr, *d_alias_tn = nullptr; // [V][K], [V]
   int32_t *d_alias_a = nullptr;                        // [V][K]
-  KernelLaunch sp_z;                                   // of the current corpus: plan.spalias with the LDS of lists of sp_cap entries
-  int32_t sp_cap = 0;
+  int32_t sp_cap = 0;                                  // of the current corpus: entries of a document's list of non-zero topics
   // scheme=lightpclda (ggs_z_lightpc.hpp): the pcgs model and spalias's tables, a Metropolis-Hastings z step
-  bool lightpc = false;
-  bool has_alias() const { return spalias || lightpc; }
   double alpha_sum = 0;                                // the k-order sum of alpha
   unsigned long long *d_mh = nullptr;                  // [3]: ggs_get_mh_stats, zeroed by ggs_set_corpus
   uint64_t *d_lcg = nullptr;                           // ggs_collapsed_serial_sweep: the java.util.Random state
@@ -366,7 +369,7 @@ int check_status(ggs_handle *h) {
   if (!st) return GGS_OK;
   HIP_TRY(h, hipMemsetAsync(h->d_status, 0, sizeof(uint32_t), h->stream));
   if (st & ST_INVALID_TOPIC)
-    return set_err(h, GGS_ERR_INVALID_TOPIC, h->collapsed ? "SimpleLDA: New topic not sampled." /* MSLDA:216-218 */ : "LDAGroupedGibbsSampler: Topic sampled is invalid!");
+    return set_err(h, GGS_ERR_INVALID_TOPIC, h->scheme == Scheme::collapsed ? "SimpleLDA: New topic not sampled." /* MSLDA:216-218 */ : "LDAGroupedGibbsSampler: Topic sampled is invalid!");
   if (st & ST_NEGATIVE_COUNT) return set_err(h, GGS_ERR_NEGATIVE_COUNT, "Negative count for topic (Invalid count!)");
   if (st & ST_BAD_SHAPE) return set_err(h, GGS_ERR_BAD_ARG, "alpha and beta must be strictly positive (gamma shape <= 0)");
   return set_err(h, GGS_ERR_RNG_EXHAUSTED, "a gamma rejection loop exceeded GGS_MAX_BLOCKS Philox blocks");
@@ -707,7 +710,7 @@ int launch_phi_slice(ggs_handle *h, bool initial, const int32_t *cnt, int32_t cn
                      double *mag, double *tot, int32_t *n_k, double *phi_mean) {
   if (Ks <= 0) return GGS_OK;
   int rc;
-  if (h->polyaurn) {                                   // no magnitudes, no gammas, no exact-sum walk: the totals are integers
+  if (h->scheme == Scheme::polyaurn) {   // no magnitudes, no gammas, no exact-sum walk: the totals are integers
     if ((rc = phi_slice_poisson(h, initial, cnt, cnt_pitch, Ks, k0, out, out_pitch, 0, h->sum_nseg, true)) || (rc = phi_slice_poisson_totals(h, Ks, tot, n_k)))
       return rc;
     hipLaunchKernelGGL(phi_normalise_polyaurn_kernel, dim3(grid_for((int64_t)Ks * h->V, 256, 2)), dim3(256), 0, h->stream, out, tot, Ks, out_pitch, h->V,
@@ -743,13 +746,13 @@ int phi_step_a(ggs_handle *h) { return exchange_reduce_scatter(h); }
 int phi_step_a_clear(ggs_handle *h) { return h->seg_split > 0 ? GGS_OK : clear_send_buffer_if_dead(h, h->stream); }
 int phi_step_b1(ggs_handle *h, bool initial) {
   int rc;
-  if (h->polyaurn) {                                   // the Poisson draws of the first half (and the totals' zero fill)
+  if (h->scheme == Scheme::polyaurn) {   // the Poisson draws of the first half (and the totals' zero fill)
     if ((rc = phi_slice_poisson(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, 0, h->seg_split, true))) return rc;
   } else if ((rc = launch_magnitude_on(h, h->d_cnt_own, h->Ksm, h->Ks, h->d_mag_own, h->d_n_k_own))) {
     return rc;
   }
   if (h->seg_split > 0) {
-    if (!h->polyaurn && (rc = phi_slice_gamma(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, h->d_mag_own, 0, h->seg_split))) return rc;
+    if (h->scheme != Scheme::polyaurn && (rc = phi_slice_gamma(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, h->d_mag_own, 0, h->seg_split))) return rc;
     HIP_TRY(h, hipEventRecord(h->ev_half_drawn, h->stream));
     HIP_TRY(h, hipStreamWaitEvent(h->comm_stream, h->ev_half_drawn, 0));
   }
@@ -767,7 +770,7 @@ int phi_step_b2(ggs_handle *h, bool initial) {
     if ((rc = clear_send_buffer_if_dead(h, h->comm_stream))) return rc;
     HIP_TRY(h, hipEventRecord(h->ev_half_gathered, h->comm_stream));
   }
-  if (h->polyaurn) {                                   // the second half, then the integer totals into the slot behind the slice
+  if (h->scheme == Scheme::polyaurn) {   // the second half, then the integer totals into the slot behind the slice
     if ((rc = phi_slice_poisson(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, h->seg_split, h->sum_nseg, false))) return rc;
     return phi_slice_poisson_totals(h, h->Ks, h->d_phi_own + (size_t)h->V * h->Ksm, h->d_n_k_own);
   }
@@ -787,7 +790,7 @@ int phi_step_c(ggs_handle *h, bool accumulate_mean) {
   rp.phi_mean = accumulate_mean ? h->d_phi_mean : nullptr;
   rp.c0 = (int64_t)half0_elems(h); rp.c1 = (int64_t)half1_elems(h); rp.K = h->K; rp.Kp = h->Kp; rp.V = h->V; rp.Ksm = h->Ksm; rp.v_split = h->v_split;
   rp.phiT32 = h->d_phiT32; rp.Kp32 = h->plan.Kp32;
-  if (h->polyaurn) hipLaunchKernelGGL(phi_repack_polyaurn_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
+  if (h->scheme == Scheme::polyaurn) hipLaunchKernelGGL(phi_repack_polyaurn_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   else hipLaunchKernelGGL(phi_repack_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   HIP_TRY(h, hipGetLastError());
   h->have_phi = true;
@@ -800,7 +803,7 @@ int phi_step_c(ggs_handle *h, bool accumulate_mean) {
 // holds the whole Phi after the all-gather and builds all V words for itself: what a rank's shard contains changes
 // with the corpus, the tables' layout does not.
 int launch_alias_build(ggs_handle *h) {
-  if (!h->has_alias()) return GGS_OK;
+  if (!has_alias(h->scheme)) return GGS_OK;
   AliasParams ap{};
   ap.phiT = h->d_phiT; ap.alpha = h->d_alpha; ap.ps = h->d_alias_ps; ap.a = h->d_alias_a; ap.type_norm = h->d_alias_tn;
   ap.V = h->V; ap.K = h->K; ap.Kp = h->Kp; ap.wpb = h->plan.alias_wpb;
@@ -919,87 +922,87 @@ const void *pcgs_lane_kernel_for(int K, bool sliced, bool collapsed, bool polyau
   return collapsed ? reinterpret_cast<const void *>(pcgs_z_kernel<true>) : polyaurn ? reinterpret_cast<const void *>(polyaurn_z_kernel) : reinterpret_cast<const void *>(pcgs_z_kernel<false>);
 }
 
-// Every launch a handle of (K, V, flags) can make on the device: which kernel, how much LDS (the layout
-// functions beside the kernels), how many workgroups per CU.  `flags` with GGS_FLAG_PCGS set for every scheme that runs the
-// pcgs machinery.  No environment, no handle; the one HIP call is the occupancy query of the wave-per-document kernel.
-int plan_launches(const int K, const int V, const int32_t flags, const Knobs &kn, LaunchPlan &pl) {
-  const bool pcgs = (flags & GGS_FLAG_PCGS) != 0, collapsed = (flags & GGS_FLAG_COLLAPSED) != 0, polyaurn = (flags & GGS_FLAG_POLYAURN) != 0;
+// Every launch a handle of (K, V, scheme) can make on the device: which kernel, how much LDS (the layout functions beside
+// the kernels), how many workgroups per CU.  No environment, no handle; the only HIP calls are the occupancy queries of the
+// two wave-per-document kernels.
+int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn, LaunchPlan &pl) {
   const int Kp = (K + 1) & ~1, pitch16 = (Kp / 2) | 1;
-  // score-register kernels up to K = 160: measured on the benchmark corpus (sweep, ms; round 3) K=136: 2.13 sliced / 2.40
-  // streaming, 152: 2.33 / 2.56, 160: 2.40 / 2.50, 164: 3.06 / 2.83, 168: 3.06 / 2.75, 184: 3.24 / 2.94 (round 2: 184: 3.55 /
-  // 3.64, 192: 4.22 / 3.59) -- from KMAX = 168 on the cold kernel fills the whole register file (256 + 256) and the one-pass
-  // streaming kernel with the next theta drawn beside it wins (the sliced kernels can take K up to kSlicedMaxTopics = 192:
-  // GGS_DEBUG_ZKERNEL=1).  The sliced kernel tags chunk tokens (word ids) in bit 30.
-  const bool sliced_ok = K <= kSlicedMaxTopics && V < (1 << kSlotShift);
-  bool sliced = sliced_ok && K <= kSlicedDefaultTopics, stream = !sliced && K > 2 * kSliceTopics, two_pass = false;
-  if (kn.zkernel.set) {          // 0: whole-row tile kernel, 1: sliced where possible, 2: streaming kernel where it applies, 3: its two-pass form
-    const int mode = kn.zkernel.v;
-    sliced = sliced_ok && mode == 1;
-    stream = (mode == 2 || mode == 3) ? K > 2 * kSliceTopics : (stream && mode != 0);
-    two_pass = mode == 3;
-    if (sliced) stream = false;
+  if (scheme == Scheme::ggs) {                        // ---- the ggs z step
+    // score-register kernels up to K = 160: measured on the benchmark corpus (sweep, ms; round 3) K=136: 2.13 sliced / 2.40
+    // streaming, 152: 2.33 / 2.56, 160: 2.40 / 2.50, 164: 3.06 / 2.83, 168: 3.06 / 2.75, 184: 3.24 / 2.94 (round 2: 184: 3.55 /
+    // 3.64, 192: 4.22 / 3.59) -- from KMAX = 168 on the cold kernel fills the whole register file (256 + 256) and the one-pass
+    // streaming kernel with the next theta drawn beside it wins (the sliced kernels can take K up to kSlicedMaxTopics = 192:
+    // GGS_DEBUG_ZKERNEL=1).  The sliced kernel tags chunk tokens (word ids) in bit 30.
+    const bool sliced_ok = K <= kSlicedMaxTopics && V < (1 << kSlotShift);
+    bool sliced = sliced_ok && K <= kSlicedDefaultTopics, stream = !sliced && K > 2 * kSliceTopics, two_pass = false;
+    if (kn.zkernel.set) {          // 0: whole-row tile kernel, 1: sliced where possible, 2: streaming kernel where it applies, 3: its two-pass form
+      const int mode = kn.zkernel.v;
+      sliced = sliced_ok && mode == 1;
+      stream = (mode == 2 || mode == 3) ? K > 2 * kSliceTopics : (stream && mode != 0);
+      two_pass = mode == 3;
+      if (sliced) stream = false;
+    }
+    pl.kernel = sliced ? 1 : stream ? (two_pass ? 3 : 2) : 0;
+    // The z waves are persistent and stride the chunk table statically, so a grid is what is truly co-resident
+    // (lds_workgroups_per_cu); the passes are latency chains, so waves in flight matter more than lanes in use.
+    if (stream) {
+      // 64-token chunks, a 2-slot slice ring + the theta row zero-padded to whole slices (one-pass kernel: to whole
+      // checkpoint groups, plus a checkpoint per group and lane); no score registers, so 8 waves per CU fit the
+      // register file and LDS bounds the residency
+      const int ns = stream_slices(K);
+      // checkpoint group: the smallest that keeps the checkpoints in registers (K <= 256: one slice, <= 512: two, <= 1024: four); beyond, four slices and LDS
+      int group = ns <= kRegCheckpoints ? 1 : ns <= 2 * kRegCheckpoints ? 2 : 4;
+      if (kn.group.set && (kn.group.v == 1 || kn.group.v == 2 || kn.group.v == 4)) group = kn.group.v;
+      bool regck = !two_pass && z_stream1_groups(K, group) <= kRegCheckpoints;          // checkpoints in registers or in LDS
+      if (kn.regck.set) regck = regck && kn.regck.v != 0;
+      if (!regck) group = 4;                               // the LDS-checkpoint kernel is instantiated for groups of four
+      // Chunks of 64 consecutive tokens across ONE document boundary (two theta rows per wave) instead of near-equal
+      // cuts of single documents: 98 % of the lanes busy instead of 78 % at 200-token documents.  Where the second row
+      // would cost resident waves (K > 512: 8 KiB at K = 1024) the single-document chunks stay.
+      pl.two_rows = !two_pass && (kn.tworows.set ? kn.tworows.v != 0 : K <= 512);
+      pl.z.fn = stream_kernel_for(two_pass, regck, group);
+      pl.z.lds = two_pass ? z_stream_lds_bytes(K) : z_stream1_lds_bytes(K, group, pl.two_rows, regck);
+      if (pl.z.lds > kMaxLdsBytes) return GGS_ERR_UNSUPPORTED;   // K > ~16000: the theta row itself would need slicing
+    } else if (sliced) {
+      // 64-token chunks; one 4-wave workgroup per CU (a wave per SIMD: the score registers take most of the 512-entry file),
+      // per wave the two theta rows and the slice ring, per workgroup the hot-word table.  The cold chunks from phiT32 (a
+      // 32-topic slice per 128 bytes); its wave LDS is the fp64 form's: the ring, then two float32 theta rows and the
+      // replay's KMAX products where the two fp64 theta rows were
+      pl.f32 = !kn.phi64.is(1);
+      pl.Kp32 = round_up(K, kSlice32Topics);
+      pl.ring_base = sliced_ring_base(K); pl.wave_lds = sliced_wave_lds(K); pl.hot_pitch = table_row_pitch(K);
+      pl.hot_wave_lds = hot_wave_lds(K); pl.warm_wave_lds = warm_wave_lds(K);
+      if (kn.split.set) { pl.split = kn.split.v != 0; pl.split_forced = kn.split.v == 2; }
+      // split: the two workgroups must fit one CU together
+      pl.hot_cap = pl.split ? table_rows_beside_cold(K, pl.hot_wave_lds) : table_rows_fused(K);
+      if (kn.hot.set) pl.hot_cap = std::max(0, std::min(pl.hot_cap, kn.hot.v));
+      pl.cold = {pl.f32 ? sliced32_kernel_for(K) : sliced_kernel_for(K), kSlicedWaves * 64, sliced_cold_lds(K), 1};
+      pl.hot = {hot_kernel_for(K), kSlicedWaves * 64, table_lds(K, pl.hot_wave_lds, 0), 1};
+      // the warm tiers: the same LDS beside the cold kernel's workgroup, more of it for theta rows (warm_docs per wave), the rest a table
+      pl.warm = {warm_kernel_for(K), kSlicedWaves * 64, table_lds(K, pl.warm_wave_lds, 0), 1};
+      pl.warm_docs = warm_docs_for(sliced_kmax(K));
+      pl.warm_cap = table_rows_beside_cold(K, pl.warm_wave_lds);
+      if (pl.warm_cap < 16) pl.warm_cap = 0;               // the table loads and barriers of a tier want tokens to pay them
+      if (kn.warm.set) pl.warm_tiers_max = std::max(0, std::min(kWarmMaxTiers, kn.warm.v));
+      if (kn.warm_rows.set) pl.warm_cap = std::max(0, std::min(pl.warm_cap, kn.warm_rows.v));
+      if (kn.warm_fill.set) pl.warm_min_fill_pct = std::max(1, std::min(100, kn.warm_fill.v));
+      if (kn.warm_cpw.set) pl.warm_min_chunks_per_wave = std::max(0, kn.warm_cpw.v);
+    } else {
+      // a tile of T token rows + one theta row per wave: the largest tile that still lets 6 single-wave workgroups share a
+      // CU, but at least 8 rows
+      int T = z_tile_rows_in(kMaxLdsBytes / 6 / kLdsGranule * kLdsGranule, Kp, pitch16);
+      if (kn.tile.set) T = kn.tile.v;
+      pl.tile_tokens = std::max(8, std::min(64, T));
+      pl.z.fn = tile_kernel_for(K);
+      pl.z.lds = z_tile_lds_bytes(Kp, pitch16, pl.tile_tokens);
+      if (pl.z.lds > kMaxLdsBytes) return GGS_ERR_UNSUPPORTED;   // K > ~2400 needs a K-sliced kernel
+    }
+    if (!sliced) {
+      pl.z.per_cu = lds_workgroups_per_cu(pl.z.lds, 8);
+      if (kn.wpc.set) pl.z.per_cu = std::max(1, kn.wpc.v);
+    }
   }
-  pl.kernel = sliced ? 1 : stream ? (two_pass ? 3 : 2) : 0;
-  // The z waves are persistent and stride the chunk table statically, so a grid is what is truly co-resident
-  // (lds_workgroups_per_cu); the passes are latency chains, so waves in flight matter more than lanes in use.
-  if (stream) {
-    // 64-token chunks, a 2-slot slice ring + the theta row zero-padded to whole slices (one-pass kernel: to whole
-    // checkpoint groups, plus a checkpoint per group and lane); no score registers, so 8 waves per CU fit the
-    // register file and LDS bounds the residency
-    const int ns = stream_slices(K);
-    // checkpoint group: the smallest that keeps the checkpoints in registers (K <= 256: one slice, <= 512: two, <= 1024: four); beyond, four slices and LDS
-    int group = ns <= kRegCheckpoints ? 1 : ns <= 2 * kRegCheckpoints ? 2 : 4;
-    if (kn.group.set && (kn.group.v == 1 || kn.group.v == 2 || kn.group.v == 4)) group = kn.group.v;
-    bool regck = !two_pass && z_stream1_groups(K, group) <= kRegCheckpoints;          // checkpoints in registers or in LDS
-    if (kn.regck.set) regck = regck && kn.regck.v != 0;
-    if (!regck) group = 4;                               // the LDS-checkpoint kernel is instantiated for groups of four
-    // Chunks of 64 consecutive tokens across ONE document boundary (two theta rows per wave) instead of near-equal
-    // cuts of single documents: 98 % of the lanes busy instead of 78 % at 200-token documents.  Where the second row
-    // would cost resident waves (K > 512: 8 KiB at K = 1024) the single-document chunks stay.
-    pl.two_rows = !two_pass && (kn.tworows.set ? kn.tworows.v != 0 : K <= 512);
-    pl.z.fn = stream_kernel_for(two_pass, regck, group);
-    pl.z.lds = two_pass ? z_stream_lds_bytes(K) : z_stream1_lds_bytes(K, group, pl.two_rows, regck);
-    if (pl.z.lds > kMaxLdsBytes) return GGS_ERR_UNSUPPORTED;   // K > ~16000: the theta row itself would need slicing
-  } else if (sliced) {
-    // 64-token chunks; one 4-wave workgroup per CU (a wave per SIMD: the score registers take most of the 512-entry file),
-    // per wave the two theta rows and the slice ring, per workgroup the hot-word table.  The cold chunks from phiT32 (a
-    // 32-topic slice per 128 bytes); its wave LDS is the fp64 form's: the ring, then two float32 theta rows and the
-    // replay's KMAX products where the two fp64 theta rows were
-    pl.f32 = !kn.phi64.is(1);
-    pl.Kp32 = round_up(K, kSlice32Topics);
-    pl.ring_base = sliced_ring_base(K); pl.wave_lds = sliced_wave_lds(K); pl.hot_pitch = table_row_pitch(K);
-    pl.hot_wave_lds = hot_wave_lds(K); pl.warm_wave_lds = warm_wave_lds(K);
-    if (kn.split.set) { pl.split = kn.split.v != 0; pl.split_forced = kn.split.v == 2; }
-    // split: the two workgroups must fit one CU together
-    pl.hot_cap = pl.split ? table_rows_beside_cold(K, pl.hot_wave_lds) : table_rows_fused(K);
-    if (kn.hot.set) pl.hot_cap = std::max(0, std::min(pl.hot_cap, kn.hot.v));
-    pl.cold = {pl.f32 ? sliced32_kernel_for(K) : sliced_kernel_for(K), kSlicedWaves * 64, sliced_cold_lds(K), 1};
-    pl.hot = {hot_kernel_for(K), kSlicedWaves * 64, table_lds(K, pl.hot_wave_lds, 0), 1};
-    // the warm tiers: the same LDS beside the cold kernel's workgroup, more of it for theta rows (warm_docs per wave), the rest a table
-    pl.warm = {warm_kernel_for(K), kSlicedWaves * 64, table_lds(K, pl.warm_wave_lds, 0), 1};
-    pl.warm_docs = warm_docs_for(sliced_kmax(K));
-    pl.warm_cap = table_rows_beside_cold(K, pl.warm_wave_lds);
-    if (pl.warm_cap < 16) pl.warm_cap = 0;               // the table loads and barriers of a tier want tokens to pay them
-    if (kn.warm.set) pl.warm_tiers_max = std::max(0, std::min(kWarmMaxTiers, kn.warm.v));
-    if (kn.warm_rows.set) pl.warm_cap = std::max(0, std::min(pl.warm_cap, kn.warm_rows.v));
-    if (kn.warm_fill.set) pl.warm_min_fill_pct = std::max(1, std::min(100, kn.warm_fill.v));
-    if (kn.warm_cpw.set) pl.warm_min_chunks_per_wave = std::max(0, kn.warm_cpw.v);
-  } else {
-    // a tile of T token rows + one theta row per wave: the largest tile that still lets 6 single-wave workgroups share a
-    // CU, but at least 8 rows
-    int T = z_tile_rows_in(kMaxLdsBytes / 6 / kLdsGranule * kLdsGranule, Kp, pitch16);
-    if (kn.tile.set) T = kn.tile.v;
-    pl.tile_tokens = std::max(8, std::min(64, T));
-    pl.z.fn = tile_kernel_for(K);
-    pl.z.lds = z_tile_lds_bytes(Kp, pitch16, pl.tile_tokens);
-    if (pl.z.lds > kMaxLdsBytes) return GGS_ERR_UNSUPPORTED;   // K > ~2400 needs a K-sliced kernel
-  }
-  if (!sliced) {
-    pl.z.per_cu = lds_workgroups_per_cu(pl.z.lds, 8);
-    if (kn.wpc.set) pl.z.per_cu = std::max(1, kn.wpc.v);
-  }
-
-  // ---- the theta draw
+  // ---- the theta draw: of every sweep for scheme ggs, of the log posterior's diagnostic theta for the pcgs family
   int B = 64;
   while (B > 1 && theta_lds_bytes(K, B) > 32 * 1024) B >>= 1;
   if (theta_lds_bytes(K, B) > kMaxLdsBytes) return GGS_ERR_UNSUPPORTED;
@@ -1022,24 +1025,27 @@ int plan_launches(const int K, const int V, const int32_t flags, const Knobs &kn
   // K > 192 (one-pass streaming z kernel): theta workgroups small enough to sit BESIDE the z waves -- on the LDS the z
   // waves give up -- so that the next theta of a part of the documents is drawn while the following parts are sampled
   // (z_phase).  The padded request caps them at kBeside per CU while z runs.
-  pl.parts_forced = kn.zparts.set;
-  int parts = kn.zparts.set ? std::max(1, std::min(8, kn.zparts.v)) : (stream && !two_pass && !pcgs) ? 8 : 1;   // measured at K = 1024: 1 part 18.4 ms per sweep, 2: 18.1, 4: 16.5, 8: 15.9
   pl.cfg_parts = pl.cfg_plain;
-  if (parts > 1 && stream && !two_pass) {
-    const int kBeside = kn.beside.set ? std::max(1, kn.beside.v) : 4;   // measured at K = 1024 (sweep): 2 -> 16.9 ms, 3 -> 16.1, 4 -> 15.0, 5 -> 15.0
-    int Bt = 64;
-    while (Bt > 1 && theta_lds_bytes(K, Bt) > 10 * 1024) Bt >>= 1;
-    const int t_lds = theta_lds_bytes(K, Bt), z_alloc = lds_alloc_of(pl.z.lds);
-    const int zw = std::min(pl.z.per_cu, (kMaxLdsBytes - kLdsGranule - kBeside * lds_alloc_of(t_lds)) / z_alloc);
-    if (t_lds <= 12 * 1024 && zw >= 2)
-      pl.cfg_parts = {parts, zw, Bt, std::max(t_lds, theta_quarter), std::max(t_lds, (kMaxLdsBytes - kLdsGranule - zw * z_alloc) / kBeside / kLdsGranule * kLdsGranule)};
-    else
-      parts = 1;
+  if (scheme == Scheme::ggs) {                        // the parts of the one-pass streaming kernel's z step (pl.kernel == 2)
+    pl.parts_forced = kn.zparts.set;
+    int parts = kn.zparts.set ? std::max(1, std::min(8, kn.zparts.v)) : pl.kernel == 2 ? 8 : 1;   // measured at K = 1024: 1 part 18.4 ms per sweep, 2: 18.1, 4: 16.5, 8: 15.9
+    if (parts > 1 && pl.kernel == 2) {
+      const int kBeside = kn.beside.set ? std::max(1, kn.beside.v) : 4;   // measured at K = 1024 (sweep): 2 -> 16.9 ms, 3 -> 16.1, 4 -> 15.0, 5 -> 15.0
+      int Bt = 64;
+      while (Bt > 1 && theta_lds_bytes(K, Bt) > 10 * 1024) Bt >>= 1;
+      const int t_lds = theta_lds_bytes(K, Bt), z_alloc = lds_alloc_of(pl.z.lds);
+      const int zw = std::min(pl.z.per_cu, (kMaxLdsBytes - kLdsGranule - kBeside * lds_alloc_of(t_lds)) / z_alloc);
+      if (t_lds <= 12 * 1024 && zw >= 2)
+        pl.cfg_parts = {parts, zw, Bt, std::max(t_lds, theta_quarter), std::max(t_lds, (kMaxLdsBytes - kLdsGranule - zw * z_alloc) / kBeside / kLdsGranule * kLdsGranule)};
+      else
+        parts = 1;
+    }
+    pl.cfg_parts.parts = parts;
+    return GGS_OK;
   }
-  pl.cfg_parts.parts = parts;
-  if (!pcgs) return GGS_OK;
 
-  // ---- scheme pcgs / collapsed / polyaurn / spalias
+  // ---- the pcgs family: a lane or a wave per document; the alias schemes' table build and their own z kernel
+  const bool collapsed = scheme == Scheme::collapsed, polyaurn = scheme == Scheme::polyaurn;
   // the wave-per-document kernel: any K up to 4096, any document length.  Waves per CU (the grid is persistent: exactly what
   // is resident): what the kernel's registers allow (asked of the runtime) and what LDS allows (the runtime's answer
   // ignores the allocation granule)
@@ -1060,16 +1066,13 @@ int plan_launches(const int K, const int V, const int32_t flags, const Knobs &kn
   pl.lane.per_cu = lds_workgroups_per_cu(pl.lane.lds, 8);
   if (!pl.wave_forced) pl.lane.fn = pcgs_lane_kernel_for(K, lane_sliced, collapsed, polyaurn);
   if (collapsed) pl.serial.fn = reinterpret_cast<const void *>(collapsed_serial_kernel);
-  if (flags & GGS_FLAG_SPALIAS) {
+  if (has_alias(scheme)) {
     pl.alias_wpb = alias_words_per_block(K);
     pl.alias = {reinterpret_cast<const void *>(alias_build_kernel), 64, (int)alias_lds_bytes(K, pl.alias_wpb), 0};
     pl.alias.per_cu = lds_workgroups_per_cu(pl.alias.lds, 16);
-    pl.spalias.fn = reinterpret_cast<const void *>(spalias_wave_kernel);
   }
-  if (flags & GGS_FLAG_LIGHTPCLDA) {
-    pl.alias_wpb = alias_words_per_block(K);
-    pl.alias = {reinterpret_cast<const void *>(alias_build_kernel), 64, (int)alias_lds_bytes(K, pl.alias_wpb), 0};
-    pl.alias.per_cu = lds_workgroups_per_cu(pl.alias.lds, 16);
+  if (scheme == Scheme::spalias) pl.spalias.fn = reinterpret_cast<const void *>(spalias_wave_kernel);
+  if (scheme == Scheme::lightpclda) {
     // the resident single-wave workgroups: what the kernel's registers allow (asked of the runtime) and what LDS allows, at
     // most the CU's 32 -- a lone wave issues at a fraction of a SIMD's rate, and the step is a chain of dependent operations
     pl.lightpc = {reinterpret_cast<const void *>(lightpc_wave_kernel), 64, (int)lightpc_lds_bytes(K), 0};
@@ -1080,6 +1083,9 @@ int plan_launches(const int K, const int V, const int32_t flags, const Knobs &kn
   return GGS_OK;
 }
 
+const KernelLaunch &pcgs_entry(const LaunchPlan &pl, Scheme s, bool wave) {
+  return s == Scheme::lightpclda ? pl.lightpc : s == Scheme::spalias ? pl.spalias : wave ? pl.wave : pl.lane;
+}
 int launch_pcgs_z(ggs_handle *h) {
   if (h->N == 0) return GGS_OK;
   PcgsParams pp{};
@@ -1088,23 +1094,17 @@ int launch_pcgs_z(ggs_handle *h) {
   pp.num_docs = h->pcgs_order_len; pp.tok_base = h->tok_base; pp.seed = h->seed; pp.iteration = (uint32_t)h->iteration;   // the length of the (padded) order list
   pp.K = h->K; pp.Kp = h->Kp;
   int rc;
-  if (h->spalias) {                                    // one wave per document over the non-zero topics (ggs_z_spalias.hpp)
-    if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
-    SpaliasParams sp{};
+  if (h->alias_stale && (rc = launch_alias_build(h))) return rc;   // spalias, lightpclda
+  SpaliasParams sp{};
+  LightpcParams lp{};
+  void *args[] = {&pp, &h->margin_scale};              // the wave-per-document kernel takes both, the lane-per-document kernels the first
+  if (h->scheme == Scheme::spalias) {                  // one wave per document over the non-zero topics (ggs_z_spalias.hpp)
     sp.b = pp; sp.ps = h->d_alias_ps; sp.a = h->d_alias_a; sp.type_norm = h->d_alias_tn; sp.cap = h->sp_cap; sp.margin_scale = h->margin_scale;
-    void *args[] = {&sp};
-    HIP_TRY(h, launch(h, h->sp_z, h->pcgs_order_len, args, h->stream));
-    return GGS_OK;
-  }
-  if (h->lightpc) {                                    // one wave per document, two proposals per token (ggs_z_lightpc.hpp)
-    if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
-    LightpcParams lp{};
+    args[0] = &sp;
+  } else if (h->scheme == Scheme::lightpclda) {        // one wave per document, two proposals per token (ggs_z_lightpc.hpp)
     lp.b = pp; lp.ps = h->d_alias_ps; lp.a = h->d_alias_a; lp.mh = h->d_mh; lp.alpha_sum = h->alpha_sum;
-    void *args[] = {&lp};
-    HIP_TRY(h, launch(h, h->plan.lightpc, h->pcgs_order_len, args, h->stream));
-    return GGS_OK;
-  }
-  if (h->collapsed) {
+    args[0] = &lp;
+  } else if (h->scheme == Scheme::collapsed) {
     // the sweep-start ratios (beta + n_wk)/(betaSum + n_k) of the corpus-wide counts, then the pcgs loop over them
     if ((rc = launch_magnitude(h))) return rc;
     pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;   // betaSum = beta * numTypes, MSLDA:136
@@ -1112,11 +1112,7 @@ int launch_pcgs_z(ggs_handle *h) {
                        h->K, h->Kp, h->V);
     HIP_TRY(h, hipGetLastError());
   }
-  // one wave per document (wide topic rows, or a document the lane-per-document kernels' int16 counts cannot hold), or
-  // one lane: 64 documents of the order list per wave
-  void *wave_args[] = {&pp, &h->margin_scale}, *lane_args[] = {&pp};
-  if (h->pcgs_wave) HIP_TRY(h, launch(h, h->plan.wave, h->pcgs_order_len, wave_args, h->stream));
-  else HIP_TRY(h, launch(h, h->plan.lane, (h->pcgs_order_len + 63) / 64, lane_args, h->stream));
+  HIP_TRY(h, launch(h, h->pcgs_z, h->pcgs_items, args, h->stream));
   return GGS_OK;
 }
 
@@ -1127,7 +1123,7 @@ int launch_pcgs_z(ggs_handle *h) {
 // on the rank) 0.139 / 0.132 ms against 0.040 of count kernel; N = 4 (100) 0.290 / 0.26 against 0.05; N = 2 (200) 0.627 / 0.52
 // against 0.07 -- they pay up to about 64 tokens per word (GGS_DEBUG_ZCOUNTS=2 forces them).
 bool z_counts_itself(const ggs_handle *h) {
-  return h->xg && h->z_counts && h->plan.sliced() && !(h->flags & GGS_FLAG_PCGS) && (h->z_counts_forced || h->N <= (int64_t)64 * h->V) && !use_sparse(h);
+  return h->xg && h->z_counts && h->plan.sliced() && (h->z_counts_forced || h->N <= (int64_t)64 * h->V) && !use_sparse(h);
 }
 // `defer_join` (with `count`, split form): the hot words' count launch follows the hot kernel on ITS stream and the
 // handle's stream is not made to wait for that stream here -- the caller does (join_hot_stream), behind the z step's end
@@ -1135,16 +1131,13 @@ bool z_counts_itself(const ggs_handle *h) {
 int launch_count_hot(ggs_handle *h);
 int launch_z(ggs_handle *h, bool force_fused = false, int64_t c0 = 0, int64_t c1 = -1, bool count = false, bool defer_join = false) {
   h->hot_join_pending = false;
-  if (h->C == 0) return GGS_OK;
-  if (c1 < 0) c1 = h->C;
-  if (c1 <= c0) return GGS_OK;
+  if (h->N == 0) return GGS_OK;
   const LaunchPlan &pl = h->plan;
   ZParams zp{};
   zp.tok = h->d_tok; zp.inv_perm = h->d_inv_perm; zp.z = h->d_z; zp.zw = h->d_zw; zp.chunk_start = h->d_chunk_start; zp.chunk_doc = h->d_chunk_doc; zp.chunk_len = h->d_chunk_len;
   zp.theta = h->d_theta; zp.phiT = h->d_phiT; zp.status = h->d_status;
   zp.tok_base = h->tok_base; zp.seed = h->seed; zp.iteration = (uint32_t)h->iteration;
   zp.K = h->K; zp.Kp = h->Kp; zp.pitch16 = h->pitch16; zp.tile_tokens = pl.tile_tokens;
-  zp.num_chunks = h->C;
   zp.margin_scale = h->margin_scale;
   zp.chunk_doc1 = h->d_chunk_doc1; zp.two_rows = (pl.two_rows && h->d_chunk_doc1) ? 1 : 0;
   zp.ct_tok = h->d_ct_tok; zp.ct_idx = h->d_ct_idx; zp.ct_ip = h->d_ct_ip; zp.c_docs = h->d_c_docs; zp.num_cold = h->Cc;
@@ -1159,6 +1152,8 @@ int launch_z(ggs_handle *h, bool force_fused = false, int64_t c0 = 0, int64_t c1
   void *args[] = {&zp};
   if (!pl.sliced()) {
     // a range of the chunk table (the one-document chunks are in document order); persistent single-wave workgroups stride it
+    if (c1 < 0) c1 = h->C;
+    if (c1 <= c0) return GGS_OK;
     zp.chunk_start += c0; zp.chunk_doc += c0; zp.chunk_len += c0; zp.num_chunks = c1 - c0;
     if (zp.chunk_doc1) zp.chunk_doc1 += c0;
     KernelLaunch z = pl.z;
@@ -1309,9 +1304,9 @@ int z_phase(ggs_handle *h) {
   if (h->ev_pending >= kEvRing - 2 && (rc = settle_sweeps(h))) return rc;   // keep this slot and the next one free
   h->ev_head = (h->ev_head + 1) % kEvRing;
   Events &E = h->evs[h->ev_head];
-  E.light = h->xg && h->have_frac && h->detail_every > 1 && !h->force_detail && (h->sweeps_enqueued % h->detail_every) != 0 && !h->collapsed;
+  E.light = h->xg && h->have_frac && h->detail_every > 1 && !h->force_detail && (h->sweeps_enqueued % h->detail_every) != 0 && h->scheme != Scheme::collapsed;
   h->sweeps_enqueued += 1;
-  if (h->flags & GGS_FLAG_PCGS) {                       // no theta: it is integrated out (UPLDA:1509-1513)
+  if (pcgs_family(h->scheme)) {                         // no theta: it is integrated out (UPLDA:1509-1513)
     E.used_ahead = false;
     HIP_TRY(h, hipEventRecord(E.e[0], h->stream));
     HIP_TRY(h, hipEventRecord(E.e[1], h->stream));
@@ -1376,7 +1371,7 @@ int z_phase(ggs_handle *h) {
     HIP_TRY(h, hipEventRecord(E.e[2], h->stream));
     h->theta_ahead_iter = (int64_t)h->iteration + 1;
   } else {
-    const bool counting = z_counts_itself(h) && h->C > 0;
+    const bool counting = z_counts_itself(h) && h->Cs > 0;
     if (counting && !h->cnt_send_zeroed && (rc = clear_send_buffer(h, h->stream))) return rc;   // nobody cleared it behind the last reduce-scatter (or none came): counts no z step asked for are overwritten, as a count rebuild overwrites them
     h->hot_counted = false;
     if ((rc = launch_z(h, false, 0, -1, counting, /*defer_join=*/counting))) return rc;
@@ -1436,7 +1431,7 @@ int finish_sweep_enqueue_on(ggs_handle *h, bool with_phi) {
   E.exchanged = false;
   if (with_phi) {
     acc = (h->flags & GGS_FLAG_SAVE_PHI_MEAN) && sample_phi_this_iteration(h);
-    if (h->collapsed) {                    // no Phi in the count form: the merge (with an exchange: the gather of the count slices) and tokensPerTopic
+    if (h->scheme == Scheme::collapsed) {   // no Phi in the count form: the merge (with an exchange: the gather of the count slices) and tokensPerTopic
       acc = false;
       if ((rc = launch_magnitude(h))) return rc;
     } else {
@@ -1583,6 +1578,22 @@ int group_collective(ggs_handle **hs, int32_t n, Step step) {
   return r;
 }
 
+// The scheme a configuration asks for (`poisson_L`: polyaurn's alias_poisson_threshold), or what is wrong with the request:
+// answered before any device is asked for.
+int scheme_of(const ggs_config *cfg, Scheme &scheme, int32_t &poisson_L) {
+  const int32_t f = cfg->flags;
+  // spalias runs over the pcgs model only (polyaurn over the sparse z step is not provided); lightpclda likewise, and it is
+  // not spalias: one z step per handle
+  if ((f & GGS_FLAG_SPALIAS) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN))) return GGS_ERR_BAD_ARG;
+  if ((f & GGS_FLAG_LIGHTPCLDA) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS))) return GGS_ERR_BAD_ARG;
+  scheme = (f & GGS_FLAG_LIGHTPCLDA) ? Scheme::lightpclda : (f & GGS_FLAG_SPALIAS) ? Scheme::spalias : (f & GGS_FLAG_POLYAURN) ? Scheme::polyaurn
+         : (f & GGS_FLAG_COLLAPSED) ? Scheme::collapsed : (f & GGS_FLAG_PCGS) ? Scheme::pcgs : Scheme::ggs;
+  poisson_L = cfg->alias_poisson_threshold == 0 ? 100 : cfg->alias_poisson_threshold;   // LDAConfiguration.java:44
+  if (scheme == Scheme::polyaurn && ((f & GGS_FLAG_COLLAPSED) || poisson_L < 1 || poisson_L > kPoissonMaxThreshold)) return GGS_ERR_BAD_ARG;
+  if (has_alias(scheme) && cfg->num_topics > kPcgsWaveMaxTopics) return GGS_ERR_UNSUPPORTED;
+  return GGS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1596,11 +1607,8 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
   *out = nullptr;
   if (cfg->struct_size != (int32_t)sizeof(ggs_config)) return GGS_ERR_BAD_ARG;
   if (cfg->num_topics <= 0 || cfg->num_types <= 0 || !(cfg->beta > 0)) return GGS_ERR_BAD_ARG;
-  // scheme=spalias runs over the pcgs model only (polyaurn over the sparse z step is not provided): an argument error,
-  // answered before any device is asked for
-  if ((cfg->flags & GGS_FLAG_SPALIAS) && (cfg->flags & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN))) return GGS_ERR_BAD_ARG;
-  // scheme=lightpclda likewise, and it is not spalias: one z step per handle
-  if ((cfg->flags & GGS_FLAG_LIGHTPCLDA) && (cfg->flags & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS))) return GGS_ERR_BAD_ARG;
+  Scheme scheme = Scheme::ggs; int32_t poisson_L = 0;
+  if (const int rc = scheme_of(cfg, scheme, poisson_L)) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device_id < 0 || cfg->device_id >= ndev) return GGS_ERR_HIP;
   ggs_handle *h = new (std::nothrow) ggs_handle();
@@ -1612,20 +1620,7 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
   h->Kp = (h->K + 1) & ~1;
   h->pitch16 = (h->Kp / 2) | 1;             // odd number of 16-byte units per LDS row
   h->beta = cfg->beta; h->seed = cfg->seed; h->flags = cfg->flags;
-  if (h->flags & GGS_FLAG_COLLAPSED) { h->collapsed = true; h->flags |= GGS_FLAG_PCGS; }   // the lane-per-document z loop, a different matrix
-  if (h->flags & GGS_FLAG_POLYAURN) {                 // the pcgs z loop (two rules of its own) over a Poisson-drawn Phi
-    const int32_t L = cfg->alias_poisson_threshold == 0 ? 100 : cfg->alias_poisson_threshold;   // LDAConfiguration.java:44
-    if (h->collapsed || L < 1 || L > kPoissonMaxThreshold) { delete h; return GGS_ERR_BAD_ARG; }
-    h->polyaurn = true; h->flags |= GGS_FLAG_PCGS; h->pa_L = L;
-  }
-  if (h->flags & GGS_FLAG_SPALIAS) {                  // the pcgs model; the z step draws from the same conditional another way
-    if (h->K > kPcgsWaveMaxTopics) { delete h; return GGS_ERR_UNSUPPORTED; }
-    h->spalias = true; h->flags |= GGS_FLAG_PCGS;
-  }
-  if (h->flags & GGS_FLAG_LIGHTPCLDA) {               // the pcgs model and spalias's tables; a Metropolis-Hastings z step
-    if (h->K > kPcgsWaveMaxTopics) { delete h; return GGS_ERR_UNSUPPORTED; }
-    h->lightpc = true; h->flags |= GGS_FLAG_PCGS;
-  }
+  h->scheme = scheme; h->pa_L = poisson_L;
   h->phi_burn_in = cfg->phi_burn_in; h->phi_thin = cfg->phi_mean_thin > 0 ? cfg->phi_mean_thin : 1;
   h->alpha.assign(h->K, cfg->alpha_scalar);
   if (cfg->alpha) std::copy(cfg->alpha, cfg->alpha + h->K, h->alpha.begin());
@@ -1653,9 +1648,10 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) return bail(GGS_ERR_HIP);
     h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
-  if ((rc = plan_launches(h->K, h->V, h->flags, kn, h->plan))) return bail(rc);
+  if ((rc = plan_launches(h->K, h->V, h->scheme, kn, h->plan))) return bail(rc);
   h->cfg = &h->plan.cfg_parts;
   h->z_split = h->plan.split;
+  if (pcgs_family(h->scheme)) h->pcgs_z = pcgs_entry(h->plan, h->scheme, h->plan.wave_forced);
   // The attribute is process-global per kernel, not per handle: always the hardware maximum, so that a later handle
   // with a smaller K never lowers the cap under a live one.
   for (const KernelLaunch *l : h->plan.all())
@@ -1688,15 +1684,15 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
       hipMemset(h->d_n_k, 0, sizeof(int32_t) * h->K) != hipSuccess || hipMemset(h->d_status, 0, 16) != hipSuccess ||
       (h->d_phi_mean && hipMemset(h->d_phi_mean, 0, sizeof(double) * kv) != hipSuccess))
     return bail(GGS_ERR_HIP);
-  if (h->has_alias() && ((rc = dev_alloc(h, &h->d_alias_ps, kv)) || (rc = dev_alloc(h, &h->d_alias_a, kv)) || (rc = dev_alloc(h, &h->d_alias_tn, (size_t)h->V)))) return bail(rc);
-  if (h->lightpc && ((rc = dev_alloc(h, &h->d_mh, 3)) || hipMemset(h->d_mh, 0, 3 * sizeof(unsigned long long)) != hipSuccess)) return bail(rc ? rc : GGS_ERR_HIP);
-  if (h->polyaurn) {
+  if (has_alias(h->scheme) && ((rc = dev_alloc(h, &h->d_alias_ps, kv)) || (rc = dev_alloc(h, &h->d_alias_a, kv)) || (rc = dev_alloc(h, &h->d_alias_tn, (size_t)h->V)))) return bail(rc);
+  if (h->scheme == Scheme::lightpclda && ((rc = dev_alloc(h, &h->d_mh, 3)) || hipMemset(h->d_mh, 0, 3 * sizeof(unsigned long long)) != hipSuccess)) return bail(rc ? rc : GGS_ERR_HIP);
+  if (h->scheme == Scheme::polyaurn) {
     std::vector<double> T;
     build_poisson_table(h->beta, h->pa_L, T);
     h->pa_t00 = T[0];
     if ((rc = upload(h, &h->d_pa_table, T)) || (rc = dev_alloc(h, &h->d_pa_acc, (size_t)h->K * kPoissonAccStride))) return bail(rc);
   }
-  if (h->collapsed && (rc = dev_alloc(h, &h->d_lcg, 2))) return bail(rc);
+  if (h->scheme == Scheme::collapsed && (rc = dev_alloc(h, &h->d_lcg, 2))) return bail(rc);
   // 5. events and streams
   for (auto &e : h->ev_part)
     if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return bail(GGS_ERR_HIP);
@@ -1796,26 +1792,28 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   if (!pl.parts_forced && parts > 1) parts = D <= (int64_t)h->V ? 1 : D < 2 * (int64_t)h->V ? std::min(parts, 4) : parts;
   h->cfg = parts > 1 ? &pl.cfg_parts : &pl.cfg_plain;
 
-  // 3. the lists, on the host (ggs_corpus_lists.hpp)
+  // 3. the lists, on the host (ggs_corpus_lists.hpp): the count rebuild's, and those of the z step the plan launches
+  const bool pcgs = pcgs_family(h->scheme);
   CorpusShape shape;
-  shape.V = h->V; shape.pcgs = (h->flags & GGS_FLAG_PCGS) != 0; shape.sliced = pl.sliced(); shape.two_rows = pl.two_rows;
-  shape.tile_tokens = pl.tile_tokens; shape.z_parts = parts;
+  shape.V = h->V; shape.tile_tokens = pl.tile_tokens; shape.z_parts = parts;
+  shape.pcgs = pcgs; shape.sliced = pl.sliced(); shape.two_rows = pl.two_rows;
   shape.hot_cap = pl.hot_cap; shape.warm_cap = pl.warm_cap; shape.warm_docs = pl.warm_docs;
   shape.warm_tiers_max = pl.warm_tiers_max; shape.warm_min_fill_pct = pl.warm_min_fill_pct; shape.warm_min_chunks_per_wave = pl.warm_min_chunks_per_wave;
   shape.sliced_waves = (int64_t)h->num_cus * kSlicedWaves; shape.pcgs_waves = (int64_t)h->num_cus * pl.lane.per_cu;
   const CorpusLists L = build_corpus_lists(shape, D, doc_ptr, tokens);
-  if (shape.pcgs) {
+  if (pcgs) {
     // the lane-per-document kernels keep the counts as int16: a longer document sends the corpus to the wave-per-document kernel
     h->pcgs_wave = pl.wave_forced || L.longest > kPcgsMaxDocLen;
     if (h->pcgs_wave && !pl.wave.fn) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=pcgs: a document of 32768 tokens or more with more than 4096 topics");
-    if (h->spalias) {
+    h->pcgs_z = pcgs_entry(pl, h->scheme, h->pcgs_wave);
+    h->pcgs_items = (has_alias(h->scheme) || h->pcgs_wave) ? (int64_t)L.order.size() : ((int64_t)L.order.size() + 63) / 64;   // a wave or a lane per entry
+    if (h->scheme == Scheme::spalias) {
       // the list of a document's non-zero topics holds at most min(K, its length) entries; the resident waves are what LDS allows,
       // at most the CU's 32
       h->sp_cap = (int32_t)std::max<int64_t>(1, std::min<int64_t>(h->K, L.longest));
-      h->sp_z = pl.spalias;
-      h->sp_z.lds = (int)spalias_lds_bytes(h->K, h->sp_cap);
-      h->sp_z.per_cu = lds_workgroups_per_cu(h->sp_z.lds, 32);
-      if (const char *e = debug_env("GGS_DEBUG_SPALIAS_WPC")) h->sp_z.per_cu = std::max(1, std::min(h->sp_z.per_cu, std::atoi(e)));
+      h->pcgs_z.lds = (int)spalias_lds_bytes(h->K, h->sp_cap);
+      h->pcgs_z.per_cu = lds_workgroups_per_cu(h->pcgs_z.lds, 32);
+      if (const char *e = debug_env("GGS_DEBUG_SPALIAS_WPC")) h->pcgs_z.per_cu = std::max(1, std::min(h->pcgs_z.per_cu, std::atoi(e)));
     }
   }
   h->D = D; h->N = N; h->C = (int64_t)L.cstart.size(); h->S = (int64_t)L.seg_word.size(); h->doc_base = doc_base; h->tok_base = tok_base;
@@ -1828,27 +1826,28 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   // 4. upload (on the null stream), the state of the corpus zeroed
   const size_t theta_elems = (size_t)D * h->K + 2;
   if ((rc = upload(h, &h->d_doc_ptr, doc_ptr, (size_t)D + 1)) || (rc = upload(h, &h->d_tok, tokens, (size_t)N)) ||
-      (rc = upload(h, &h->d_chunk_start, L.cstart)) || (rc = upload(h, &h->d_chunk_doc, L.cdoc)) || (rc = upload(h, &h->d_chunk_len, L.clen)) ||
-      (pl.two_rows && h->C && (rc = upload(h, &h->d_chunk_doc1, L.cdoc1))) ||
       (rc = upload(h, &h->d_perm, L.perm)) || (rc = upload(h, &h->d_inv_perm, L.inv)) ||
-      (rc = upload(h, &h->d_seg_word, L.seg_word)) || (rc = upload(h, &h->d_seg_begin, L.seg_begin)) ||
-      (rc = upload(h, &h->d_hseg_word, L.hseg_word)) || (rc = upload(h, &h->d_hseg_begin, L.hseg_begin)) || (rc = upload(h, &h->d_hseg_end, L.hseg_end)) ||
-      (shape.pcgs && (rc = upload(h, &h->d_order, L.order))))
+      (rc = upload(h, &h->d_seg_word, L.seg_word)) || (rc = upload(h, &h->d_seg_begin, L.seg_begin)))
     return rc;
+  if (pcgs && (rc = upload(h, &h->d_order, L.order))) return rc;
   if (pl.sliced() && ((rc = upload(h, &h->d_ct_tok, L.ct_tok)) || (rc = upload(h, &h->d_ct_idx, L.ct_idx)) || (rc = upload(h, &h->d_ct_ip, L.ct_ip)) ||
                       (rc = upload(h, &h->d_c_docs, L.c_docs)) || (rc = upload(h, &h->d_hot_words, L.hot_words)) ||
-                      (rc = upload(h, &h->d_ht_pack, L.ht_pack)) || (rc = upload(h, &h->d_h_docs, L.h_docs))))
+                      (rc = upload(h, &h->d_ht_pack, L.ht_pack)) || (rc = upload(h, &h->d_h_docs, L.h_docs)) ||
+                      (rc = upload(h, &h->d_hseg_word, L.hseg_word)) || (rc = upload(h, &h->d_hseg_begin, L.hseg_begin)) || (rc = upload(h, &h->d_hseg_end, L.hseg_end))))
+    return rc;
+  if (h->C && ((rc = upload(h, &h->d_chunk_start, L.cstart)) || (rc = upload(h, &h->d_chunk_doc, L.cdoc)) || (rc = upload(h, &h->d_chunk_len, L.clen)) ||
+               (pl.two_rows && (rc = upload(h, &h->d_chunk_doc1, L.cdoc1)))))
     return rc;
   if (L.warm_tiers > 0 && ((rc = upload(h, &h->d_wt_pack, L.wt_pack)) || (rc = upload(h, &h->d_w_docs, L.w_docs)) ||
                            (rc = upload(h, &h->d_warm_words, L.warm_words)) || (rc = upload(h, &h->d_warm_meta, L.warm_meta))))
     return rc;
   if ((rc = dev_alloc(h, &h->d_z, (size_t)N)) || (rc = dev_alloc(h, &h->d_zw, (size_t)N)) ||
-      (rc = dev_alloc(h, &h->d_theta, theta_elems)) || (rc = dev_alloc(h, &h->d_theta_next, theta_elems)))
+      (rc = dev_alloc(h, &h->d_theta, theta_elems)) || (!pcgs && (rc = dev_alloc(h, &h->d_theta_next, theta_elems))))   // theta_next: what the ggs z phase swaps in
     return rc;
   HIP_TRY(h, hipMemset(h->d_z, 0, sizeof(int32_t) * std::max<size_t>((size_t)N, 1)));
   HIP_TRY(h, hipMemset(h->d_zw, 0, sizeof(int32_t) * std::max<size_t>((size_t)N, 1)));
   HIP_TRY(h, hipMemset(h->d_theta, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
-  HIP_TRY(h, hipMemset(h->d_theta_next, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
+  if (!pcgs) HIP_TRY(h, hipMemset(h->d_theta_next, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
   if (h->d_mh) HIP_TRY(h, hipMemset(h->d_mh, 0, 3 * sizeof(unsigned long long)));
   HIP_TRY(h, hipDeviceSynchronize());   // the uploads and memsets above ran on the null stream; the handle's stream may not synchronise with it
 
@@ -1867,7 +1866,7 @@ int ggs_init_z_java_lcg(ggs_handle *h, int32_t seed) {
   // One sequential stream, so it runs on the host exactly once at start-up.
   std::vector<int32_t> z((size_t)h->N);
   const uint64_t lcg_state = java_lcg_next_ints(seed, h->K, h->N, z.data());
-  if (h->collapsed) {
+  if (h->scheme == Scheme::collapsed) {
     // SerialCollapsedLDA owns ONE Randoms(seed) (SerialCollapsedLDA.java:60-65): addInstances draws the initial topics
     // from it (:789) and the sampling loop goes on with the same object (MSLDA:206): the serial sweep continues this stream
     HIP_TRY(h, hipMemcpyAsync(h->d_lcg, &lcg_state, sizeof lcg_state, hipMemcpyHostToDevice, h->stream));
@@ -1899,7 +1898,7 @@ int ggs_set_z(ggs_handle *h, const int32_t *z, int32_t redraw_phi) {
 int ggs_init_phi(ggs_handle *h) {
   int rc = require_ready(h, false);
   if (rc) return rc;
-  if (h->collapsed) {                                  // nothing to draw: corpus-wide counts and tokensPerTopic are the whole model
+  if (h->scheme == Scheme::collapsed) {   // nothing to draw: corpus-wide counts and tokensPerTopic are the whole model
     if ((rc = launch_magnitude(h))) return rc;
     h->have_phi = true;
     return check_status(h);
@@ -1914,7 +1913,7 @@ int ggs_get_iteration(const ggs_handle *h, int32_t *it) { if (!h || !it) return 
 // see theta_main: only where the z step is one launch pair (no parts), theta is drawn at all, no collective is in the chain, and
 // the theta draw (D x K gammas) is the longer leg (the Phi chain draws V x K)
 bool chain_on_side_ok(const ggs_handle *h) {
-  return h->theta_main && h->plan.sliced() && h->side_hot && h->ev_chain_done && !h->xg && !h->collapsed && !(h->flags & GGS_FLAG_PCGS) &&
+  return h->theta_main && h->plan.sliced() && h->side_hot && h->ev_chain_done && !h->xg &&
          (h->D >= (int64_t)h->V || h->theta_main_always);
 }
 
@@ -1966,7 +1965,7 @@ int ggs_sweep(ggs_handle *h, int32_t n_sweeps) {
 int ggs_collapsed_serial_sweep(ggs_handle *h, int32_t java_seed, int32_t n_sweeps) {
   int rc = require_ready(h, false);
   if (rc) return rc;
-  if (!h->collapsed) return set_err(h, GGS_ERR_STATE, "ggs_collapsed_serial_sweep needs GGS_FLAG_COLLAPSED");
+  if (h->scheme != Scheme::collapsed) return set_err(h, GGS_ERR_STATE, "ggs_collapsed_serial_sweep needs GGS_FLAG_COLLAPSED");
   if (h->xg || h->tok_base != 0) return set_err(h, GGS_ERR_STATE, "the serial chain runs over ONE unsharded corpus");
   if (h->in_sweep) return set_err(h, GGS_ERR_STATE, "inside a split sweep");
   if ((size_t)h->K * 16 > (size_t)kMaxLdsBytes) return set_err(h, GGS_ERR_UNSUPPORTED, "num_topics too large for the serial kernel's LDS");
@@ -1993,7 +1992,7 @@ int ggs_sample_z_given_phi(ggs_handle *h, int32_t n_sweeps) {
   int rc = require_ready(h, true);
   if (rc) return rc;
   if (h->in_sweep) return set_err(h, GGS_ERR_STATE, "inside a split sweep");
-  if (h->collapsed) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed has no Phi to condition on");
+  if (h->scheme == Scheme::collapsed) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed has no Phi to condition on");
   for (int32_t i = 0; i < n_sweeps; ++i) {
     h->iteration += 1;                                 // UPLDA:980
     h->force_detail = true;
@@ -2257,7 +2256,7 @@ int ggs_group_set_z(ggs_handle **hs, int32_t n, const int32_t *const *z, int32_t
   for (int32_t i = 0; i < n; ++i)
     if ((rc = ggs_set_z(hs[i], z[i], 0))) return rc;          // this shard's counts
   if (!redraw_phi) return GGS_OK;
-  if (hs[0]->collapsed) {                                        // no Phi: the merged counts and tokensPerTopic are the model
+  if (hs[0]->scheme == Scheme::collapsed) {                                        // no Phi: the merged counts and tokensPerTopic are the model
     if ((rc = group_gather_counts(hs, n))) return rc;
     for (int32_t i = 0; i < n; ++i) {
       if ((rc = bind_device(hs[i])) || (rc = launch_magnitude(hs[i]))) return rc;
@@ -2273,7 +2272,7 @@ int ggs_group_sweep(ggs_handle **hs, int32_t n, int32_t n_sweeps) {
   if (!is_group(hs, n)) return GGS_ERR_BAD_ARG;
   int rc;
   for (int32_t s = 0; s < n_sweeps; ++s) {
-    if (hs[0]->collapsed && (rc = group_gather_counts(hs, n))) return rc;   // the z step conditions on the corpus-wide sweep-start counts
+    if (hs[0]->scheme == Scheme::collapsed && (rc = group_gather_counts(hs, n))) return rc;   // the z step conditions on the corpus-wide sweep-start counts
     for (int32_t i = 0; i < n; ++i) {
       ggs_handle *h = hs[i];
       if ((rc = require_ready(h, true))) return rc;
@@ -2281,7 +2280,7 @@ int ggs_group_sweep(ggs_handle **hs, int32_t n, int32_t n_sweeps) {
       h->iteration += 1;
       if ((rc = z_phase(h))) return rc;
     }
-    if (hs[0]->collapsed) {                                      // the AD-LDA merge: gathered counts, then tokensPerTopic; no Phi
+    if (hs[0]->scheme == Scheme::collapsed) {                                      // the AD-LDA merge: gathered counts, then tokensPerTopic; no Phi
       if ((rc = group_gather_counts(hs, n))) return rc;
       for (int32_t i = 0; i < n; ++i) {
         ggs_handle *h = hs[i];
@@ -2351,7 +2350,7 @@ int ggs_get_phi(ggs_handle *h, double *phi) {
   if (!h || !phi) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (h->collapsed) {                                  // the point estimate from the current counts
+  if (h->scheme == Scheme::collapsed) {   // the point estimate from the current counts
     if ((rc = launch_magnitude(h))) return rc;
     hipLaunchKernelGGL(psi_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, h->d_n_wk, h->d_n_k, h->beta, h->beta * (double)h->V,
                        h->d_phiT, h->K, h->Kp, h->V);
@@ -2382,7 +2381,7 @@ int ggs_get_alias_tables(ggs_handle *h, double *ps, int32_t *a, double *type_nor
   if (!h) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (!h->has_alias()) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS or GGS_FLAG_LIGHTPCLDA");
+  if (!has_alias(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS or GGS_FLAG_LIGHTPCLDA");
   if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
   if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
   const size_t kv = (size_t)h->K * h->V;
@@ -2396,7 +2395,7 @@ int ggs_get_mh_stats(ggs_handle *h, int64_t out[3]) {
   if (!h || !out) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (!h->lightpc) return set_err(h, GGS_ERR_STATE, "ggs_get_mh_stats needs GGS_FLAG_LIGHTPCLDA");
+  if (h->scheme != Scheme::lightpclda) return set_err(h, GGS_ERR_STATE, "ggs_get_mh_stats needs GGS_FLAG_LIGHTPCLDA");
   unsigned long long v[3];
   HIP_TRY(h, hipMemcpyAsync(v, h->d_mh, sizeof(v), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2470,9 +2469,9 @@ int ggs_log_posterior(ggs_handle *h, double *doc_side, double *topic_side) {
   int rc = require_ready(h, true);
   if (rc) return rc;
   if (!doc_side || !topic_side) return set_err(h, GGS_ERR_BAD_ARG, "null output");
-  if (h->collapsed) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed has no Phi: the log posterior of UPLDA:1573-1634 does not apply");
+  if (h->scheme == Scheme::collapsed) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed has no Phi: the log posterior of UPLDA:1573-1634 does not apply");
   if ((rc = ll_check_topics(h))) return rc;
-  if (h->flags & GGS_FLAG_PCGS) {
+  if (pcgs_family(h->scheme)) {
     // UPLDA:710-714: every scheme but ggs draws theta_d ~ Dir(n_d. + alpha) afresh for the diagnostics
     // (LDAUtils.drawDirichlets); here: the theta draw of GGS:57-72 under the stream GGS_PURPOSE_THETA at the current iteration
     if ((rc = drop_theta_ahead(h)) || (rc = launch_theta(h, h->stream, h->d_theta, h->iteration))) return rc;
@@ -2687,28 +2686,29 @@ int ggs_check_invariants(ggs_handle *h) {
 int ggs_get_launch_info(ggs_handle *h, int64_t *num_chunks, int32_t *lds_bytes_z, int32_t *docs_per_block_theta) {
   if (!h) return GGS_ERR_BAD_ARG;
   const LaunchPlan &pl = h->plan;
-  if (num_chunks) *num_chunks = pl.sliced() ? h->Cs + h->Cw : h->C;
-  if (lds_bytes_z) *lds_bytes_z = pl.sliced() ? sliced_fused_lds(h->K, pl.hot_cap) : pl.z.lds;
+  const bool pcgs = pcgs_family(h->scheme);            // what launch_pcgs_z launches, over what
+  if (num_chunks) *num_chunks = pcgs ? h->pcgs_items : pl.sliced() ? h->Cs + h->Cw : h->C;
+  if (lds_bytes_z) *lds_bytes_z = pcgs ? h->pcgs_z.lds : pl.sliced() ? sliced_fused_lds(h->K, pl.hot_cap) : pl.z.lds;
   if (docs_per_block_theta) *docs_per_block_theta = h->cfg->theta_docs;
   return GGS_OK;
 }
 
 int ggs_get_num_hot_words(ggs_handle *h, int32_t *num_hot) {
   if (!h || !num_hot) return GGS_ERR_BAD_ARG;
-  *num_hot = (h->plan.sliced() && !(h->flags & GGS_FLAG_PCGS)) ? h->num_hot + h->num_warm : 0;
+  *num_hot = h->plan.sliced() ? h->num_hot + h->num_warm : 0;
   return GGS_OK;
 }
 
 int ggs_get_z_parts(ggs_handle *h, int32_t *parts) {
   if (!h || !parts) return GGS_ERR_BAD_ARG;
   const int32_t P = (int32_t)h->part_doc.size() - 1;
-  *parts = (h->plan.stream() && h->overlap_theta && P > 1 && !(h->flags & GGS_FLAG_PCGS)) ? P : 1;
+  *parts = (h->plan.stream() && h->overlap_theta && P > 1) ? P : 1;
   return GGS_OK;
 }
 
 int ggs_get_warm_tiers(ggs_handle *h, int32_t *tiers, int32_t *warm_words, int32_t *docs_per_chunk) {
   if (!h) return GGS_ERR_BAD_ARG;
-  const bool on = h->have_corpus && h->plan.sliced() && !(h->flags & GGS_FLAG_PCGS);
+  const bool on = h->have_corpus && h->plan.sliced();
   if (tiers) *tiers = on ? h->warm_tiers : 0;
   if (warm_words) *warm_words = on ? h->num_warm : 0;
   if (docs_per_chunk) *docs_per_chunk = on && h->warm_tiers ? h->plan.warm_docs : 0;
@@ -2717,10 +2717,9 @@ int ggs_get_warm_tiers(ggs_handle *h, int32_t *tiers, int32_t *warm_words, int32
 
 int ggs_get_z_form(ggs_handle *h, int32_t *kernel, int32_t *form, int32_t *calibrated) {
   if (!h) return GGS_ERR_BAD_ARG;
-  const bool pcgs = (h->flags & GGS_FLAG_PCGS) != 0;
-  const bool splittable = !pcgs && h->plan.sliced() && h->Cs > h->Cc && h->Cc > 0;
-  if (kernel) *kernel = h->lightpc ? 7 : h->spalias ? 6 : pcgs ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
-  if (form) *form = (!pcgs && h->plan.sliced()) ? (splittable && h->z_split ? 1 : 2) : 0;
+  const bool splittable = h->plan.sliced() && h->Cs > h->Cc && h->Cc > 0;
+  if (kernel) *kernel = h->scheme == Scheme::lightpclda ? 7 : h->scheme == Scheme::spalias ? 6 : pcgs_family(h->scheme) ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
+  if (form) *form = h->plan.sliced() ? (splittable && h->z_split ? 1 : 2) : 0;
   if (calibrated) *calibrated = (splittable && h->z_split_tried && !h->plan.split_forced && h->plan.split) ? 1 : 0;
   return GGS_OK;
 }

@@ -1,6 +1,7 @@
 // ggs_corpus_lists.hpp -- the host half of ggs_set_corpus that touches no GPU: from a corpus and the few numbers the
-// launch plan fixes, every list the kernels read (chunk table, count segments, word-sorted permutation, the cold / hot / warm
-// chunk lists and their packed forms, the pcgs document order, the parts of the z step).  Plain C++: no HIP header, so a
+// launch plan fixes, every list the handle's kernels read: the count rebuild's (word-sorted permutation, count segments) and
+// those of the ONE z step the plan launches (chunk table and the parts of the z step, or the cold / hot / warm chunk lists
+// and their packed forms, or the pcgs document order).  Plain C++: no HIP header, so a
 // host compiler builds it and tests/test_corpus_lists_cpu.py checks it without a GPU.
 #pragma once
 #include <stdint.h>
@@ -13,11 +14,12 @@
 
 namespace ggs {
 
-// What the lists depend on besides the corpus.
+// What the lists depend on besides the corpus.  One family of z-step lists per handle: `pcgs` goes before `sliced`, and
+// with neither the chunk table of the tile and streaming kernels is built.
 struct CorpusShape {
   int32_t V = 0;
-  bool pcgs = false;                 // the document order of the pcgs kernels
-  bool sliced = false;               // the cold / hot / warm chunk lists of the score-register kernels
+  bool pcgs = false;                 // the document order of the pcgs kernels, and no other z list
+  bool sliced = false;               // the cold / hot / warm chunk lists of the score-register kernels and the hot words' count segments
   bool two_rows = false;             // chunk table: 64 consecutive tokens across at most one document boundary
   int32_t tile_tokens = 64;          // ... otherwise near-equal cuts of single documents, this many tokens at most
   int32_t z_parts = 1;               // parts of consecutive documents the z step is cut into
@@ -32,7 +34,7 @@ struct CorpusLists {
   // chunk table of the tile and streaming kernels; two_rows: clen = tokens | tokens of the first document << 8, cdoc1 the second document
   std::vector<int64_t> cstart;
   std::vector<int32_t> cdoc, clen, cdoc1;
-  std::vector<int64_t> part_doc, part_chunk;           // [parts + 1] boundaries of the z step's parts
+  std::vector<int64_t> part_doc, part_chunk;           // [parts + 1] boundaries of the z step's parts (with the chunk table)
   // tokens sorted by word (stable) and its inverse; each word's run cut into segments; the hot words' segments once more
   std::vector<int32_t> perm, inv, seg_word, seg_begin, hot_words, hseg_word, hseg_begin, hseg_end;
   // pcgs: documents longest first, or the padded two-round list (-1 = no document)
@@ -155,7 +157,7 @@ inline std::vector<int32_t> word_order(const CorpusShape &s, const int32_t *toke
   std::vector<int64_t> cur(wptr.begin(), wptr.end() - 1);
   for (int64_t i = 0; i < N; ++i) L.perm[(size_t)cur[(size_t)tokens[i]]++] = (int32_t)i;
   for (int64_t i = 0; i < N; ++i) L.inv[(size_t)L.perm[(size_t)i]] = (int32_t)i;
-  if (s.sliced && s.hot_cap > 0) {
+  if (s.sliced && !s.pcgs && s.hot_cap > 0) {
     std::vector<int32_t> order((size_t)s.V);
     for (int32_t w = 0; w < s.V; ++w) order[(size_t)w] = w;
     const size_t nh = (size_t)std::min<int32_t>(s.hot_cap, s.V);
@@ -301,11 +303,15 @@ inline void sliced_lists(const CorpusShape &s, const int64_t D, const int64_t *d
 inline CorpusLists build_corpus_lists(const CorpusShape &s, const int64_t D, const int64_t *doc_ptr, const int32_t *tokens) {
   CorpusLists L;
   L.D = D; L.N = doc_ptr[D];
-  lists_detail::chunk_table(s, D, doc_ptr, L);
-  lists_detail::z_parts(s, D, doc_ptr, L);
-  std::vector<int32_t> warm_cand = lists_detail::word_order(s, tokens, L);
-  if (s.pcgs) lists_detail::pcgs_order(s, D, doc_ptr, L);
-  if (s.sliced) lists_detail::sliced_lists(s, D, doc_ptr, tokens, std::move(warm_cand), L);
+  std::vector<int32_t> warm_cand = lists_detail::word_order(s, tokens, L);   // every handle: the count rebuild's
+  if (s.pcgs) {
+    lists_detail::pcgs_order(s, D, doc_ptr, L);
+  } else if (s.sliced) {
+    lists_detail::sliced_lists(s, D, doc_ptr, tokens, std::move(warm_cand), L);
+  } else {
+    lists_detail::chunk_table(s, D, doc_ptr, L);
+    lists_detail::z_parts(s, D, doc_ptr, L);
+  }
   return L;
 }
 

@@ -61,7 +61,6 @@ struct ZParams {
   uint64_t seed;
   uint32_t iteration;
   int32_t K, Kp, pitch16, tile_tokens;
-  int32_t ablate;   // timing-only experiments, concluded: the host leaves it 0 (the kernels' branches go with the next change of device code)
   // z_sliced_kernel only (ggs_z_sliced.hpp): its own chunk lists -- cold chunks [0, num_cold), hot chunks
   // [num_cold, num_chunks) -- stored chunk-major, 64 entries per chunk
   const int32_t *ct_tok;       // cold: word id, hot: row of the LDS table; | (0 or 1: which of the chunk's documents) << 30
@@ -95,7 +94,6 @@ struct ZParams {
   const int32_t *warm_words;   // [warm_tiers][warm_rows] word ids of the tables' rows
   const int64_t *warm_meta;    // [warm_tiers + 1] first chunk of a tier, then [warm_tiers] rows of its table
   int32_t warm_tiers, warm_rows;
-  long long *dbg;              // the phase trace of z_warm_kernel's chunk loop, concluded: the host leaves it null
   // z_sliced_kernel<KMAX, true> (ggs_z_sliced.hpp): the cold chunks scored from the float32 shadow of phiT and decided by
   // the margin of its header; the tokens too close to call are replayed from phiT and theta
   const float *phiT32;         // [V][Kp32], Kp32 = K rounded up to whole 32-topic slices, the pad columns zero
@@ -174,16 +172,14 @@ __global__ __launch_bounds__(64) void z_kernel(ZParams p) {
     }
 
     // ---- stage: one DMA per token row
-    if (!(p.ablate & 4)) {
-      for (int i = 0; i < len; ++i) {
-        const int wi = __builtin_amdgcn_readlane(w, i);              // wave-uniform word id of row i
-        const unsigned char *rb = phib + (size_t)wi * rowbytes;
-        unsigned char *dst = smem + (size_t)i * pitch;
-        for (int u0 = 0; u0 < upr; u0 += 64) {
-          const int u = u0 + lane;
-          if (u < upr)
-            __builtin_amdgcn_global_load_lds((glb_cvoid_t *)(rb + (size_t)u * 16), (lds_void_t *)(dst + (size_t)u0 * 16), 16, 0, 0);
-        }
+    for (int i = 0; i < len; ++i) {
+      const int wi = __builtin_amdgcn_readlane(w, i);              // wave-uniform word id of row i
+      const unsigned char *rb = phib + (size_t)wi * rowbytes;
+      unsigned char *dst = smem + (size_t)i * pitch;
+      for (int u0 = 0; u0 < upr; u0 += 64) {
+        const int u = u0 + lane;
+        if (u < upr)
+          __builtin_amdgcn_global_load_lds((glb_cvoid_t *)(rb + (size_t)u * 16), (lds_void_t *)(dst + (size_t)u0 * 16), 16, 0, 0);
       }
     }
     // LDS-DMA completion is tracked by vmcnt and the compiler does not know the LDS reads
@@ -201,8 +197,7 @@ __global__ __launch_bounds__(64) void z_kernel(ZParams p) {
         sum += (S##0).a * (A##0).a; sum += (S##0).b * (A##0).b; sum += (S##1).a * (A##1).a; sum += (S##1).b * (A##1).b; \
         sum += (S##2).a * (A##2).a; sum += (S##2).b * (A##2).b; sum += (S##3).a * (A##3).a; sum += (S##3).b * (A##3).b; }
       double sum = 0.0;
-      if (p.ablate & 8) sum = 1.0;
-      else {
+      {
         int j = 0;
         if (K >= 8) {
           D2 a0, a1, a2, a3, b0, b1, b2, b3, s0, s1, s2, s3, t0, t1, t2, t3;
@@ -241,8 +236,7 @@ __global__ __launch_bounds__(64) void z_kernel(ZParams p) {
       // newTopic + 1 == #{k : sample before subtracting score[k] was > 0}.  The subtraction
       // itself is the same sequential fp64 chain; the wave leaves when no lane is still > 0.
       int cnt = 0;
-      bool live = !(p.ablate & 2);
-      if (!live) { cnt = 1 + (int)(U * K); sample = 0.0; }
+      bool live = true;
 #define GGS_STEP(TH, PHI) { cnt += (sample > 0.0); sample -= (TH) * (PHI); }
 #define GGS_WALK8(A, S) { \
         GGS_STEP((S##0).a, (A##0).a) GGS_STEP((S##0).b, (A##0).b) GGS_STEP((S##1).a, (A##1).a) GGS_STEP((S##1).b, (A##1).b) \

@@ -2,6 +2,7 @@
 (tests/corpus_lists_driver.cpp) is compiled with the host compiler and the lists it prints are checked against the
 corpus -- every token in exactly one of the cold / hot / warm lists, chunk sizes and document limits, active lanes a
 prefix, the two-row chunk table a gapless cover, the pcgs order a permutation, the warm tiers' keep rule."""
+import hashlib
 import os
 import shutil
 import subprocess
@@ -66,6 +67,7 @@ def run(driver, tmp_path, c, shape):
         name, n, *vals = line.split()
         L[name] = np.array(vals, np.int64)
         assert len(L[name]) == int(n)
+    L["lines"] = {line.split()[0]: line for line in out.splitlines()}
     for k in ("kChunkDocs", "kSlotShift", "kWarmSlotShift", "kWarmDocSlots", "kPcgsMaxDocLen", "kSegTokens", "longest", "Cc", "Cs", "warm_tiers", "num_warm",
               "warm_rows_max", "Cw", "warm_chunks_max"):
         L[k] = int(L[k][0])
@@ -246,3 +248,55 @@ def test_pcgs_order(driver, tmp_path, cname, c, sname):
     else:
         assert len(order) == D and (np.diff(lens[order]) <= 0).all(), "longest first"
         assert (np.diff(order)[np.diff(lens[order]) == 0] > 0).all(), "equal lengths in document order"
+
+
+COUNT_LISTS = ("perm", "inv", "seg_word", "seg_begin")
+CHUNK_TABLE = ("cstart", "cdoc", "clen", "cdoc1", "part_doc", "part_chunk")
+SLICED_LISTS = ("hot_words", "hseg_word", "hseg_begin", "hseg_end", "ct_tok", "ct_idx", "ct_ip", "c_docs", "Cc", "Cs", "ht_pack", "h_docs", "warm_tiers", "num_warm",
+                "warm_rows_max", "Cw", "warm_chunks_max", "wt_pack", "w_docs", "warm_words", "warm_meta")
+
+
+def absent(L, names):
+    return all(np.size(L[k]) == 0 if isinstance(L[k], np.ndarray) else L[k] == 0 for k in names)
+
+
+@pytest.mark.parametrize("cname,c", corpora(), ids=[n for n, _ in corpora()])
+def test_one_list_family_per_shape(driver, tmp_path, cname, c):
+    """A shape builds the lists of ONE z step and, always, what the count rebuild reads."""
+    Ls = {name: run(driver, tmp_path, c, shape) for name, shape in SHAPES.items()}
+    for name, L in Ls.items():
+        for k in COUNT_LISTS:
+            assert np.array_equal(L[k], Ls["tile"][k]), (name, k)
+    for name in ("pcgs", "pcgs_wide"):
+        L = Ls[name]
+        assert absent(L, CHUNK_TABLE) and absent(L, SLICED_LISTS), "no chunk table, no z parts, no sliced lists"
+        assert len(L["order"]) >= c.num_docs and L["longest"] == np.diff(c.doc_ptr).max()
+    for name in ("sliced", "sliced_no_warm"):
+        L = Ls[name]
+        assert absent(L, CHUNK_TABLE) and absent(L, ("order", "longest")), "no tile / streaming chunk table, no document order"
+        assert (L["Cs"] > 0) == (c.num_tokens > 0)
+    for name in ("tile", "two_rows"):
+        L = Ls[name]
+        assert absent(L, SLICED_LISTS) and absent(L, ("order", "longest"))
+        assert (len(L["cstart"]) > 0) == (c.num_tokens > 0) and len(L["part_doc"]) == len(L["part_chunk"]) >= 2
+
+
+# sha256 of the driver's SLICED_LISTS lines as the commit before a shape built one family of z lists printed them (the corpora are seeded)
+SLICED_PINS = {
+    ("ragged", "sliced"): "e6194a599369ab67b1c91086a49f977f248e8b0a0d0fb61b9e79304621964276",
+    ("ragged", "sliced_no_warm"): "b6eb8672e8c818e18cd76ef75e0329208823099ca1fd1ad7fae3bcca1a59269d",
+    ("many_docs", "sliced"): "2d60f4e86922c7d6273604b7c89ba14a2e7bb6579f43f987679ed3b0b30eff65",
+    ("many_docs", "sliced_no_warm"): "582918b393c23376f2d89ae3ee0902750a6519a815d4db553485f318a549b10b",
+    ("long_doc", "sliced"): "99a04ccf7fa89e67544444bda0a9872fcdecd00ba84fbbef1809f5bd2ae8073f",
+    ("long_doc", "sliced_no_warm"): "979425a12860cd56454817a276c7aea65a918133dc34d6ae2f72a288b36749ea",
+    ("empty", "sliced"): "61b0c45d0f5eaefe75d37f827156c0171d194eed4f6f6fd8365c076e9d17b8dd",
+    ("empty", "sliced_no_warm"): "61b0c45d0f5eaefe75d37f827156c0171d194eed4f6f6fd8365c076e9d17b8dd",
+}
+
+
+@pytest.mark.parametrize("cname,c", corpora(), ids=[n for n, _ in corpora()])
+@pytest.mark.parametrize("sname", ["sliced", "sliced_no_warm"])
+def test_sliced_lists_unchanged(driver, tmp_path, cname, c, sname):
+    L = run(driver, tmp_path, c, SHAPES[sname])
+    text = "".join(L["lines"][k] + "\n" for k in SLICED_LISTS)
+    assert hashlib.sha256(text.encode()).hexdigest() == SLICED_PINS[cname, sname]
