@@ -94,7 +94,7 @@ enum {
                                      rebuilt whenever Phi changes (ggs_init_phi, every sweep, ggs_set_phi); ggs_get_alias_tables
                                      reads them back.  K up to 4096, any document length.  With GGS_FLAG_COLLAPSED or
                                      GGS_FLAG_POLYAURN: GGS_ERR_BAD_ARG.  A new bit, not a new ABI version. */
-  GGS_FLAG_LIGHTPCLDA = 1 << 6    /* scheme=lightpclda (LightPCLDA, ParallelLDA.java:469-473; LightPCLDA.java:86-221): the pcgs model
+  GGS_FLAG_LIGHTPCLDA = 1 << 6,   /* scheme=lightpclda (LightPCLDA, ParallelLDA.java:469-473; LightPCLDA.java:86-221): the pcgs model
                                      (implied: GGS_FLAG_PCGS is set internally; Phi, counts, phi mean and exchange exactly as pcgs)
                                      with a Metropolis-Hastings z step, O(1) per token: a proposal from the word's alias table
                                      and one from the document's own indicator array, each accepted on a ratio of a few numbers.
@@ -108,6 +108,30 @@ enum {
                                      GGS_ERR_INVALID_TOPIC.  The chain is approximate by design and is not repaired.
                                      K up to 4096, any document length.  With GGS_FLAG_COLLAPSED, GGS_FLAG_POLYAURN or
                                      GGS_FLAG_SPALIAS: GGS_ERR_BAD_ARG.  A new bit, not a new ABI version. */
+  GGS_FLAG_POLYAURN_SPARSE = 1 << 7 /* scheme=polyaurn_sparse (PolyaUrnSpaliasLDA.sampleTopicAssignmentsParallel,
+                                     PolyaUrnSpaliasLDA.java:180-334): polyaurn's model (implied: GGS_FLAG_PCGS is set internally; Phi
+                                     initial and per sweep, counts, tokensPerTopic, phi mean and exchange exactly as under
+                                     GGS_FLAG_POLYAURN, alias_poisson_threshold read the same way) with the doubly sparse z step the
+                                     reference builds for Phi's exact zeros.  After every Phi (ggs_init_phi, every sweep, ggs_set_phi)
+                                     spalias's alias tables are rebuilt and, per word w, nzw[w] = the topics k with
+                                     phi[k][w] != 0.0 in ascending k, nw[w] their number (ggs_get_word_topic_lists);
+                                     ggs_sample_z_given_phi reuses what ggs_set_phi built.  The document keeps spalias's state:
+                                     counts cnt[K] and the list of its non-zero topics (a topic appended on first occurrence, a
+                                     removed topic replaced by the last entry).  Per token, with its uniform U (purpose Z, element =
+                                     global token index), all in fp64 in this order: the old topic is removed; nd = the document
+                                     list's length; the candidates c_0..c_{n-1} are nzw[w] if nw[w] < nd (:261-267), otherwise, a tie
+                                     included, the document's list.  n == 0 (a one-token document, an all-zero Phi column):
+                                     topic = min((int)(U * K), K - 1) (:276-277; the reference does not clamp, it throws when
+                                     floor(U * K) reaches K).  Otherwise cum[0] = (double)cnt[c_0] * phi[c_0][w],
+                                     cum[i] = (double)cnt[c_i] * phi[c_i][w] + cum[i-1], sum = cum[n-1], tn = typeNorm[w]; if
+                                     U < tn / (tn + sum) the topic is the alias draw sample(w, U + (sum * U) / tn) (i == K:
+                                     GGS_ERR_INVALID_TOPIC); else ul = U * (tn + sum) - tn and the topic is the candidate at the
+                                     smallest i with ul <= cum[i], the last candidate if there is none (ours, as under
+                                     GGS_FLAG_SPALIAS; so for 0 / 0, which fails the first comparison).  A word-list candidate
+                                     with cnt == 0 scores 0.0 and is walked like any other.  ggs_get_sparse_stats counts which list
+                                     the tokens took.  K up to 4096, any document length.  With GGS_FLAG_COLLAPSED,
+                                     GGS_FLAG_POLYAURN, GGS_FLAG_SPALIAS or GGS_FLAG_LIGHTPCLDA: GGS_ERR_BAD_ARG.  A new bit, not a
+                                     new ABI version. */
 };
 
 /* RNG stream addressing.  The reference draws from ThreadLocalRandom and a
@@ -138,7 +162,7 @@ typedef struct ggs_config {
   int32_t phi_mean_thin;  /* cfg key phi_mean_thin, UPLDA:208                                  */
   int32_t alias_poisson_threshold; /* cfg key alias_poisson_threshold (ParsedLDAConfiguration.java:480-482; default 100,
                              LDAConfiguration.java:44): counts below it draw their Poisson variate from a table.  Read only
-                             under GGS_FLAG_POLYAURN: 0 means 100, 1..512 allowed, anything else GGS_ERR_BAD_ARG.  (The
+                             under GGS_FLAG_POLYAURN and GGS_FLAG_POLYAURN_SPARSE: 0 means 100, 1..512 allowed, anything else GGS_ERR_BAD_ARG.  (The
                              field was `reserved` before ABI version 6; layout and struct_size are unchanged.) */
 } ggs_config;
 
@@ -352,8 +376,8 @@ int ggs_reset_timings(ggs_handle *h);
  * counterpart: there is no delta matrix, the counts are rebuilt from z every sweep.) */
 int ggs_check_invariants(ggs_handle *h);
 /* Launch geometry of the z kernel the handle launches (ggs_get_z_form names it), for bench.py's roofline accounting.
- * lds_bytes_z: the dynamic LDS of that launch (score-register kernels: of the fused form with a full hot table; scheme
- * spalias: of the current corpus, since its lists are sized by the longest document).  num_chunks: the work items the
+ * lds_bytes_z: the dynamic LDS of that launch (score-register kernels: of the fused form with a full hot table; schemes
+ * spalias and polyaurn_sparse: of the current corpus, since their lists are sized by the longest document).  num_chunks: the work items the
  * persistent grid strides -- chunks for scheme ggs; for the other schemes entries of the document order (wave per
  * document) or groups of 64 of them (lane per document); 0 before ggs_set_corpus. */
 int ggs_get_launch_info(ggs_handle *h, int64_t *num_chunks, int32_t *lds_bytes_z, int32_t *docs_per_block_theta);
@@ -372,7 +396,7 @@ int ggs_get_z_parts(ggs_handle *h, int32_t *parts);
 /* Which z kernel(s) the sweeps of the current corpus run, so that a benchmark line can NAME what it timed instead of
  * assuming it: *kernel = 0 whole-row tile kernel, 1 score-register kernels (K <= 160), 2 one-pass streaming kernel,
  * 3 its two-pass cross-check, 4 pcgs lane-per-document, 5 pcgs wave-per-document, 6 spalias wave-per-document,
- * 7 lightpclda wave-per-document; *form (kernel 1 only, else 0) =
+ * 7 lightpclda wave-per-document, 8 polyaurn_sparse wave-per-document; *form (kernel 1 only, else 0) =
  * 1 split (cold chunks and hot chunks as two kernels side by side), 2 fused (one kernel takes both in turn);
  * *calibrated = 1 once the first z step of the corpus has timed both forms and kept the faster (0 before that, and
  * when a form is forced or there is nothing to split).  ABI version 4. */
@@ -391,14 +415,23 @@ int ggs_debug_poisson(int32_t device_id, double beta, int32_t threshold, uint64_
  * product kernel from phi [K][V] and alpha [K]: ps [V][K], a [V][K] and type_norm [V] = the k-order sum of phi[k][w] * alpha[k].
  * A draw x in [0, 1) from word w's table: ups = x * K, i = (int)ups, topic = (ups - i) > ps[w][i] ? a[w][i] : i.  K up to 4096. */
 int ggs_debug_alias(int32_t device_id, int32_t V, int32_t K, const double *phi, const double *alpha, double *ps, int32_t *a, double *type_norm);
-/* the tables of the handle's current Phi (GGS_FLAG_SPALIAS or GGS_FLAG_LIGHTPCLDA; GGS_ERR_STATE otherwise or before the
- * first Phi); any of the three outputs may be null */
+/* the tables of the handle's current Phi (GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA or GGS_FLAG_POLYAURN_SPARSE; GGS_ERR_STATE
+ * otherwise or before the first Phi); any of the three outputs may be null */
 int ggs_get_alias_tables(ggs_handle *h, double *ps /*[V][K]*/, int32_t *a /*[V][K]*/, double *type_norm /*[V]*/);
 /* scheme=lightpclda's Metropolis-Hastings counters, cumulative since ggs_set_corpus (the three the reference keeps
  * commented out, LightPCLDA.java:28-44), every token in exactly one: out[0] tokens whose word proposal was accepted and
  * kept, out[1] tokens whose document proposal was accepted, out[2] tokens left on their old topic.  GGS_ERR_STATE
  * without GGS_FLAG_LIGHTPCLDA. */
 int ggs_get_mh_stats(ggs_handle *h, int64_t out[3]);
+/* scheme=polyaurn_sparse's word lists of the handle's current Phi: nw[w] = the number of topics with phi[k][w] != 0.0,
+ * topics[w][0 .. nw[w]) those topics in ascending order, -1 behind them.  Either output may be null.  GGS_ERR_STATE without
+ * GGS_FLAG_POLYAURN_SPARSE or before the first Phi. */
+int ggs_get_word_topic_lists(ggs_handle *h, int32_t *nw /*V*/, int32_t *topics /*[V][K]*/);
+/* scheme=polyaurn_sparse's counters, cumulative since ggs_set_corpus, every token in exactly one of the first three:
+ * out[0] tokens that walked the word's list, out[1] tokens that walked the document's list, out[2] tokens drawn uniformly
+ * (no candidate), out[3] the sum of n, the number of candidates, over all tokens.  GGS_ERR_STATE without
+ * GGS_FLAG_POLYAURN_SPARSE. */
+int ggs_get_sparse_stats(ggs_handle *h, int64_t out[4]);
 /* replaces: modelLogLikelihood (UPLDA:1644-1758), the Dirichlet-multinomial log likelihood of the current topic
  * assignments, split where a doc-sharded run splits it: doc_side covers THIS handle's documents (sum_d [...] +
  * D*lgS(alphaSum), UPLDA:1674-1694) and topic_side the (replicated) type-topic counts (UPLDA:1701-1747); the model's

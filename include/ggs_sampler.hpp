@@ -51,7 +51,8 @@ struct LDAConfiguration {
   bool polyaurn = false;          // scheme=polyaurn (ParallelLDA.java:444-447, PolyaUrnSpaliasLDA): the pcgs z step over a Poisson-drawn Phi
   bool spalias = false;           // scheme=spalias (ParallelLDA.java:439-442, SpaliasUncollapsedParallelLDA): the pcgs model, a sparse z step over alias tables
   bool lightpclda = false;        // scheme=lightpclda (ParallelLDA.java:469-473, LightPCLDA): the pcgs model, a Metropolis-Hastings z step over alias tables
-  int alias_poisson_threshold = 100;   // ALIAS_POISSON_DEFAULT_THRESHOLD (LDAConfiguration.java:44); read under polyaurn only
+  bool polyaurn_sparse = false;   // scheme=polyaurn_sparse (PolyaUrnSpaliasLDA.java:180-334): polyaurn's model, the doubly sparse z step
+  int alias_poisson_threshold = 100;   // ALIAS_POISSON_DEFAULT_THRESHOLD (LDAConfiguration.java:44); read under polyaurn and polyaurn_sparse only
   int device_id = 0;
   // the diagnostics of the sampling loop (UPLDA:695-905), computed on the device, written as the Java driver writes them
   bool compute_likelihood = false;   // model LL (+ held-out LL with a test set) every iteration, UPLDA:838-850
@@ -87,7 +88,8 @@ class LDAGroupedGibbsSampler {
     c.seed = (uint64_t)(int64_t)startSeed_;
     c.flags = (config_.paranoid ? GGS_FLAG_PARANOID : 0) | (config_.save_phi_mean ? GGS_FLAG_SAVE_PHI_MEAN : 0) |
               (config_.pcgs ? GGS_FLAG_PCGS : 0) | (config_.collapsed ? GGS_FLAG_COLLAPSED : 0) | (config_.polyaurn ? GGS_FLAG_POLYAURN : 0) |
-              (config_.spalias ? GGS_FLAG_SPALIAS : 0) | (config_.lightpclda ? GGS_FLAG_LIGHTPCLDA : 0);
+              (config_.spalias ? GGS_FLAG_SPALIAS : 0) | (config_.lightpclda ? GGS_FLAG_LIGHTPCLDA : 0) |
+              (config_.polyaurn_sparse ? GGS_FLAG_POLYAURN_SPARSE : 0);
     c.alias_poisson_threshold = config_.alias_poisson_threshold;
     c.phi_burn_in = (int32_t)(((double)config_.phi_mean_burnin / 100) * config_.iterations);   // UPLDA:206-207
     c.phi_mean_thin = config_.phi_mean_thin;

@@ -138,6 +138,8 @@ SIGNATURES = {
     "ggs_debug_alias": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _ip, _dp]),
     "ggs_get_alias_tables": (C.c_int, [_vp, _dp, _ip, _dp]),
     "ggs_get_mh_stats": (C.c_int, [_vp, _lp]),
+    "ggs_get_word_topic_lists": (C.c_int, [_vp, _ip, _ip]),
+    "ggs_get_sparse_stats": (C.c_int, [_vp, _lp]),
     "ggs_model_log_likelihood": (C.c_int, [_vp, _dp, _dp]),
     "ggs_log_posterior": (C.c_int, [_vp, _dp, _dp]),
     "ggs_set_test_corpus": (C.c_int, [_vp, C.c_int64, _lp, _ip, C.c_int64]),

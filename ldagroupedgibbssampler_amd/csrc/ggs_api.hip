@@ -22,6 +22,7 @@
 #include "ggs_phi_poisson.hpp"
 #include "ggs_alias.hpp"
 #include "ggs_z_spalias.hpp"
+#include "ggs_z_polyaurn_sparse.hpp"
 #include "ggs_z_lightpc.hpp"
 #include "ggs_loglik.hpp"
 #include "ggs_heldout.hpp"
@@ -66,9 +67,10 @@ constexpr int kThetaBlock = 256;
 
 // What a handle samples and how: derived once from ggs_config::flags (scheme_of).  Every scheme but ggs runs the pcgs
 // machinery: no theta in the chain, a document order instead of chunk lists, the plan's lane / wave / ... entries.
-enum class Scheme { ggs, pcgs, collapsed, polyaurn, spalias, lightpclda };
+enum class Scheme { ggs, pcgs, collapsed, polyaurn, spalias, lightpclda, polyaurn_sparse };
 constexpr bool pcgs_family(Scheme s) { return s != Scheme::ggs; }
-constexpr bool has_alias(Scheme s) { return s == Scheme::spalias || s == Scheme::lightpclda; }
+constexpr bool has_alias(Scheme s) { return s == Scheme::spalias || s == Scheme::lightpclda || s == Scheme::polyaurn_sparse; }
+constexpr bool poisson_phi(Scheme s) { return s == Scheme::polyaurn || s == Scheme::polyaurn_sparse; }   // Phi drawn as polyaurn draws it
 
 // One kernel as a handle launches it: the function, its workgroup, its dynamic LDS and the workgroups per CU of its
 // persistent grid.  The table kernels' LDS is given without table rows (they differ by corpus).
@@ -104,11 +106,12 @@ struct LaunchPlan {
   KernelLaunch theta;                  // its LDS and documents per workgroup: the configuration's, or ...
   int32_t theta_docs_main = 0, theta_lds_main = 0;   // ... where the theta draw is the critical leg (theta_main)
   // scheme pcgs / collapsed / polyaurn: a lane or a wave per document; spalias: the table build and the sparse walk (LDS per corpus);
-  // lightpclda: the same table build and the Metropolis-Hastings step
-  KernelLaunch lane, wave, alias, spalias, lightpc, serial;
+  // lightpclda: the same table build and the Metropolis-Hastings step; polyaurn_sparse: the table build, the words' lists and
+  // the doubly sparse walk (LDS per corpus)
+  KernelLaunch lane, wave, alias, spalias, lightpc, serial, wordlist, pusparse;
   bool wave_forced = false;            // ... because of K; otherwise per corpus (a document of 32 768 tokens or more)
   int32_t alias_wpb = 0;
-  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial}; }
+  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse}; }
 };
 
 // The phase events of one sweep.  Sweeps are settled (waited for, checked, timed) in batches, so a ring of them:
@@ -170,6 +173,11 @@ struct ggs_handle {
   // scheme=lightpclda (ggs_z_lightpc.hpp): the pcgs model and spalias's tables, a Metropolis-Hastings z step
   double alpha_sum = 0;                                // the k-order sum of alpha
   unsigned long long *d_mh = nullptr;                  // [3]: ggs_get_mh_stats, zeroed by ggs_set_corpus
+  // scheme=polyaurn_sparse (ggs_z_polyaurn_sparse.hpp): polyaurn's Phi, spalias's tables and document lists, and per word the
+  // ascending list of its topics with phi != 0, rebuilt with the tables
+  uint16_t *d_nzw = nullptr;                           // [V][K]
+  int32_t *d_nw = nullptr;                             // [V]
+  unsigned long long *d_ps_stats = nullptr;            // [4]: ggs_get_sparse_stats, zeroed by ggs_set_corpus
   uint64_t *d_lcg = nullptr;                           // ggs_collapsed_serial_sweep: the java.util.Random state
   bool lcg_ready = false;
   int32_t num_hot = 0;
@@ -710,7 +718,7 @@ int launch_phi_slice(ggs_handle *h, bool initial, const int32_t *cnt, int32_t cn
                      double *mag, double *tot, int32_t *n_k, double *phi_mean) {
   if (Ks <= 0) return GGS_OK;
   int rc;
-  if (h->scheme == Scheme::polyaurn) {   // no magnitudes, no gammas, no exact-sum walk: the totals are integers
+  if (poisson_phi(h->scheme)) {   // no magnitudes, no gammas, no exact-sum walk: the totals are integers
     if ((rc = phi_slice_poisson(h, initial, cnt, cnt_pitch, Ks, k0, out, out_pitch, 0, h->sum_nseg, true)) || (rc = phi_slice_poisson_totals(h, Ks, tot, n_k)))
       return rc;
     hipLaunchKernelGGL(phi_normalise_polyaurn_kernel, dim3(grid_for((int64_t)Ks * h->V, 256, 2)), dim3(256), 0, h->stream, out, tot, Ks, out_pitch, h->V,
@@ -746,13 +754,13 @@ int phi_step_a(ggs_handle *h) { return exchange_reduce_scatter(h); }
 int phi_step_a_clear(ggs_handle *h) { return h->seg_split > 0 ? GGS_OK : clear_send_buffer_if_dead(h, h->stream); }
 int phi_step_b1(ggs_handle *h, bool initial) {
   int rc;
-  if (h->scheme == Scheme::polyaurn) {   // the Poisson draws of the first half (and the totals' zero fill)
+  if (poisson_phi(h->scheme)) {   // the Poisson draws of the first half (and the totals' zero fill)
     if ((rc = phi_slice_poisson(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, 0, h->seg_split, true))) return rc;
   } else if ((rc = launch_magnitude_on(h, h->d_cnt_own, h->Ksm, h->Ks, h->d_mag_own, h->d_n_k_own))) {
     return rc;
   }
   if (h->seg_split > 0) {
-    if (h->scheme != Scheme::polyaurn && (rc = phi_slice_gamma(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, h->d_mag_own, 0, h->seg_split))) return rc;
+    if (!poisson_phi(h->scheme) && (rc = phi_slice_gamma(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, h->d_mag_own, 0, h->seg_split))) return rc;
     HIP_TRY(h, hipEventRecord(h->ev_half_drawn, h->stream));
     HIP_TRY(h, hipStreamWaitEvent(h->comm_stream, h->ev_half_drawn, 0));
   }
@@ -770,7 +778,7 @@ int phi_step_b2(ggs_handle *h, bool initial) {
     if ((rc = clear_send_buffer_if_dead(h, h->comm_stream))) return rc;
     HIP_TRY(h, hipEventRecord(h->ev_half_gathered, h->comm_stream));
   }
-  if (h->scheme == Scheme::polyaurn) {   // the second half, then the integer totals into the slot behind the slice
+  if (poisson_phi(h->scheme)) {   // the second half, then the integer totals into the slot behind the slice
     if ((rc = phi_slice_poisson(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, h->seg_split, h->sum_nseg, false))) return rc;
     return phi_slice_poisson_totals(h, h->Ks, h->d_phi_own + (size_t)h->V * h->Ksm, h->d_n_k_own);
   }
@@ -790,7 +798,7 @@ int phi_step_c(ggs_handle *h, bool accumulate_mean) {
   rp.phi_mean = accumulate_mean ? h->d_phi_mean : nullptr;
   rp.c0 = (int64_t)half0_elems(h); rp.c1 = (int64_t)half1_elems(h); rp.K = h->K; rp.Kp = h->Kp; rp.V = h->V; rp.Ksm = h->Ksm; rp.v_split = h->v_split;
   rp.phiT32 = h->d_phiT32; rp.Kp32 = h->plan.Kp32;
-  if (h->scheme == Scheme::polyaurn) hipLaunchKernelGGL(phi_repack_polyaurn_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
+  if (poisson_phi(h->scheme)) hipLaunchKernelGGL(phi_repack_polyaurn_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   else hipLaunchKernelGGL(phi_repack_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   HIP_TRY(h, hipGetLastError());
   h->have_phi = true;
@@ -809,6 +817,12 @@ int launch_alias_build(ggs_handle *h) {
   ap.V = h->V; ap.K = h->K; ap.Kp = h->Kp; ap.wpb = h->plan.alias_wpb;
   void *args[] = {&ap};
   HIP_TRY(h, launch(h, h->plan.alias, ((int64_t)h->V + ap.wpb - 1) / ap.wpb, args, h->stream));
+  if (h->scheme == Scheme::polyaurn_sparse) {          // the words' lists of non-zero topics, of the same Phi
+    WordListParams wp{};
+    wp.phiT = h->d_phiT; wp.nzw = h->d_nzw; wp.nw = h->d_nw; wp.V = h->V; wp.K = h->K; wp.Kp = h->Kp;
+    void *wargs[] = {&wp};
+    HIP_TRY(h, launch(h, h->plan.wordlist, h->V, wargs, h->stream));
+  }
   h->alias_stale = false;
   return GGS_OK;
 }
@@ -1072,6 +1086,10 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
     pl.alias.per_cu = lds_workgroups_per_cu(pl.alias.lds, 16);
   }
   if (scheme == Scheme::spalias) pl.spalias.fn = reinterpret_cast<const void *>(spalias_wave_kernel);
+  if (scheme == Scheme::polyaurn_sparse) {             // a wave per word, four to a workgroup; the z kernel's LDS comes with the corpus
+    pl.wordlist = {reinterpret_cast<const void *>(word_list_build_kernel), kWordListBlock, 0, 8};
+    pl.pusparse.fn = reinterpret_cast<const void *>(polyaurn_sparse_wave_kernel);
+  }
   if (scheme == Scheme::lightpclda) {
     // the resident single-wave workgroups: what the kernel's registers allow (asked of the runtime) and what LDS allows, at
     // most the CU's 32 -- a lone wave issues at a fraction of a SIMD's rate, and the step is a chain of dependent operations
@@ -1084,7 +1102,7 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
 }
 
 const KernelLaunch &pcgs_entry(const LaunchPlan &pl, Scheme s, bool wave) {
-  return s == Scheme::lightpclda ? pl.lightpc : s == Scheme::spalias ? pl.spalias : wave ? pl.wave : pl.lane;
+  return s == Scheme::lightpclda ? pl.lightpc : s == Scheme::spalias ? pl.spalias : s == Scheme::polyaurn_sparse ? pl.pusparse : wave ? pl.wave : pl.lane;
 }
 int launch_pcgs_z(ggs_handle *h) {
   if (h->N == 0) return GGS_OK;
@@ -1094,13 +1112,18 @@ int launch_pcgs_z(ggs_handle *h) {
   pp.num_docs = h->pcgs_order_len; pp.tok_base = h->tok_base; pp.seed = h->seed; pp.iteration = (uint32_t)h->iteration;   // the length of the (padded) order list
   pp.K = h->K; pp.Kp = h->Kp;
   int rc;
-  if (h->alias_stale && (rc = launch_alias_build(h))) return rc;   // spalias, lightpclda
+  if (h->alias_stale && (rc = launch_alias_build(h))) return rc;   // spalias, lightpclda, polyaurn_sparse
   SpaliasParams sp{};
   LightpcParams lp{};
+  PolyaurnSparseParams ps{};
   void *args[] = {&pp, &h->margin_scale};              // the wave-per-document kernel takes both, the lane-per-document kernels the first
   if (h->scheme == Scheme::spalias) {                  // one wave per document over the non-zero topics (ggs_z_spalias.hpp)
     sp.b = pp; sp.ps = h->d_alias_ps; sp.a = h->d_alias_a; sp.type_norm = h->d_alias_tn; sp.cap = h->sp_cap; sp.margin_scale = h->margin_scale;
     args[0] = &sp;
+  } else if (h->scheme == Scheme::polyaurn_sparse) {   // one wave per document over the shorter of the word's and the document's list
+    ps.b = pp; ps.ps = h->d_alias_ps; ps.a = h->d_alias_a; ps.type_norm = h->d_alias_tn; ps.nzw = h->d_nzw; ps.nw = h->d_nw;
+    ps.stats = h->d_ps_stats; ps.cap = h->sp_cap; ps.margin_scale = h->margin_scale;
+    args[0] = &ps;
   } else if (h->scheme == Scheme::lightpclda) {        // one wave per document, two proposals per token (ggs_z_lightpc.hpp)
     lp.b = pp; lp.ps = h->d_alias_ps; lp.a = h->d_alias_a; lp.mh = h->d_mh; lp.alpha_sum = h->alpha_sum;
     args[0] = &lp;
@@ -1586,10 +1609,12 @@ int scheme_of(const ggs_config *cfg, Scheme &scheme, int32_t &poisson_L) {
   // not spalias: one z step per handle
   if ((f & GGS_FLAG_SPALIAS) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN))) return GGS_ERR_BAD_ARG;
   if ((f & GGS_FLAG_LIGHTPCLDA) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS))) return GGS_ERR_BAD_ARG;
-  scheme = (f & GGS_FLAG_LIGHTPCLDA) ? Scheme::lightpclda : (f & GGS_FLAG_SPALIAS) ? Scheme::spalias : (f & GGS_FLAG_POLYAURN) ? Scheme::polyaurn
+  // polyaurn_sparse is a scheme of its own: polyaurn's Phi under the doubly sparse step, none of the other z steps beside it
+  if ((f & GGS_FLAG_POLYAURN_SPARSE) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA))) return GGS_ERR_BAD_ARG;
+  scheme = (f & GGS_FLAG_POLYAURN_SPARSE) ? Scheme::polyaurn_sparse : (f & GGS_FLAG_LIGHTPCLDA) ? Scheme::lightpclda : (f & GGS_FLAG_SPALIAS) ? Scheme::spalias : (f & GGS_FLAG_POLYAURN) ? Scheme::polyaurn
          : (f & GGS_FLAG_COLLAPSED) ? Scheme::collapsed : (f & GGS_FLAG_PCGS) ? Scheme::pcgs : Scheme::ggs;
   poisson_L = cfg->alias_poisson_threshold == 0 ? 100 : cfg->alias_poisson_threshold;   // LDAConfiguration.java:44
-  if (scheme == Scheme::polyaurn && ((f & GGS_FLAG_COLLAPSED) || poisson_L < 1 || poisson_L > kPoissonMaxThreshold)) return GGS_ERR_BAD_ARG;
+  if (poisson_phi(scheme) && ((f & GGS_FLAG_COLLAPSED) || poisson_L < 1 || poisson_L > kPoissonMaxThreshold)) return GGS_ERR_BAD_ARG;
   if (has_alias(scheme) && cfg->num_topics > kPcgsWaveMaxTopics) return GGS_ERR_UNSUPPORTED;
   return GGS_OK;
 }
@@ -1686,7 +1711,13 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     return bail(GGS_ERR_HIP);
   if (has_alias(h->scheme) && ((rc = dev_alloc(h, &h->d_alias_ps, kv)) || (rc = dev_alloc(h, &h->d_alias_a, kv)) || (rc = dev_alloc(h, &h->d_alias_tn, (size_t)h->V)))) return bail(rc);
   if (h->scheme == Scheme::lightpclda && ((rc = dev_alloc(h, &h->d_mh, 3)) || hipMemset(h->d_mh, 0, 3 * sizeof(unsigned long long)) != hipSuccess)) return bail(rc ? rc : GGS_ERR_HIP);
-  if (h->scheme == Scheme::polyaurn) {
+  if (h->scheme == Scheme::polyaurn_sparse) {          // lists and counters start zeroed: no entry is ever read that the build did not write
+    if ((rc = dev_alloc(h, &h->d_nzw, kv)) || (rc = dev_alloc(h, &h->d_nw, (size_t)h->V)) || (rc = dev_alloc(h, &h->d_ps_stats, 4))) return bail(rc);
+    if (hipMemset(h->d_nzw, 0, kv * sizeof(uint16_t)) != hipSuccess || hipMemset(h->d_nw, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess ||
+        hipMemset(h->d_ps_stats, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
+      return bail(GGS_ERR_HIP);
+  }
+  if (poisson_phi(h->scheme)) {
     std::vector<double> T;
     build_poisson_table(h->beta, h->pa_L, T);
     h->pa_t00 = T[0];
@@ -1807,12 +1838,19 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
     if (h->pcgs_wave && !pl.wave.fn) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=pcgs: a document of 32768 tokens or more with more than 4096 topics");
     h->pcgs_z = pcgs_entry(pl, h->scheme, h->pcgs_wave);
     h->pcgs_items = (has_alias(h->scheme) || h->pcgs_wave) ? (int64_t)L.order.size() : ((int64_t)L.order.size() + 63) / 64;   // a wave or a lane per entry
-    if (h->scheme == Scheme::spalias) {
+    if (h->scheme == Scheme::spalias || h->scheme == Scheme::polyaurn_sparse) {
       // the list of a document's non-zero topics holds at most min(K, its length) entries; the resident waves are what LDS allows,
       // at most the CU's 32
       h->sp_cap = (int32_t)std::max<int64_t>(1, std::min<int64_t>(h->K, L.longest));
       h->pcgs_z.lds = (int)spalias_lds_bytes(h->K, h->sp_cap);
       h->pcgs_z.per_cu = lds_workgroups_per_cu(h->pcgs_z.lds, 32);
+      if (h->scheme == Scheme::polyaurn_sparse) {
+        // ... and what its registers allow (asked of the runtime): a workgroup of the persistent grid that is not resident
+        // would walk its share of the documents only after the others have finished theirs
+        int by_regs = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, h->pcgs_z.fn, 64, (size_t)h->pcgs_z.lds) != hipSuccess || by_regs < 1) by_regs = 1;
+        h->pcgs_z.per_cu = std::min(h->pcgs_z.per_cu, by_regs);
+      }
       if (const char *e = debug_env("GGS_DEBUG_SPALIAS_WPC")) h->pcgs_z.per_cu = std::max(1, std::min(h->pcgs_z.per_cu, std::atoi(e)));
     }
   }
@@ -1849,6 +1887,7 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   HIP_TRY(h, hipMemset(h->d_theta, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
   if (!pcgs) HIP_TRY(h, hipMemset(h->d_theta_next, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
   if (h->d_mh) HIP_TRY(h, hipMemset(h->d_mh, 0, 3 * sizeof(unsigned long long)));
+  if (h->d_ps_stats) HIP_TRY(h, hipMemset(h->d_ps_stats, 0, 4 * sizeof(unsigned long long)));
   HIP_TRY(h, hipDeviceSynchronize());   // the uploads and memsets above ran on the null stream; the handle's stream may not synchronise with it
 
   // 5. a new corpus: no Phi, no sweep in progress, the z form to be timed again
@@ -2381,7 +2420,7 @@ int ggs_get_alias_tables(ggs_handle *h, double *ps, int32_t *a, double *type_nor
   if (!h) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (!has_alias(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS or GGS_FLAG_LIGHTPCLDA");
+  if (!has_alias(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA or GGS_FLAG_POLYAURN_SPARSE");
   if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
   if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
   const size_t kv = (size_t)h->K * h->V;
@@ -2400,6 +2439,36 @@ int ggs_get_mh_stats(ggs_handle *h, int64_t out[3]) {
   HIP_TRY(h, hipMemcpyAsync(v, h->d_mh, sizeof(v), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   for (int i = 0; i < 3; ++i) out[i] = (int64_t)v[i];
+  return GGS_OK;
+}
+int ggs_get_word_topic_lists(ggs_handle *h, int32_t *nw, int32_t *topics) {
+  if (!h) return GGS_ERR_BAD_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (h->scheme != Scheme::polyaurn_sparse) return set_err(h, GGS_ERR_STATE, "ggs_get_word_topic_lists needs GGS_FLAG_POLYAURN_SPARSE");
+  if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
+  if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
+  const size_t kv = (size_t)h->K * h->V;
+  std::vector<int32_t> n((size_t)h->V);
+  std::vector<uint16_t> l(topics ? kv : 0);
+  HIP_TRY(h, hipMemcpyAsync(n.data(), h->d_nw, n.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (topics) HIP_TRY(h, hipMemcpyAsync(l.data(), h->d_nzw, kv * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (nw) std::copy(n.begin(), n.end(), nw);
+  if (topics)
+    for (int32_t w = 0; w < h->V; ++w)
+      for (int32_t i = 0; i < h->K; ++i) topics[(size_t)w * h->K + i] = i < n[(size_t)w] ? (int32_t)l[(size_t)w * h->K + i] : -1;
+  return GGS_OK;
+}
+int ggs_get_sparse_stats(ggs_handle *h, int64_t out[4]) {
+  if (!h || !out) return GGS_ERR_BAD_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (h->scheme != Scheme::polyaurn_sparse) return set_err(h, GGS_ERR_STATE, "ggs_get_sparse_stats needs GGS_FLAG_POLYAURN_SPARSE");
+  unsigned long long v[4];
+  HIP_TRY(h, hipMemcpyAsync(v, h->d_ps_stats, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int i = 0; i < 4; ++i) out[i] = (int64_t)v[i];
   return GGS_OK;
 }
 int ggs_get_phi_mean(ggs_handle *h, double *phi_mean, int32_t *n_sampled) {
@@ -2718,7 +2787,7 @@ int ggs_get_warm_tiers(ggs_handle *h, int32_t *tiers, int32_t *warm_words, int32
 int ggs_get_z_form(ggs_handle *h, int32_t *kernel, int32_t *form, int32_t *calibrated) {
   if (!h) return GGS_ERR_BAD_ARG;
   const bool splittable = h->plan.sliced() && h->Cs > h->Cc && h->Cc > 0;
-  if (kernel) *kernel = h->scheme == Scheme::lightpclda ? 7 : h->scheme == Scheme::spalias ? 6 : pcgs_family(h->scheme) ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
+  if (kernel) *kernel = h->scheme == Scheme::polyaurn_sparse ? 8 : h->scheme == Scheme::lightpclda ? 7 : h->scheme == Scheme::spalias ? 6 : pcgs_family(h->scheme) ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
   if (form) *form = h->plan.sliced() ? (splittable && h->z_split ? 1 : 2) : 0;
   if (calibrated) *calibrated = (splittable && h->z_split_tried && !h->plan.split_forced && h->plan.split) ? 1 : 0;
   return GGS_OK;

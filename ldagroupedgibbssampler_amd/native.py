@@ -9,6 +9,7 @@ OK = 0
 ERR_NEGATIVE_COUNT, ERR_INVALID_TOPIC, ERR_RNG_EXHAUSTED, ERR_BAD_ARG = 1, 2, 3, 4
 ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_INVARIANT = 5, 6, 7, 8
 FLAG_PARANOID, FLAG_SAVE_PHI_MEAN, FLAG_PCGS, FLAG_COLLAPSED, FLAG_POLYAURN, FLAG_SPALIAS, FLAG_LIGHTPCLDA = 1, 2, 4, 8, 16, 32, 64
+FLAG_POLYAURN_SPARSE = 128
 PURPOSE_Z, PURPOSE_THETA, PURPOSE_PHI, PURPOSE_INIT_PHI = 1, 2, 3, 4
 
 
@@ -52,7 +53,7 @@ def _make_config(num_topics, num_types, alpha, beta, seed, device_id, flags, phi
     cfg.beta = float(beta)
     cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     cfg.flags, cfg.phi_burn_in, cfg.phi_mean_thin = int(flags), int(phi_burn_in), int(phi_mean_thin)
-    cfg.alias_poisson_threshold = int(alias_poisson_threshold)      # FLAG_POLYAURN only; 0 = the default 100
+    cfg.alias_poisson_threshold = int(alias_poisson_threshold)      # FLAG_POLYAURN, FLAG_POLYAURN_SPARSE only; 0 = the default 100
     return cfg, keep
 
 
@@ -256,7 +257,7 @@ class GGSHandle:
         return (out, n.value) if n.value else (None, 0)
 
     def alias_tables(self):
-        """scheme=spalias or lightpclda: the alias tables of the current Phi, (ps [V][K], a [V][K], type_norm [V])."""
+        """scheme=spalias, lightpclda or polyaurn_sparse: the alias tables of the current Phi, (ps [V][K], a [V][K], type_norm [V])."""
         ps, a, tn = np.empty((self.V, self.K), np.float64), np.empty((self.V, self.K), np.int32), np.empty(self.V, np.float64)
         self._chk(self._L.ggs_get_alias_tables(self._h, _dp(ps), _ip(a), _dp(tn)))
         return ps, a, tn
@@ -266,6 +267,20 @@ class GGSHandle:
         tokens left on their old topic, cumulative since set_corpus (int64 [3]; they sum to the tokens sampled)."""
         out = np.zeros(3, np.int64)
         self._chk(self._L.ggs_get_mh_stats(self._h, _lp(out)))
+        return out
+
+    def word_topic_lists(self):
+        """scheme=polyaurn_sparse: (nw [V], topics [V][K]) of the current Phi -- per word the number of topics with
+        phi[k][w] != 0 and those topics in ascending order, -1 behind them."""
+        nw, topics = np.empty(self.V, np.int32), np.empty((self.V, self.K), np.int32)
+        self._chk(self._L.ggs_get_word_topic_lists(self._h, _ip(nw), _ip(topics)))
+        return nw, topics
+
+    def sparse_stats(self):
+        """scheme=polyaurn_sparse: tokens that walked the word's list, the document's list, tokens drawn uniformly (no
+        candidate) and the sum of the candidates' number over all tokens, cumulative since set_corpus (int64 [4])."""
+        out = np.zeros(4, np.int64)
+        self._chk(self._L.ggs_get_sparse_stats(self._h, _lp(out)))
         return out
 
     def get_theta(self, doc_begin=0, doc_end=None):
@@ -336,7 +351,8 @@ class GGSHandle:
 
 Z_KERNEL_NAMES = {0: "z_kernel (whole-row tiles)", 1: "z_sliced_kernel + z_hot_kernel (score registers)", 2: "z_stream1_kernel (one pass)",
                   3: "z_stream_kernel (two passes)", 4: "pcgs_sliced_kernel (lane per document)", 5: "pcgs_wave_kernel (wave per document)",
-                  6: "spalias_wave_kernel (wave per document)", 7: "lightpc_wave_kernel (wave per document)"}
+                  6: "spalias_wave_kernel (wave per document)", 7: "lightpc_wave_kernel (wave per document)",
+                  8: "polyaurn_sparse_wave_kernel (wave per document)"}
 
 
 class GGSGroup:

@@ -37,7 +37,7 @@ class SimpleLDAConfiguration:
         self.save_phi_mean = bool(kw.pop("save_phi_mean", False))    # SAVE_PHI_MEAN_DEFAULT
         self.phi_mean_burnin = int(kw.pop("phi_mean_burnin", 0))     # percent of iterations, PHI_BURN_IN_DEFAULT
         self.phi_mean_thin = int(kw.pop("phi_mean_thin", 1))         # PHI_THIN_DEFAULT
-        self.alias_poisson_threshold = int(kw.pop("alias_poisson_threshold", 100))   # ALIAS_POISSON_DEFAULT_THRESHOLD; scheme=polyaurn only
+        self.alias_poisson_threshold = int(kw.pop("alias_poisson_threshold", 100))   # ALIAS_POISSON_DEFAULT_THRESHOLD; scheme=polyaurn and polyaurn_sparse only
         self.paranoid = bool(kw.pop("paranoid", False))              # run the UPLDA:299-338 invariants every sweep
         self.device_id = int(kw.pop("device_id", 0))                 # optional gpu_* key; default first visible GPU
         # the diagnostics of the sampling loop (UPLDA:695-905), computed on the device and written in the Java driver's formats
@@ -435,6 +435,29 @@ class LightPCLDA(LDAPartiallyCollapsedGibbsSampler):
         return self._h.mh_stats()
 
 
+class PolyaUrnSparseLDA(LDAPartiallyCollapsedGibbsSampler):
+    """scheme=polyaurn_sparse (the sampler topics/PolyaUrnSpaliasLDA.java builds, sampleTopicAssignmentsParallel :180-334):
+    polyaurn's model -- Phi drawn as Poisson counts with exact zeros, config key alias_poisson_threshold -- with the doubly
+    sparse z step: the alias table of the word for alpha_k * phi[k][w], and n_dk * phi[k][w] walked over the shorter of the
+    word's list of non-zero topics and the document's: O(min(nnz_w, nnz_d)) per token."""
+    _scheme_flags = native.FLAG_POLYAURN_SPARSE
+
+    def getTheta(self):
+        raise NotImplementedError("scheme=polyaurn_sparse never draws theta; use getThetaEstimate() (UPLDA:716-720 does the same)")
+
+    def getAliasTables(self):
+        """(ps [V][K], a [V][K], typeNorm [V]) of the current Phi"""
+        return self._h.alias_tables()
+
+    def getWordTopicLists(self):
+        """(nw [V], topics [V][K]): per word the topics with phi != 0 in ascending order, -1 behind them"""
+        return self._h.word_topic_lists()
+
+    def getSparseStats(self):
+        """tokens that walked the word's list, the document's list, tokens drawn uniformly, the sum of candidates (cumulative)"""
+        return self._h.sparse_stats()
+
+
 class SerialCollapsedLDA(LDAGroupedGibbsSampler):
     """scheme=collapsed (topics/SerialCollapsedLDA.java; the conditional it samples from is sampleTopicsForOneDoc,
     MSLDA:158-226).  `schedule`:
@@ -471,7 +494,7 @@ class SerialCollapsedLDA(LDAGroupedGibbsSampler):
 
 def create_model(config, scheme=None):
     """The `case "ggs"` / `case "pcgs"` / `case "collapsed"` / `case "polyaurn"` / `case "spalias"` / `case "lightpclda"` of tui/ParallelLDA.createModel
-    (ParallelLDA.java:401-490)."""
+    (ParallelLDA.java:401-490); "polyaurn_sparse" is this build's name for polyaurn over the sparse z step the reference's class holds."""
     scheme = scheme or config.scheme
     if scheme == "ggs":
         return LDAGroupedGibbsSampler(config)
@@ -485,4 +508,6 @@ def create_model(config, scheme=None):
         return SpaliasUncollapsedParallelLDA(config)
     if scheme == "lightpclda":
         return LightPCLDA(config)
-    raise ValueError("scheme %r is not provided by this build (only the ggs, pcgs, collapsed, polyaurn, spalias and lightpclda z loops are in scope)" % scheme)
+    if scheme == "polyaurn_sparse":
+        return PolyaUrnSparseLDA(config)
+    raise ValueError("scheme %r is not provided by this build (only the ggs, pcgs, collapsed, polyaurn, spalias, lightpclda and polyaurn_sparse z loops are in scope)" % scheme)

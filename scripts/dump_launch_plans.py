@@ -2,8 +2,8 @@
 """Which kernels a handle launches, with how much LDS, for every kernel family: one line per (K, scheme) with what
 ggs_get_z_form, ggs_get_launch_info, ggs_get_z_parts, ggs_get_warm_tiers and ggs_get_num_hot_words answer after one
 seeded corpus is set (or the error code where the combination is unsupported).  A row describes the z step the handle
-launches: for the pcgs family lds_bytes_z is the dynamic LDS of the lane-per-document, wave-per-document, spalias or
-lightpclda kernel and num_chunks the entries of the document order it strides (groups of 64 for the lane-per-document
+launches: for the pcgs family lds_bytes_z is the dynamic LDS of the lane-per-document, wave-per-document, spalias,
+lightpclda or polyaurn_sparse kernel and num_chunks the entries of the document order it strides (groups of 64 for the lane-per-document
 kernel).  Two builds of the library that make the same launches print the same text: run it before and after a change of the host code (GGS_HIP_LIB selects the library)
 and compare.  usage: python scripts/dump_launch_plans.py [--out FILE]"""
 import argparse
@@ -19,7 +19,7 @@ from ldagroupedgibbssampler_amd.corpus import zipf_unigram_corpus  # noqa: E402
 
 TOPICS = (8, 20, 100, 160, 161, 176, 192, 200, 256, 512, 1024, 2048, 4096)
 SCHEMES = {"ggs": 0, "pcgs": native.FLAG_PCGS, "collapsed": native.FLAG_COLLAPSED, "polyaurn": native.FLAG_POLYAURN, "spalias": native.FLAG_SPALIAS,
-           "lightpclda": native.FLAG_LIGHTPCLDA}
+           "lightpclda": native.FLAG_LIGHTPCLDA, "polyaurn_sparse": native.FLAG_POLYAURN_SPARSE}
 
 
 def main():
