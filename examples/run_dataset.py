@@ -21,7 +21,9 @@ def main():
     ap.add_argument("dataset")
     ap.add_argument("--stoplist", default=None, help="one stop word per line (LDAConfiguration: stoplist.txt)")
     ap.add_argument("--rare-threshold", type=int, default=0)
-    ap.add_argument("--scheme", default="ggs", choices=["ggs", "pcgs", "collapsed", "polyaurn", "spalias", "lightpclda", "polyaurn_sparse"])
+    ap.add_argument("--scheme", default="ggs", choices=["ggs", "pcgs", "collapsed", "polyaurn", "spalias", "spalias_priors", "lightpclda", "polyaurn_sparse"])
+    ap.add_argument("--topic-priors", default=None, metavar="FILE",
+                    help="scheme spalias_priors: lines `topic,word,word,...`; those words may only belong to that topic (topic_prior_filename)")
     ap.add_argument("--topics", type=int, default=20)
     ap.add_argument("--alpha", type=float, default=0.1)
     ap.add_argument("--beta", type=float, default=0.01)
@@ -30,6 +32,8 @@ def main():
     ap.add_argument("--top-words", type=int, default=8)
     ap.add_argument("--out", default=None, help="directory for the driver's files (phi / theta / counts / likelihood)")
     args = ap.parse_args()
+    if args.topic_priors and args.scheme != "spalias_priors":
+        ap.error("--topic-priors belongs to --scheme spalias_priors")
 
     from ldagroupedgibbssampler_amd import formats as F
     from ldagroupedgibbssampler_amd.frontend import load_dataset
@@ -41,7 +45,8 @@ def main():
     if args.out:
         os.makedirs(args.out, exist_ok=True)
     cfg = SimpleLDAConfiguration(scheme=args.scheme, topics=args.topics, alpha=args.alpha, beta=args.beta, iterations=args.iterations,
-                                 seed=args.seed, exec_time=None, compute_likelihood=bool(args.out), log_dir=args.out)
+                                 seed=args.seed, exec_time=None, compute_likelihood=bool(args.out), log_dir=args.out,
+                                 topic_prior_filename=args.topic_priors)
     model = create_model(cfg)
     model.setRandomSeed(cfg.get_seed())
     model.addInstances(c)

@@ -418,6 +418,30 @@ int ggs_debug_alias(int32_t device_id, int32_t V, int32_t K, const double *phi, 
 /* the tables of the handle's current Phi (GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA or GGS_FLAG_POLYAURN_SPARSE; GGS_ERR_STATE
  * otherwise or before the first Phi); any of the three outputs may be null */
 int ggs_get_alias_tables(ggs_handle *h, double *ps /*[V][K]*/, int32_t *a /*[V][K]*/, double *type_norm /*[V]*/);
+/* scheme=spalias_priors (SpaliasUncollapsedParallelWithPriors, ParallelLDA.java:464-468; LDASamplerWithPriors): topic priors,
+ * "anchor words".  No flag of its own and no new ABI version: a GGS_FLAG_SPALIAS handle on which ggs_set_topic_priors has been
+ * called (any other handle: GGS_ERR_STATE).  Without the call a spalias handle plans, allocates and launches exactly what it did
+ * before; everything the priors need is planned and allocated by the call.
+ *   ggs_set_topic_priors  the n_zero cells (topic[i], word[i]) get prior 0.0, every other cell 1.0.  Duplicates are allowed,
+ *       n_zero == 0 too ("a priors file that names nothing": the conditional draw below over an all-ones matrix, NOT bit-equal to
+ *       plain spalias, as in the reference whenever a file is named).  Legal before or after ggs_set_corpus but only while the
+ *       handle has no Phi (before ggs_init_phi, ggs_set_z with redraw, ggs_set_phi: afterwards GGS_ERR_STATE); a later call
+ *       replaces an earlier one.  GGS_ERR_BAD_ARG, the handle left as it was: a topic or word out of range, a topic with all V
+ *       words zero, a word with all K topics zero (ensureConsistentPriors).  With an exchange attached every rank makes the
+ *       same call; it is not a collective.  On the device the priors are one bit per (word, topic).
+ *   ggs_get_topic_priors  getTopicPriors: priors[k][v] = 1.0 or 0.0; all 1.0 when none were set.
+ * With priors set:
+ *   the initial Phi (ggs_init_phi, ggs_set_z with redraw) is the usual draw, run to its end, then phi[k][v] *= prior[k][v]; rows
+ *       are not renormalised;
+ *   the Phi of a sweep is the conditional draw over each topic's allowed words (ConditionalDirichlet.nextConditionalDistribution):
+ *       g = Gamma(shape) on the Philox stream of element k*V + v as ever (a zeroed cell's stream is not used), g <= 0 -> 0.0001,
+ *       sum_gamma and sum_phi (of the OLD row) in index order, phi[k][v] = (g / sum_gamma) * sum_phi; zeroed cells stay +0.0.  Rows
+ *       therefore keep the mass their allowed words had in the initial draw;
+ *   the z step is spalias's, unchanged: the reference's factor prior[k][w] on the list scores has the bits of the product without
+ *       it as long as Phi is exactly 0 wherever the prior is.  So that nothing can break that, ggs_set_phi returns
+ *       GGS_ERR_BAD_ARG for a Phi with a non-zero value in a zeroed cell (our decision: the reference copies the matrix). */
+int ggs_set_topic_priors(ggs_handle *h, int64_t n_zero, const int32_t *topic, const int32_t *word);
+int ggs_get_topic_priors(ggs_handle *h, double *priors /*[K][V]*/);
 /* scheme=lightpclda's Metropolis-Hastings counters, cumulative since ggs_set_corpus (the three the reference keeps
  * commented out, LightPCLDA.java:28-44), every token in exactly one: out[0] tokens whose word proposal was accepted and
  * kept, out[1] tokens whose document proposal was accepted, out[2] tokens left on their old topic.  GGS_ERR_STATE

@@ -137,6 +137,8 @@ SIGNATURES = {
     "ggs_debug_poisson": (C.c_int, [C.c_int32, C.c_double, C.c_int32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int64, _ip, _ip]),
     "ggs_debug_alias": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _ip, _dp]),
     "ggs_get_alias_tables": (C.c_int, [_vp, _dp, _ip, _dp]),
+    "ggs_set_topic_priors": (C.c_int, [_vp, C.c_int64, _ip, _ip]),
+    "ggs_get_topic_priors": (C.c_int, [_vp, _dp]),
     "ggs_get_mh_stats": (C.c_int, [_vp, _lp]),
     "ggs_get_word_topic_lists": (C.c_int, [_vp, _ip, _ip]),
     "ggs_get_sparse_stats": (C.c_int, [_vp, _lp]),

@@ -170,6 +170,13 @@ struct ggs_handle {
   double *d_alias_ps = nullptr, *d_alias_tn = nullptr; // [V][K], [V]
   int32_t *d_alias_a = nullptr;                        // [V][K]
   int32_t sp_cap = 0;                                  // of the current corpus: entries of a document's list of non-zero topics
+  // topic priors (ggs_set_topic_priors, spalias only): everything here is planned and allocated by that call
+  bool have_priors = false;
+  int32_t pr_pitch = 0;                                // uint32 words per vocabulary row of the bit mask: ceil(K / 32)
+  std::vector<uint32_t> pr_mask;                       // [V][pr_pitch], bit k & 31 of word k >> 5 set = cell (k, v) is zero (the host's copy: ggs_set_phi's check)
+  uint32_t *d_pr_mask = nullptr;
+  double *d_pr_sum_phi = nullptr;                      // [K] index-order column sums of the old phiT (sum_phi of the conditional draw)
+  double *d_pr_pref = nullptr, *d_pr_fn = nullptr;     // that sum's own guess and segment functions: d_sum_pref stays the magnitudes'
   // scheme=lightpclda (ggs_z_lightpc.hpp): the pcgs model and spalias's tables, a Metropolis-Hastings z step
   double alpha_sum = 0;                                // the k-order sum of alpha
   unsigned long long *d_mh = nullptr;                  // [3]: ggs_get_mh_stats, zeroed by ggs_set_corpus
@@ -473,14 +480,15 @@ int launch_count_hot(ggs_handle *h) {
 // magnitude sum over the same buffer); otherwise two extra launches make one.  The walk leaves the exact running
 // sums there (write_pref): the next sweep's guess, and this sweep's guess for the sum of the gammas.
 template <typename T, bool MAGNITUDE>
-void launch_column_sum(ggs_handle *h, const T *src, int32_t pitch, int32_t Ks, double *out, int32_t *n_k, bool guided, bool write_pref) {
+void launch_column_sum(ggs_handle *h, const T *src, int32_t pitch, int32_t Ks, double *out, int32_t *n_k, bool guided, bool write_pref,
+                       double *guess = nullptr, double *fn = nullptr) {   // work space other than the handle's d_sum_pref / d_sum_fn
   if (Ks <= 0) return;
   if (!h->exact_sum) {
     hipLaunchKernelGGL((column_chain_kernel<T, MAGNITUDE>), dim3((Ks + 7) / 8), dim3(256), 0, h->stream, src, pitch, Ks, h->V, h->beta, out);
     return;
   }
   SumParams sp{};
-  sp.src = src; sp.guess = h->d_sum_pref; sp.fn = h->d_sum_fn; sp.out = out; sp.beta = h->beta; sp.n_k = n_k;
+  sp.src = src; sp.guess = guess ? guess : h->d_sum_pref; sp.fn = fn ? fn : h->d_sum_fn; sp.out = out; sp.beta = h->beta; sp.n_k = n_k;
   sp.pitch = pitch; sp.K = Ks; sp.V = h->V; sp.nseg = h->sum_nseg; sp.write_pref = write_pref ? 1 : 0;
   const dim3 rows((unsigned)h->sum_nseg, (unsigned)((Ks + kSumBlock - 1) / kSumBlock));
   if (!guided) {
@@ -634,6 +642,25 @@ int launch_magnitude(ggs_handle *h) {
   return GGS_OK;
 }
 
+// Topic priors (ggs_set_topic_priors).  The sweep draw is then the CONDITIONAL one (conditional_phi): the masked gamma draw, and
+// (g / sum_gamma) * sum_phi in place of the division and its clamp.  sum_phi[k], the index-order sum of the OLD phi row (masked
+// cells are +0.0 and leave the running sum as it is), is an exact column sum of phiT over all K topics -- every rank of an exchange
+// holds the whole old phiT and sums it for itself -- taken before anything overwrites phiT, unguided, in work space of its own.
+// The initial draw runs to its end as ever and is then multiplied by the priors (phi_apply_priors).
+bool conditional_phi(const ggs_handle *h, bool initial) { return h->have_priors && !initial; }
+int launch_sum_phi(ggs_handle *h) {
+  launch_column_sum<double, false>(h, h->d_phiT, h->Kp, h->K, h->d_pr_sum_phi, nullptr, false, false, h->d_pr_pref, h->d_pr_fn);
+  HIP_TRY(h, hipGetLastError());
+  return GGS_OK;
+}
+int phi_apply_priors(ggs_handle *h) {
+  hipLaunchKernelGGL(phi_apply_priors_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, h->d_phiT, h->d_pr_mask, h->pr_pitch, h->K,
+                     h->Kp, h->V, h->d_phiT32, h->plan.Kp32);
+  HIP_TRY(h, hipGetLastError());
+  h->alias_stale = true;
+  return GGS_OK;
+}
+
 // Phi draw: initial (K8) or per sweep (K6) for the topics [k0, k0 + Ks) from their corpus-wide counts
 // cnt [V][cnt_pitch]; rows into out [V][out_pitch].  In steps, so that the exchange can slot its collectives in:
 //   phi_slice_magnitude   the Dirichlet magnitudes (and tokensPerTopic)
@@ -667,7 +694,13 @@ int phi_slice_gamma(ggs_handle *h, bool initial, const int32_t *cnt, int32_t cnt
   gp.guess = h->exact_sum ? h->d_sum_pref : nullptr; gp.fn = h->d_sum_fn;
   const int64_t tiles = (int64_t)(seg1 - seg0) * gp.ncg;
   // single-wave workgroups; a grid of at most 32 per CU, the rest by striding
-  hipLaunchKernelGGL(phi_gamma_kernel, dim3((unsigned)std::min<int64_t>(tiles, (int64_t)h->num_cus * 32)), dim3(64), 0, h->stream, gp);
+  const dim3 grid((unsigned)std::min<int64_t>(tiles, (int64_t)h->num_cus * 32));
+  if (conditional_phi(h, initial)) {                   // the masked draw; its sums' guess is still the magnitudes' (any guess will do)
+    gp.zero_mask = h->d_pr_mask; gp.mask_pitch = h->pr_pitch;
+    hipLaunchKernelGGL(phi_gamma_kernel<true>, grid, dim3(64), 0, h->stream, gp);
+  } else {
+    hipLaunchKernelGGL(phi_gamma_kernel<false>, grid, dim3(64), 0, h->stream, gp);
+  }
   HIP_TRY(h, hipGetLastError());
   return GGS_OK;
 }
@@ -729,8 +762,12 @@ int launch_phi_slice(ggs_handle *h, bool initial, const int32_t *cnt, int32_t cn
   if ((rc = launch_magnitude_on(h, cnt, cnt_pitch, Ks, mag, n_k)) || (rc = phi_slice_gamma(h, initial, cnt, cnt_pitch, Ks, k0, out, out_pitch, mag, 0, h->sum_nseg)) ||
       (rc = phi_slice_total(h, out, out_pitch, Ks, tot)))
     return rc;
-  hipLaunchKernelGGL(phi_normalise_kernel, dim3(grid_for((int64_t)Ks * h->V, 256, 2)), dim3(256), 0, h->stream, out, tot, Ks, out_pitch, h->V, phi_mean,
-                     out == h->d_phiT ? h->d_phiT32 : nullptr, h->plan.Kp32);
+  if (conditional_phi(h, initial))                     // one GPU: the slice is the whole matrix, sum_phi's columns are its columns
+    hipLaunchKernelGGL(phi_normalise_conditional_kernel, dim3(grid_for((int64_t)Ks * h->V, 256, 2)), dim3(256), 0, h->stream, out, tot, h->d_pr_sum_phi, Ks,
+                       out_pitch, h->V, phi_mean, out == h->d_phiT ? h->d_phiT32 : nullptr, h->plan.Kp32);
+  else
+    hipLaunchKernelGGL(phi_normalise_kernel, dim3(grid_for((int64_t)Ks * h->V, 256, 2)), dim3(256), 0, h->stream, out, tot, Ks, out_pitch, h->V, phi_mean,
+                       out == h->d_phiT ? h->d_phiT32 : nullptr, h->plan.Kp32);
   HIP_TRY(h, hipGetLastError());
   return GGS_OK;
 }
@@ -754,6 +791,7 @@ int phi_step_a(ggs_handle *h) { return exchange_reduce_scatter(h); }
 int phi_step_a_clear(ggs_handle *h) { return h->seg_split > 0 ? GGS_OK : clear_send_buffer_if_dead(h, h->stream); }
 int phi_step_b1(ggs_handle *h, bool initial) {
   int rc;
+  if (conditional_phi(h, initial) && (rc = launch_sum_phi(h))) return rc;   // phiT is the old Phi until step C
   if (poisson_phi(h->scheme)) {   // the Poisson draws of the first half (and the totals' zero fill)
     if ((rc = phi_slice_poisson(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, 0, h->seg_split, true))) return rc;
   } else if ((rc = launch_magnitude_on(h, h->d_cnt_own, h->Ksm, h->Ks, h->d_mag_own, h->d_n_k_own))) {
@@ -792,17 +830,19 @@ int phi_join_halves(ggs_handle *h) {                   // the main stream goes o
   if (h->seg_split > 0) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_half_gathered, 0));
   return GGS_OK;
 }
-int phi_step_c(ggs_handle *h, bool accumulate_mean) {
+int phi_step_c(ggs_handle *h, bool initial, bool accumulate_mean) {
   PhiRepackParams rp{};
   rp.all0 = h->d_phi_all0; rp.all1 = h->d_phi_all1; rp.krank = h->d_krank; rp.kcol = h->d_kcol; rp.phiT = h->d_phiT;
   rp.phi_mean = accumulate_mean ? h->d_phi_mean : nullptr;
   rp.c0 = (int64_t)half0_elems(h); rp.c1 = (int64_t)half1_elems(h); rp.K = h->K; rp.Kp = h->Kp; rp.V = h->V; rp.Ksm = h->Ksm; rp.v_split = h->v_split;
-  rp.phiT32 = h->d_phiT32; rp.Kp32 = h->plan.Kp32;
+  rp.phiT32 = h->d_phiT32; rp.Kp32 = h->plan.Kp32; rp.sum_phi = h->d_pr_sum_phi;
   if (poisson_phi(h->scheme)) hipLaunchKernelGGL(phi_repack_polyaurn_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
+  else if (conditional_phi(h, initial)) hipLaunchKernelGGL(phi_repack_conditional_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   else hipLaunchKernelGGL(phi_repack_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   HIP_TRY(h, hipGetLastError());
   h->have_phi = true;
   h->alias_stale = true;
+  if (h->have_priors && initial) return phi_apply_priors(h);
   return GGS_OK;
 }
 
@@ -840,13 +880,15 @@ int launch_phi(ggs_handle *h, bool initial, bool accumulate_mean, Events *E = nu
     // on different streams at once (they could not share the links anyway), whatever the transport does about that itself
     if ((rc = phi_join_halves(h)) || (rc = phi_step_g1(h))) return rc;
     if (E) HIP_TRY(h, hipEventRecord(E->x[2], h->stream));
-    if ((rc = phi_step_c(h, accumulate_mean))) return rc;
+    if ((rc = phi_step_c(h, initial, accumulate_mean))) return rc;
     return launch_alias_build(h);
   }
+  if (conditional_phi(h, initial) && (rc = launch_sum_phi(h))) return rc;   // before the draw overwrites phiT
   if ((rc = launch_phi_slice(h, initial, h->d_n_wk, h->K, h->K, 0, h->d_phiT, h->Kp, h->d_mag, h->d_tot, h->d_n_k, accumulate_mean ? h->d_phi_mean : nullptr)))
     return rc;
   h->n_k_valid = true;
   h->have_phi = true;
+  if (h->have_priors && initial && (rc = phi_apply_priors(h))) return rc;
   return launch_alias_build(h);
 }
 
@@ -2212,7 +2254,7 @@ int group_phi(ggs_handle **hs, int32_t n, bool initial, bool in_sweep) {
     return rc;
   for (int32_t i = 0; i < n; ++i) {
     ggs_handle *h = hs[i];
-    if ((rc = bind_device(h)) || (rc = phi_step_c(h, acc[(size_t)i] != 0)) || (rc = launch_alias_build(h))) return rc;
+    if ((rc = bind_device(h)) || (rc = phi_step_c(h, initial, acc[(size_t)i] != 0)) || (rc = launch_alias_build(h))) return rc;
     if (in_sweep) {
       HIP_TRY(h, hipEventRecord(h->evs[h->ev_head].e[5], h->stream));
       if (acc[(size_t)i]) h->n_sampled_phi++;
@@ -2402,6 +2444,13 @@ int ggs_set_phi(ggs_handle *h, const double *phi) {
   int rc = bind_device(h);
   if (rc) return rc;
   const size_t kv = (size_t)h->K * h->V;
+  if (h->have_priors) {   // the z step leaves the prior factor out because Phi is exactly zero wherever the prior is (ggs_hip.h)
+    for (int32_t v = 0; v < h->V; ++v)
+      for (int32_t j = 0; j < h->pr_pitch; ++j)
+        for (uint32_t bits = h->pr_mask[(size_t)v * h->pr_pitch + j]; bits; bits &= bits - 1)
+          if (phi[(size_t)(j * 32 + __builtin_ctz(bits)) * h->V + v] != 0.0)
+            return set_err(h, GGS_ERR_BAD_ARG, "ggs_set_phi: phi is not zero in a cell the topic priors zero");
+  }
   if ((rc = ensure_scratch(h, kv * sizeof(double)))) return rc;
   HIP_TRY(h, hipMemcpyAsync(h->d_scratch, phi, kv * sizeof(double), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(phi_to_phiT_kernel, dim3(grid_for((int64_t)kv, 256)), dim3(256), 0, h->stream, static_cast<const double *>(h->d_scratch),
@@ -2413,6 +2462,57 @@ int ggs_set_phi(ggs_handle *h, const double *phi) {
   if ((rc = launch_alias_build(h))) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->have_phi = true;
+  return GGS_OK;
+}
+
+int ggs_set_topic_priors(ggs_handle *h, int64_t n_zero, const int32_t *topic, const int32_t *word) {
+  if (!h) return GGS_ERR_BAD_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (h->scheme != Scheme::spalias) return set_err(h, GGS_ERR_STATE, "ggs_set_topic_priors needs GGS_FLAG_SPALIAS");
+  if (h->have_phi) return set_err(h, GGS_ERR_STATE, "ggs_set_topic_priors: the handle already has a Phi");
+  if (n_zero < 0 || (n_zero > 0 && (!topic || !word))) return set_err(h, GGS_ERR_BAD_ARG, "bad topic prior arguments");
+  // 1. validate into a mask of its own: a refused call leaves the handle as it was
+  const int32_t pitch = (h->K + 31) / 32;
+  std::vector<uint32_t> mask((size_t)h->V * pitch, 0u);
+  std::vector<int32_t> per_topic((size_t)h->K, 0), per_word((size_t)h->V, 0);
+  for (int64_t i = 0; i < n_zero; ++i) {
+    const int32_t k = topic[i], v = word[i];
+    if (k < 0 || k >= h->K || v < 0 || v >= h->V) return set_err(h, GGS_ERR_BAD_ARG, "topic prior cell outside [0, num_topics) x [0, num_types)");
+    uint32_t &m = mask[(size_t)v * pitch + (k >> 5)];
+    if (m & (1u << (k & 31))) continue;                // duplicates are allowed
+    m |= 1u << (k & 31);
+    per_topic[(size_t)k] += 1; per_word[(size_t)v] += 1;
+  }
+  // ensureConsistentPriors, SpaliasUncollapsedParallelWithPriors.java:102-121
+  for (int32_t k = 0; k < h->K; ++k)
+    if (per_topic[(size_t)k] == h->V) return set_err(h, GGS_ERR_BAD_ARG, "Inconsistent prior spec, one topic has all Zero priors!");
+  for (int32_t v = 0; v < h->V; ++v)
+    if (per_word[(size_t)v] == h->K) return set_err(h, GGS_ERR_BAD_ARG, "Inconsistent prior spec, word " + std::to_string(v) + " has all Zero priors!");
+  // 2. what the conditional Phi phase needs
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if ((rc = upload(h, &h->d_pr_mask, mask)) || (rc = dev_alloc(h, &h->d_pr_sum_phi, (size_t)h->K))) return rc;
+  if (h->exact_sum && ((rc = dev_alloc(h, &h->d_pr_pref, ((size_t)h->sum_nseg + 1) * h->K)) || (rc = dev_alloc(h, &h->d_pr_fn, (size_t)h->sum_nseg * h->K * 4))))
+    return rc;
+  h->pr_mask.swap(mask);
+  h->pr_pitch = pitch;
+  h->have_priors = true;
+  return GGS_OK;
+}
+
+int ggs_get_topic_priors(ggs_handle *h, double *priors) {
+  if (!h || !priors) return GGS_ERR_BAD_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (h->scheme != Scheme::spalias) return set_err(h, GGS_ERR_STATE, "ggs_get_topic_priors needs GGS_FLAG_SPALIAS");
+  std::fill(priors, priors + (size_t)h->K * h->V, 1.0);
+  if (!h->have_priors) return GGS_OK;
+  std::vector<uint32_t> mask((size_t)h->V * h->pr_pitch);       // the mask the kernels read
+  if ((rc = copy_out(h, mask.data(), h->d_pr_mask, mask.size() * sizeof(uint32_t)))) return rc;
+  for (int32_t v = 0; v < h->V; ++v)
+    for (int32_t j = 0; j < h->pr_pitch; ++j)
+      for (uint32_t bits = mask[(size_t)v * h->pr_pitch + j]; bits; bits &= bits - 1)
+        priors[(size_t)(j * 32 + __builtin_ctz(bits)) * h->V + v] = 0.0;
   return GGS_OK;
 }
 

@@ -461,7 +461,12 @@ struct PhiGammaParams {
   // guess = the EXACT running magnitude sums [nseg + 1][K] (E Gamma(a) = a).  Null: not wanted.
   const double *guess;
   double *fn;          // [nseg][K][4]
+  // topic priors (phi_gamma_kernel<true> only): bit (k0 + k) & 31 of zero_mask[v * mask_pitch + ((k0 + k) >> 5)] set = cell (k0 + k, v)
+  // is zero -- laid out by word, as phiT is
+  const uint32_t *zero_mask;
+  int32_t mask_pitch;
 };
+constexpr double kConditionalMinGamma = 0.0001;   // ConditionalDirichlet.java:90-92
 
 // ONE WAVE per workgroup takes tiles of one 64-row segment x kc <= kPhiCols adjacent topics: the straight-line first try
 // for all of the tile's elements, then the general rejection loops for the elements it left over (queued in LDS, so that
@@ -469,8 +474,14 @@ struct PhiGammaParams {
 // that has a gamma in hand also adds its quantised value to the tile's segment functions (LDS atomic adds of integers,
 // ggs_exact_sum.hpp): the column sums of the gammas need no pass of their own over the matrix.  Single waves because
 // they balance: a topic slice of one rank in eight is 391 segments x 3 column groups per launch.
+//
+// PRIORS (scheme spalias_priors, the sweep draw only): the CONDITIONAL draw over each topic's allowed words
+// (ConditionalDirichlet.java:80-101 under SpaliasUncollapsedParallelWithPriors.java:343-359).  A masked cell draws nothing -- its
+// Philox stream is simply not used -- and holds +0.0, which leaves the column's running sum as it is; a gamma <= 0 becomes 1e-4
+// BEFORE it is summed.  The segment functions take those values, so the walk's result is the reference's sum_gamma.
 constexpr int kPhiCols = 6, kPhiQueue = 128;
 
+template <bool PRIORS>
 __global__ __launch_bounds__(64) void phi_gamma_kernel(PhiGammaParams p) {
   // With an exchange the slice's draw is on the critical path and the next theta has the whole Phi phase to finish: issue
   // ahead of the theta draw on the side stream (behind the chain's short kernels).  One GPU: the next z step waits for
@@ -511,6 +522,7 @@ __global__ __launch_bounds__(64) void phi_gamma_kernel(PhiGammaParams p) {
     if (lane == 0) qn = 0;
     __syncthreads();
     auto emit = [&](int v, int c, double g) {                            // the gamma to memory, its quantised value to the segment functions
+      if constexpr (PRIORS) { if (g <= 0) g = kConditionalMinGamma; }
       p.phiT[(size_t)v * p.Kp + kb + c] = g;
       const int e_lo = e_los[c];
       if (e_lo == kSegNoGuess) return;
@@ -522,6 +534,10 @@ __global__ __launch_bounds__(64) void phi_gamma_kernel(PhiGammaParams p) {
 #pragma unroll 1
     for (int j = lane; j < n; j += 64) {
       const int dv = udiv_small(j, m_kw), v = v0 + dv, c = j - dv * kw, k = kb + c;
+      if constexpr (PRIORS) {
+        const int kg = p.k0 + k;
+        if ((p.zero_mask[(size_t)v * p.mask_pitch + (kg >> 5)] >> (kg & 31)) & 1u) { p.phiT[(size_t)v * p.Kp + k] = 0.0; continue; }
+      }
       const double shape = shape_of(v, k);
       double g;
       if (shape > 0) {
@@ -555,9 +571,12 @@ __device__ __forceinline__ float phi32_of(const double x) { return (x >= 0.0 && 
 
 // POLYAURN (scheme polyaurn, PolyaUrnDirichletFixedCoeffPoisson.java:33-40): tot is an integer count of the row's Poisson
 // draws; exact zeros stay zero (no clamp), and a row whose total is 0 becomes all zero (the draws are all 0 there anyway).
-template <bool POLYAURN>
+// CONDITIONAL (scheme spalias_priors, ConditionalDirichlet.java:97-99): (g / sum_gamma) * sum_phi, the division first, no clamp behind
+// it; a masked cell holds +0.0 and keeps it (sum_gamma >= 1e-4: every topic has an allowed word and its gamma is clamped).
+enum PhiNorm { kPhiDirichlet, kPhiPolyaurn, kPhiConditional };
+template <int MODE>
 __device__ __forceinline__ void phi_normalise_body(double *phiT, const double *tot, int32_t K, int32_t Kp, int32_t V, double *phi_mean, float *phiT32,
-                                                   int32_t Kp32) {
+                                                   int32_t Kp32, const double *sum_phi = nullptr) {
   __builtin_amdgcn_s_setprio(3);
   const int64_t n = (int64_t)V * K;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -565,8 +584,11 @@ __device__ __forceinline__ void phi_normalise_body(double *phiT, const double *t
     const int v = (int)(i / K), k = (int)(i - (int64_t)v * K);
     double x = phiT[(size_t)v * Kp + k];
     const double s = tot[k];
-    if constexpr (POLYAURN) {
+    if constexpr (MODE == kPhiPolyaurn) {
       x = s > 0 ? x / s : 0.0;
+      phiT[(size_t)v * Kp + k] = x;
+    } else if constexpr (MODE == kPhiConditional) {
+      x = (x / s) * sum_phi[k];
       phiT[(size_t)v * Kp + k] = x;
     } else if (s != 0) {
       x = x / s;
@@ -579,11 +601,29 @@ __device__ __forceinline__ void phi_normalise_body(double *phiT, const double *t
 }
 __global__ __launch_bounds__(256) void phi_normalise_kernel(double *phiT, const double *tot, int32_t K, int32_t Kp, int32_t V,
                                                             double *phi_mean /* [V][K] or null */, float *phiT32 /* or null */, int32_t Kp32) {
-  phi_normalise_body<false>(phiT, tot, K, Kp, V, phi_mean, phiT32, Kp32);
+  phi_normalise_body<kPhiDirichlet>(phiT, tot, K, Kp, V, phi_mean, phiT32, Kp32);
 }
 __global__ __launch_bounds__(256) void phi_normalise_polyaurn_kernel(double *phiT, const double *tot, int32_t K, int32_t Kp, int32_t V, double *phi_mean,
                                                                      float *phiT32, int32_t Kp32) {
-  phi_normalise_body<true>(phiT, tot, K, Kp, V, phi_mean, phiT32, Kp32);
+  phi_normalise_body<kPhiPolyaurn>(phiT, tot, K, Kp, V, phi_mean, phiT32, Kp32);
+}
+__global__ __launch_bounds__(256) void phi_normalise_conditional_kernel(double *phiT, const double *tot, const double *sum_phi, int32_t K, int32_t Kp, int32_t V,
+                                                                        double *phi_mean, float *phiT32, int32_t Kp32) {
+  phi_normalise_body<kPhiConditional>(phiT, tot, K, Kp, V, phi_mean, phiT32, Kp32, sum_phi);
+}
+// The initial draw under topic priors (SpaliasUncollapsedParallelWithPriors.java:63-72): phi[k][v] *= P[k][v] on the finished Phi,
+// rows NOT renormalised.  The multiplication is the reference's (x * 1.0 = x, x * 0.0 = +0.0 for the positive x of the draw).
+__global__ __launch_bounds__(256) void phi_apply_priors_kernel(double *phiT, const uint32_t *zero_mask, int32_t mask_pitch, int32_t K, int32_t Kp, int32_t V,
+                                                               float *phiT32, int32_t Kp32) {
+  const int64_t n = (int64_t)V * K;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int v = (int)(i / K), k = (int)(i - (int64_t)v * K);
+    const double prior = ((zero_mask[(size_t)v * mask_pitch + (k >> 5)] >> (k & 31)) & 1u) ? 0.0 : 1.0;
+    const double x = phiT[(size_t)v * Kp + k] * prior;
+    phiT[(size_t)v * Kp + k] = x;
+    if (phiT32) phiT32[(size_t)v * Kp32 + k] = phi32_of(x);
+  }
 }
 
 // ---- exchange layout <-> device layout (one GPU of several; see include/ggs_hip.h, "multi-GPU") ----
@@ -599,8 +639,9 @@ struct PhiRepackParams {
   int32_t K, Kp, V, Ksm, v_split;
   float *phiT32;                 // or null
   int32_t Kp32;
+  const double *sum_phi;         // kPhiConditional: [K] index-order column sums of the OLD phiT, summed by this rank itself
 };
-template <bool POLYAURN>
+template <int MODE>
 __device__ __forceinline__ void phi_repack_body(const PhiRepackParams &p) {
   __builtin_amdgcn_s_setprio(3);
   const int64_t n = (int64_t)p.V * p.K;
@@ -612,8 +653,10 @@ __device__ __forceinline__ void phi_repack_body(const PhiRepackParams &p) {
     const double *h1 = p.all1 + (int64_t)r * p.c1;
     double x = v < p.v_split ? p.all0[(int64_t)r * p.c0 + (int64_t)v * p.Ksm + j] : h1[(int64_t)(v - p.v_split) * p.Ksm + j];
     const double s = h1[tot_off + j];
-    if constexpr (POLYAURN) {                                        // as phi_normalise_body<true>
+    if constexpr (MODE == kPhiPolyaurn) {                            // as phi_normalise_body
       x = s > 0 ? x / s : 0.0;
+    } else if constexpr (MODE == kPhiConditional) {
+      x = (x / s) * p.sum_phi[k];
     } else if (s != 0) {
       x = x / s;
       if (x <= 0) x = kJavaMinValue;
@@ -623,8 +666,9 @@ __device__ __forceinline__ void phi_repack_body(const PhiRepackParams &p) {
     if (p.phi_mean) p.phi_mean[i] += x;
   }
 }
-__global__ __launch_bounds__(256) void phi_repack_kernel(PhiRepackParams p) { phi_repack_body<false>(p); }
-__global__ __launch_bounds__(256) void phi_repack_polyaurn_kernel(PhiRepackParams p) { phi_repack_body<true>(p); }
+__global__ __launch_bounds__(256) void phi_repack_kernel(PhiRepackParams p) { phi_repack_body<kPhiDirichlet>(p); }
+__global__ __launch_bounds__(256) void phi_repack_polyaurn_kernel(PhiRepackParams p) { phi_repack_body<kPhiPolyaurn>(p); }
+__global__ __launch_bounds__(256) void phi_repack_conditional_kernel(PhiRepackParams p) { phi_repack_body<kPhiConditional>(p); }
 // cnt_all [nranks][V][Ksm] (the all-gathered count slices) -> n_wk [V][K]
 __global__ __launch_bounds__(256) void counts_unslice_kernel(const int32_t *cnt_all, const int64_t *koff, int32_t Ksm, int32_t *n_wk, int32_t K,
                                                              int32_t V) {

@@ -262,6 +262,20 @@ class GGSHandle:
         self._chk(self._L.ggs_get_alias_tables(self._h, _dp(ps), _ip(a), _dp(tn)))
         return ps, a, tn
 
+    def set_topic_priors(self, topics, words):
+        """scheme=spalias_priors: the cells (topics[i], words[i]) of Phi are pinned to zero ("anchor words"); a FLAG_SPALIAS handle,
+        before its first Phi.  Empty lists are allowed: the conditional Phi draw over an all-ones prior matrix."""
+        topics, words = np.ascontiguousarray(topics, np.int32).ravel(), np.ascontiguousarray(words, np.int32).ravel()
+        if topics.size != words.size:
+            raise ValueError("one word per topic")
+        self._chk(self._L.ggs_set_topic_priors(self._h, topics.size, _ip(topics), _ip(words)))
+
+    def get_topic_priors(self):
+        """getTopicPriors: [K][V], 1.0 or 0.0 (all 1.0 when no priors were set)."""
+        out = np.empty((self.K, self.V), np.float64)
+        self._chk(self._L.ggs_get_topic_priors(self._h, _dp(out)))
+        return out
+
     def mh_stats(self):
         """scheme=lightpclda: tokens whose word proposal was accepted and kept, whose document proposal was accepted, and
         tokens left on their old topic, cumulative since set_corpus (int64 [3]; they sum to the tokens sampled)."""

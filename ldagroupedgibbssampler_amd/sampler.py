@@ -38,6 +38,7 @@ class SimpleLDAConfiguration:
         self.phi_mean_burnin = int(kw.pop("phi_mean_burnin", 0))     # percent of iterations, PHI_BURN_IN_DEFAULT
         self.phi_mean_thin = int(kw.pop("phi_mean_thin", 1))         # PHI_THIN_DEFAULT
         self.alias_poisson_threshold = int(kw.pop("alias_poisson_threshold", 100))   # ALIAS_POISSON_DEFAULT_THRESHOLD; scheme=polyaurn and polyaurn_sparse only
+        self.topic_prior_filename = kw.pop("topic_prior_filename", None)   # TOPIC_PRIOR_FILENAME, default none; scheme=spalias_priors only
         self.paranoid = bool(kw.pop("paranoid", False))              # run the UPLDA:299-338 invariants every sweep
         self.device_id = int(kw.pop("device_id", 0))                 # optional gpu_* key; default first visible GPU
         # the diagnostics of the sampling loop (UPLDA:695-905), computed on the device and written in the Java driver's formats
@@ -150,9 +151,13 @@ class LDAGroupedGibbsSampler:
                                    alias_poisson_threshold=getattr(cfg, "alias_poisson_threshold", 100))
         self._corpus = training
         self._h.set_corpus(training.doc_ptr, training.tokens)
+        self._before_initial_state(training)
         self._h.init_z_java_lcg(self.startSeed)          # initialDrawTopicIndicator, UPLDA:458-460
         self._h.init_phi()                               # initialSamplePhi, UPLDA:1287-1294
         self.currentIteration = 0
+
+    def _before_initial_state(self, training):
+        """what a scheme sets on the new handle before the initial z and Phi are drawn"""
 
     def addTestInstances(self, test_set):
         """MSLDA:918-923: the test set of the held-out estimator; it must share the training alphabet
@@ -417,6 +422,31 @@ class SpaliasUncollapsedParallelLDA(LDAPartiallyCollapsedGibbsSampler):
         return self._h.alias_tables()
 
 
+class SpaliasUncollapsedParallelWithPriors(SpaliasUncollapsedParallelLDA):
+    """scheme=spalias_priors (topics/SpaliasUncollapsedParallelWithPriors.java, ParallelLDA.java:464-468; LDASamplerWithPriors):
+    spalias with topic priors, "anchor words".  The cfg key topic_prior_filename names a file of lines `topic,word,word,...`
+    (priors.py); those words may only belong to that topic, and Phi is exactly zero for them everywhere else: the initial Phi is
+    multiplied by the priors, every later Phi is the conditional Dirichlet draw over each topic's allowed words.  With no file
+    named it is spalias (haveTopicPriors == false)."""
+
+    def _before_initial_state(self, training):
+        self._topic_priors = None
+        path = getattr(self.config, "topic_prior_filename", None)
+        if path is None:
+            return
+        if training.vocab is None:
+            raise ValueError("topic_prior_filename needs a corpus with a vocabulary (Corpus.vocab)")
+        from . import priors
+        topics, words = priors.load_zero_cells(path, self.numTopics, training.vocab)     # initializePriors, :170-189
+        self._h.set_topic_priors(topics, words)
+        self._topic_priors = (topics, words)
+
+    def getTopicPriors(self):
+        """double[K][V], 1.0 or 0.0 (LDASamplerWithPriors.getTopicPriors), read back from the device"""
+        self._need_data()
+        return self._h.get_topic_priors()
+
+
 class LightPCLDA(LDAPartiallyCollapsedGibbsSampler):
     """scheme=lightpclda (topics/LightPCLDA.java, ParallelLDA.java:469-473): the pcgs model and driver and spalias's alias
     tables; the z step makes two Metropolis-Hastings proposals per token, one from the word's table and one from the
@@ -494,7 +524,7 @@ class SerialCollapsedLDA(LDAGroupedGibbsSampler):
 
 def create_model(config, scheme=None):
     """The `case "ggs"` / `case "pcgs"` / `case "collapsed"` / `case "polyaurn"` / `case "spalias"` / `case "lightpclda"` of tui/ParallelLDA.createModel
-    (ParallelLDA.java:401-490); "polyaurn_sparse" is this build's name for polyaurn over the sparse z step the reference's class holds."""
+    (ParallelLDA.java:401-490); "spalias_priors" is :464-468; "polyaurn_sparse" is this build's name for polyaurn over the sparse z step the reference's class holds."""
     scheme = scheme or config.scheme
     if scheme == "ggs":
         return LDAGroupedGibbsSampler(config)
@@ -506,8 +536,10 @@ def create_model(config, scheme=None):
         return PolyaUrnSpaliasLDA(config)
     if scheme == "spalias":
         return SpaliasUncollapsedParallelLDA(config)
+    if scheme == "spalias_priors":
+        return SpaliasUncollapsedParallelWithPriors(config)
     if scheme == "lightpclda":
         return LightPCLDA(config)
     if scheme == "polyaurn_sparse":
         return PolyaUrnSparseLDA(config)
-    raise ValueError("scheme %r is not provided by this build (only the ggs, pcgs, collapsed, polyaurn, spalias, lightpclda and polyaurn_sparse z loops are in scope)" % scheme)
+    raise ValueError("scheme %r is not provided by this build (only the ggs, pcgs, collapsed, polyaurn, spalias, spalias_priors, lightpclda and polyaurn_sparse z loops are in scope)" % scheme)

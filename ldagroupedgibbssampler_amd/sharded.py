@@ -62,16 +62,18 @@ class ShardedGGS:
                 sweep_begin, sweep_end, set_global_token_count, get_z, ...)
     exchange    object with allreduce_startup() / allreduce_sweep() acting on whatever the
                 engine exchanges (the HIP engine: its count buffer, both times)
+    topic_priors  scheme=spalias_priors: (topics, words), the zero cells of priors.load_zero_cells -- the SAME cells on every
+                rank (every rank masks its own topic slice and sums the whole old Phi itself; nothing more travels)
     """
 
-    def __init__(self, engine, exchange_factory, corpus, rank, world_size):
+    def __init__(self, engine, exchange_factory, corpus, rank, world_size, topic_priors=None):
         self.engine, self.rank, self.world = engine, int(rank), int(world_size)
         self.bounds = even_split(corpus.num_docs, self.world)
         sub, doc_base, tok_base = corpus.shard(self.bounds[self.rank], self.bounds[self.rank + 1])
-        self._attach(exchange_factory, sub, doc_base, tok_base, corpus.num_tokens)
+        self._attach(exchange_factory, sub, doc_base, tok_base, corpus.num_tokens, topic_priors)
 
     @classmethod
-    def from_local_shard(cls, engine, exchange_factory, shard, shard_sizes, rank, world_size):
+    def from_local_shard(cls, engine, exchange_factory, shard, shard_sizes, rank, world_size, topic_priors=None):
         """The rank already holds its documents (a corpus too large to build on every rank: each rank
         loads or generates its own part).  ``shard_sizes`` = [(num_docs, num_tokens)] of every rank in
         rank order, e.g. from an all-gather; the global corpus is the concatenation of the shards."""
@@ -82,14 +84,16 @@ class ShardedGGS:
         docs = np.concatenate([[0], np.cumsum([int(d) for d, _ in shard_sizes])])
         toks = np.concatenate([[0], np.cumsum([int(t) for _, t in shard_sizes])])
         self.bounds = [int(x) for x in docs]
-        self._attach(exchange_factory, shard, int(docs[self.rank]), int(toks[self.rank]), int(toks[-1]))
+        self._attach(exchange_factory, shard, int(docs[self.rank]), int(toks[self.rank]), int(toks[-1]), topic_priors)
         return self
 
-    def _attach(self, exchange_factory, sub, doc_base, tok_base, global_tokens):
+    def _attach(self, exchange_factory, sub, doc_base, tok_base, global_tokens, topic_priors=None):
         self.local, self.doc_base, self.tok_base, self.global_tokens = sub, doc_base, tok_base, global_tokens
         self.exchange = exchange_factory(self.engine)        # a native exchange must be attached before the corpus
         self.engine.set_corpus(sub.doc_ptr, sub.tokens, doc_base, tok_base)
         self.engine.set_global_token_count(global_tokens)
+        if topic_priors is not None:                         # before the first Phi (set_z_local draws it)
+            self.engine.set_topic_priors(*topic_priors)
 
     def set_z_global(self, z_global):
         """Start-up: every rank takes its slice of the corpus-wide z (e.g. the seeded
