@@ -33,7 +33,9 @@ def padded(lists, K):
 
 def token_draw(st, phi_w, nzw_w, ps_w, a_w, tn, U, K, detail=None):
     """The new topic of one token whose old topic has already been removed from st.  phi_w = the word's Phi column [K],
-    nzw_w = the word's list.  detail["kind"] = WORD / DOC / UNIFORM, detail["n"] = the number of candidates."""
+    nzw_w = the word's list.  detail["kind"] = WORD / DOC / UNIFORM, detail["n"] = the number of candidates; with
+    candidates also cand, cum, sum, thr, prior, and then ul (the walk) or x, ups, i, frac and, where i < K, ps_i (the
+    alias draw)."""
     nd, nw = len(st.list), len(nzw_w)
     use_word = nw < nd                                              # a tie goes to the document's list
     cand = [int(k) for k in nzw_w] if use_word else st.list
@@ -49,10 +51,19 @@ def token_draw(st, phi_w, nzw_w, ps_w, a_w, tn, U, K, detail=None):
         thr = np.float64(tn) / (np.float64(tn) + np.float64(s))
         prior = bool(U < thr)
         if detail is not None:
-            detail.update(cum=cum, sum=s, thr=float(thr), prior=prior)
+            detail.update(cand=cand, cum=cum, sum=s, thr=float(thr), prior=prior)
         if prior:
-            return alias_sample(ps_w, a_w, U + (s * U) / tn)
+            x = U + (s * U) / tn
+            if detail is not None:                                  # alias_sample's own quantities, for the edge builders
+                ups = x * float(K)
+                i = int(ups)
+                detail.update(x=x, ups=ups, i=i, frac=ups - float(i))
+                if i < K:
+                    detail["ps_i"] = float(ps_w[i])
+            return alias_sample(ps_w, a_w, x)
         ul = U * (tn + s) - tn
+    if detail is not None:
+        detail["ul"] = float(ul)
     return cand[list_search(cum, ul)]
 
 
