@@ -61,6 +61,7 @@ struct Knobs {
   // the handle's
   Knob margin{"GGS_DEBUG_MARGIN"}, replays{"GGS_DEBUG_REPLAYS"}, chain{"GGS_DEBUG_CHAIN"}, guided{"GGS_DEBUG_GUIDED"};
   Knob no_overlap{"GGS_DEBUG_NO_OVERLAP"}, theta_main{"GGS_DEBUG_THETA_MAIN"}, gamma_queue{"GGS_DEBUG_GAMMA_QUEUE"};
+  Knob num_cus{"GGS_DEBUG_NUM_CUS"};
 };
 
 constexpr int kThetaBlock = 256;
@@ -1714,6 +1715,10 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) return bail(GGS_ERR_HIP);
     h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    // GGS_DEBUG_NUM_CUS: a smaller count for every persistent grid and list sized by it (it can only lower the count, and a
+    // smaller grid is always resident; no kernel waits on another workgroup).  Results do not depend on it: the tests give
+    // one CU many items per workgroup, which the real chip gets only from a large corpus
+    if (kn.num_cus.set) h->num_cus = std::max(1, std::min(h->num_cus, kn.num_cus.v));
   }
   if ((rc = plan_launches(h->K, h->V, h->scheme, kn, h->plan))) return bail(rc);
   h->cfg = &h->plan.cfg_parts;
