@@ -13,9 +13,13 @@ State index convention: z[0] is the MOST significant digit, index = sum_i z[i] *
 
 The mutants of ReferenceSampler exist only to show that the statistics have power: each is a slip that a restatement and
 its kernel could share without a parity test noticing.
+
+scheme=spalias_priors leaves another law invariant, with the row masses of its masked Phi as a parameter: the second half of
+this file ("the constrained posterior") enumerates it and has a sampler and mutants of its own.
 """
 import collections
 import itertools
+import math
 
 import numpy as np
 from scipy import special, stats
@@ -140,7 +144,7 @@ N_LONG = 12000
 BURN_IN = 50
 # sweeps between two samples: the lag at which a scheme's samples of z are as good as independent on fixture A (at thin 4 the
 # ggs chain's lag autocorrelation of a state indicator is still 0.065, and a correct chain is rejected)
-THIN = {"ggs": 8, "pcgs": 4, "spalias": 4, "collapsed": 2, "collapsed_parallel": 2, "polyaurn": 4}
+THIN = {"ggs": 8, "pcgs": 4, "spalias": 4, "collapsed": 2, "collapsed_parallel": 2, "polyaurn": 4, "spalias_priors": 4}
 
 
 def oracle_chain(O, fixture, scheme, seed, n=N_SAMPLES):
@@ -242,3 +246,160 @@ class ReferenceSampler:
 
     def get_z(self):
         return self.z
+
+
+# ---- scheme=spalias_priors: the constrained posterior -----------------------------------------------------------------
+# Topic priors P [K][V] in {0, 1}; A_k the words topic k is allowed.  The initial Phi is the unconstrained draw times P, rows
+# not renormalised, and every sweep rescales row k to the mass it had: m_k = sum_v P_kv phi0_kv is a constant of the chain.
+# With phi_k = m_k psi_k, psi_k on the simplex over A_k, a sweep is
+#     psi_k | z ~ Dir(beta + n_k.) over A_k          (the draw's ((beta + n) / mag) * mag shape is beta + n to an ulp)
+#     p(z_i = k | z_-i, psi) ~ (n_dk^-i + alpha_k) m_k psi_k[w_i]
+# the two Gibbs conditionals of
+#     p(z | w, m) ~ prod_d prod_k Gamma(n_dk + alpha_k)
+#                   * prod_k [ m_k^n_k * prod_{v in A_k} Gamma(n_kv + beta) / Gamma(n_k + |A_k| beta) ],
+# zero for a z that puts a token on a masked (topic, word) cell.
+#
+# The fixture: fixture A with two cells masked.  Word 2 is the one-token document's, so that document's alias-only draw meets
+# a zero weight.  For a padded K every padded topic k is masked at word k mod 3 (mask bits 3 ... K - 1 set, across the 32-bit
+# words of the device's bit mask); every topic keeps two allowed words and every word an allowed topic.
+PRIOR_CELLS = ((0, 2), (1, 2))                                      # (topics, words): cells (0, 1) and (2, 2)
+PRIOR_CELLS_RB = ((0, 2), (1, 0))                                   # the Rao-Blackwell check's mask: cells (0, 1) and (2, 0)
+
+
+def prior_cells(K, base=PRIOR_CELLS):
+    """(topics, words) int32: base, plus (k, k mod 3) for every padded topic k >= 3"""
+    t, w = list(base[0]) + list(range(3, K)), list(base[1]) + [k % 3 for k in range(3, K)]
+    return np.asarray(t, np.int32), np.asarray(w, np.int32)
+
+
+def prior_matrix(K, V, cells):
+    """[K][V] float64, 0.0 at the cells and 1.0 elsewhere (written here, not taken from the code under test)"""
+    P = np.ones((K, V), np.float64)
+    for k, v in zip(*cells):
+        P[int(k), int(v)] = 0.0
+    return P
+
+
+def enumerate_constrained_posterior(fixture, P, m):
+    """The law above on fixture's corpus: Posterior with p = 0 off the support, e_theta = E[(n_dk + alpha_k) / (N_d + sum alpha)]
+    and e_phi = E[m_k P_kv (n_kv + beta) / (n_k + |A_k| beta)]."""
+    K, V, N = fixture.K, fixture.V, len(fixture.tokens)
+    if K ** N > MAX_STATES:
+        raise ValueError("K**N = %d states: too many to enumerate (limit %d)" % (K ** N, MAX_STATES))
+    P = np.asarray(P, np.float64)
+    m = np.broadcast_to(np.asarray(m, np.float64), (K,))
+    if P.shape != (K, V) or not np.isin(P, (0.0, 1.0)).all() or not (m > 0).all():
+        raise ValueError("P must be [K][V] in {0, 1} and m positive")
+    alpha = np.broadcast_to(np.asarray(fixture.alpha, np.float64), (K,))
+    beta = float(fixture.beta)
+    allowed = P != 0.0
+    n_allowed = allowed.sum(axis=1).astype(np.float64)
+    lens = np.diff(np.asarray(fixture.doc_ptr, np.int64)).astype(np.float64)
+    states = np.array(list(itertools.product(range(K), repeat=N)), np.int64).reshape(K ** N, N)
+    logp = np.full(len(states), -np.inf, np.float64)
+    th = np.zeros((len(states), len(lens), K), np.float64)
+    ph = np.zeros((len(states), K, V), np.float64)
+    for i, z in enumerate(states):
+        n_dk, n_kw = counts_of(fixture.doc_ptr, fixture.tokens, z, K, V)
+        if n_kw[~allowed].any():
+            continue
+        n_k = n_kw.sum(axis=1)
+        logp[i] = (special.gammaln(n_dk + alpha).sum() + special.gammaln(n_kw + beta)[allowed].sum()
+                   - special.gammaln(n_k + n_allowed * beta).sum() + (n_k * np.log(m)).sum())
+        th[i] = (n_dk + alpha) / (lens + alpha.sum())[:, None]
+        ph[i] = m[:, None] * P * (n_kw + beta) / (n_k + n_allowed * beta)[:, None]
+    p = np.exp(logp - special.logsumexp(logp))
+    return Posterior(K, N, states, p, np.tensordot(p, th, 1), np.tensordot(p, ph, 1))
+
+
+def off_support(indices, p):
+    """how many of the visited states have probability 0"""
+    return int((np.asarray(p)[np.asarray(indices, np.int64)] == 0.0).sum())
+
+
+CONSTRAINED_MUTANTS = (None, "renormalised", "beta_double", "mask_transposed")
+
+
+class ConstrainedSampler:
+    """A Gibbs sampler of the constrained law from its two conditionals, in NumPy; it starts from a z inside the support.
+
+    mutant: None, or one slip --
+      "renormalised"     the rows of Phi are normalised to 1: the mass m_k is dropped from the z step
+      "beta_double"      the Phi draw uses 2 beta
+      "mask_transposed"  P is read as [V][K] (K == V)
+    """
+
+    def __init__(self, fixture, P, m, seed, mutant=None):
+        if mutant not in CONSTRAINED_MUTANTS:
+            raise ValueError("mutant %r" % (mutant,))
+        self.K, self.V, self.mutant = fixture.K, fixture.V, mutant
+        P = np.asarray(P, np.float64)
+        self.P = np.ascontiguousarray(P.T) if mutant == "mask_transposed" else P.copy()
+        self.m = np.broadcast_to(np.asarray(m, np.float64), (self.K,)).copy()
+        self.alpha = np.broadcast_to(np.asarray(fixture.alpha, np.float64), (self.K,)).copy()
+        self.beta_phi = fixture.beta * (2.0 if mutant == "beta_double" else 1.0)
+        self.doc_ptr = np.asarray(fixture.doc_ptr, np.int64)
+        self.tokens = np.asarray(fixture.tokens, np.int64)
+        self.doc = np.repeat(np.arange(self.doc_ptr.size - 1), np.diff(self.doc_ptr))
+        self.rng = np.random.default_rng(seed)
+        self.z = np.array([self.rng.choice(np.flatnonzero(self.P[:, w] != 0.0)) for w in self.tokens], np.int64)
+        self.phi = None
+
+    def sweep(self, n=1):
+        for _ in range(n):
+            n_dk, n_kw = counts_of(self.doc_ptr, self.tokens, self.z, self.K, self.V)
+            g = self.rng.standard_gamma(n_kw + self.beta_phi) * self.P
+            self.phi = g / g.sum(axis=1, keepdims=True)
+            if self.mutant != "renormalised":
+                self.phi = self.phi * self.m[:, None]
+            for i in range(self.tokens.size):
+                d = self.doc[i]
+                n_dk[d, self.z[i]] -= 1
+                cum = np.cumsum((n_dk[d] + self.alpha) * self.phi[:, self.tokens[i]])
+                new = min(int((cum < self.rng.random() * cum[-1]).sum()), self.K - 1)
+                n_dk[d, new] += 1
+                self.z[i] = new
+
+    def get_z(self):
+        return self.z
+
+
+def exact_row_sums(phi):
+    """row sums without a rounding of their own (math.fsum): nothing of the measurement in the figure"""
+    return np.asarray([math.fsum(row) for row in np.asarray(phi, np.float64).tolist()])
+
+
+def oracle_row_masses(O, fixture, cells, seed):
+    """(m [K], phi0 * P [K][V]): the CPU oracle's unmasked initial Phi of a sampler seeded like the parity tests seed one, times
+    the prior matrix, and its row sums -- the reference for the chain's constant, not the code under test."""
+    o = O.OracleSampler(fixture.K, fixture.V, np.asarray(fixture.alpha), fixture.beta, seed)
+    o.set_corpus(fixture.doc_ptr, np.asarray(fixture.tokens, np.int32))
+    o.init_z_java_lcg(seed)
+    o.init_phi()
+    phi0 = o.get_phi() * prior_matrix(fixture.K, fixture.V, cells)
+    o.close()
+    return exact_row_sums(phi0), phi0
+
+
+def mass_bound(sweeps, V):
+    """relative drift of a row's mass after `sweeps` sweeps: a sweep sums the V cells of the old row (one rounding per summand)
+    and rescales the new row to that sum (a division and a multiplication per cell); at worst the roundings add up linearly"""
+    return sweeps * (V + 2) * 2.0 ** -53
+
+
+def spalias_priors_chain(O, fixture, cells, seed, n=N_SAMPLES, masses=None):
+    """(state indices base 3 [n], m [K]) of tests/spalias_priors_restatement.Model under the prior cells, from the z0 that
+    init_z_java_lcg(seed) gives; m from oracle_row_masses.  masses, a list, receives the model's exact row sums after the
+    initial draw, after the burn-in and at the end."""
+    from tests import spalias_priors_restatement as PR
+    m, _ = oracle_row_masses(O, fixture, cells, seed)
+    z0 = O.jrandom_ints(seed, fixture.K, len(fixture.tokens))
+    mdl = PR.Model(fixture.K, fixture.V, np.asarray(fixture.alpha), fixture.beta, seed, fixture.doc_ptr, fixture.tokens, z0, cells=cells)
+    mdl.init_phi()
+    note = (lambda: masses.append(exact_row_sums(mdl.phi))) if masses is not None else (lambda: None)
+    note()
+    mdl.sweep(BURN_IN)
+    note()
+    idx = run_chain(mdl.sweep, lambda: mdl.z, 3, n, THIN["spalias_priors"], 0, max_topic=2)
+    note()
+    return idx, m
