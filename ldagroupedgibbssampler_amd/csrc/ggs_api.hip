@@ -1156,17 +1156,15 @@ int launch_pcgs_z(ggs_handle *h) {
   pp.K = h->K; pp.Kp = h->Kp;
   int rc;
   if (h->alias_stale && (rc = launch_alias_build(h))) return rc;   // spalias, lightpclda, polyaurn_sparse
-  SpaliasParams sp{};
+  PolyaurnSparseParams sp{};                           // spalias's kernel takes its base, SpaliasParams
   LightpcParams lp{};
-  PolyaurnSparseParams ps{};
   void *args[] = {&pp, &h->margin_scale};              // the wave-per-document kernel takes both, the lane-per-document kernels the first
-  if (h->scheme == Scheme::spalias) {                  // one wave per document over the non-zero topics (ggs_z_spalias.hpp)
+  if (h->scheme == Scheme::spalias || h->scheme == Scheme::polyaurn_sparse) {
+    // one wave per document over its non-zero topics (ggs_z_spalias.hpp), or over the word's where they are fewer
+    // (ggs_z_polyaurn_sparse.hpp: the lists and the counters, null in a spalias handle)
     sp.b = pp; sp.ps = h->d_alias_ps; sp.a = h->d_alias_a; sp.type_norm = h->d_alias_tn; sp.cap = h->sp_cap; sp.margin_scale = h->margin_scale;
-    args[0] = &sp;
-  } else if (h->scheme == Scheme::polyaurn_sparse) {   // one wave per document over the shorter of the word's and the document's list
-    ps.b = pp; ps.ps = h->d_alias_ps; ps.a = h->d_alias_a; ps.type_norm = h->d_alias_tn; ps.nzw = h->d_nzw; ps.nw = h->d_nw;
-    ps.stats = h->d_ps_stats; ps.cap = h->sp_cap; ps.margin_scale = h->margin_scale;
-    args[0] = &ps;
+    sp.nzw = h->d_nzw; sp.nw = h->d_nw; sp.stats = h->d_ps_stats;
+    args[0] = static_cast<SpaliasParams *>(&sp);
   } else if (h->scheme == Scheme::lightpclda) {        // one wave per document, two proposals per token (ggs_z_lightpc.hpp)
     lp.b = pp; lp.ps = h->d_alias_ps; lp.a = h->d_alias_a; lp.mh = h->d_mh; lp.alpha_sum = h->alpha_sum;
     args[0] = &lp;

@@ -42,6 +42,11 @@ __device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
   const uint64_t m = ((uint64_t)(a >> 6) << 27) + (uint64_t)(b >> 5);
   return (double)m * 0x1.0p-53;
 }
+// the z step's uniform of global token gtok: the first double of block 0 of (gtok, GGS_PURPOSE_Z, iteration, seed)
+__device__ __forceinline__ double z_uniform(uint64_t gtok, uint32_t iteration, uint64_t seed) {
+  const U4 o = philox4x32_10((uint32_t)gtok, (uint32_t)(gtok >> 32), (uint32_t)GGS_PURPOSE_Z << 24, iteration, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return u53(o.x, o.y);
+}
 
 __device__ __forceinline__ int32_t hi32(double x) { return (int32_t)(__double_as_longlong(x) >> 32); }
 __device__ __forceinline__ uint32_t lo32(double x) { return (uint32_t)__double_as_longlong(x); }

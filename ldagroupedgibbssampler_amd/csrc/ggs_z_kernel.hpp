@@ -225,9 +225,7 @@ __global__ __launch_bounds__(64) void z_kernel(ZParams p) {
 #undef GGS_SUM8
 
       const uint64_t gtok = (uint64_t)(p.tok_base + start + lane);
-      const U4 o = philox4x32_10((uint32_t)gtok, (uint32_t)(gtok >> 32), (uint32_t)GGS_PURPOSE_Z << 24, p.iteration,
-                                 (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-      const double U = u53(o.x, o.y);
+      const double U = z_uniform(gtok, p.iteration, p.seed);
       double sample = U * sum;
 
       // ---- pass 2: the walk of GGS:108-113,

@@ -168,9 +168,7 @@ __device__ __forceinline__ void pcgs_z_body(PcgsParams &p) {
             }
             if (j == NS - 1) {                                     // UPLDA:1519-1520; the walk runs negated, see ggs_z_sliced.hpp
               const uint64_t gtok = (uint64_t)(p.tok_base + beg + t);
-              const U4 o = philox4x32_10((uint32_t)gtok, (uint32_t)(gtok >> 32), (uint32_t)GGS_PURPOSE_Z << 24, p.iteration,
-                                         (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-              U = u53(o.x, o.y);
+              U = z_uniform(gtok, p.iteration, p.seed);
               tt = 0.0 - U * sum;
             }
           } else {                                                 // UPLDA:1522-1526

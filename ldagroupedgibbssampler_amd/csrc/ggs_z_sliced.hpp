@@ -216,9 +216,7 @@ __device__ __forceinline__ void cold_chunks32(const ZParams &p, unsigned char *t
   // U, the decision, the replay and the stores of one chunk c
   auto finish = [&](const float (&a)[KMAX], const int64_t c, const int idx, const int ip, const int w) {
     const uint64_t gtok = (uint64_t)(p.tok_base + idx);
-    const U4 o = philox4x32_10((uint32_t)gtok, (uint32_t)(gtok >> 32), (uint32_t)GGS_PURPOSE_Z << 24, p.iteration,
-                               (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-    const double U = u53(o.x, o.y);
+    const double U = z_uniform(gtok, p.iteration, p.seed);
     const float A = a[KMAX - 1];
     const float t0 = (float)(U * (double)A);
     const float delta = ((float)(2 * K + 8) * 0x1p-24f * A) * mscale;
@@ -435,9 +433,7 @@ __device__ __forceinline__ void z_sliced_body(const ZParams &p) {
   auto finish = [&](const double (&sc)[KMAX], const double sum, const int idx, const int ip, const int word) {
     if (idx < 0) return;
     const uint64_t gtok = (uint64_t)(p.tok_base + idx);
-    const U4 o = philox4x32_10((uint32_t)gtok, (uint32_t)(gtok >> 32), (uint32_t)GGS_PURPOSE_Z << 24, p.iteration,
-                               (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-    const double U = u53(o.x, o.y);
+    const double U = z_uniform(gtok, p.iteration, p.seed);
     // The walk of GGS:108-113, negated and in counting form.  t = -(sample): t_0 = 0 - U*sum and
     // t_{j+1} = t_j + score[j] round exactly as sample_{j+1} = sample_j - score[j] does (round to
     // nearest is symmetric), x + (-x) gives +0, and scores are >= +0, so t is never -0 and
@@ -732,9 +728,7 @@ __device__ __forceinline__ int hot_token(const ZParams &p, const int K, const un
     ck[s] = sum;
   });
   const uint64_t gtok = (uint64_t)(p.tok_base + id0);
-  const U4 o = philox4x32_10((uint32_t)gtok, (uint32_t)(gtok >> 32), (uint32_t)GGS_PURPOSE_Z << 24, p.iteration,
-                             (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-  const double t0 = u53(o.x, o.y) * sum;                       // GGS:107-108
+  const double t0 = z_uniform(gtok, p.iteration, p.seed) * sum;   // GGS:107-108
   const double delta = (sum * (double)K) * 0x1p-51 * p.margin_scale;
   // the first slice whose closing checkpoint proves the walk has stopped (d = t0 - s is monotone)
   int gsel = NS;

@@ -150,9 +150,7 @@ __global__ __launch_bounds__(64) void z_stream_kernel(ZParams p) {
           }
           if (j == NS - 1) {
             const uint64_t gtok = (uint64_t)(p.tok_base + start0 + lane);
-            const U4 o = philox4x32_10((uint32_t)gtok, (uint32_t)(gtok >> 32), (uint32_t)GGS_PURPOSE_Z << 24, p.iteration,
-                                       (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-            U = u53(o.x, o.y);
+            U = z_uniform(gtok, p.iteration, p.seed);
             sample = U * sum;
           }
         } else {

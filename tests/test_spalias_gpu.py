@@ -158,6 +158,34 @@ def test_one_token_documents_draw_from_the_alias_table(native, oracle):
     g.close()
 
 
+@pytest.mark.parametrize("margin", FORMS)
+def test_one_token_documents_of_a_zeroed_column_keep_their_topic(native, oracle, monkeypatch, margin):
+    """The empty list at both typeNorms, K = 3: word 0's Phi column is all zero (typeNorm 0.0: 0 / 0 fails the comparison,
+    the token keeps its topic, in the replay whatever the margin), word 1's is not (threshold 1.0: the alias draw at x = U)."""
+    force_form(monkeypatch, margin)
+    K = 3
+    c = Corpus(np.arange(13, dtype=np.int64), (np.arange(12) % 2).astype(np.int32), 2)   # 12 documents of one token
+    z0 = (np.arange(12) // 2 % K).astype(np.int32)
+    g = native.GGSHandle(K, 2, 0.5, 0.1, SEED, flags=native.FLAG_SPALIAS)
+    g.set_corpus(c.doc_ptr, c.tokens)
+    g.set_z(z0, redraw_phi=True)
+    phi = g.get_phi()
+    phi[:, 0] = 0.0
+    g.set_phi(phi)
+    g.set_iteration(0)
+    g.sample_z_given_phi(1)
+    tables = R.alias_tables(phi, 0.5)
+    assert tables[2][0] == 0.0 and tables[2][1] > 0.0
+    want = z0.astype(np.int64)
+    n_prior, nnz_sum = R.z_step(c.doc_ptr, c.tokens, want, phi, tables, SEED, 1)
+    assert n_prior == 6 and nnz_sum == 0                            # word 1's six tokens draw from the table, no list has an entry
+    z = g.get_z()
+    assert_bit_equal(z, want.astype(np.int32), "z of one-token documents")
+    assert (z[0::2] == z0[0::2]).all()
+    assert z_kernel(g).startswith("spalias_wave_kernel")
+    g.close()
+
+
 # ---- knife-edge rows ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("margin", FORMS)
 def test_knife_edge_rows(native, oracle, monkeypatch, margin):
