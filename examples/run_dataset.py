@@ -21,7 +21,7 @@ def main():
     ap.add_argument("dataset")
     ap.add_argument("--stoplist", default=None, help="one stop word per line (LDAConfiguration: stoplist.txt)")
     ap.add_argument("--rare-threshold", type=int, default=0)
-    ap.add_argument("--scheme", default="ggs", choices=["ggs", "pcgs", "collapsed", "polyaurn", "spalias", "spalias_priors", "lightpclda", "polyaurn_sparse"])
+    ap.add_argument("--scheme", default="ggs", choices=["ggs", "pcgs", "collapsed", "polyaurn", "spalias", "spalias_priors", "lightpclda", "polyaurn_sparse", "lightcollapsed"])
     ap.add_argument("--topic-priors", default=None, metavar="FILE",
                     help="scheme spalias_priors: lines `topic,word,word,...`; those words may only belong to that topic (topic_prior_filename)")
     ap.add_argument("--topics", type=int, default=20)

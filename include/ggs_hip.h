@@ -108,7 +108,7 @@ enum {
                                      GGS_ERR_INVALID_TOPIC.  The chain is approximate by design and is not repaired.
                                      K up to 4096, any document length.  With GGS_FLAG_COLLAPSED, GGS_FLAG_POLYAURN or
                                      GGS_FLAG_SPALIAS: GGS_ERR_BAD_ARG.  A new bit, not a new ABI version. */
-  GGS_FLAG_POLYAURN_SPARSE = 1 << 7 /* scheme=polyaurn_sparse (PolyaUrnSpaliasLDA.sampleTopicAssignmentsParallel,
+  GGS_FLAG_POLYAURN_SPARSE = 1 << 7,/* scheme=polyaurn_sparse (PolyaUrnSpaliasLDA.sampleTopicAssignmentsParallel,
                                      PolyaUrnSpaliasLDA.java:180-334): polyaurn's model (implied: GGS_FLAG_PCGS is set internally; Phi
                                      initial and per sweep, counts, tokensPerTopic, phi mean and exchange exactly as under
                                      GGS_FLAG_POLYAURN, alias_poisson_threshold read the same way) with the doubly sparse z step the
@@ -132,6 +132,26 @@ enum {
                                      the tokens took.  K up to 4096, any document length.  With GGS_FLAG_COLLAPSED,
                                      GGS_FLAG_POLYAURN, GGS_FLAG_SPALIAS or GGS_FLAG_LIGHTPCLDA: GGS_ERR_BAD_ARG.  A new bit, not a
                                      new ABI version. */
+  GGS_FLAG_LIGHTCOLLAPSED = 1 << 8  /* scheme=lightcollapsed (CollapsedLightLDA, ParallelLDA.java:429-433): the collapsed model --
+                                     no theta, no Phi; counts, tokensPerTopic, merge, exchange, ggs_get_phi (the point estimate),
+                                     the likelihoods and ggs_check_invariants exactly as under GGS_FLAG_COLLAPSED -- under the
+                                     LightLDA z step: per token a word proposal from the word's alias table over the counts and
+                                     a document proposal from the document's indicator array, each accepted on a product of
+                                     count quotients (calculateWordAcceptanceProbability, calculateDocumentAcceptanceProbability,
+                                     CollapsedLightLDA.java:1050-1128; the formulas term by term in ggs_z_lightcollapsed.hpp).  The
+                                     schedule is GGS_FLAG_COLLAPSED's parallel one, AD-LDA with one worker per document: a token
+                                     is sampled against the sweep-start counts with only itself moved.  At the head of every
+                                     sweep, per word w: the ascending list of its topics with n_wk > 0 (ggs_get_word_topic_lists),
+                                     p_i = n_wk / ((double)n_k + betaSum), type_norm[w] = their i-order sum, and the alias table
+                                     of the nw[w] values p_i / type_norm[w] (ggs_get_alias_tables).  The uniforms are
+                                     GGS_FLAG_LIGHTPCLDA's four; ggs_get_mh_stats keeps the same three counters.  A table draw with
+                                     i == nw[w] and a beta- or alpha-branch topic == K: GGS_ERR_INVALID_TOPIC.
+                                     ggs_sample_z_given_phi, ggs_log_posterior, ggs_set_phi and ggs_get_theta:
+                                     GGS_ERR_UNSUPPORTED; ggs_collapsed_serial_sweep: GGS_ERR_STATE.  The chain is approximate as
+                                     the reference writes it and is not repaired.  K up to 4096, any document
+                                     length.  With any of GGS_FLAG_COLLAPSED, GGS_FLAG_PCGS, GGS_FLAG_POLYAURN, GGS_FLAG_SPALIAS,
+                                     GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE: GGS_ERR_BAD_ARG.  A new bit, not a new ABI
+                                     version. */
 };
 
 /* RNG stream addressing.  The reference draws from ThreadLocalRandom and a
@@ -416,7 +436,12 @@ int ggs_debug_poisson(int32_t device_id, double beta, int32_t threshold, uint64_
  * A draw x in [0, 1) from word w's table: ups = x * K, i = (int)ups, topic = (ups - i) > ps[w][i] ? a[w][i] : i.  K up to 4096. */
 int ggs_debug_alias(int32_t device_id, int32_t V, int32_t K, const double *phi, const double *alpha, double *ps, int32_t *a, double *type_norm);
 /* the tables of the handle's current Phi (GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA or GGS_FLAG_POLYAURN_SPARSE; GGS_ERR_STATE
- * otherwise or before the first Phi); any of the three outputs may be null */
+ * otherwise or before the first Phi); any of the three outputs may be null.  GGS_FLAG_LIGHTCOLLAPSED: the tables of the handle's
+ * current counts, which the next sweep builds at its head (after ggs_set_corpus, outside a split sweep): the call itself
+ * rebuilds all V lists and tables from the corpus-wide counts, overwriting those the last z step used, and with an exchange
+ * attached gathering the counts is a collective -- every rank makes the call, in the same order.  The first nw[w] entries of row w are
+ * the word's table over its list (a draw x: ups = x * nw[w], i = (int)ups, topics[w][(ups - i) > ps[w][i] ? a[w][i] : i]), the
+ * entries behind them read ps = 1.0, a = their index; type_norm[w] = typeMass, 0.0 for a word without tokens */
 int ggs_get_alias_tables(ggs_handle *h, double *ps /*[V][K]*/, int32_t *a /*[V][K]*/, double *type_norm /*[V]*/);
 /* scheme=spalias_priors (SpaliasUncollapsedParallelWithPriors, ParallelLDA.java:464-468; LDASamplerWithPriors): topic priors,
  * "anchor words".  No flag of its own and no new ABI version: a GGS_FLAG_SPALIAS handle on which ggs_set_topic_priors has been
@@ -444,12 +469,14 @@ int ggs_set_topic_priors(ggs_handle *h, int64_t n_zero, const int32_t *topic, co
 int ggs_get_topic_priors(ggs_handle *h, double *priors /*[K][V]*/);
 /* scheme=lightpclda's Metropolis-Hastings counters, cumulative since ggs_set_corpus (the three the reference keeps
  * commented out, LightPCLDA.java:28-44), every token in exactly one: out[0] tokens whose word proposal was accepted and
- * kept, out[1] tokens whose document proposal was accepted, out[2] tokens left on their old topic.  GGS_ERR_STATE
- * without GGS_FLAG_LIGHTPCLDA. */
+ * kept, out[1] tokens whose document proposal was accepted, out[2] tokens left on their old topic.  The same three classes
+ * under GGS_FLAG_LIGHTCOLLAPSED.  GGS_ERR_STATE without either flag. */
 int ggs_get_mh_stats(ggs_handle *h, int64_t out[3]);
 /* scheme=polyaurn_sparse's word lists of the handle's current Phi: nw[w] = the number of topics with phi[k][w] != 0.0,
  * topics[w][0 .. nw[w]) those topics in ascending order, -1 behind them.  Either output may be null.  GGS_ERR_STATE without
- * GGS_FLAG_POLYAURN_SPARSE or before the first Phi. */
+ * GGS_FLAG_POLYAURN_SPARSE or before the first Phi.  GGS_FLAG_LIGHTCOLLAPSED: the lists of the handle's current counts, nw[w] = the
+ * number of topics with n_wk > 0 (0 for a word without tokens); the same rebuild and, with an exchange, the same collective as
+ * ggs_get_alias_tables under that flag. */
 int ggs_get_word_topic_lists(ggs_handle *h, int32_t *nw /*V*/, int32_t *topics /*[V][K]*/);
 /* scheme=polyaurn_sparse's counters, cumulative since ggs_set_corpus, every token in exactly one of the first three:
  * out[0] tokens that walked the word's list, out[1] tokens that walked the document's list, out[2] tokens drawn uniformly

@@ -39,6 +39,39 @@ constexpr int kAliasLdsBudget = 48 * 1024;
 inline int alias_words_per_block(int K) { return std::max(1, std::min(64, kAliasLdsBudget / (12 * K))); }
 inline size_t alias_lds_bytes(int K, int wpb) { return (size_t)wpb * K * 12 + 64 * sizeof(double); }
 
+// One word's pairing chain over n entries, on one lane, out of LDS: b [n] holds bs and takes ps[l] in the slot of every paired
+// l, aw [n] the alias (preset to the index), s [n] both stacks.  n = K for the tables over Phi (alias_build_kernel), n = the
+// word's number of non-zero topics for the tables over the counts (count_alias_build_kernel, ggs_z_lightcollapsed.hpp).
+__device__ __forceinline__ void alias_pairing_chain(double *b, uint16_t *s, uint16_t *aw, const int n) {
+  int nl = 0, hp = n;                                                              // lows: s[0, nl), top s[nl - 1]; highs: s[hp, n), top s[hp]
+  for (int k = 0; k < n; ++k) {
+    if (b[k] < 0.0) s[nl++] = (uint16_t)k;
+    else s[--hp] = (uint16_t)k;
+  }
+  if (nl > 0 && hp < n) {
+    int h = s[hp];
+    double d = b[h];
+    while (true) {
+      const int l = s[--nl];
+      const double c = b[l];
+      b[l] = 1.0 + (double)n * c;                                                  // ps[l]
+      aw[l] = (uint16_t)h;
+      d = c + d;
+      if (d <= 0.0) {                                                              // highs loses h ...
+        ++hp;
+        if (d < 0.0) s[nl++] = (uint16_t)h;                                        // ... and lows takes it
+        b[h] = d;
+        if (nl == 0 || hp == n) break;
+        h = s[hp];
+        d = b[h];
+      } else if (nl == 0) {
+        b[h] = d;
+        break;
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(64) void alias_build_kernel(AliasParams p) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int K = p.K, wpb = p.wpb, lane = threadIdx.x;
@@ -67,37 +100,7 @@ __global__ __launch_bounds__(64) void alias_build_kernel(AliasParams p) {
     __syncthreads();
     for (int idx = lane; idx < cells; idx += 64) bs[idx] = bs[idx] / tnl[idx / K] - inv_k;
     __syncthreads();
-    if (lane < nw) {
-      double *b = bs + (size_t)lane * K;
-      uint16_t *s = st + (size_t)lane * K, *aw = al + (size_t)lane * K;
-      int nl = 0, hp = K;                                                          // lows: s[0, nl), top s[nl - 1]; highs: s[hp, K), top s[hp]
-      for (int k = 0; k < K; ++k) {
-        if (b[k] < 0.0) s[nl++] = (uint16_t)k;
-        else s[--hp] = (uint16_t)k;
-      }
-      if (nl > 0 && hp < K) {
-        int h = s[hp];
-        double d = b[h];
-        while (true) {
-          const int l = s[--nl];
-          const double c = b[l];
-          b[l] = 1.0 + (double)K * c;                                              // ps[l]
-          aw[l] = (uint16_t)h;
-          d = c + d;
-          if (d <= 0.0) {                                                          // highs loses h ...
-            ++hp;
-            if (d < 0.0) s[nl++] = (uint16_t)h;                                    // ... and lows takes it
-            b[h] = d;
-            if (nl == 0 || hp == K) break;
-            h = s[hp];
-            d = b[h];
-          } else if (nl == 0) {
-            b[h] = d;
-            break;
-          }
-        }
-      }
-    }
+    if (lane < nw) alias_pairing_chain(bs + (size_t)lane * K, st + (size_t)lane * K, al + (size_t)lane * K, K);
     __syncthreads();
     for (int idx = lane; idx < cells; idx += 64) {
       const int wi = idx / K, k = idx - wi * K, av = al[idx];

@@ -24,6 +24,7 @@
 #include "ggs_z_spalias.hpp"
 #include "ggs_z_polyaurn_sparse.hpp"
 #include "ggs_z_lightpc.hpp"
+#include "ggs_z_lightcollapsed.hpp"
 #include "ggs_loglik.hpp"
 #include "ggs_heldout.hpp"
 #include "ggs_exchange.hpp"
@@ -68,9 +69,14 @@ constexpr int kThetaBlock = 256;
 
 // What a handle samples and how: derived once from ggs_config::flags (scheme_of).  Every scheme but ggs runs the pcgs
 // machinery: no theta in the chain, a document order instead of chunk lists, the plan's lane / wave / ... entries.
-enum class Scheme { ggs, pcgs, collapsed, polyaurn, spalias, lightpclda, polyaurn_sparse };
+enum class Scheme { ggs, pcgs, collapsed, polyaurn, spalias, lightpclda, polyaurn_sparse, lightcollapsed };
 constexpr bool pcgs_family(Scheme s) { return s != Scheme::ggs; }
 constexpr bool has_alias(Scheme s) { return s == Scheme::spalias || s == Scheme::lightpclda || s == Scheme::polyaurn_sparse; }
+// the count form: no Phi, the model is the type-topic counts and tokensPerTopic; the sweep's merge is the (word, z) histogram
+constexpr bool count_form(Scheme s) { return s == Scheme::collapsed || s == Scheme::lightcollapsed; }
+constexpr bool has_tables(Scheme s) { return has_alias(s) || s == Scheme::lightcollapsed; }   // ps / a / type_norm [V][K]: over Phi, or (lightcollapsed) over the counts
+constexpr bool has_word_lists(Scheme s) { return s == Scheme::polyaurn_sparse || s == Scheme::lightcollapsed; }
+constexpr bool has_mh(Scheme s) { return s == Scheme::lightpclda || s == Scheme::lightcollapsed; }
 constexpr bool poisson_phi(Scheme s) { return s == Scheme::polyaurn || s == Scheme::polyaurn_sparse; }   // Phi drawn as polyaurn draws it
 
 // One kernel as a handle launches it: the function, its workgroup, its dynamic LDS and the workgroups per CU of its
@@ -108,11 +114,11 @@ struct LaunchPlan {
   int32_t theta_docs_main = 0, theta_lds_main = 0;   // ... where the theta draw is the critical leg (theta_main)
   // scheme pcgs / collapsed / polyaurn: a lane or a wave per document; spalias: the table build and the sparse walk (LDS per corpus);
   // lightpclda: the same table build and the Metropolis-Hastings step; polyaurn_sparse: the table build, the words' lists and
-  // the doubly sparse walk (LDS per corpus)
-  KernelLaunch lane, wave, alias, spalias, lightpc, serial, wordlist, pusparse;
+  // the doubly sparse walk (LDS per corpus); lightcollapsed: the lists and tables over the counts and its Metropolis-Hastings step
+  KernelLaunch lane, wave, alias, spalias, lightpc, serial, wordlist, pusparse, countalias, lightcol;
   bool wave_forced = false;            // ... because of K; otherwise per corpus (a document of 32 768 tokens or more)
   int32_t alias_wpb = 0;
-  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse}; }
+  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse, &countalias, &lightcol}; }
 };
 
 // The phase events of one sweep.  Sweeps are settled (waited for, checked, timed) in batches, so a ring of them:
@@ -181,6 +187,7 @@ struct ggs_handle {
   // scheme=lightpclda (ggs_z_lightpc.hpp): the pcgs model and spalias's tables, a Metropolis-Hastings z step
   double alpha_sum = 0;                                // the k-order sum of alpha
   unsigned long long *d_mh = nullptr;                  // [3]: ggs_get_mh_stats, zeroed by ggs_set_corpus
+  int32_t *d_tpt = nullptr;                            // scheme=lightcollapsed (ggs_z_lightcollapsed.hpp): [V] tokensPerType of the sweep-start counts
   // scheme=polyaurn_sparse (ggs_z_polyaurn_sparse.hpp): polyaurn's Phi, spalias's tables and document lists, and per word the
   // ascending list of its topics with phi != 0, rebuilt with the tables
   uint16_t *d_nzw = nullptr;                           // [V][K]
@@ -385,7 +392,7 @@ int check_status(ggs_handle *h) {
   if (!st) return GGS_OK;
   HIP_TRY(h, hipMemsetAsync(h->d_status, 0, sizeof(uint32_t), h->stream));
   if (st & ST_INVALID_TOPIC)
-    return set_err(h, GGS_ERR_INVALID_TOPIC, h->scheme == Scheme::collapsed ? "SimpleLDA: New topic not sampled." /* MSLDA:216-218 */ : "LDAGroupedGibbsSampler: Topic sampled is invalid!");
+    return set_err(h, GGS_ERR_INVALID_TOPIC, h->scheme == Scheme::collapsed ? "SimpleLDA: New topic not sampled." /* MSLDA:216-218 */ : h->scheme == Scheme::lightcollapsed ? "Collapsed Light-LDA: Sampled invalid topic." /* CollapsedLightLDA.java:957-959 */ : "LDAGroupedGibbsSampler: Topic sampled is invalid!");
   if (st & ST_NEGATIVE_COUNT) return set_err(h, GGS_ERR_NEGATIVE_COUNT, "Negative count for topic (Invalid count!)");
   if (st & ST_BAD_SHAPE) return set_err(h, GGS_ERR_BAD_ARG, "alpha and beta must be strictly positive (gamma shape <= 0)");
   return set_err(h, GGS_ERR_RNG_EXHAUSTED, "a gamma rejection loop exceeded GGS_MAX_BLOCKS Philox blocks");
@@ -868,6 +875,21 @@ int launch_alias_build(ggs_handle *h) {
   return GGS_OK;
 }
 
+// scheme=lightcollapsed: the words' lists and tables of the corpus-wide counts now in d_n_wk / d_n_k (count_alias_build_kernel),
+// on the handle's stream: at the head of every z step, and for the getters.  With an exchange every rank holds the gathered
+// counts and builds all V words for itself.
+int launch_count_alias_build(ggs_handle *h) {
+  int rc = launch_magnitude(h);                        // the counts gathered, tokensPerTopic in step with them
+  if (rc) return rc;
+  CountAliasParams cp{};
+  cp.n_wk = h->d_n_wk; cp.n_k = h->d_n_k; cp.ps = h->d_alias_ps; cp.a = h->d_alias_a; cp.type_norm = h->d_alias_tn;
+  cp.nzw = h->d_nzw; cp.nw = h->d_nw; cp.tpt = h->d_tpt; cp.beta_sum = h->beta * (double)h->V;
+  cp.V = h->V; cp.K = h->K; cp.wpb = h->plan.alias_wpb;
+  void *args[] = {&cp};
+  HIP_TRY(h, launch(h, h->plan.countalias, ((int64_t)h->V + cp.wpb - 1) / cp.wpb, args, h->stream));
+  return GGS_OK;
+}
+
 // Phi draw: initial (K8) or per sweep (K6).  One GPU: the whole matrix in place (and tokensPerTopic refreshed);
 // with an exchange: steps A, B, C above.
 int launch_phi(ggs_handle *h, bool initial, bool accumulate_mean, Events *E = nullptr) {
@@ -1141,11 +1163,21 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, pl.lightpc.fn, 64, (size_t)pl.lightpc.lds) != hipSuccess || by_regs < 1) by_regs = 1;
     pl.lightpc.per_cu = lds_workgroups_per_cu(pl.lightpc.lds, std::min(by_regs, 32));
   }
+  if (scheme == Scheme::lightcollapsed) {
+    // the tables over the counts: alias_build_kernel's words per workgroup and residency; the z step: lightpc's rule
+    pl.alias_wpb = alias_words_per_block(K);
+    pl.countalias = {reinterpret_cast<const void *>(count_alias_build_kernel), 64, (int)count_alias_lds_bytes(K, pl.alias_wpb), 0};
+    pl.countalias.per_cu = lds_workgroups_per_cu(pl.countalias.lds, 16);
+    pl.lightcol = {reinterpret_cast<const void *>(lightcollapsed_wave_kernel), 64, (int)lightcollapsed_lds_bytes(K), 0};
+    int by_regs = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, pl.lightcol.fn, 64, (size_t)pl.lightcol.lds) != hipSuccess || by_regs < 1) by_regs = 1;
+    pl.lightcol.per_cu = lds_workgroups_per_cu(pl.lightcol.lds, std::min(by_regs, 32));
+  }
   return GGS_OK;
 }
 
 const KernelLaunch &pcgs_entry(const LaunchPlan &pl, Scheme s, bool wave) {
-  return s == Scheme::lightpclda ? pl.lightpc : s == Scheme::spalias ? pl.spalias : s == Scheme::polyaurn_sparse ? pl.pusparse : wave ? pl.wave : pl.lane;
+  return s == Scheme::lightcollapsed ? pl.lightcol : s == Scheme::lightpclda ? pl.lightpc : s == Scheme::spalias ? pl.spalias : s == Scheme::polyaurn_sparse ? pl.pusparse : wave ? pl.wave : pl.lane;
 }
 int launch_pcgs_z(ggs_handle *h) {
   if (h->N == 0) return GGS_OK;
@@ -1158,6 +1190,7 @@ int launch_pcgs_z(ggs_handle *h) {
   if (h->alias_stale && (rc = launch_alias_build(h))) return rc;   // spalias, lightpclda, polyaurn_sparse
   PolyaurnSparseParams sp{};                           // spalias's kernel takes its base, SpaliasParams
   LightpcParams lp{};
+  LightCollapsedParams lc{};
   void *args[] = {&pp, &h->margin_scale};              // the wave-per-document kernel takes both, the lane-per-document kernels the first
   if (h->scheme == Scheme::spalias || h->scheme == Scheme::polyaurn_sparse) {
     // one wave per document over its non-zero topics (ggs_z_spalias.hpp), or over the word's where they are fewer
@@ -1168,6 +1201,11 @@ int launch_pcgs_z(ggs_handle *h) {
   } else if (h->scheme == Scheme::lightpclda) {        // one wave per document, two proposals per token (ggs_z_lightpc.hpp)
     lp.b = pp; lp.ps = h->d_alias_ps; lp.a = h->d_alias_a; lp.mh = h->d_mh; lp.alpha_sum = h->alpha_sum;
     args[0] = &lp;
+  } else if (h->scheme == Scheme::lightcollapsed) {    // the tables of the sweep-start counts, then one wave per document (ggs_z_lightcollapsed.hpp)
+    if ((rc = launch_count_alias_build(h))) return rc;
+    pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;   // betaSum as the collapsed path forms it
+    lc.b = pp; lc.ps = h->d_alias_ps; lc.a = h->d_alias_a; lc.nzw = h->d_nzw; lc.nw = h->d_nw; lc.tpt = h->d_tpt; lc.mh = h->d_mh; lc.alpha_sum = h->alpha_sum;
+    args[0] = &lc;
   } else if (h->scheme == Scheme::collapsed) {
     // the sweep-start ratios (beta + n_wk)/(betaSum + n_k) of the corpus-wide counts, then the pcgs loop over them
     if ((rc = launch_magnitude(h))) return rc;
@@ -1368,7 +1406,7 @@ int z_phase(ggs_handle *h) {
   if (h->ev_pending >= kEvRing - 2 && (rc = settle_sweeps(h))) return rc;   // keep this slot and the next one free
   h->ev_head = (h->ev_head + 1) % kEvRing;
   Events &E = h->evs[h->ev_head];
-  E.light = h->xg && h->have_frac && h->detail_every > 1 && !h->force_detail && (h->sweeps_enqueued % h->detail_every) != 0 && h->scheme != Scheme::collapsed;
+  E.light = h->xg && h->have_frac && h->detail_every > 1 && !h->force_detail && (h->sweeps_enqueued % h->detail_every) != 0 && !count_form(h->scheme);
   h->sweeps_enqueued += 1;
   if (pcgs_family(h->scheme)) {                         // no theta: it is integrated out (UPLDA:1509-1513)
     E.used_ahead = false;
@@ -1495,7 +1533,7 @@ int finish_sweep_enqueue_on(ggs_handle *h, bool with_phi) {
   E.exchanged = false;
   if (with_phi) {
     acc = (h->flags & GGS_FLAG_SAVE_PHI_MEAN) && sample_phi_this_iteration(h);
-    if (h->scheme == Scheme::collapsed) {   // no Phi in the count form: the merge (with an exchange: the gather of the count slices) and tokensPerTopic
+    if (count_form(h->scheme)) {   // no Phi in the count form: the merge (with an exchange: the gather of the count slices) and tokensPerTopic
       acc = false;
       if ((rc = launch_magnitude(h))) return rc;
     } else {
@@ -1652,11 +1690,13 @@ int scheme_of(const ggs_config *cfg, Scheme &scheme, int32_t &poisson_L) {
   if ((f & GGS_FLAG_LIGHTPCLDA) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS))) return GGS_ERR_BAD_ARG;
   // polyaurn_sparse is a scheme of its own: polyaurn's Phi under the doubly sparse step, none of the other z steps beside it
   if ((f & GGS_FLAG_POLYAURN_SPARSE) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA))) return GGS_ERR_BAD_ARG;
-  scheme = (f & GGS_FLAG_POLYAURN_SPARSE) ? Scheme::polyaurn_sparse : (f & GGS_FLAG_LIGHTPCLDA) ? Scheme::lightpclda : (f & GGS_FLAG_SPALIAS) ? Scheme::spalias : (f & GGS_FLAG_POLYAURN) ? Scheme::polyaurn
+  // lightcollapsed is the collapsed model under a z step of its own: none of the other schemes' flags beside it
+  if ((f & GGS_FLAG_LIGHTCOLLAPSED) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_PCGS | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA | GGS_FLAG_POLYAURN_SPARSE))) return GGS_ERR_BAD_ARG;
+  scheme = (f & GGS_FLAG_LIGHTCOLLAPSED) ? Scheme::lightcollapsed : (f & GGS_FLAG_POLYAURN_SPARSE) ? Scheme::polyaurn_sparse : (f & GGS_FLAG_LIGHTPCLDA) ? Scheme::lightpclda : (f & GGS_FLAG_SPALIAS) ? Scheme::spalias : (f & GGS_FLAG_POLYAURN) ? Scheme::polyaurn
          : (f & GGS_FLAG_COLLAPSED) ? Scheme::collapsed : (f & GGS_FLAG_PCGS) ? Scheme::pcgs : Scheme::ggs;
   poisson_L = cfg->alias_poisson_threshold == 0 ? 100 : cfg->alias_poisson_threshold;   // LDAConfiguration.java:44
   if (poisson_phi(scheme) && ((f & GGS_FLAG_COLLAPSED) || poisson_L < 1 || poisson_L > kPoissonMaxThreshold)) return GGS_ERR_BAD_ARG;
-  if (has_alias(scheme) && cfg->num_topics > kPcgsWaveMaxTopics) return GGS_ERR_UNSUPPORTED;
+  if (has_tables(scheme) && cfg->num_topics > kPcgsWaveMaxTopics) return GGS_ERR_UNSUPPORTED;
   return GGS_OK;
 }
 
@@ -1730,8 +1770,10 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
   for (const void *f : {reinterpret_cast<const void *>(ll_docs_kernel), reinterpret_cast<const void *>(lp_docs_kernel)})
     if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess) return bail(GGS_ERR_HIP);
   // 4. the model's buffers
+  // (a lightcollapsed handle has no Phi: ggs_get_phi allocates the buffer of its point estimate when it is first asked for one)
+  const bool with_phi = h->scheme != Scheme::lightcollapsed;
   const size_t kv = (size_t)h->K * h->V, phi_elems = (size_t)h->V * h->Kp + kPhiTailPadBytes / 8;
-  if ((rc = dev_alloc(h, &h->d_alpha, h->K)) || (rc = dev_alloc(h, &h->d_phiT, phi_elems)) ||
+  if ((rc = dev_alloc(h, &h->d_alpha, h->K)) || (with_phi && (rc = dev_alloc(h, &h->d_phiT, phi_elems))) ||
       (rc = dev_alloc(h, &h->d_mag, h->K)) || (rc = dev_alloc(h, &h->d_tot, h->K)) || (rc = dev_alloc(h, &h->d_n_wk, kv)) ||
       (rc = dev_alloc(h, &h->d_n_k, h->K)) || (rc = dev_alloc(h, &h->d_status, 4)))
     return bail(rc);
@@ -1749,13 +1791,13 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
                        (rc = dev_alloc(h, &h->d_sum_fn, (size_t)h->sum_nseg * h->K * 4))))
     return bail(rc);
   if (hipMemcpy(h->d_alpha, h->alpha.data(), sizeof(double) * h->K, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemset(h->d_phiT, 0, sizeof(double) * phi_elems) != hipSuccess ||
+      (with_phi && hipMemset(h->d_phiT, 0, sizeof(double) * phi_elems) != hipSuccess) ||
       hipMemset(h->d_n_wk, 0, sizeof(int32_t) * kv) != hipSuccess ||
       hipMemset(h->d_n_k, 0, sizeof(int32_t) * h->K) != hipSuccess || hipMemset(h->d_status, 0, 16) != hipSuccess ||
       (h->d_phi_mean && hipMemset(h->d_phi_mean, 0, sizeof(double) * kv) != hipSuccess))
     return bail(GGS_ERR_HIP);
-  if (has_alias(h->scheme) && ((rc = dev_alloc(h, &h->d_alias_ps, kv)) || (rc = dev_alloc(h, &h->d_alias_a, kv)) || (rc = dev_alloc(h, &h->d_alias_tn, (size_t)h->V)))) return bail(rc);
-  if (h->scheme == Scheme::lightpclda && ((rc = dev_alloc(h, &h->d_mh, 3)) || hipMemset(h->d_mh, 0, 3 * sizeof(unsigned long long)) != hipSuccess)) return bail(rc ? rc : GGS_ERR_HIP);
+  if (has_tables(h->scheme) && ((rc = dev_alloc(h, &h->d_alias_ps, kv)) || (rc = dev_alloc(h, &h->d_alias_a, kv)) || (rc = dev_alloc(h, &h->d_alias_tn, (size_t)h->V)))) return bail(rc);
+  if (has_mh(h->scheme) && ((rc = dev_alloc(h, &h->d_mh, 3)) || hipMemset(h->d_mh, 0, 3 * sizeof(unsigned long long)) != hipSuccess)) return bail(rc ? rc : GGS_ERR_HIP);
   if (h->scheme == Scheme::polyaurn_sparse) {          // lists and counters start zeroed: no entry is ever read that the build did not write
     if ((rc = dev_alloc(h, &h->d_nzw, kv)) || (rc = dev_alloc(h, &h->d_nw, (size_t)h->V)) || (rc = dev_alloc(h, &h->d_ps_stats, 4))) return bail(rc);
     if (hipMemset(h->d_nzw, 0, kv * sizeof(uint16_t)) != hipSuccess || hipMemset(h->d_nw, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess ||
@@ -1767,6 +1809,13 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     build_poisson_table(h->beta, h->pa_L, T);
     h->pa_t00 = T[0];
     if ((rc = upload(h, &h->d_pa_table, T)) || (rc = dev_alloc(h, &h->d_pa_acc, (size_t)h->K * kPoissonAccStride))) return bail(rc);
+  }
+  if (h->scheme == Scheme::lightcollapsed) {           // lists and tables start zeroed: no entry is ever read that the build did not write
+    if ((rc = dev_alloc(h, &h->d_nzw, kv)) || (rc = dev_alloc(h, &h->d_nw, (size_t)h->V)) || (rc = dev_alloc(h, &h->d_tpt, (size_t)h->V))) return bail(rc);
+    if (hipMemset(h->d_nzw, 0, kv * sizeof(uint16_t)) != hipSuccess || hipMemset(h->d_nw, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess ||
+        hipMemset(h->d_tpt, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess || hipMemset(h->d_alias_ps, 0, kv * sizeof(double)) != hipSuccess ||
+        hipMemset(h->d_alias_a, 0, kv * sizeof(int32_t)) != hipSuccess || hipMemset(h->d_alias_tn, 0, (size_t)h->V * sizeof(double)) != hipSuccess)
+      return bail(GGS_ERR_HIP);
   }
   if (h->scheme == Scheme::collapsed && (rc = dev_alloc(h, &h->d_lcg, 2))) return bail(rc);
   // 5. events and streams
@@ -1882,7 +1931,7 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
     h->pcgs_wave = pl.wave_forced || L.longest > kPcgsMaxDocLen;
     if (h->pcgs_wave && !pl.wave.fn) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=pcgs: a document of 32768 tokens or more with more than 4096 topics");
     h->pcgs_z = pcgs_entry(pl, h->scheme, h->pcgs_wave);
-    h->pcgs_items = (has_alias(h->scheme) || h->pcgs_wave) ? (int64_t)L.order.size() : ((int64_t)L.order.size() + 63) / 64;   // a wave or a lane per entry
+    h->pcgs_items = (has_tables(h->scheme) || h->pcgs_wave) ? (int64_t)L.order.size() : ((int64_t)L.order.size() + 63) / 64;   // a wave or a lane per entry
     if (h->scheme == Scheme::spalias || h->scheme == Scheme::polyaurn_sparse) {
       // the list of a document's non-zero topics holds at most min(K, its length) entries; the resident waves are what LDS allows,
       // at most the CU's 32
@@ -1924,12 +1973,13 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   if (L.warm_tiers > 0 && ((rc = upload(h, &h->d_wt_pack, L.wt_pack)) || (rc = upload(h, &h->d_w_docs, L.w_docs)) ||
                            (rc = upload(h, &h->d_warm_words, L.warm_words)) || (rc = upload(h, &h->d_warm_meta, L.warm_meta))))
     return rc;
+  const bool with_theta = h->scheme != Scheme::lightcollapsed;   // no theta in its chain and none for a diagnostic (ggs_log_posterior is unsupported)
   if ((rc = dev_alloc(h, &h->d_z, (size_t)N)) || (rc = dev_alloc(h, &h->d_zw, (size_t)N)) ||
-      (rc = dev_alloc(h, &h->d_theta, theta_elems)) || (!pcgs && (rc = dev_alloc(h, &h->d_theta_next, theta_elems))))   // theta_next: what the ggs z phase swaps in
+      (with_theta && (rc = dev_alloc(h, &h->d_theta, theta_elems))) || (!pcgs && (rc = dev_alloc(h, &h->d_theta_next, theta_elems))))   // theta_next: what the ggs z phase swaps in
     return rc;
   HIP_TRY(h, hipMemset(h->d_z, 0, sizeof(int32_t) * std::max<size_t>((size_t)N, 1)));
   HIP_TRY(h, hipMemset(h->d_zw, 0, sizeof(int32_t) * std::max<size_t>((size_t)N, 1)));
-  HIP_TRY(h, hipMemset(h->d_theta, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
+  if (with_theta) HIP_TRY(h, hipMemset(h->d_theta, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
   if (!pcgs) HIP_TRY(h, hipMemset(h->d_theta_next, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
   if (h->d_mh) HIP_TRY(h, hipMemset(h->d_mh, 0, 3 * sizeof(unsigned long long)));
   if (h->d_ps_stats) HIP_TRY(h, hipMemset(h->d_ps_stats, 0, 4 * sizeof(unsigned long long)));
@@ -1982,7 +2032,7 @@ int ggs_set_z(ggs_handle *h, const int32_t *z, int32_t redraw_phi) {
 int ggs_init_phi(ggs_handle *h) {
   int rc = require_ready(h, false);
   if (rc) return rc;
-  if (h->scheme == Scheme::collapsed) {   // nothing to draw: corpus-wide counts and tokensPerTopic are the whole model
+  if (count_form(h->scheme)) {   // nothing to draw: corpus-wide counts and tokensPerTopic are the whole model
     if ((rc = launch_magnitude(h))) return rc;
     h->have_phi = true;
     return check_status(h);
@@ -2076,7 +2126,7 @@ int ggs_sample_z_given_phi(ggs_handle *h, int32_t n_sweeps) {
   int rc = require_ready(h, true);
   if (rc) return rc;
   if (h->in_sweep) return set_err(h, GGS_ERR_STATE, "inside a split sweep");
-  if (h->scheme == Scheme::collapsed) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed has no Phi to condition on");
+  if (count_form(h->scheme)) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed and scheme=lightcollapsed have no Phi to condition on");
   for (int32_t i = 0; i < n_sweeps; ++i) {
     h->iteration += 1;                                 // UPLDA:980
     h->force_detail = true;
@@ -2340,7 +2390,7 @@ int ggs_group_set_z(ggs_handle **hs, int32_t n, const int32_t *const *z, int32_t
   for (int32_t i = 0; i < n; ++i)
     if ((rc = ggs_set_z(hs[i], z[i], 0))) return rc;          // this shard's counts
   if (!redraw_phi) return GGS_OK;
-  if (hs[0]->scheme == Scheme::collapsed) {                                        // no Phi: the merged counts and tokensPerTopic are the model
+  if (count_form(hs[0]->scheme)) {                                                 // no Phi: the merged counts and tokensPerTopic are the model
     if ((rc = group_gather_counts(hs, n))) return rc;
     for (int32_t i = 0; i < n; ++i) {
       if ((rc = bind_device(hs[i])) || (rc = launch_magnitude(hs[i]))) return rc;
@@ -2356,7 +2406,7 @@ int ggs_group_sweep(ggs_handle **hs, int32_t n, int32_t n_sweeps) {
   if (!is_group(hs, n)) return GGS_ERR_BAD_ARG;
   int rc;
   for (int32_t s = 0; s < n_sweeps; ++s) {
-    if (hs[0]->scheme == Scheme::collapsed && (rc = group_gather_counts(hs, n))) return rc;   // the z step conditions on the corpus-wide sweep-start counts
+    if (count_form(hs[0]->scheme) && (rc = group_gather_counts(hs, n))) return rc;   // the z step conditions on the corpus-wide sweep-start counts
     for (int32_t i = 0; i < n; ++i) {
       ggs_handle *h = hs[i];
       if ((rc = require_ready(h, true))) return rc;
@@ -2364,7 +2414,7 @@ int ggs_group_sweep(ggs_handle **hs, int32_t n, int32_t n_sweeps) {
       h->iteration += 1;
       if ((rc = z_phase(h))) return rc;
     }
-    if (hs[0]->scheme == Scheme::collapsed) {                                      // the AD-LDA merge: gathered counts, then tokensPerTopic; no Phi
+    if (count_form(hs[0]->scheme)) {                                               // the AD-LDA merge: gathered counts, then tokensPerTopic; no Phi
       if ((rc = group_gather_counts(hs, n))) return rc;
       for (int32_t i = 0; i < n; ++i) {
         ggs_handle *h = hs[i];
@@ -2434,7 +2484,8 @@ int ggs_get_phi(ggs_handle *h, double *phi) {
   if (!h || !phi) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (h->scheme == Scheme::collapsed) {   // the point estimate from the current counts
+  if (count_form(h->scheme)) {   // the point estimate from the current counts
+    if (!h->d_phiT && (rc = dev_alloc(h, &h->d_phiT, (size_t)h->V * h->Kp + kPhiTailPadBytes / 8))) return rc;   // lightcollapsed: only now
     if ((rc = launch_magnitude(h))) return rc;
     hipLaunchKernelGGL(psi_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, h->d_n_wk, h->d_n_k, h->beta, h->beta * (double)h->V,
                        h->d_phiT, h->K, h->Kp, h->V);
@@ -2446,6 +2497,7 @@ int ggs_set_phi(ggs_handle *h, const double *phi) {
   if (!h || !phi) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
+  if (h->scheme == Scheme::lightcollapsed) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=lightcollapsed has no Phi to set");
   const size_t kv = (size_t)h->K * h->V;
   if (h->have_priors) {   // the z step leaves the prior factor out because Phi is exactly zero wherever the prior is (ggs_hip.h)
     for (int32_t v = 0; v < h->V; ++v)
@@ -2523,10 +2575,25 @@ int ggs_get_alias_tables(ggs_handle *h, double *ps, int32_t *a, double *type_nor
   if (!h) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (!has_alias(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA or GGS_FLAG_POLYAURN_SPARSE");
+  if (!has_tables(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE or GGS_FLAG_LIGHTCOLLAPSED");
+  const size_t kv = (size_t)h->K * h->V;
+  if (h->scheme == Scheme::lightcollapsed) {           // the tables of the current counts: what the next sweep builds at its head
+    if ((rc = require_ready(h, false)) || (rc = launch_count_alias_build(h))) return rc;
+    std::vector<int32_t> n((size_t)h->V);
+    HIP_TRY(h, hipMemcpyAsync(n.data(), h->d_nw, n.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (ps) HIP_TRY(h, hipMemcpyAsync(ps, h->d_alias_ps, kv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (a) HIP_TRY(h, hipMemcpyAsync(a, h->d_alias_a, kv * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (type_norm) HIP_TRY(h, hipMemcpyAsync(type_norm, h->d_alias_tn, (size_t)h->V * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int32_t w = 0; w < h->V; ++w)                 // the kernel writes a row's first nw[w] entries: behind them ps = 1.0, a = the index
+      for (int32_t i = n[(size_t)w]; i < h->K; ++i) {
+        if (ps) ps[(size_t)w * h->K + i] = 1.0;
+        if (a) a[(size_t)w * h->K + i] = i;
+      }
+    return GGS_OK;
+  }
   if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
   if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
-  const size_t kv = (size_t)h->K * h->V;
   if (ps) HIP_TRY(h, hipMemcpyAsync(ps, h->d_alias_ps, kv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (a) HIP_TRY(h, hipMemcpyAsync(a, h->d_alias_a, kv * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   if (type_norm) HIP_TRY(h, hipMemcpyAsync(type_norm, h->d_alias_tn, (size_t)h->V * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2537,7 +2604,7 @@ int ggs_get_mh_stats(ggs_handle *h, int64_t out[3]) {
   if (!h || !out) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (h->scheme != Scheme::lightpclda) return set_err(h, GGS_ERR_STATE, "ggs_get_mh_stats needs GGS_FLAG_LIGHTPCLDA");
+  if (!has_mh(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_mh_stats needs GGS_FLAG_LIGHTPCLDA or GGS_FLAG_LIGHTCOLLAPSED");
   unsigned long long v[3];
   HIP_TRY(h, hipMemcpyAsync(v, h->d_mh, sizeof(v), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2548,9 +2615,13 @@ int ggs_get_word_topic_lists(ggs_handle *h, int32_t *nw, int32_t *topics) {
   if (!h) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (h->scheme != Scheme::polyaurn_sparse) return set_err(h, GGS_ERR_STATE, "ggs_get_word_topic_lists needs GGS_FLAG_POLYAURN_SPARSE");
-  if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
-  if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
+  if (!has_word_lists(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_word_topic_lists needs GGS_FLAG_POLYAURN_SPARSE or GGS_FLAG_LIGHTCOLLAPSED");
+  if (h->scheme == Scheme::lightcollapsed) {           // of the current counts
+    if ((rc = require_ready(h, false)) || (rc = launch_count_alias_build(h))) return rc;
+  } else {
+    if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
+    if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
+  }
   const size_t kv = (size_t)h->K * h->V;
   std::vector<int32_t> n((size_t)h->V);
   std::vector<uint16_t> l(topics ? kv : 0);
@@ -2587,6 +2658,7 @@ int ggs_get_theta(ggs_handle *h, int64_t doc_begin, int64_t doc_end, double *the
   int rc = require_ready(h, false);
   if (rc) return rc;
   if (doc_begin < 0 || doc_end > h->D || doc_begin > doc_end || (!theta && doc_end > doc_begin)) return set_err(h, GGS_ERR_BAD_ARG, "bad document range");
+  if (h->scheme == Scheme::lightcollapsed) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=lightcollapsed keeps no theta");
   return copy_out(h, theta, h->d_theta + (size_t)doc_begin * h->K, sizeof(double) * (size_t)(doc_end - doc_begin) * h->K);
 }
 int ggs_get_doc_topic_counts(ggs_handle *h, int64_t doc_begin, int64_t doc_end, int32_t *n_dk) {
@@ -2641,7 +2713,7 @@ int ggs_log_posterior(ggs_handle *h, double *doc_side, double *topic_side) {
   int rc = require_ready(h, true);
   if (rc) return rc;
   if (!doc_side || !topic_side) return set_err(h, GGS_ERR_BAD_ARG, "null output");
-  if (h->scheme == Scheme::collapsed) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed has no Phi: the log posterior of UPLDA:1573-1634 does not apply");
+  if (count_form(h->scheme)) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed and scheme=lightcollapsed have no Phi: the log posterior of UPLDA:1573-1634 does not apply");
   if ((rc = ll_check_topics(h))) return rc;
   if (pcgs_family(h->scheme)) {
     // UPLDA:710-714: every scheme but ggs draws theta_d ~ Dir(n_d. + alpha) afresh for the diagnostics
@@ -2890,7 +2962,7 @@ int ggs_get_warm_tiers(ggs_handle *h, int32_t *tiers, int32_t *warm_words, int32
 int ggs_get_z_form(ggs_handle *h, int32_t *kernel, int32_t *form, int32_t *calibrated) {
   if (!h) return GGS_ERR_BAD_ARG;
   const bool splittable = h->plan.sliced() && h->Cs > h->Cc && h->Cc > 0;
-  if (kernel) *kernel = h->scheme == Scheme::polyaurn_sparse ? 8 : h->scheme == Scheme::lightpclda ? 7 : h->scheme == Scheme::spalias ? 6 : pcgs_family(h->scheme) ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
+  if (kernel) *kernel = h->scheme == Scheme::lightcollapsed ? 9 : h->scheme == Scheme::polyaurn_sparse ? 8 : h->scheme == Scheme::lightpclda ? 7 : h->scheme == Scheme::spalias ? 6 : pcgs_family(h->scheme) ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
   if (form) *form = h->plan.sliced() ? (splittable && h->z_split ? 1 : 2) : 0;
   if (calibrated) *calibrated = (splittable && h->z_split_tried && !h->plan.split_forced && h->plan.split) ? 1 : 0;
   return GGS_OK;

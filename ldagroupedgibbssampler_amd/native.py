@@ -10,6 +10,7 @@ ERR_NEGATIVE_COUNT, ERR_INVALID_TOPIC, ERR_RNG_EXHAUSTED, ERR_BAD_ARG = 1, 2, 3,
 ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_INVARIANT = 5, 6, 7, 8
 FLAG_PARANOID, FLAG_SAVE_PHI_MEAN, FLAG_PCGS, FLAG_COLLAPSED, FLAG_POLYAURN, FLAG_SPALIAS, FLAG_LIGHTPCLDA = 1, 2, 4, 8, 16, 32, 64
 FLAG_POLYAURN_SPARSE = 128
+FLAG_LIGHTCOLLAPSED = 256
 PURPOSE_Z, PURPOSE_THETA, PURPOSE_PHI, PURPOSE_INIT_PHI = 1, 2, 3, 4
 
 
@@ -257,7 +258,9 @@ class GGSHandle:
         return (out, n.value) if n.value else (None, 0)
 
     def alias_tables(self):
-        """scheme=spalias, lightpclda or polyaurn_sparse: the alias tables of the current Phi, (ps [V][K], a [V][K], type_norm [V])."""
+        """scheme=spalias, lightpclda or polyaurn_sparse: the alias tables of the current Phi, (ps [V][K], a [V][K], type_norm [V]).
+        scheme=lightcollapsed: the tables of the current counts (what the next sweep builds at its head): row w holds the word's
+        table in its first nw[w] entries, ps = 1.0 and a = the index behind them; type_norm [V] = typeMass."""
         ps, a, tn = np.empty((self.V, self.K), np.float64), np.empty((self.V, self.K), np.int32), np.empty(self.V, np.float64)
         self._chk(self._L.ggs_get_alias_tables(self._h, _dp(ps), _ip(a), _dp(tn)))
         return ps, a, tn
@@ -277,7 +280,7 @@ class GGSHandle:
         return out
 
     def mh_stats(self):
-        """scheme=lightpclda: tokens whose word proposal was accepted and kept, whose document proposal was accepted, and
+        """scheme=lightpclda and lightcollapsed: tokens whose word proposal was accepted and kept, whose document proposal was accepted, and
         tokens left on their old topic, cumulative since set_corpus (int64 [3]; they sum to the tokens sampled)."""
         out = np.zeros(3, np.int64)
         self._chk(self._L.ggs_get_mh_stats(self._h, _lp(out)))
@@ -285,7 +288,8 @@ class GGSHandle:
 
     def word_topic_lists(self):
         """scheme=polyaurn_sparse: (nw [V], topics [V][K]) of the current Phi -- per word the number of topics with
-        phi[k][w] != 0 and those topics in ascending order, -1 behind them."""
+        phi[k][w] != 0 and those topics in ascending order, -1 behind them.  scheme=lightcollapsed: of the current counts, the
+        topics with n_wk > 0."""
         nw, topics = np.empty(self.V, np.int32), np.empty((self.V, self.K), np.int32)
         self._chk(self._L.ggs_get_word_topic_lists(self._h, _ip(nw), _ip(topics)))
         return nw, topics
@@ -366,7 +370,7 @@ class GGSHandle:
 Z_KERNEL_NAMES = {0: "z_kernel (whole-row tiles)", 1: "z_sliced_kernel + z_hot_kernel (score registers)", 2: "z_stream1_kernel (one pass)",
                   3: "z_stream_kernel (two passes)", 4: "pcgs_sliced_kernel (lane per document)", 5: "pcgs_wave_kernel (wave per document)",
                   6: "spalias_wave_kernel (wave per document)", 7: "lightpc_wave_kernel (wave per document)",
-                  8: "polyaurn_sparse_wave_kernel (wave per document)"}
+                  8: "polyaurn_sparse_wave_kernel (wave per document)", 9: "lightcollapsed_wave_kernel (wave per document)"}
 
 
 class GGSGroup:

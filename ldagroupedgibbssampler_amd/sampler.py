@@ -219,7 +219,7 @@ class LDAGroupedGibbsSampler:
         indicators; each value is kept in the Java-named list and, with a log_dir, appended in the Java file format."""
         cfg = self.config
         from . import formats as F
-        if cfg.start_diagnostic > 0 and iteration >= cfg.start_diagnostic and not (self._scheme_flags & native.FLAG_COLLAPSED):   # pcgs: with a fresh theta, UPLDA:710-714
+        if cfg.start_diagnostic > 0 and iteration >= cfg.start_diagnostic and not (self._scheme_flags & (native.FLAG_COLLAPSED | native.FLAG_LIGHTCOLLAPSED)):   # pcgs: with a fresh theta, UPLDA:710-714
             lp = self.computeLogPosterior()                               # UPLDA:818-821
             self.logPosterior.append(lp)
             if cfg.log_dir:
@@ -522,8 +522,38 @@ class SerialCollapsedLDA(LDAGroupedGibbsSampler):
         raise NotImplementedError("scheme=collapsed has no Phi to condition on")
 
 
+class CollapsedLightLDA(LDAGroupedGibbsSampler):
+    """scheme=lightcollapsed (topics/CollapsedLightLDA.java, ParallelLDA.java:429-433): the collapsed model -- no theta and no
+    Phi are drawn, getPhi() is the point estimate (beta + n_wk)/(betaSum + n_k) -- under the LightLDA z step: per token a
+    word proposal from the word's alias table over the counts and a document proposal from the document's own indicator
+    array, each accepted on a product of count quotients: O(1) per token.  Documents are sampled side by side on the
+    sweep-start counts and merged after the sweep (the AD-LDA decomposition of scheme=collapsed's parallel schedule); the chain
+    is approximate as the reference writes it."""
+    _scheme_flags = native.FLAG_LIGHTCOLLAPSED
+
+    def getTheta(self):
+        raise NotImplementedError("scheme=lightcollapsed never draws theta; use getThetaEstimate()")
+
+    def sampleZGivenPhi(self, iterations):
+        raise NotImplementedError("scheme=lightcollapsed has no Phi to condition on")
+
+    def getAliasTables(self):
+        """(ps [V][K], a [V][K], typeMass [V]) of the current counts: a word's table in the first nw[w] entries of its row"""
+        self._need_data()
+        return self._h.alias_tables()
+
+    def getWordTopicLists(self):
+        """(nw [V], topics [V][K]): per word the topics with n_wk > 0 in ascending order, -1 behind them"""
+        self._need_data()
+        return self._h.word_topic_lists()
+
+    def getMHStats(self):
+        """tokens whose word proposal was kept, whose document proposal was accepted, left on their old topic (cumulative)"""
+        return self._h.mh_stats()
+
+
 def create_model(config, scheme=None):
-    """The `case "ggs"` / `case "pcgs"` / `case "collapsed"` / `case "polyaurn"` / `case "spalias"` / `case "lightpclda"` of tui/ParallelLDA.createModel
+    """The `case "ggs"` / `case "pcgs"` / `case "collapsed"` / `case "lightcollapsed"` / `case "polyaurn"` / `case "spalias"` / `case "lightpclda"` of tui/ParallelLDA.createModel
     (ParallelLDA.java:401-490); "spalias_priors" is :464-468; "polyaurn_sparse" is this build's name for polyaurn over the sparse z step the reference's class holds."""
     scheme = scheme or config.scheme
     if scheme == "ggs":
@@ -542,4 +572,6 @@ def create_model(config, scheme=None):
         return LightPCLDA(config)
     if scheme == "polyaurn_sparse":
         return PolyaUrnSparseLDA(config)
-    raise ValueError("scheme %r is not provided by this build (only the ggs, pcgs, collapsed, polyaurn, spalias, spalias_priors, lightpclda and polyaurn_sparse z loops are in scope)" % scheme)
+    if scheme == "lightcollapsed":
+        return CollapsedLightLDA(config)
+    raise ValueError("scheme %r is not provided by this build (only the ggs, pcgs, collapsed, lightcollapsed, polyaurn, spalias, spalias_priors, lightpclda and polyaurn_sparse z loops are in scope)" % scheme)

@@ -1,0 +1,489 @@
+"""scheme=lightcollapsed on the device (GGS_FLAG_LIGHTCOLLAPSED): whole sweeps bit for bit against the CPU restatement
+(tests/lightcollapsed_restatement.py) -- z, n_wk, n_k, the three Metropolis-Hastings counters and, before every sweep, the
+tables (ps / a, type_norm), the words' lists and their lengths; sharded runs against one handle; the persistent grids on one
+CU; the interface; the held-out likelihood against scheme=collapsed's parallel schedule; the driver and the host mirrors.
+
+There are two kernels, count_alias_build_kernel (the lists and tables over the counts, at the head of every sweep) and
+lightcollapsed_wave_kernel (a wave per document), each with one way through it: no margins, no replay."""
+import os
+import subprocess
+import sys
+import threading
+
+import numpy as np
+import pytest
+
+from ldagroupedgibbssampler_amd.corpus import Corpus, even_split, random_corpus, synthetic_lda_corpus
+from ldagroupedgibbssampler_amd.sharded import java_lcg_initial_z
+from tests import lightcollapsed_restatement as R
+from tests import persistent_grid as PG
+from tests.test_native_exchange_gpu import ThreadTransport, assert_bit_equal
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SEED = 777
+KERNEL = "lightcollapsed_wave_kernel"
+# the plan's caps of the two kernels (ggs_api.hip, plan_launches), beside persistent_grid's CAP_* constants: the z kernel is a
+# single-wave document kernel planned by lightpc's rule, min(what LDS and registers allow, 32) -- at its 173 VGPRs the registers
+# allow 2 waves per SIMD, 8 workgroups per CU, so 32 is an upper bound of the real grid and a trip count computed with it holds;
+# the build takes alias_build_kernel's words per workgroup and its cap of 16
+CAP_LIGHTCOLLAPSED_WAVE, CAP_COUNT_ALIAS = PG.CAP_WAVE, PG.CAP_ALIAS
+
+
+def z_kernel(g):
+    return g.launch_info()["z_kernel"]
+
+
+def assert_tables_equal(g, m, what=""):
+    """the tables and lists of the current counts: what the next sweep builds at its head"""
+    ps, a, tn, nw, lists, _ = m.tables()
+    gps, ga, gtn = g.alias_tables()
+    gnw, glists = g.word_topic_lists()
+    assert_bit_equal(gnw, nw, "nw " + what)
+    assert_bit_equal(glists, lists, "lists " + what)
+    assert_bit_equal(gtn, tn, "type_norm " + what)
+    assert_bit_equal(ga, a, "a " + what)
+    assert_bit_equal(gps, ps, "ps " + what)
+    return nw
+
+
+def assert_state_equal(g, m, what=""):
+    assert_bit_equal(g.get_z(), m.z.astype(np.int32), "z " + what)
+    assert_bit_equal(g.mh_stats(), m.stats, "MH counters " + what)
+    assert_bit_equal(g.get_type_topic_counts(), m.counts(), "n_wk " + what)
+    assert_bit_equal(g.get_topic_totals(), m.topic_totals(), "n_k " + what)
+
+
+# ---- whole runs ---------------------------------------------------------------------------------------------------
+def run_pair(native, c, K, alpha, beta, sweeps, zseed=5, on_token=None, tables_every_sweep=True):
+    g = native.GGSHandle(K, c.num_types, alpha, beta, SEED, flags=native.FLAG_LIGHTCOLLAPSED | native.FLAG_PARANOID)
+    g.set_corpus(c.doc_ptr, c.tokens)
+    g.init_z_java_lcg(zseed)
+    z0 = g.get_z()
+    assert_bit_equal(z0, java_lcg_initial_z(c.num_tokens, K, zseed), "initial z")
+    g.init_phi()
+    m = R.Model(K, c.num_types, alpha, beta, SEED, c.doc_ptr, c.tokens, z0)
+    m.on_token = on_token
+    for s in range(sweeps):
+        if tables_every_sweep or s == 0:
+            assert_tables_equal(g, m, "before sweep %d" % (s + 1))
+        g.sweep(1)
+        m.sweep(1)
+        assert_state_equal(g, m, "after sweep %d" % (s + 1))
+    assert_tables_equal(g, m, "after the last sweep")
+    assert z_kernel(g).startswith(KERNEL)
+    assert_bit_equal(g.get_phi(), m.phi(), "the point estimate")
+    assert int(m.stats.sum()) == sweeps * c.num_tokens
+    return g, m
+
+
+@pytest.mark.parametrize("K,alpha,beta", [(3, 5.0, 7.0), (20, 0.1, 0.01)])
+def test_cats_sweeps_equal_the_restatement(native, oracle, cats, K, alpha, beta):
+    g, m = run_pair(native, cats, K, alpha, beta, 5)
+    print("MH counters %s, word-proposal branches (table, beta) %s" % (m.stats.tolist(), m.branches.tolist()))
+    assert (m.stats > 0).all()                                      # all three outcomes occur
+    assert (m.branches >= 20).all()                                 # and both branches of the word proposal
+    g.close()
+
+
+def test_cats_with_asymmetric_alpha(native, oracle, cats):
+    alpha = 0.02 + 0.07 * np.arange(20)                             # alpha[oldTopic] stands where alpha[t] belongs: a wrong index shows
+    g, m = run_pair(native, cats, 20, alpha, 0.01, 5)
+    g.close()
+
+
+def test_ragged_corpus(native, oracle):
+    """Documents of 0, 1, 63, 64, 65 (chunk boundaries), 130 and 700 tokens over V = 5 plus one word no token has.  Counted
+    from the restatement: at least 20 tokens draw their document proposal from an earlier position of the same 64-token
+    chunk (the register), from an earlier chunk (memory, behind the chunk's store) and from the token's own position."""
+    rng = np.random.default_rng(3)
+    lens = np.array([63, 0, 1, 64, 700, 65, 1, 130, 0, 2], np.int64)
+    tokens = rng.integers(0, 5, lens.sum()).astype(np.int32)
+    c = Corpus(np.concatenate(([0], np.cumsum(lens))).astype(np.int64), tokens, 6)
+    counts = {}
+
+    def on_token(d, pos, det):
+        idx = det["idx"]
+        src = "alpha" if idx is None else "own" if idx == pos else "later" if idx > pos else "chunk" if idx >= pos - pos % 64 else "earlier"
+        counts[src] = counts.get(src, 0) + 1
+
+    g, m = run_pair(native, c, 7, 0.3, 0.1, 5, on_token=on_token)
+    nw, _ = g.word_topic_lists()
+    g.close()
+    print("document proposals by source: %s" % sorted(counts.items()))
+    assert (m.stats > 0).all() and (m.branches > 0).all()
+    for src in ("chunk", "earlier", "own"):
+        assert counts.get(src, 0) >= 20, (src, counts)
+    assert nw[5] == 0 and (nw[:5] > 0).all()                        # the unused word builds nothing
+
+
+def test_word_lists_across_the_64_topic_seam(native, oracle):
+    """V = 3, K = 200, 30 documents of 300 tokens: every word has more than 64 and fewer than 200 non-zero topics, so its list
+    is made by more than one ballot and does not fill the row -- asserted from the restatement before every sweep.  The
+    initial z is NOT ggs_init_z_java_lcg's uniform one: 9 000 tokens over 3 words are 3 000 tokens per word, which over 200
+    topics leave no topic empty, so every list would be full.  z starts on 90 of the 200 topics instead, through ggs_set_z: the
+    lists then hold 90, and 155 to 171 topics before the later sweeps."""
+    rng = np.random.default_rng(17)
+    lens = np.full(30, 300, np.int64)
+    c = Corpus(np.concatenate(([0], np.cumsum(lens))).astype(np.int64), rng.integers(0, 3, lens.sum()).astype(np.int32), 3)
+    K = 200
+    z0 = rng.permutation(K)[:90][rng.integers(0, 90, c.num_tokens)].astype(np.int32)
+    g = native.GGSHandle(K, 3, 0.1, 0.01, SEED, flags=native.FLAG_LIGHTCOLLAPSED | native.FLAG_PARANOID)
+    g.set_corpus(c.doc_ptr, c.tokens)
+    g.set_z(z0, redraw_phi=True)
+    m = R.Model(K, 3, 0.1, 0.01, SEED, c.doc_ptr, c.tokens, z0)
+    for s in range(3):
+        nw = assert_tables_equal(g, m, "before sweep %d" % (s + 1))
+        assert ((nw > 64) & (nw < K)).all(), nw
+        g.sweep(1)
+        m.sweep(1)
+        assert_state_equal(g, m, "after sweep %d" % (s + 1))
+    g.close()
+
+
+@pytest.mark.parametrize("K", [1024, 4096])
+def test_wide_topic_rows_on_a_small_vocabulary(native, oracle, K):
+    """40 documents of exactly 200 tokens (8 000 tokens), words uniform over V = 150 (frequencies 34 to 78), 2 sweeps, beta =
+    0.01: beta * K is about 10 at K = 1024 and about 41 at K = 4096 against word frequencies of about 53, so both branches of
+    the word proposal are taken (about 15 % and 43 % of the tokens take the beta branch)."""
+    rng = np.random.default_rng(K)
+    lens = np.full(40, 200, np.int64)
+    c = Corpus(np.concatenate(([0], np.cumsum(lens))).astype(np.int64), rng.integers(0, 150, lens.sum()).astype(np.int32), 150)
+    assert c.num_docs == 40 and c.num_tokens == 8000 and c.num_types == 150
+    g, m = run_pair(native, c, K, 0.05, 0.01, 2)
+    print("K = %d: word-proposal branches (table, beta) %s" % (K, m.branches.tolist()))
+    assert (m.branches >= 20).all()
+    g.close()
+
+
+def test_one_document_of_33000_tokens(native, oracle):
+    rng = np.random.default_rng(8)
+    lens = np.array([5, 33000, 70], np.int64)
+    tokens = rng.integers(0, 50, lens.sum()).astype(np.int32)
+    c = Corpus(np.concatenate(([0], np.cumsum(lens))).astype(np.int64), tokens, 50)
+    g, m = run_pair(native, c, 40, 0.1, 0.01, 2)
+    g.close()
+
+
+def test_one_cu_takes_every_workgroup_through_three_items(native, oracle, monkeypatch):
+    """GGS_DEBUG_NUM_CUS=1 over persistent_grid's WAVE_KINDS corpus (200 documents: over 128 tokens, one-token, empty) at
+    K = 1000, V = 210: the z kernel's grid is at most 32 workgroups for 200 documents, the build's at most 16 for 53 groups of
+    4 words, the last one of 2 -- some workgroup of each takes at least 3 items, asserted before anything is compared."""
+    K, V = 1000, 210
+    c = PG.mixed_corpus(PG.WAVE_KINDS, V, 77)
+    PG.assert_kinds(c)
+    monkeypatch.setenv(PG.KNOB, "1")
+    g = native.GGSHandle(K, V, 0.1, 0.01, SEED, flags=native.FLAG_LIGHTCOLLAPSED | native.FLAG_PARANOID)
+    g.set_corpus(c.doc_ptr, c.tokens)
+    info = g.launch_info()
+    assert info["z_kernel"].startswith(KERNEL) and info["num_chunks"] == c.num_docs and info["lds_bytes_z"] == 4 * K
+    PG.assert_trips(info["num_chunks"], 1, CAP_LIGHTCOLLAPSED_WAVE, "lightcollapsed_wave_kernel")
+    assert PG.alias_words_per_block(K) == 4 and V % 4 != 0          # a ragged last trip
+    PG.assert_trips(PG.alias_items(V, K), 1, CAP_COUNT_ALIAS, "count_alias_build_kernel")
+    g.init_z_java_lcg(5)
+    g.init_phi()
+    m = R.Model(K, V, 0.1, 0.01, SEED, c.doc_ptr, c.tokens, g.get_z())
+    for s in range(2):
+        assert_tables_equal(g, m, "before sweep %d" % (s + 1))
+        g.sweep(1)
+        m.sweep(1)
+        assert_state_equal(g, m, "after sweep %d" % (s + 1))
+    g.close()
+
+
+# ---- sharded: bit-identical to one handle -------------------------------------------------------------------------
+def _rank(native, tr, rank, world, whole, K, mode, sweeps, out, errs):
+    import torch
+    from ldagroupedgibbssampler_amd.sharded import _DevPtr
+    try:
+        dev = torch.device("cuda", 0)
+
+        def view(ptr, n, typestr):
+            return torch.as_tensor(_DevPtr(ptr, n, typestr), device=dev)
+
+        def reduce_scatter_i32(send, recv, count, stream):
+            torch.cuda.synchronize()
+            parts = tr.exchange(rank, view(send, count * world, "<i4").cpu().numpy().reshape(world, count))
+            view(recv, count, "<i4").copy_(torch.from_numpy(np.sum([p[rank] for p in parts], axis=0, dtype=np.int32)))
+            torch.cuda.synchronize()
+            return 0
+
+        def all_gather(typestr):
+            def cb(send, recv, count, stream):
+                torch.cuda.synchronize()
+                parts = tr.exchange(rank, view(send, count, typestr).cpu().numpy())
+                view(recv, count * world, typestr).copy_(torch.from_numpy(np.concatenate(parts)))
+                torch.cuda.synchronize()
+                return 0
+            return cb
+
+        def all_to_all_v(send, soff, scnt, recv, roff, rcnt, stream):
+            torch.cuda.synchronize()
+            total = max(soff[i] + scnt[i] for i in range(world))
+            mine = view(send, max(total, 1), "<i4").cpu().numpy()
+            everyone = tr.exchange(rank, [mine[soff[d]:soff[d] + scnt[d]].copy() for d in range(world)])
+            for s_ in range(world):
+                got = everyone[s_][rank]
+                if got.size:
+                    view(recv + 4 * roff[s_], got.size, "<i4").copy_(torch.from_numpy(got))
+            torch.cuda.synchronize()
+            return 0
+
+        bounds = even_split(whole.num_docs, world)
+        sub, doc_base, tok_base = whole.shard(bounds[rank], bounds[rank + 1])
+        h = native.GGSHandle(K, whole.num_types, 0.1, 0.01, SEED, flags=native.FLAG_LIGHTCOLLAPSED)
+        h.attach_exchange(rank, world, reduce_scatter_i32, all_gather("<f8"), all_gather("<i4"), all_to_all_v)
+        h.set_count_exchange(mode)
+        h.set_corpus(sub.doc_ptr, sub.tokens, doc_base, tok_base)
+        h.set_global_token_count(whole.num_tokens)
+        z0 = java_lcg_initial_z(whole.num_tokens, K, 17)
+        h.set_z(z0[tok_base:tok_base + sub.num_tokens], redraw_phi=True)
+        h.sweep(sweeps)
+        h.check_invariants()
+        out[rank] = dict(z=h.get_z(), nwk=h.get_type_topic_counts(), nk=h.get_topic_totals(), phi=h.get_phi(), how=h.count_exchange(),
+                         tables=h.alias_tables(), lists=h.word_topic_lists(), kernel=z_kernel(h), mh=h.mh_stats())
+        h.close()
+    except BaseException as e:                      # noqa: BLE001 -- re-raised by the test body
+        errs.append(e)
+        tr.bar.abort()
+
+
+def one_handle(native, whole, K, sweeps):
+    h = native.GGSHandle(K, whole.num_types, 0.1, 0.01, SEED, flags=native.FLAG_LIGHTCOLLAPSED)
+    h.set_corpus(whole.doc_ptr, whole.tokens)
+    h.set_z(java_lcg_initial_z(whole.num_tokens, K, 17), redraw_phi=True)
+    h.sweep(sweeps)
+    r = dict(z=h.get_z(), nwk=h.get_type_topic_counts(), nk=h.get_topic_totals(), phi=h.get_phi(), tables=h.alias_tables(), lists=h.word_topic_lists(),
+             mh=h.mh_stats())
+    h.close()
+    return r
+
+
+@pytest.mark.parametrize("world,mode,K,V", [(2, "dense", 40, 900), (3, "sparse", 100, 900)])
+def test_sharded_runs_equal_one_handle(native, oracle, world, mode, K, V):
+    whole = random_corpus(310, V, 90, seed=K + V, empty_every=9)
+    sweeps = 5
+    tr, out, errs = ThreadTransport(world), [None] * world, []
+    ts = [threading.Thread(target=_rank, args=(native, tr, r, world, whole, K, mode, sweeps, out, errs)) for r in range(world)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    if errs:
+        raise errs[0]
+    ref = one_handle(native, whole, K, sweeps)
+    z = np.concatenate([out[r]["z"] for r in range(world)])
+    assert z.size == whole.num_tokens
+    assert_bit_equal(z, ref["z"], "z")
+    assert_bit_equal(np.sum([out[r]["mh"] for r in range(world)], axis=0), ref["mh"], "summed MH counters")
+    assert int(ref["mh"].sum()) == sweeps * whole.num_tokens
+    for r in range(world):
+        assert out[r]["how"]["sparse"] == (mode == "sparse")
+        assert out[r]["kernel"].startswith(KERNEL)
+        assert_bit_equal(out[r]["nwk"], ref["nwk"], "n_wk rank %d" % r)
+        assert_bit_equal(out[r]["nk"], ref["nk"], "n_k rank %d" % r)
+        assert_bit_equal(out[r]["phi"], ref["phi"], "the point estimate rank %d" % r)
+        for i, name in enumerate(("ps", "a", "typeNorm")):
+            assert_bit_equal(out[r]["tables"][i], ref["tables"][i], "%s rank %d" % (name, r))
+        for i, name in enumerate(("nw", "lists")):
+            assert_bit_equal(out[r]["lists"][i], ref["lists"][i], "%s rank %d" % (name, r))
+
+
+def test_one_process_group_equals_the_restatement(native, oracle):
+    """ggs_group_create / ggs_group_set_z / ggs_group_sweep with the one device there is: the merge is the grouped gather of the
+    count slices, as for scheme=collapsed."""
+    c = random_corpus(150, 300, 90, seed=3, empty_every=6)
+    K = 40
+    z0 = java_lcg_initial_z(c.num_tokens, K, 9)
+    g = native.GGSGroup(K, c.num_types, 0.1, 0.01, SEED, device_ids=[0], flags=native.FLAG_LIGHTCOLLAPSED)
+    h = g.handles[0]
+    h.set_corpus(c.doc_ptr, c.tokens)
+    g.set_z([z0], redraw_phi=True)
+    g.sweep(3)
+    g.gather_counts()
+    m = R.Model(K, c.num_types, 0.1, 0.01, SEED, c.doc_ptr, c.tokens, z0)
+    m.sweep(3)
+    assert_state_equal(h, m, "after the group's 3 sweeps")
+    g.close()
+
+
+# ---- statistics ---------------------------------------------------------------------------------------------------
+def heldout_after(native, flags, train, test, K, sweeps):
+    h = native.GGSHandle(K, train.num_types, 0.1, 0.01, 4711, flags=flags)
+    h.set_corpus(train.doc_ptr, train.tokens)
+    h.init_z_java_lcg(4711)
+    h.init_phi()
+    out = []
+    done = 0
+    for s in sweeps:
+        h.sweep(s - done)
+        done = s
+        h.set_test_corpus(test.doc_ptr, test.tokens)
+        out.append(h.heldout_log_likelihood(100)[0])
+    h.close()
+    return out
+
+
+def test_heldout_likelihood_against_the_collapsed_parallel_schedule(native):
+    """The recipe of test_lightpclda_gpu.py::test_heldout_likelihood_against_pcgs; the yardstick is scheme=collapsed's parallel
+    schedule after its 300 sweeps.  An MH chain moves less per sweep, so the gaps at S = 300, 600 and 1200 are printed
+    (DESIGN.md 6g records them) and the project's 1 % is asserted at S = 1200."""
+    full = synthetic_lda_corpus(2200, 2000, 60, true_topics=20, seed=99)
+    train, _, _ = full.shard(0, 2000)
+    test, _, _ = full.shard(2000, 2200)
+    K = 20
+    co = heldout_after(native, native.FLAG_COLLAPSED, train, test, K, [300])[0]
+    lc = heldout_after(native, native.FLAG_LIGHTCOLLAPSED, train, test, K, [300, 600, 1200])
+    gaps = [abs(v - co) / abs(co) for v in lc]
+    print("held-out log likelihood: collapsed (parallel schedule) after 300 sweeps %.2f; lightcollapsed after 300 / 600 / 1200 sweeps %s, gaps %s"
+          % (co, ["%.2f" % v for v in lc], ["%.4f" % x for x in gaps]))
+    assert gaps[-1] < 0.01
+
+
+# ---- the interface ------------------------------------------------------------------------------------------------
+def test_launch_info_z_form_and_mh_stats(native, cats):
+    import ctypes as C
+    g = native.GGSHandle(20, cats.num_types, 0.1, 0.01, SEED, flags=native.FLAG_LIGHTCOLLAPSED)
+    g.set_corpus(cats.doc_ptr, cats.tokens)
+    assert (g.mh_stats() == 0).all()
+    zk, zf, zc = C.c_int32(), C.c_int32(), C.c_int32()
+    assert g._L.ggs_get_z_form(g._h, C.byref(zk), C.byref(zf), C.byref(zc)) == 0
+    assert zk.value == 9 and zf.value == 0
+    info = g.launch_info()
+    assert info["z_kernel"] == "lightcollapsed_wave_kernel (wave per document)" and info["lds_bytes_z"] == 4 * 20 and info["num_chunks"] == cats.num_docs
+    g.init_z_java_lcg(1)
+    g.init_phi()
+    g.sweep(3)
+    s = g.mh_stats()
+    assert s.dtype == np.int64 and s.sum() == 3 * cats.num_tokens and (s > 0).all()
+    g.set_corpus(cats.doc_ptr, cats.tokens)                         # cumulative since set_corpus
+    assert (g.mh_stats() == 0).all()
+    g.close()
+
+
+def test_paranoid_sweeps_the_likelihoods_and_the_split_sweep(native, cats):
+    g = native.GGSHandle(20, cats.num_types, 0.1, 0.01, SEED, flags=native.FLAG_LIGHTCOLLAPSED | native.FLAG_PARANOID)
+    g.set_corpus(cats.doc_ptr, cats.tokens)
+    g.init_z_java_lcg(1)
+    g.init_phi()
+    g.sweep(2)
+    g.check_invariants()
+    g.sweep_begin()                                                 # the two halves are one sweep
+    g.sweep_end()
+    h = native.GGSHandle(20, cats.num_types, 0.1, 0.01, SEED, flags=native.FLAG_LIGHTCOLLAPSED)
+    h.set_corpus(cats.doc_ptr, cats.tokens)
+    h.init_z_java_lcg(1)
+    h.init_phi()
+    h.sweep(3)
+    assert_bit_equal(g.get_z(), h.get_z(), "z after 2 + 1 sweeps")
+    doc_side, topic_side = g.model_log_likelihood()
+    assert np.isfinite(doc_side) and np.isfinite(topic_side) and doc_side + topic_side < 0
+    g.set_test_corpus(cats.doc_ptr, cats.tokens)
+    total, per_doc = g.heldout_log_likelihood(10)
+    assert np.isfinite(total) and total < 0 and per_doc.size == cats.num_docs
+    phi = g.get_phi()
+    assert np.allclose(phi.sum(axis=1), 1.0)
+    g.close()
+    h.close()
+
+
+def test_unsupported_calls_and_misuse(native, cats):
+    for other in (native.FLAG_COLLAPSED, native.FLAG_PCGS, native.FLAG_POLYAURN, native.FLAG_SPALIAS, native.FLAG_LIGHTPCLDA, native.FLAG_POLYAURN_SPARSE):
+        with pytest.raises(native.GGSError) as e:
+            native.GGSHandle(5, 10, 0.1, 0.01, 1, flags=native.FLAG_LIGHTCOLLAPSED | other)
+        assert e.value.code == native.ERR_BAD_ARG
+    with pytest.raises(native.GGSError) as e:
+        native.GGSHandle(4097, 10, 0.1, 0.01, 1, flags=native.FLAG_LIGHTCOLLAPSED)
+    assert e.value.code == native.ERR_UNSUPPORTED
+    g = native.GGSHandle(5, cats.num_types, 0.1, 0.01, 1, flags=native.FLAG_LIGHTCOLLAPSED)
+    g.set_corpus(cats.doc_ptr, cats.tokens)
+    g.init_z_java_lcg(1)
+    g.init_phi()
+    # no Phi to set and no theta kept (the handle allocates neither): unsupported too, unlike under FLAG_COLLAPSED
+    for call, code in ((lambda: g.sample_z_given_phi(1), native.ERR_UNSUPPORTED), (g.log_posterior, native.ERR_UNSUPPORTED),
+                       (lambda: g.set_phi(np.full((5, cats.num_types), 1.0 / cats.num_types)), native.ERR_UNSUPPORTED),
+                       (g.get_theta, native.ERR_UNSUPPORTED), (lambda: g.collapsed_serial_sweep(1, 1), native.ERR_STATE)):
+        with pytest.raises(native.GGSError) as e:
+            call()
+        assert e.value.code == code
+    g.sweep(1)                                                      # the refusals left the handle usable
+    g.close()
+    for flags in (native.FLAG_PCGS, native.FLAG_COLLAPSED):
+        h = native.GGSHandle(5, 10, 0.1, 0.01, 1, flags=flags)
+        with pytest.raises(native.GGSError) as e:
+            h.mh_stats()
+        assert e.value.code == native.ERR_STATE
+        with pytest.raises(native.GGSError) as e:
+            h.word_topic_lists()
+        assert e.value.code == native.ERR_STATE
+        h.close()
+
+
+# ---- the host mirrors and the driver ------------------------------------------------------------------------------
+def test_host_mirror_end_to_end(native, cats):
+    from ldagroupedgibbssampler_amd import sampler
+    cfg = sampler.SimpleLDAConfiguration(scheme="lightcollapsed", topics=20, alpha=0.1, beta=0.01, iterations=5, seed=42, exec_time=None)
+    m = sampler.create_model(cfg, "lightcollapsed")
+    assert type(m) is sampler.CollapsedLightLDA
+    m.setRandomSeed(cfg.get_seed())
+    m.addInstances(cats)
+    m.sample(5)
+    assert m.getCurrentIteration() == 5
+    phi = np.asarray(m.getPhi())
+    assert phi.shape == (20, cats.num_types) and not np.isnan(phi).any()
+    assert np.allclose(phi.sum(axis=1), 1.0)
+    n_wk = np.asarray(m.getTypeTopicMatrix())
+    assert n_wk.sum() == cats.num_tokens
+    assert m.getMHStats().sum() == 5 * cats.num_tokens
+    ps, a, tn = m.getAliasTables()
+    nw, lists = m.getWordTopicLists()
+    want = R.build_tables(n_wk, n_wk.sum(axis=0), 0.01)
+    assert_bit_equal(tn, want[2], "typeMass of the model's counts")
+    assert_bit_equal(nw, want[3], "nw of the model's counts")
+    assert_bit_equal(lists, want[4], "lists of the model's counts")
+    with pytest.raises(NotImplementedError):
+        m.getTheta()
+    with pytest.raises(NotImplementedError):
+        m.sampleZGivenPhi(1)
+
+
+def test_cpp_mirror_end_to_end(native, tmp_path):
+    """include/ggs_sampler.hpp with config_.lightcollapsed: the C++ mirror's z and topic totals are the handle's."""
+    exe = os.path.join(ROOT, "examples", "ggs_host_demo")
+    if not os.path.exists(exe):
+        pytest.fail("examples/ggs_host_demo is not built: run __graft_entry__.build()")
+    c = random_corpus(60, 90, 70, seed=12, empty_every=8)
+    path = os.path.join(str(tmp_path), "corpus.txt")
+    with open(path, "w") as f:
+        f.write("%d %d\n" % (c.num_docs, c.num_types))
+        for d in range(c.num_docs):
+            t = c.tokens[c.doc_ptr[d]:c.doc_ptr[d + 1]]
+            f.write(" ".join([str(len(t))] + [str(int(x)) for x in t]) + "\n")
+    K, alpha, beta, seed, its = 6, 0.5, 0.1, 99, 3
+    logs = tmp_path / "logs"
+    logs.mkdir()
+    out = subprocess.run([exe, path, str(K), str(alpha), str(beta), str(seed), str(its), str(logs), "lightcollapsed"], capture_output=True, text=True,
+                         timeout=120)
+    assert out.returncode == 0, out.stderr
+    lines = dict(l.split(" ", 1) for l in out.stdout.strip().splitlines())
+    g = native.GGSHandle(K, c.num_types, alpha, beta, seed, flags=native.FLAG_LIGHTCOLLAPSED)
+    g.set_corpus(c.doc_ptr, c.tokens)
+    g.init_z_java_lcg(seed)
+    g.init_phi()
+    g.sweep(its)
+    assert lines["iteration"] == "%d hooks %d %d" % (its, its, its)
+    assert np.array_equal(np.array(lines["z"].split(), np.int32), g.get_z())
+    assert np.array_equal(np.array(lines["nk"].split(), np.int32), g.get_topic_totals())
+    assert "z_3.csv" in os.listdir(logs)
+    g.close()
+
+
+def test_run_dataset_writes_the_driver_files(tmp_path):
+    ds = os.path.join(ROOT, "tests", "golden", "datasets", "cats.txt")
+    out = tmp_path / "run"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "run_dataset.py"), ds, "--scheme", "lightcollapsed", "--topics", "5",
+                        "--iterations", "3", "--seed", "7", "--out", str(out)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    files = os.listdir(out)
+    assert "type_topic_counts.csv" in files and any(f.startswith("phi") for f in files), files
