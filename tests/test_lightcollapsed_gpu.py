@@ -4,7 +4,10 @@ tables (ps / a, type_norm), the words' lists and their lengths; sharded runs aga
 CU; the interface; the held-out likelihood against scheme=collapsed's parallel schedule; the driver and the host mirrors.
 
 There are two kernels, count_alias_build_kernel (the lists and tables over the counts, at the head of every sweep) and
-lightcollapsed_wave_kernel (a wave per document), each with one way through it: no margins, no replay."""
+lightcollapsed_wave_kernel (a wave per document), each with one way through it: no margins, no replay.  The corpora here are
+random; every comparison of the token step with its two sides equal or one double apart, and the table build on words
+whose topics all weigh the same, are in tests/test_lightcollapsed_knife_edge_gpu.py (rows of
+tests/lightcollapsed_knife_edge.py, their power shown by tests/test_lightcollapsed_knife_edge_model.py)."""
 import os
 import subprocess
 import sys
