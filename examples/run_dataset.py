@@ -21,9 +21,11 @@ def main():
     ap.add_argument("dataset")
     ap.add_argument("--stoplist", default=None, help="one stop word per line (LDAConfiguration: stoplist.txt)")
     ap.add_argument("--rare-threshold", type=int, default=0)
-    ap.add_argument("--scheme", default="ggs", choices=["ggs", "pcgs", "collapsed", "polyaurn", "spalias", "spalias_priors", "lightpclda", "polyaurn_sparse", "lightcollapsed"])
+    ap.add_argument("--scheme", default="ggs", choices=["ggs", "pcgs", "collapsed", "polyaurn", "spalias", "spalias_priors", "lightpclda", "polyaurn_sparse", "lightcollapsed", "nzvsspalias"])
     ap.add_argument("--topic-priors", default=None, metavar="FILE",
                     help="scheme spalias_priors: lines `topic,word,word,...`; those words may only belong to that topic (topic_prior_filename)")
+    ap.add_argument("--vs-prior", type=float, default=0.5, metavar="X",
+                    help="scheme nzvsspalias: the prior probability that a cell without tokens stays in its topic (variable_selection_prior)")
     ap.add_argument("--topics", type=int, default=20)
     ap.add_argument("--alpha", type=float, default=0.1)
     ap.add_argument("--beta", type=float, default=0.01)
@@ -46,8 +48,12 @@ def main():
         os.makedirs(args.out, exist_ok=True)
     cfg = SimpleLDAConfiguration(scheme=args.scheme, topics=args.topics, alpha=args.alpha, beta=args.beta, iterations=args.iterations,
                                  seed=args.seed, exec_time=None, compute_likelihood=bool(args.out), log_dir=args.out,
-                                 topic_prior_filename=args.topic_priors)
-    model = create_model(cfg)
+                                 topic_prior_filename=args.topic_priors, variable_selection_prior=args.vs_prior)
+    if args.scheme == "nzvsspalias":                          # not in create_model's registry: the class itself
+        from ldagroupedgibbssampler_amd.sampler import NZVSSpaliasUncollapsedParallelLDA
+        model = NZVSSpaliasUncollapsedParallelLDA(cfg)
+    else:
+        model = create_model(cfg)
     model.setRandomSeed(cfg.get_seed())
     model.addInstances(c)
     model.sample(args.iterations)

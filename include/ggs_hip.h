@@ -132,7 +132,7 @@ enum {
                                      the tokens took.  K up to 4096, any document length.  With GGS_FLAG_COLLAPSED,
                                      GGS_FLAG_POLYAURN, GGS_FLAG_SPALIAS or GGS_FLAG_LIGHTPCLDA: GGS_ERR_BAD_ARG.  A new bit, not a
                                      new ABI version. */
-  GGS_FLAG_LIGHTCOLLAPSED = 1 << 8  /* scheme=lightcollapsed (CollapsedLightLDA, ParallelLDA.java:429-433): the collapsed model --
+  GGS_FLAG_LIGHTCOLLAPSED = 1 << 8, /* scheme=lightcollapsed (CollapsedLightLDA, ParallelLDA.java:429-433): the collapsed model --
                                      no theta, no Phi; counts, tokensPerTopic, merge, exchange, ggs_get_phi (the point estimate),
                                      the likelihoods and ggs_check_invariants exactly as under GGS_FLAG_COLLAPSED -- under the
                                      LightLDA z step: per token a word proposal from the word's alias table over the counts and
@@ -152,6 +152,37 @@ enum {
                                      length.  With any of GGS_FLAG_COLLAPSED, GGS_FLAG_PCGS, GGS_FLAG_POLYAURN, GGS_FLAG_SPALIAS,
                                      GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE: GGS_ERR_BAD_ARG.  A new bit, not a new ABI
                                      version. */
+  GGS_FLAG_NZVSSPALIAS = 1 << 9   /* scheme=nzvsspalias (NZVSSpaliasUncollapsedParallelLDA, ParallelLDA.java; types/VSDirichlet.java:34-112):
+                                     the pcgs model (implied: GGS_FLAG_PCGS is set internally; initial Phi, counts and alias tables as
+                                     under GGS_FLAG_SPALIAS) with a VARIABLE-SELECTION Dirichlet for Phi, which has exact zeros.
+                                     Phi of a sweep, per topic k: n_k = the topic's int token count, s = the zeros of the old row; the
+                                     cells are visited in index order.  A cell with a count is drawn and leaves s alone.  A cell
+                                     without one computes a = s * beta, r = exp(lgS(a + beta) + lgS(a + n_k) - lgS(a + beta + n_k)
+                                     - lgS(a)) * (pi / (1 - pi)), p = r / (1 + r) (lgS = Dirichlet.logGammaStirling, exp = StrictMath's)
+                                     and takes U, the first uniform of the stream GGS_PURPOSE_VS, element k*V + v: U > p leaves it
+                                     UNDRAWN, +0.0 (s++ if the old cell was not 0.0), otherwise it is drawn (s-- if it was).  s == 0:
+                                     p = 0 with n_k > 0 (lgS(0) = +inf), NaN with n_k == 0, and U > NaN is false: drawn.  p > 1 or
+                                     p < 0 (the reference throws): GGS_ERR_INVARIANT.  A drawn cell holds Gamma(n + beta) from the stream
+                                     GGS_PURPOSE_PHI of element k*V + v (an undrawn cell uses none of it), no clamp: an underflow to 0.0
+                                     is a drawn cell that holds 0.0.  Every cell is divided by the row's index-order sum; ours: a row
+                                     whose sum is 0 becomes all +0.0 (the reference writes NaN).  pi is
+                                     ggs_set_variable_selection_prior's, 0.5 by default.  The device solves the chain in parallel and
+                                     proves the sequential result (csrc/ggs_phi_vs.hpp); ggs_get_vs_stats counts its rounds.
+                                     Lists (ggs_get_word_topic_lists): after a sweep nzw[w] = the topics whose cell (k, w) was DRAWN,
+                                     ascending -- not phi != 0.0; after ggs_init_phi and the redraw of ggs_set_z every list is empty, as
+                                     in the reference, so the first z step draws from the alias tables alone; after ggs_set_phi
+                                     (ours; the reference leaves them stale) the cells with phi != 0.0.
+                                     The z step is GGS_FLAG_POLYAURN_SPARSE's, formula for formula, except that a token without a
+                                     candidate (n == 0) draws sample(w, U) from its word's alias table (:252-254; i == K:
+                                     GGS_ERR_INVALID_TOPIC).  ggs_get_sparse_stats counts such tokens in out[2].
+                                     With GGS_FLAG_SAVE_PHI_MEAN the mean stays zero while n_sampled advances: the reference's
+                                     loopOverTopics override never adds to it.  With an exchange a rank runs the indicator chain of
+                                     its own topic slice (counts [V][Ksm] from the reduce-scatter, the old Phi from its full phiT)
+                                     and every topic's drawn set reaches every rank inside the all-gathers of the gammas: an undrawn
+                                     cell travels as -0.0, a drawn one that underflowed as +0.0, and the sign is cleared on arrival.
+                                     Results are bit-identical to one handle.  K up to 4096, any document length.  With any of GGS_FLAG_COLLAPSED,
+                                     GGS_FLAG_POLYAURN, GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE,
+                                     GGS_FLAG_LIGHTCOLLAPSED: GGS_ERR_BAD_ARG.  A new bit, not a new ABI version. */
 };
 
 /* RNG stream addressing.  The reference draws from ThreadLocalRandom and a
@@ -164,7 +195,8 @@ enum {
   GGS_PURPOSE_THETA = 2,   /* elem = global doc index * K + k    */
   GGS_PURPOSE_PHI = 3,     /* elem = k * V + v                   */
   GGS_PURPOSE_INIT_PHI = 4,/* elem = k * V + v                   */
-  GGS_PURPOSE_HELDOUT = 5  /* elem = global test doc * numParticles + particle; one uniform per in-vocabulary token */
+  GGS_PURPOSE_HELDOUT = 5, /* elem = global test doc * numParticles + particle; one uniform per in-vocabulary token */
+  GGS_PURPOSE_VS = 6       /* elem = k * V + v; one uniform: the variable-selection indicator (GGS_FLAG_NZVSSPALIAS) */
 };
 #define GGS_MAX_BLOCKS 4096
 
@@ -416,14 +448,15 @@ int ggs_get_z_parts(ggs_handle *h, int32_t *parts);
 /* Which z kernel(s) the sweeps of the current corpus run, so that a benchmark line can NAME what it timed instead of
  * assuming it: *kernel = 0 whole-row tile kernel, 1 score-register kernels (K <= 160), 2 one-pass streaming kernel,
  * 3 its two-pass cross-check, 4 pcgs lane-per-document, 5 pcgs wave-per-document, 6 spalias wave-per-document,
- * 7 lightpclda wave-per-document, 8 polyaurn_sparse wave-per-document; *form (kernel 1 only, else 0) =
+ * 7 lightpclda wave-per-document, 8 polyaurn_sparse wave-per-document, 9 lightcollapsed wave-per-document,
+ * 10 nzvsspalias wave-per-document; *form (kernel 1 only, else 0) =
  * 1 split (cold chunks and hot chunks as two kernels side by side), 2 fused (one kernel takes both in turn);
  * *calibrated = 1 once the first z step of the corpus has timed both forms and kept the faster (0 before that, and
  * when a form is forced or there is nothing to split).  ABI version 4. */
 int ggs_get_z_form(ggs_handle *h, int32_t *kernel, int32_t *form, int32_t *calibrated);
 /* ---- primitives, exported so the parity tests can pin each layer ----------- */
 int ggs_debug_philox(int32_t device_id, int64_t n, const uint32_t *ctr /*n*4*/, const uint32_t *key /*n*2*/, uint32_t *out /*n*4*/);
-int ggs_debug_math(int32_t device_id, int32_t op /*0 log,1 pow,2 sqrt,3 div*/, int64_t n, const double *x, const double *y, double *out);
+int ggs_debug_math(int32_t device_id, int32_t op /*0 log,1 pow,2 sqrt,3 div,4 exp*/, int64_t n, const double *x, const double *y, double *out);
 int ggs_debug_draw(int32_t device_id, int32_t kind /*0 uniform,1 gaussian,2 gamma (general loops),3 gamma as the kernels draw it: first try then general,4 as 3 with first-try results negated*/, uint64_t seed, uint32_t iteration,
                    uint32_t purpose, uint64_t elem0, int64_t n, const double *shape, double *out, int32_t *status);
 /* scheme=polyaurn's Poisson draw (PoissonFixedCoeffSampler.java:31-50, PolyaUrnDirichlet.java:102-107; GGS_FLAG_POLYAURN):
@@ -435,7 +468,7 @@ int ggs_debug_poisson(int32_t device_id, double beta, int32_t threshold, uint64_
  * product kernel from phi [K][V] and alpha [K]: ps [V][K], a [V][K] and type_norm [V] = the k-order sum of phi[k][w] * alpha[k].
  * A draw x in [0, 1) from word w's table: ups = x * K, i = (int)ups, topic = (ups - i) > ps[w][i] ? a[w][i] : i.  K up to 4096. */
 int ggs_debug_alias(int32_t device_id, int32_t V, int32_t K, const double *phi, const double *alpha, double *ps, int32_t *a, double *type_norm);
-/* the tables of the handle's current Phi (GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA or GGS_FLAG_POLYAURN_SPARSE; GGS_ERR_STATE
+/* the tables of the handle's current Phi (GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE or GGS_FLAG_NZVSSPALIAS; GGS_ERR_STATE
  * otherwise or before the first Phi); any of the three outputs may be null.  GGS_FLAG_LIGHTCOLLAPSED: the tables of the handle's
  * current counts, which the next sweep builds at its head (after ggs_set_corpus, outside a split sweep): the call itself
  * rebuilds all V lists and tables from the corpus-wide counts, overwriting those the last z step used, and with an exchange
@@ -476,13 +509,29 @@ int ggs_get_mh_stats(ggs_handle *h, int64_t out[3]);
  * topics[w][0 .. nw[w]) those topics in ascending order, -1 behind them.  Either output may be null.  GGS_ERR_STATE without
  * GGS_FLAG_POLYAURN_SPARSE or before the first Phi.  GGS_FLAG_LIGHTCOLLAPSED: the lists of the handle's current counts, nw[w] = the
  * number of topics with n_wk > 0 (0 for a word without tokens); the same rebuild and, with an exchange, the same collective as
- * ggs_get_alias_tables under that flag. */
+ * ggs_get_alias_tables under that flag.  GGS_FLAG_NZVSSPALIAS: the lists as that flag defines them (the drawn cells). */
 int ggs_get_word_topic_lists(ggs_handle *h, int32_t *nw /*V*/, int32_t *topics /*[V][K]*/);
 /* scheme=polyaurn_sparse's counters, cumulative since ggs_set_corpus, every token in exactly one of the first three:
  * out[0] tokens that walked the word's list, out[1] tokens that walked the document's list, out[2] tokens drawn uniformly
  * (no candidate), out[3] the sum of n, the number of candidates, over all tokens.  GGS_ERR_STATE without
- * GGS_FLAG_POLYAURN_SPARSE. */
+ * GGS_FLAG_POLYAURN_SPARSE or GGS_FLAG_NZVSSPALIAS (there out[2] counts the tokens drawn from the alias table for want of a
+ * candidate). */
 int ggs_get_sparse_stats(ggs_handle *h, int64_t out[4]);
+/* scheme=nzvsspalias: pi, the prior probability that a cell without tokens keeps its place in the topic (vsPrior of
+ * VSDirichlet; 0.5 until set).  Callable until the handle has a Phi (afterwards GGS_ERR_STATE); pi outside (0, 1):
+ * GGS_ERR_BAD_ARG; without GGS_FLAG_NZVSSPALIAS: GGS_ERR_STATE. */
+int ggs_set_variable_selection_prior(ggs_handle *h, double pi);
+/* out[0] the cells the last variable-selection draw left undrawn (0 before the first sweep), out[1] the cells of the
+ * current Phi that are 0.0, out[2] the largest number of rounds a topic's indicator chain took in that draw (with an exchange:
+ * of the rank's own topics; out[0] and out[1] cover all topics on every rank).  out[0] and out[2] are 0 again after
+ * ggs_init_phi, the redraw of ggs_set_z and ggs_set_phi.  GGS_ERR_STATE without GGS_FLAG_NZVSSPALIAS or before the first Phi. */
+int ggs_get_vs_stats(ggs_handle *h, int64_t out[3]);
+/* The indicator chain on its own (csrc/ggs_phi_vs.hpp): counts [K][V] >= 0 and prev_phi [K][V] as the Java arrays,
+ * drawn_out [K][V] = 1 where the cell is drawn (every cell with a count is), s_end [K] = the chain's s behind the last
+ * cell, rounds [K] = the rounds each topic took.  u [K][V], if given, replaces the Philox uniforms (tests put U on
+ * p(s) and one ulp above it).  GGS_ERR_INVARIANT where the reference's range check would throw. */
+int ggs_debug_vs_indicators(int32_t device_id, int32_t V, int32_t K, const int32_t *counts, const double *prev_phi, double beta, double pi, uint64_t seed,
+                            uint32_t iteration, const double *u /*or NULL*/, uint8_t *drawn_out, int32_t *s_end, int32_t *rounds);
 /* replaces: modelLogLikelihood (UPLDA:1644-1758), the Dirichlet-multinomial log likelihood of the current topic
  * assignments, split where a doc-sharded run splits it: doc_side covers THIS handle's documents (sum_d [...] +
  * D*lgS(alphaSum), UPLDA:1674-1694) and topic_side the (replicated) type-topic counts (UPLDA:1701-1747); the model's

@@ -142,6 +142,10 @@ SIGNATURES = {
     "ggs_get_mh_stats": (C.c_int, [_vp, _lp]),
     "ggs_get_word_topic_lists": (C.c_int, [_vp, _ip, _ip]),
     "ggs_get_sparse_stats": (C.c_int, [_vp, _lp]),
+    "ggs_set_variable_selection_prior": (C.c_int, [_vp, C.c_double]),
+    "ggs_get_vs_stats": (C.c_int, [_vp, _lp]),
+    "ggs_debug_vs_indicators": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _ip, _dp, C.c_double, C.c_double, C.c_uint64, C.c_uint32, _dp,
+                                          C.POINTER(C.c_uint8), _ip, _ip]),
     "ggs_model_log_likelihood": (C.c_int, [_vp, _dp, _dp]),
     "ggs_log_posterior": (C.c_int, [_vp, _dp, _dp]),
     "ggs_set_test_corpus": (C.c_int, [_vp, C.c_int64, _lp, _ip, C.c_int64]),

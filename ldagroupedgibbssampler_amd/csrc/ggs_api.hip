@@ -23,6 +23,7 @@
 #include "ggs_alias.hpp"
 #include "ggs_z_spalias.hpp"
 #include "ggs_z_polyaurn_sparse.hpp"
+#include "ggs_phi_vs.hpp"
 #include "ggs_z_lightpc.hpp"
 #include "ggs_z_lightcollapsed.hpp"
 #include "ggs_loglik.hpp"
@@ -62,20 +63,22 @@ struct Knobs {
   // the handle's
   Knob margin{"GGS_DEBUG_MARGIN"}, replays{"GGS_DEBUG_REPLAYS"}, chain{"GGS_DEBUG_CHAIN"}, guided{"GGS_DEBUG_GUIDED"};
   Knob no_overlap{"GGS_DEBUG_NO_OVERLAP"}, theta_main{"GGS_DEBUG_THETA_MAIN"}, gamma_queue{"GGS_DEBUG_GAMMA_QUEUE"};
-  Knob num_cus{"GGS_DEBUG_NUM_CUS"};
+  Knob num_cus{"GGS_DEBUG_NUM_CUS"}, vs_global{"GGS_DEBUG_VS_GLOBAL"};
 };
 
 constexpr int kThetaBlock = 256;
 
 // What a handle samples and how: derived once from ggs_config::flags (scheme_of).  Every scheme but ggs runs the pcgs
 // machinery: no theta in the chain, a document order instead of chunk lists, the plan's lane / wave / ... entries.
-enum class Scheme { ggs, pcgs, collapsed, polyaurn, spalias, lightpclda, polyaurn_sparse, lightcollapsed };
+enum class Scheme { ggs, pcgs, collapsed, polyaurn, spalias, lightpclda, polyaurn_sparse, lightcollapsed, nzvsspalias };
 constexpr bool pcgs_family(Scheme s) { return s != Scheme::ggs; }
-constexpr bool has_alias(Scheme s) { return s == Scheme::spalias || s == Scheme::lightpclda || s == Scheme::polyaurn_sparse; }
+constexpr bool has_alias(Scheme s) { return s == Scheme::spalias || s == Scheme::lightpclda || s == Scheme::polyaurn_sparse || s == Scheme::nzvsspalias; }
 // the count form: no Phi, the model is the type-topic counts and tokensPerTopic; the sweep's merge is the (word, z) histogram
 constexpr bool count_form(Scheme s) { return s == Scheme::collapsed || s == Scheme::lightcollapsed; }
 constexpr bool has_tables(Scheme s) { return has_alias(s) || s == Scheme::lightcollapsed; }   // ps / a / type_norm [V][K]: over Phi, or (lightcollapsed) over the counts
-constexpr bool has_word_lists(Scheme s) { return s == Scheme::polyaurn_sparse || s == Scheme::lightcollapsed; }
+constexpr bool has_word_lists(Scheme s) { return s == Scheme::polyaurn_sparse || s == Scheme::lightcollapsed || s == Scheme::nzvsspalias; }
+constexpr bool doubly_sparse(Scheme s) { return s == Scheme::polyaurn_sparse || s == Scheme::nzvsspalias; }   // sparse_wave_body<true>: the words' lists and the counters
+constexpr bool sparse_walk(Scheme s) { return s == Scheme::spalias || doubly_sparse(s); }                      // sparse_wave_body: LDS sized by the corpus
 constexpr bool has_mh(Scheme s) { return s == Scheme::lightpclda || s == Scheme::lightcollapsed; }
 constexpr bool poisson_phi(Scheme s) { return s == Scheme::polyaurn || s == Scheme::polyaurn_sparse; }   // Phi drawn as polyaurn draws it
 
@@ -116,9 +119,12 @@ struct LaunchPlan {
   // lightpclda: the same table build and the Metropolis-Hastings step; polyaurn_sparse: the table build, the words' lists and
   // the doubly sparse walk (LDS per corpus); lightcollapsed: the lists and tables over the counts and its Metropolis-Hastings step
   KernelLaunch lane, wave, alias, spalias, lightpc, serial, wordlist, pusparse, countalias, lightcol;
+  // nzvsspalias (ggs_phi_vs.hpp): the indicator chain's three kernels (its LDS comes with V), the list build from the drawn
+  // cells (wordlist stays the build from phi != 0.0, after ggs_set_phi) and the z step
+  KernelLaunch vsbits, vschain, wordmask, nzvs;
   bool wave_forced = false;            // ... because of K; otherwise per corpus (a document of 32 768 tokens or more)
   int32_t alias_wpb = 0;
-  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse, &countalias, &lightcol}; }
+  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse, &countalias, &lightcol, &vsbits, &wordmask, &nzvs}; }   // not vschain: it has static LDS, and its dynamic LDS stays below the default cap
 };
 
 // The phase events of one sweep.  Sweeps are settled (waited for, checked, timed) in batches, so a ring of them:
@@ -193,6 +199,16 @@ struct ggs_handle {
   uint16_t *d_nzw = nullptr;                           // [V][K]
   int32_t *d_nw = nullptr;                             // [V]
   unsigned long long *d_ps_stats = nullptr;            // [4]: ggs_get_sparse_stats, zeroed by ggs_set_corpus
+  // scheme=nzvsspalias (ggs_phi_vs.hpp): the pcgs model under the variable-selection Phi draw and the doubly sparse z step
+  double vs_pi = 0.5;                                  // ggs_set_variable_selection_prior
+  bool vs_global = false;                              // the chain's rows in global scratch: V > kVsLdsMaxV, or GGS_DEBUG_VS_GLOBAL=1
+  int32_t vs_W = 0, vs_pitch = 0;                      // words of a topic's bit row: ceil(V / 32); of a word's mask row: ceil(K / 32)
+  uint32_t *d_vs_cz = nullptr, *d_vs_pz = nullptr, *d_vs_und = nullptr;   // [K][vs_W]: count == 0, prevPhi == 0.0, the undrawn cells
+  uint32_t *d_vs_mask = nullptr;                       // [V][vs_pitch]: the undrawn cells in zero_mask's layout
+  int32_t *d_vs_work = nullptr, *d_vs_s_end = nullptr, *d_vs_rounds = nullptr;   // [K][2][vs_W] (vs_global only), [K], [K]
+  unsigned long long *d_vs_zero = nullptr;             // [1] ggs_get_vs_stats's count of zero cells
+  enum class VsLists { empty, drawn, nonzero } vs_lists = VsLists::empty;   // what the words' lists hold: nothing (the initial Phi), the last draw's drawn cells, phi != 0.0 (ggs_set_phi)
+  bool vs_drawn = false;                               // a variable-selection draw has run: d_vs_und, d_vs_rounds are its
   uint64_t *d_lcg = nullptr;                           // ggs_collapsed_serial_sweep: the java.util.Random state
   bool lcg_ready = false;
   int32_t num_hot = 0;
@@ -395,6 +411,7 @@ int check_status(ggs_handle *h) {
     return set_err(h, GGS_ERR_INVALID_TOPIC, h->scheme == Scheme::collapsed ? "SimpleLDA: New topic not sampled." /* MSLDA:216-218 */ : h->scheme == Scheme::lightcollapsed ? "Collapsed Light-LDA: Sampled invalid topic." /* CollapsedLightLDA.java:957-959 */ : "LDAGroupedGibbsSampler: Topic sampled is invalid!");
   if (st & ST_NEGATIVE_COUNT) return set_err(h, GGS_ERR_NEGATIVE_COUNT, "Negative count for topic (Invalid count!)");
   if (st & ST_BAD_SHAPE) return set_err(h, GGS_ERR_BAD_ARG, "alpha and beta must be strictly positive (gamma shape <= 0)");
+  if (st & ST_INVARIANT) return set_err(h, GGS_ERR_INVARIANT, "Inconsistent Indicator probability");   // VSDirichlet.java:55
   return set_err(h, GGS_ERR_RNG_EXHAUSTED, "a gamma rejection loop exceeded GGS_MAX_BLOCKS Philox blocks");
 }
 
@@ -656,6 +673,29 @@ int launch_magnitude(ggs_handle *h) {
 // holds the whole old phiT and sums it for itself -- taken before anything overwrites phiT, unguided, in work space of its own.
 // The initial draw runs to its end as ever and is then multiplied by the priors (phi_apply_priors).
 bool conditional_phi(const ggs_handle *h, bool initial) { return h->have_priors && !initial; }
+// scheme=nzvsspalias: the sweep draw is the variable-selection one (ggs_phi_vs.hpp); the initial draw is pcgs's
+bool vs_phi(const ggs_handle *h, bool initial) { return h->scheme == Scheme::nzvsspalias && !initial; }
+// The indicator chain of the topics [k0, k0 + Ks) from their counts cnt [V][cnt_pitch] (tokensPerTopic in n_k) and the Phi now
+// in d_phiT: the undrawn cells into d_vs_und (by topic) and d_vs_mask (by word).  Before anything overwrites phiT.
+int launch_vs_chain(ggs_handle *h, const int32_t *cnt, int32_t cnt_pitch, int32_t Ks, int32_t k0, const int32_t *n_k) {
+  if (Ks <= 0) return GGS_OK;
+  VsBitsParams bp{};
+  bp.cnt = cnt; bp.phiT = h->d_phiT; bp.cz = h->d_vs_cz; bp.pz = h->d_vs_pz;
+  bp.cnt_pitch = cnt_pitch; bp.Kp = h->Kp; bp.k0 = k0; bp.Ks = Ks; bp.V = h->V; bp.W = h->vs_W;
+  void *bargs[] = {&bp};
+  HIP_TRY(h, launch(h, h->plan.vsbits, (int64_t)h->vs_W * ((Ks + 63) / 64), bargs, h->stream));
+  VsChainParams cp{};
+  cp.cz = h->d_vs_cz; cp.pz = h->d_vs_pz; cp.und = h->d_vs_und; cp.work = h->d_vs_work; cp.n_k = n_k; cp.u = nullptr;
+  cp.s_end = h->d_vs_s_end; cp.rounds = h->d_vs_rounds; cp.status = h->d_status; cp.seed = h->seed; cp.iteration = (uint32_t)h->iteration;
+  cp.Ks = Ks; cp.k0 = k0; cp.V = h->V; cp.W = h->vs_W; cp.beta = h->beta; cp.odds = h->vs_pi / (1 - h->vs_pi);
+  void *cargs[] = {&cp};
+  HIP_TRY(h, hipLaunchKernel(h->plan.vschain.fn, dim3((unsigned)Ks), dim3(kVsBlock), cargs, (size_t)h->plan.vschain.lds, h->stream));   // a workgroup per topic
+  hipLaunchKernelGGL(vs_mask_kernel, dim3(grid_for((int64_t)h->V * h->vs_pitch, 256)), dim3(256), 0, h->stream, h->d_vs_und, h->vs_W, k0, Ks, h->V, h->vs_pitch,
+                     h->d_vs_mask);
+  HIP_TRY(h, hipGetLastError());
+  h->vs_drawn = true;
+  return GGS_OK;
+}
 int launch_sum_phi(ggs_handle *h) {
   launch_column_sum<double, false>(h, h->d_phiT, h->Kp, h->K, h->d_pr_sum_phi, nullptr, false, false, h->d_pr_pref, h->d_pr_fn);
   HIP_TRY(h, hipGetLastError());
@@ -706,6 +746,10 @@ int phi_slice_gamma(ggs_handle *h, bool initial, const int32_t *cnt, int32_t cnt
   if (conditional_phi(h, initial)) {                   // the masked draw; its sums' guess is still the magnitudes' (any guess will do)
     gp.zero_mask = h->d_pr_mask; gp.mask_pitch = h->pr_pitch;
     hipLaunchKernelGGL(phi_gamma_kernel<true>, grid, dim3(64), 0, h->stream, gp);
+  } else if (vs_phi(h, initial)) {                     // the cells the indicator chain left undrawn are masked; shape = beta + n
+    gp.zero_mask = h->d_vs_mask; gp.mask_pitch = h->vs_pitch;
+    gp.undrawn_negative = h->xg ? 1 : 0;               // the drawn set travels in the gathered gammas' signs of zero (phi_step_c)
+    hipLaunchKernelGGL(phi_gamma_vs_kernel, grid, dim3(64), 0, h->stream, gp);
   } else {
     hipLaunchKernelGGL(phi_gamma_kernel<false>, grid, dim3(64), 0, h->stream, gp);
   }
@@ -767,10 +811,14 @@ int launch_phi_slice(ggs_handle *h, bool initial, const int32_t *cnt, int32_t cn
     HIP_TRY(h, hipGetLastError());
     return GGS_OK;
   }
-  if ((rc = launch_magnitude_on(h, cnt, cnt_pitch, Ks, mag, n_k)) || (rc = phi_slice_gamma(h, initial, cnt, cnt_pitch, Ks, k0, out, out_pitch, mag, 0, h->sum_nseg)) ||
-      (rc = phi_slice_total(h, out, out_pitch, Ks, tot)))
+  // (nzvsspalias: the magnitudes are not the draw's, but their pass leaves tokensPerTopic for the chain and a guess for the sums)
+  if ((rc = launch_magnitude_on(h, cnt, cnt_pitch, Ks, mag, n_k)) || (vs_phi(h, initial) && (rc = launch_vs_chain(h, cnt, cnt_pitch, Ks, k0, n_k))) ||
+      (rc = phi_slice_gamma(h, initial, cnt, cnt_pitch, Ks, k0, out, out_pitch, mag, 0, h->sum_nseg)) || (rc = phi_slice_total(h, out, out_pitch, Ks, tot)))
     return rc;
-  if (conditional_phi(h, initial))                     // one GPU: the slice is the whole matrix, sum_phi's columns are its columns
+  if (vs_phi(h, initial))                              // x / sum, a row of sum 0 all +0.0; the reference's loopOverTopics override never adds to the phi mean
+    hipLaunchKernelGGL(phi_normalise_polyaurn_kernel, dim3(grid_for((int64_t)Ks * h->V, 256, 2)), dim3(256), 0, h->stream, out, tot, Ks, out_pitch, h->V,
+                       static_cast<double *>(nullptr), out == h->d_phiT ? h->d_phiT32 : nullptr, h->plan.Kp32);
+  else if (conditional_phi(h, initial))                     // one GPU: the slice is the whole matrix, sum_phi's columns are its columns
     hipLaunchKernelGGL(phi_normalise_conditional_kernel, dim3(grid_for((int64_t)Ks * h->V, 256, 2)), dim3(256), 0, h->stream, out, tot, h->d_pr_sum_phi, Ks,
                        out_pitch, h->V, phi_mean, out == h->d_phiT ? h->d_phiT32 : nullptr, h->plan.Kp32);
   else
@@ -805,6 +853,9 @@ int phi_step_b1(ggs_handle *h, bool initial) {
   } else if ((rc = launch_magnitude_on(h, h->d_cnt_own, h->Ksm, h->Ks, h->d_mag_own, h->d_n_k_own))) {
     return rc;
   }
+  // nzvsspalias: the indicator chain of the rank's own topics, from their corpus-wide counts and the old Phi (phiT until step C);
+  // d_vs_mask then holds the slice's undrawn cells for the two halves' draws
+  if (vs_phi(h, initial) && (rc = launch_vs_chain(h, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_n_k_own))) return rc;
   if (h->seg_split > 0) {
     if (!poisson_phi(h->scheme) && (rc = phi_slice_gamma(h, initial, h->d_cnt_own, h->Ksm, h->Ks, h->k0, h->d_phi_own, h->Ksm, h->d_mag_own, 0, h->seg_split))) return rc;
     HIP_TRY(h, hipEventRecord(h->ev_half_drawn, h->stream));
@@ -844,12 +895,17 @@ int phi_step_c(ggs_handle *h, bool initial, bool accumulate_mean) {
   rp.phi_mean = accumulate_mean ? h->d_phi_mean : nullptr;
   rp.c0 = (int64_t)half0_elems(h); rp.c1 = (int64_t)half1_elems(h); rp.K = h->K; rp.Kp = h->Kp; rp.V = h->V; rp.Ksm = h->Ksm; rp.v_split = h->v_split;
   rp.phiT32 = h->d_phiT32; rp.Kp32 = h->plan.Kp32; rp.sum_phi = h->d_pr_sum_phi;
-  if (poisson_phi(h->scheme)) hipLaunchKernelGGL(phi_repack_polyaurn_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
+  if (vs_phi(h, initial)) {                            // every topic's undrawn cells from the signs of zero, then the repack that clears them
+    rp.phi_mean = nullptr;                             // the reference's loopOverTopics override never adds to the phi mean
+    hipLaunchKernelGGL(vs_mask_gathered_kernel, dim3(grid_for((int64_t)h->V * h->vs_pitch, 256)), dim3(256), 0, h->stream, rp, h->d_vs_mask, h->vs_pitch);
+    hipLaunchKernelGGL(phi_repack_vs_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
+  } else if (poisson_phi(h->scheme)) hipLaunchKernelGGL(phi_repack_polyaurn_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   else if (conditional_phi(h, initial)) hipLaunchKernelGGL(phi_repack_conditional_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   else hipLaunchKernelGGL(phi_repack_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, rp);
   HIP_TRY(h, hipGetLastError());
   h->have_phi = true;
   h->alias_stale = true;
+  if (h->scheme == Scheme::nzvsspalias) { h->vs_lists = initial ? ggs_handle::VsLists::empty : ggs_handle::VsLists::drawn; if (initial) h->vs_drawn = false; }
   if (h->have_priors && initial) return phi_apply_priors(h);
   return GGS_OK;
 }
@@ -865,11 +921,15 @@ int launch_alias_build(ggs_handle *h) {
   ap.V = h->V; ap.K = h->K; ap.Kp = h->Kp; ap.wpb = h->plan.alias_wpb;
   void *args[] = {&ap};
   HIP_TRY(h, launch(h, h->plan.alias, ((int64_t)h->V + ap.wpb - 1) / ap.wpb, args, h->stream));
-  if (h->scheme == Scheme::polyaurn_sparse) {          // the words' lists of non-zero topics, of the same Phi
+  if (h->scheme == Scheme::nzvsspalias && h->vs_lists == ggs_handle::VsLists::empty) {   // the reference fills no list before its first samplePhi
+    HIP_TRY(h, hipMemsetAsync(h->d_nw, 0, (size_t)h->V * sizeof(int32_t), h->stream));
+  } else if (doubly_sparse(h->scheme)) {               // the words' lists of non-zero topics, of the same Phi (nzvsspalias after a sweep: of its drawn cells)
+    const bool from_mask = h->scheme == Scheme::nzvsspalias && h->vs_lists == ggs_handle::VsLists::drawn;
     WordListParams wp{};
     wp.phiT = h->d_phiT; wp.nzw = h->d_nzw; wp.nw = h->d_nw; wp.V = h->V; wp.K = h->K; wp.Kp = h->Kp;
+    wp.zero_mask = h->d_vs_mask; wp.mask_pitch = h->vs_pitch;
     void *wargs[] = {&wp};
-    HIP_TRY(h, launch(h, h->plan.wordlist, h->V, wargs, h->stream));
+    HIP_TRY(h, launch(h, from_mask ? h->plan.wordmask : h->plan.wordlist, h->V, wargs, h->stream));
   }
   h->alias_stale = false;
   return GGS_OK;
@@ -911,6 +971,7 @@ int launch_phi(ggs_handle *h, bool initial, bool accumulate_mean, Events *E = nu
     return rc;
   h->n_k_valid = true;
   h->have_phi = true;
+  if (h->scheme == Scheme::nzvsspalias) { h->vs_lists = initial ? ggs_handle::VsLists::empty : ggs_handle::VsLists::drawn; if (initial) h->vs_drawn = false; }
   if (h->have_priors && initial && (rc = phi_apply_priors(h))) return rc;
   return launch_alias_build(h);
 }
@@ -1155,6 +1216,15 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
     pl.wordlist = {reinterpret_cast<const void *>(word_list_build_kernel), kWordListBlock, 0, 8};
     pl.pusparse.fn = reinterpret_cast<const void *>(polyaurn_sparse_wave_kernel);
   }
+  if (scheme == Scheme::nzvsspalias) {                 // both list builds, the chain's kernels (LDS by V, a workgroup per topic) and the z step
+    pl.wordlist = {reinterpret_cast<const void *>(word_list_build_kernel), kWordListBlock, 0, 8};
+    pl.wordmask = {reinterpret_cast<const void *>(word_list_mask_kernel), kWordListBlock, 0, 8};
+    pl.vsbits = {reinterpret_cast<const void *>(vs_bits_kernel), 64, 0, 32};
+    const bool global = V > kVsLdsMaxV || (kn.vs_global.set && kn.vs_global.v != 0);
+    pl.vschain = {global ? reinterpret_cast<const void *>(vs_chain_kernel<true>) : reinterpret_cast<const void *>(vs_chain_kernel<false>), kVsBlock,
+                  global ? 0 : (int)vs_chain_lds_bytes((V + 31) / 32), 1};
+    pl.nzvs.fn = reinterpret_cast<const void *>(nzvs_wave_kernel);
+  }
   if (scheme == Scheme::lightpclda) {
     // the resident single-wave workgroups: what the kernel's registers allow (asked of the runtime) and what LDS allows, at
     // most the CU's 32 -- a lone wave issues at a fraction of a SIMD's rate, and the step is a chain of dependent operations
@@ -1177,7 +1247,7 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
 }
 
 const KernelLaunch &pcgs_entry(const LaunchPlan &pl, Scheme s, bool wave) {
-  return s == Scheme::lightcollapsed ? pl.lightcol : s == Scheme::lightpclda ? pl.lightpc : s == Scheme::spalias ? pl.spalias : s == Scheme::polyaurn_sparse ? pl.pusparse : wave ? pl.wave : pl.lane;
+  return s == Scheme::lightcollapsed ? pl.lightcol : s == Scheme::lightpclda ? pl.lightpc : s == Scheme::spalias ? pl.spalias : s == Scheme::polyaurn_sparse ? pl.pusparse : s == Scheme::nzvsspalias ? pl.nzvs : wave ? pl.wave : pl.lane;
 }
 int launch_pcgs_z(ggs_handle *h) {
   if (h->N == 0) return GGS_OK;
@@ -1192,7 +1262,7 @@ int launch_pcgs_z(ggs_handle *h) {
   LightpcParams lp{};
   LightCollapsedParams lc{};
   void *args[] = {&pp, &h->margin_scale};              // the wave-per-document kernel takes both, the lane-per-document kernels the first
-  if (h->scheme == Scheme::spalias || h->scheme == Scheme::polyaurn_sparse) {
+  if (sparse_walk(h->scheme)) {
     // one wave per document over its non-zero topics (ggs_z_spalias.hpp), or over the word's where they are fewer
     // (ggs_z_polyaurn_sparse.hpp: the lists and the counters, null in a spalias handle)
     sp.b = pp; sp.ps = h->d_alias_ps; sp.a = h->d_alias_a; sp.type_norm = h->d_alias_tn; sp.cap = h->sp_cap; sp.margin_scale = h->margin_scale;
@@ -1692,7 +1762,9 @@ int scheme_of(const ggs_config *cfg, Scheme &scheme, int32_t &poisson_L) {
   if ((f & GGS_FLAG_POLYAURN_SPARSE) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA))) return GGS_ERR_BAD_ARG;
   // lightcollapsed is the collapsed model under a z step of its own: none of the other schemes' flags beside it
   if ((f & GGS_FLAG_LIGHTCOLLAPSED) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_PCGS | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA | GGS_FLAG_POLYAURN_SPARSE))) return GGS_ERR_BAD_ARG;
-  scheme = (f & GGS_FLAG_LIGHTCOLLAPSED) ? Scheme::lightcollapsed : (f & GGS_FLAG_POLYAURN_SPARSE) ? Scheme::polyaurn_sparse : (f & GGS_FLAG_LIGHTPCLDA) ? Scheme::lightpclda : (f & GGS_FLAG_SPALIAS) ? Scheme::spalias : (f & GGS_FLAG_POLYAURN) ? Scheme::polyaurn
+  // nzvsspalias is the pcgs model under a Phi draw and a z step of its own
+  if ((f & GGS_FLAG_NZVSSPALIAS) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA | GGS_FLAG_POLYAURN_SPARSE | GGS_FLAG_LIGHTCOLLAPSED))) return GGS_ERR_BAD_ARG;
+  scheme = (f & GGS_FLAG_NZVSSPALIAS) ? Scheme::nzvsspalias : (f & GGS_FLAG_LIGHTCOLLAPSED) ? Scheme::lightcollapsed : (f & GGS_FLAG_POLYAURN_SPARSE) ? Scheme::polyaurn_sparse : (f & GGS_FLAG_LIGHTPCLDA) ? Scheme::lightpclda : (f & GGS_FLAG_SPALIAS) ? Scheme::spalias : (f & GGS_FLAG_POLYAURN) ? Scheme::polyaurn
          : (f & GGS_FLAG_COLLAPSED) ? Scheme::collapsed : (f & GGS_FLAG_PCGS) ? Scheme::pcgs : Scheme::ggs;
   poisson_L = cfg->alias_poisson_threshold == 0 ? 100 : cfg->alias_poisson_threshold;   // LDAConfiguration.java:44
   if (poisson_phi(scheme) && ((f & GGS_FLAG_COLLAPSED) || poisson_L < 1 || poisson_L > kPoissonMaxThreshold)) return GGS_ERR_BAD_ARG;
@@ -1802,6 +1874,20 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     if ((rc = dev_alloc(h, &h->d_nzw, kv)) || (rc = dev_alloc(h, &h->d_nw, (size_t)h->V)) || (rc = dev_alloc(h, &h->d_ps_stats, 4))) return bail(rc);
     if (hipMemset(h->d_nzw, 0, kv * sizeof(uint16_t)) != hipSuccess || hipMemset(h->d_nw, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess ||
         hipMemset(h->d_ps_stats, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
+      return bail(GGS_ERR_HIP);
+  }
+  if (h->scheme == Scheme::nzvsspalias) {              // the lists and counters as polyaurn_sparse's; the chain's rows, the mask, its outputs
+    h->vs_W = (h->V + 31) / 32; h->vs_pitch = (h->K + 31) / 32;
+    h->vs_global = h->plan.vschain.lds == 0;
+    const size_t kw = (size_t)h->K * h->vs_W, vm = (size_t)h->V * h->vs_pitch;
+    if ((rc = dev_alloc(h, &h->d_nzw, kv)) || (rc = dev_alloc(h, &h->d_nw, (size_t)h->V)) || (rc = dev_alloc(h, &h->d_ps_stats, 4)) ||
+        (rc = dev_alloc(h, &h->d_vs_cz, kw)) || (rc = dev_alloc(h, &h->d_vs_pz, kw)) || (rc = dev_alloc(h, &h->d_vs_und, kw)) ||
+        (rc = dev_alloc(h, &h->d_vs_mask, vm)) || (rc = dev_alloc(h, &h->d_vs_s_end, (size_t)h->K)) || (rc = dev_alloc(h, &h->d_vs_rounds, (size_t)h->K)) ||
+        (rc = dev_alloc(h, &h->d_vs_zero, 1)) || (h->vs_global && (rc = dev_alloc(h, &h->d_vs_work, 2 * kw))))
+      return bail(rc);
+    if (hipMemset(h->d_nzw, 0, kv * sizeof(uint16_t)) != hipSuccess || hipMemset(h->d_nw, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess ||
+        hipMemset(h->d_ps_stats, 0, 4 * sizeof(unsigned long long)) != hipSuccess || hipMemset(h->d_vs_und, 0, kw * sizeof(uint32_t)) != hipSuccess ||
+        hipMemset(h->d_vs_mask, 0, vm * sizeof(uint32_t)) != hipSuccess || hipMemset(h->d_vs_rounds, 0, (size_t)h->K * sizeof(int32_t)) != hipSuccess)
       return bail(GGS_ERR_HIP);
   }
   if (poisson_phi(h->scheme)) {
@@ -1932,13 +2018,13 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
     if (h->pcgs_wave && !pl.wave.fn) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=pcgs: a document of 32768 tokens or more with more than 4096 topics");
     h->pcgs_z = pcgs_entry(pl, h->scheme, h->pcgs_wave);
     h->pcgs_items = (has_tables(h->scheme) || h->pcgs_wave) ? (int64_t)L.order.size() : ((int64_t)L.order.size() + 63) / 64;   // a wave or a lane per entry
-    if (h->scheme == Scheme::spalias || h->scheme == Scheme::polyaurn_sparse) {
+    if (sparse_walk(h->scheme)) {
       // the list of a document's non-zero topics holds at most min(K, its length) entries; the resident waves are what LDS allows,
       // at most the CU's 32
       h->sp_cap = (int32_t)std::max<int64_t>(1, std::min<int64_t>(h->K, L.longest));
       h->pcgs_z.lds = (int)spalias_lds_bytes(h->K, h->sp_cap);
       h->pcgs_z.per_cu = lds_workgroups_per_cu(h->pcgs_z.lds, 32);
-      if (h->scheme == Scheme::polyaurn_sparse) {
+      if (doubly_sparse(h->scheme)) {
         // ... and what its registers allow (asked of the runtime): a workgroup of the persistent grid that is not resident
         // would walk its share of the documents only after the others have finished theirs
         int by_regs = 0;
@@ -2514,6 +2600,8 @@ int ggs_set_phi(ggs_handle *h, const double *phi) {
   // UPLDA:1897-1902: `if (savePhiMeans()) phiMean = new double[numTopics][numTypes]` -- the running sum restarts, noSampledPhi keeps counting
   if (h->d_phi_mean) HIP_TRY(h, hipMemsetAsync(h->d_phi_mean, 0, kv * sizeof(double), h->stream));
   h->alias_stale = true;
+  h->vs_lists = ggs_handle::VsLists::nonzero;          // nzvsspalias: the lists of a Phi that was set are its non-zero cells (ours)
+  h->vs_drawn = false;                                 // ... and no draw stands behind it: ggs_get_vs_stats reports none
   if ((rc = launch_alias_build(h))) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->have_phi = true;
@@ -2575,7 +2663,7 @@ int ggs_get_alias_tables(ggs_handle *h, double *ps, int32_t *a, double *type_nor
   if (!h) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (!has_tables(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE or GGS_FLAG_LIGHTCOLLAPSED");
+  if (!has_tables(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE, GGS_FLAG_LIGHTCOLLAPSED or GGS_FLAG_NZVSSPALIAS");
   const size_t kv = (size_t)h->K * h->V;
   if (h->scheme == Scheme::lightcollapsed) {           // the tables of the current counts: what the next sweep builds at its head
     if ((rc = require_ready(h, false)) || (rc = launch_count_alias_build(h))) return rc;
@@ -2615,7 +2703,7 @@ int ggs_get_word_topic_lists(ggs_handle *h, int32_t *nw, int32_t *topics) {
   if (!h) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (!has_word_lists(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_word_topic_lists needs GGS_FLAG_POLYAURN_SPARSE or GGS_FLAG_LIGHTCOLLAPSED");
+  if (!has_word_lists(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_word_topic_lists needs GGS_FLAG_POLYAURN_SPARSE, GGS_FLAG_LIGHTCOLLAPSED or GGS_FLAG_NZVSSPALIAS");
   if (h->scheme == Scheme::lightcollapsed) {           // of the current counts
     if ((rc = require_ready(h, false)) || (rc = launch_count_alias_build(h))) return rc;
   } else {
@@ -2638,11 +2726,41 @@ int ggs_get_sparse_stats(ggs_handle *h, int64_t out[4]) {
   if (!h || !out) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (h->scheme != Scheme::polyaurn_sparse) return set_err(h, GGS_ERR_STATE, "ggs_get_sparse_stats needs GGS_FLAG_POLYAURN_SPARSE");
+  if (!doubly_sparse(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_sparse_stats needs GGS_FLAG_POLYAURN_SPARSE or GGS_FLAG_NZVSSPALIAS");
   unsigned long long v[4];
   HIP_TRY(h, hipMemcpyAsync(v, h->d_ps_stats, sizeof(v), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   for (int i = 0; i < 4; ++i) out[i] = (int64_t)v[i];
+  return GGS_OK;
+}
+int ggs_set_variable_selection_prior(ggs_handle *h, double pi) {
+  if (!h) return GGS_ERR_BAD_ARG;
+  if (h->scheme != Scheme::nzvsspalias) return set_err(h, GGS_ERR_STATE, "ggs_set_variable_selection_prior needs GGS_FLAG_NZVSSPALIAS");
+  if (h->have_phi) return set_err(h, GGS_ERR_STATE, "ggs_set_variable_selection_prior: the handle already has a Phi");
+  if (!(pi > 0.0 && pi < 1.0)) return set_err(h, GGS_ERR_BAD_ARG, "the variable-selection prior must lie in (0, 1)");
+  h->vs_pi = pi;
+  return GGS_OK;
+}
+int ggs_get_vs_stats(ggs_handle *h, int64_t out[3]) {
+  if (!h || !out) return GGS_ERR_BAD_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (h->scheme != Scheme::nzvsspalias) return set_err(h, GGS_ERR_STATE, "ggs_get_vs_stats needs GGS_FLAG_NZVSSPALIAS");
+  if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
+  out[0] = out[1] = out[2] = 0;
+  HIP_TRY(h, hipMemsetAsync(h->d_vs_zero, 0, sizeof(unsigned long long), h->stream));
+  hipLaunchKernelGGL(vs_zero_cells_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 4)), dim3(256), 0, h->stream, h->d_phiT, h->K, h->Kp, h->V, h->d_vs_zero);
+  HIP_TRY(h, hipGetLastError());
+  unsigned long long zero = 0;
+  if ((rc = copy_out(h, &zero, h->d_vs_zero, sizeof zero))) return rc;
+  out[1] = (int64_t)zero;
+  if (!h->vs_drawn) return GGS_OK;                     // no variable-selection draw yet: nothing undrawn, no rounds
+  std::vector<uint32_t> und((size_t)h->V * h->vs_pitch);    // the by-word mask: every topic's cells, with an exchange too
+  std::vector<int32_t> rounds((size_t)h->Ks);               // the chains this handle ran: its own topics
+  if ((rc = copy_out(h, und.data(), h->d_vs_mask, und.size() * sizeof(uint32_t))) || (rc = copy_out(h, rounds.data(), h->d_vs_rounds, rounds.size() * sizeof(int32_t))))
+    return rc;
+  for (uint32_t w : und) out[0] += __builtin_popcount(w);
+  for (int32_t r : rounds) out[2] = std::max<int64_t>(out[2], r);
   return GGS_OK;
 }
 int ggs_get_phi_mean(ggs_handle *h, double *phi_mean, int32_t *n_sampled) {
@@ -2962,7 +3080,7 @@ int ggs_get_warm_tiers(ggs_handle *h, int32_t *tiers, int32_t *warm_words, int32
 int ggs_get_z_form(ggs_handle *h, int32_t *kernel, int32_t *form, int32_t *calibrated) {
   if (!h) return GGS_ERR_BAD_ARG;
   const bool splittable = h->plan.sliced() && h->Cs > h->Cc && h->Cc > 0;
-  if (kernel) *kernel = h->scheme == Scheme::lightcollapsed ? 9 : h->scheme == Scheme::polyaurn_sparse ? 8 : h->scheme == Scheme::lightpclda ? 7 : h->scheme == Scheme::spalias ? 6 : pcgs_family(h->scheme) ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
+  if (kernel) *kernel = h->scheme == Scheme::nzvsspalias ? 10 : h->scheme == Scheme::lightcollapsed ? 9 : h->scheme == Scheme::polyaurn_sparse ? 8 : h->scheme == Scheme::lightpclda ? 7 : h->scheme == Scheme::spalias ? 6 : pcgs_family(h->scheme) ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
   if (form) *form = h->plan.sliced() ? (splittable && h->z_split ? 1 : 2) : 0;
   if (calibrated) *calibrated = (splittable && h->z_split_tried && !h->plan.split_forced && h->plan.split) ? 1 : 0;
   return GGS_OK;
@@ -3064,6 +3182,53 @@ int ggs_debug_alias(int32_t device_id, int32_t V, int32_t K, const double *phi, 
       hipMemcpy(a, da, kv * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(type_norm, dtn, (size_t)V * 8, hipMemcpyDeviceToHost) != hipSuccess)
     return GGS_ERR_HIP;
   return GGS_OK;
+}
+
+int ggs_debug_vs_indicators(int32_t device_id, int32_t V, int32_t K, const int32_t *counts, const double *prev_phi, double beta, double pi, uint64_t seed,
+                            uint32_t iteration, const double *u, uint8_t *drawn_out, int32_t *s_end, int32_t *rounds) {
+  if (V <= 0 || K <= 0 || !counts || !prev_phi || !drawn_out || !s_end || !rounds || !(beta > 0) || !(pi > 0.0 && pi < 1.0) || hipSetDevice(device_id) != hipSuccess)
+    return GGS_ERR_BAD_ARG;
+  const Knobs kn;
+  const bool global = V > kVsLdsMaxV || (kn.vs_global.set && kn.vs_global.v != 0);
+  const size_t kv = (size_t)K * V;
+  const int32_t W = (V + 31) / 32;
+  const size_t kw = (size_t)K * W;
+  std::vector<int32_t> cntT(kv), n_k((size_t)K, 0);     // [V][K], as the handle keeps them
+  std::vector<double> phiT(kv);
+  for (int32_t k = 0; k < K; ++k)
+    for (int32_t v = 0; v < V; ++v) {
+      const int32_t c = counts[(size_t)k * V + v];
+      if (c < 0) return GGS_ERR_BAD_ARG;
+      cntT[(size_t)v * K + k] = c; n_k[(size_t)k] += c;
+      phiT[(size_t)v * K + k] = prev_phi[(size_t)k * V + v];
+    }
+  TmpDev t;
+  auto *dc = static_cast<int32_t *>(t.get(kv * 4)); auto *dphi = static_cast<double *>(t.get(kv * 8)); auto *dnk = static_cast<int32_t *>(t.get((size_t)K * 4));
+  auto *dcz = static_cast<uint32_t *>(t.get(kw * 4)); auto *dpz = static_cast<uint32_t *>(t.get(kw * 4)); auto *dun = static_cast<uint32_t *>(t.get(kw * 4));
+  auto *dwork = static_cast<int32_t *>(t.get(global ? 2 * kw * 4 : 16)); auto *du = static_cast<double *>(t.get(u ? kv * 8 : 16));
+  auto *dse = static_cast<int32_t *>(t.get((size_t)K * 4)); auto *dro = static_cast<int32_t *>(t.get((size_t)K * 4)); auto *dst = static_cast<uint32_t *>(t.get(16));
+  if (!dc || !dphi || !dnk || !dcz || !dpz || !dun || !dwork || !du || !dse || !dro || !dst) return GGS_ERR_HIP;
+  if (hipMemcpy(dc, cntT.data(), kv * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dphi, phiT.data(), kv * 8, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(dnk, n_k.data(), (size_t)K * 4, hipMemcpyHostToDevice) != hipSuccess || (u && hipMemcpy(du, u, kv * 8, hipMemcpyHostToDevice) != hipSuccess) ||
+      hipMemset(dst, 0, 16) != hipSuccess)
+    return GGS_ERR_HIP;
+  VsBitsParams bp{};
+  bp.cnt = dc; bp.phiT = dphi; bp.cz = dcz; bp.pz = dpz; bp.cnt_pitch = K; bp.Kp = K; bp.k0 = 0; bp.Ks = K; bp.V = V; bp.W = W;
+  hipLaunchKernelGGL(vs_bits_kernel, dim3((unsigned)std::min<int64_t>((int64_t)W * ((K + 63) / 64), 4096)), dim3(64), 0, nullptr, bp);
+  VsChainParams cp{};
+  cp.cz = dcz; cp.pz = dpz; cp.und = dun; cp.work = dwork; cp.n_k = dnk; cp.u = u ? du : nullptr; cp.s_end = dse; cp.rounds = dro; cp.status = dst;
+  cp.seed = seed; cp.iteration = iteration; cp.Ks = K; cp.k0 = 0; cp.V = V; cp.W = W; cp.beta = beta; cp.odds = pi / (1 - pi);
+  if (global) hipLaunchKernelGGL(vs_chain_kernel<true>, dim3((unsigned)K), dim3(kVsBlock), 0, nullptr, cp);
+  else hipLaunchKernelGGL(vs_chain_kernel<false>, dim3((unsigned)K), dim3(kVsBlock), vs_chain_lds_bytes(W), nullptr, cp);
+  std::vector<uint32_t> und(kw);
+  uint32_t st = 0;
+  if (hipGetLastError() != hipSuccess || hipMemcpy(und.data(), dun, kw * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(s_end, dse, (size_t)K * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(rounds, dro, (size_t)K * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&st, dst, 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return GGS_ERR_HIP;
+  for (int32_t k = 0; k < K; ++k)
+    for (int32_t v = 0; v < V; ++v) drawn_out[(size_t)k * V + v] = (uint8_t)(((und[(size_t)k * W + (v >> 5)] >> (v & 31)) & 1u) ^ 1u);
+  return (st & ST_INVARIANT) ? GGS_ERR_INVARIANT : GGS_OK;
 }
 
 int ggs_debug_column_sum_guided(int32_t device_id, int32_t V, int32_t K, const double *x, const int32_t *counts, double beta, const double *guess,

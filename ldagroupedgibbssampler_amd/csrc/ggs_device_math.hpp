@@ -8,7 +8,7 @@
 //   DrawStream         java.util.Random's nextDouble()/nextGaussian() semantics
 //                      (JDK 8: 26+27 bit doubles, polar Gaussian with caching)
 //                      fed from the Philox blocks of one (purpose, iteration, elem)
-//   strict_log/pow     fdlibm 5.3 e_log.c / e_pow.c == java.lang.StrictMath
+//   strict_log/pow/exp fdlibm 5.3 e_log.c / e_pow.c / e_exp.c == java.lang.StrictMath
 //   rgamma             cc/mallet/util/ParallelRandoms.java:60-70,148-159
 #pragma once
 #include <hip/hip_runtime.h>
@@ -106,6 +106,49 @@ __device__ __noinline__ double strict_log(double x) {
   }
   if (k == 0) return f - s * (f - R);
   return dk * ln2_hi - ((s * (f - R) - dk * ln2_lo) - f);
+}
+
+// ---- StrictMath.exp (fdlibm 5.3 e_exp.c) ------------------------------------
+__device__ __noinline__ double strict_exp(double x) {
+  constexpr double huge = 1.0e+300, twom1000 = 9.33263618503218878990e-302,
+                   o_threshold = 7.09782712893383973096e+02, u_threshold = -7.45133219101941108420e+02,
+                   ln2HI = 6.93147180369123816490e-01, ln2LO = 1.90821492927058770002e-10,
+                   invln2 = 1.44269504088896338700e+00,
+                   P1 = 1.66666666666666019037e-01, P2 = -2.77777777770155933842e-03,
+                   P3 = 6.61375632143793436117e-05, P4 = -1.65339022054652515390e-06,
+                   P5 = 4.13813679705723846039e-08;
+  double hi = 0.0, lo = 0.0;
+  int32_t k = 0;
+  uint32_t hx = (uint32_t)hi32(x);
+  const int32_t xsb = (int32_t)((hx >> 31) & 1u);
+  hx &= 0x7fffffffu;
+  if (hx >= 0x40862E42u) {                                // |x| >= 709.78...
+    if (hx >= 0x7ff00000u) {
+      if (((hx & 0xfffffu) | lo32(x)) != 0) return x + x; // NaN
+      return xsb == 0 ? x : 0.0;                          // exp(+-inf) = {inf, 0}
+    }
+    if (x > o_threshold) return huge * huge;
+    if (x < u_threshold) return twom1000 * twom1000;
+  }
+  if (hx > 0x3fd62e42u) {                                 // |x| > 0.5 ln2
+    if (hx < 0x3FF0A2B2u) {                               // and |x| < 1.5 ln2
+      hi = x - (xsb ? -ln2HI : ln2HI); lo = xsb ? -ln2LO : ln2LO; k = 1 - xsb - xsb;
+    } else {
+      k = (int32_t)(invln2 * x + (xsb ? -0.5 : 0.5));
+      const double t = (double)k;
+      hi = x - t * ln2HI;
+      lo = t * ln2LO;
+    }
+    x = hi - lo;
+  } else if (hx < 0x3e300000u) {                          // |x| < 2^-28
+    if (huge + x > 1.0) return 1.0 + x;
+  }
+  const double t = x * x;
+  const double c = x - t * (P1 + t * (P2 + t * (P3 + t * (P4 + t * P5))));
+  if (k == 0) return 1.0 - ((x * c) / (c - 2.0) - x);
+  const double y = 1.0 - ((lo - (x * c) / (2.0 - c)) - hi);
+  if (k >= -1021) return set_hi(y, hi32(y) + (int32_t)((uint32_t)k << 20));
+  return set_hi(y, hi32(y) + (int32_t)((uint32_t)(k + 1000) << 20)) * twom1000;
 }
 
 // fdlibm scalbn for finite x (only reached for subnormal pow results)

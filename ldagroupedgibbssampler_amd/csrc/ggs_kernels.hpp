@@ -47,6 +47,7 @@ enum StatusBits : uint32_t {
   ST_INVALID_TOPIC = 1u << 1,
   ST_RNG_EXHAUSTED = 1u << 2,
   ST_BAD_SHAPE = 1u << 3,
+  ST_INVARIANT = 1u << 4,   // scheme nzvsspalias: the reference's "Inconsistent Indicator probability" (ggs_phi_vs.hpp)
 };
 
 // ------------------------------------------------------------------------------
@@ -461,10 +462,14 @@ struct PhiGammaParams {
   // guess = the EXACT running magnitude sums [nseg + 1][K] (E Gamma(a) = a).  Null: not wanted.
   const double *guess;
   double *fn;          // [nseg][K][4]
-  // topic priors (phi_gamma_kernel<true> only): bit (k0 + k) & 31 of zero_mask[v * mask_pitch + ((k0 + k) >> 5)] set = cell (k0 + k, v)
+  // topic priors (phi_gamma_kernel<true>) or the undrawn cells (phi_gamma_vs_kernel): bit (k0 + k) & 31 of zero_mask[v * mask_pitch + ((k0 + k) >> 5)] set = cell (k0 + k, v)
   // is zero -- laid out by word, as phiT is
   const uint32_t *zero_mask;
   int32_t mask_pitch;
+  // phi_gamma_vs_kernel with an exchange: an undrawn cell holds -0.0 (a drawn one that underflowed +0.0), so that the drawn set
+  // travels with the gathered gammas; the receiver clears the sign (phi_repack_vs_kernel).  A running sum does not see it:
+  // x + -0.0 = x and +0.0 + -0.0 = +0.0, and the cell is not given to the segment functions at all.
+  int32_t undrawn_negative;
 };
 constexpr double kConditionalMinGamma = 0.0001;   // ConditionalDirichlet.java:90-92
 
@@ -481,8 +486,14 @@ constexpr double kConditionalMinGamma = 0.0001;   // ConditionalDirichlet.java:9
 // BEFORE it is summed.  The segment functions take those values, so the walk's result is the reference's sum_gamma.
 constexpr int kPhiCols = 6, kPhiQueue = 128;
 
-template <bool PRIORS>
-__global__ __launch_bounds__(64) void phi_gamma_kernel(PhiGammaParams p) {
+//
+// VS (scheme nzvsspalias, ggs_phi_vs.hpp; VSDirichlet.java:76-84): the masked draw again -- the mask holds the cells the
+// indicator chain left undrawn -- with shape = beta + n (not ((beta + n) / mag) * mag) and no clamp: a gamma that underflows
+// to 0.0 stays 0.0.
+enum PhiDraw { kDrawPlain, kDrawPriors, kDrawVS };
+template <int MODE>
+__device__ __forceinline__ void phi_gamma_body(const PhiGammaParams &p) {
+  constexpr bool PRIORS = MODE == kDrawPriors, MASKED = MODE != kDrawPlain;
   // With an exchange the slice's draw is on the critical path and the next theta has the whole Phi phase to finish: issue
   // ahead of the theta draw on the side stream (behind the chain's short kernels).  One GPU: the next z step waits for
   // both draws, which share the VALUs -- no priority, so that they end together (with it the theta draw ended 0.17 ms
@@ -498,6 +509,7 @@ __global__ __launch_bounds__(64) void phi_gamma_kernel(PhiGammaParams p) {
     const int32_t cnt = p.n_wk[(size_t)v * p.cnt_pitch + k];
     if (p.initial) return (cnt == 0) ? p.prior_pm : p.prior_pm + (double)cnt;   // MarsagliaSparseDirichlet.java:37-41
     const double pk = p.beta + (double)cnt;                                     // GGS:188
+    if constexpr (MODE == kDrawVS) return pk;
     const double m = p.mag[k];
     return (pk / m) * m;
   };
@@ -534,9 +546,12 @@ __global__ __launch_bounds__(64) void phi_gamma_kernel(PhiGammaParams p) {
 #pragma unroll 1
     for (int j = lane; j < n; j += 64) {
       const int dv = udiv_small(j, m_kw), v = v0 + dv, c = j - dv * kw, k = kb + c;
-      if constexpr (PRIORS) {
+      if constexpr (MASKED) {
         const int kg = p.k0 + k;
-        if ((p.zero_mask[(size_t)v * p.mask_pitch + (kg >> 5)] >> (kg & 31)) & 1u) { p.phiT[(size_t)v * p.Kp + k] = 0.0; continue; }
+        if ((p.zero_mask[(size_t)v * p.mask_pitch + (kg >> 5)] >> (kg & 31)) & 1u) {
+          p.phiT[(size_t)v * p.Kp + k] = (MODE == kDrawVS && p.undrawn_negative) ? -0.0 : 0.0;
+          continue;
+        }
       }
       const double shape = shape_of(v, k);
       double g;
@@ -562,6 +577,9 @@ __global__ __launch_bounds__(64) void phi_gamma_kernel(PhiGammaParams p) {
       seg_compose(SegCand{e_los[lane], aheads[lane] != 0}, acc_lo[lane], acc_hi[lane], flag_s[lane], 0.0, p.fn + ((size_t)seg * p.K + kb + lane) * 4);
   }
 }
+template <bool PRIORS>
+__global__ __launch_bounds__(64) void phi_gamma_kernel(PhiGammaParams p) { phi_gamma_body<PRIORS ? kDrawPriors : kDrawPlain>(p); }
+__global__ __launch_bounds__(64) void phi_gamma_vs_kernel(PhiGammaParams p) { phi_gamma_body<kDrawVS>(p); }
 
 // The float32 shadow phiT32 [V][Kp32] of phiT that z_sliced_kernel<KMAX, true> gathers (ggs_z_sliced.hpp): round to nearest of
 // a value in [0, 1], NaN for anything else -- the margin there is proved for operands in [0, 1] only, and a NaN score sends
@@ -573,7 +591,8 @@ __device__ __forceinline__ float phi32_of(const double x) { return (x >= 0.0 && 
 // draws; exact zeros stay zero (no clamp), and a row whose total is 0 becomes all zero (the draws are all 0 there anyway).
 // CONDITIONAL (scheme spalias_priors, ConditionalDirichlet.java:97-99): (g / sum_gamma) * sum_phi, the division first, no clamp behind
 // it; a masked cell holds +0.0 and keeps it (sum_gamma >= 1e-4: every topic has an allowed word and its gamma is clamped).
-enum PhiNorm { kPhiDirichlet, kPhiPolyaurn, kPhiConditional };
+// VS (scheme nzvsspalias, the repack only): polyaurn's rule, and the -0.0 that marks an undrawn cell in transit becomes +0.0.
+enum PhiNorm { kPhiDirichlet, kPhiPolyaurn, kPhiConditional, kPhiVS };
 template <int MODE>
 __device__ __forceinline__ void phi_normalise_body(double *phiT, const double *tot, int32_t K, int32_t Kp, int32_t V, double *phi_mean, float *phiT32,
                                                    int32_t Kp32, const double *sum_phi = nullptr) {
@@ -655,6 +674,8 @@ __device__ __forceinline__ void phi_repack_body(const PhiRepackParams &p) {
     const double s = h1[tot_off + j];
     if constexpr (MODE == kPhiPolyaurn) {                            // as phi_normalise_body
       x = s > 0 ? x / s : 0.0;
+    } else if constexpr (MODE == kPhiVS) {
+      x = (s > 0 && x != 0.0) ? x / s : 0.0;                         // x / s of a zero is that zero: only the sign is dropped
     } else if constexpr (MODE == kPhiConditional) {
       x = (x / s) * p.sum_phi[k];
     } else if (s != 0) {
@@ -669,6 +690,24 @@ __device__ __forceinline__ void phi_repack_body(const PhiRepackParams &p) {
 __global__ __launch_bounds__(256) void phi_repack_kernel(PhiRepackParams p) { phi_repack_body<kPhiDirichlet>(p); }
 __global__ __launch_bounds__(256) void phi_repack_polyaurn_kernel(PhiRepackParams p) { phi_repack_body<kPhiPolyaurn>(p); }
 __global__ __launch_bounds__(256) void phi_repack_conditional_kernel(PhiRepackParams p) { phi_repack_body<kPhiConditional>(p); }
+__global__ __launch_bounds__(256) void phi_repack_vs_kernel(PhiRepackParams p) { phi_repack_body<kPhiVS>(p); }
+// The undrawn cells of ALL topics from the gathered gammas' signs of zero into zero_mask's layout: mask [V][pitch], a thread per
+// word of 32 topics.  Before the repack, which reads the same buffers.
+__global__ __launch_bounds__(256) void vs_mask_gathered_kernel(PhiRepackParams p, uint32_t *mask, int32_t pitch) {
+  const int64_t n = (int64_t)p.V * pitch, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int v = (int)(i / pitch), m = (int)(i - (int64_t)v * pitch);
+    uint32_t word = 0;
+    for (int b = 0; b < 32; ++b) {
+      const int k = m * 32 + b;
+      if (k >= p.K) break;
+      const int r = p.krank[k], j = p.kcol[k];
+      const double x = v < p.v_split ? p.all0[(int64_t)r * p.c0 + (int64_t)v * p.Ksm + j] : p.all1[(int64_t)r * p.c1 + (int64_t)(v - p.v_split) * p.Ksm + j];
+      word |= (uint32_t)(x == 0.0 && __builtin_signbit(x)) << b;
+    }
+    mask[i] = word;
+  }
+}
 // cnt_all [nranks][V][Ksm] (the all-gathered count slices) -> n_wk [V][K]
 __global__ __launch_bounds__(256) void counts_unslice_kernel(const int32_t *cnt_all, const int64_t *koff, int32_t Ksm, int32_t *n_wk, int32_t K,
                                                              int32_t V) {
@@ -746,6 +785,7 @@ __global__ void debug_math_kernel(int op, int64_t n, const double *x, const doub
     case 0: r = strict_log(x[i]); break;
     case 1: r = strict_pow(x[i], y[i]); break;
     case 2: r = sqrt(x[i]); break;
+    case 4: r = strict_exp(x[i]); break;
     default: r = x[i] / y[i]; break;
   }
   out[i] = r;

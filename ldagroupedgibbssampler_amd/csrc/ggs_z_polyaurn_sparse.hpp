@@ -31,11 +31,16 @@ struct WordListParams {
   uint16_t *nzw;               // [V][K]
   int32_t *nw;                 // [V]
   int32_t V, K, Kp;
+  // FROM_MASK (scheme nzvsspalias, ggs_phi_vs.hpp): the list is the cells the variable-selection draw DREW -- bit k & 31 of
+  // zero_mask[w * mask_pitch + (k >> 5)] clear -- not phi != 0.0: a drawn gamma that underflowed to 0.0 stays listed
+  const uint32_t *zero_mask;
+  int32_t mask_pitch;
 };
 
 constexpr int kWordListBlock = 256;
 
-__global__ __launch_bounds__(kWordListBlock) void word_list_build_kernel(WordListParams p) {
+template <bool FROM_MASK>
+__device__ __forceinline__ void word_list_build_body(const WordListParams &p) {
   const int lane = threadIdx.x & 63, waves = kWordListBlock / 64;
   for (int64_t w = (int64_t)blockIdx.x * waves + (threadIdx.x >> 6); w < p.V; w += (int64_t)gridDim.x * waves) {
     const double *row = p.phiT + (size_t)w * p.Kp;
@@ -43,7 +48,9 @@ __global__ __launch_bounds__(kWordListBlock) void word_list_build_kernel(WordLis
     int n = 0;
     for (int k0 = 0; k0 < p.K; k0 += 64) {
       const int k = k0 + lane;
-      const bool nz = k < p.K && row[k] != 0.0;
+      bool nz;
+      if constexpr (FROM_MASK) nz = k < p.K && !((p.zero_mask[(size_t)w * p.mask_pitch + (k >> 5)] >> (k & 31)) & 1u);
+      else nz = k < p.K && row[k] != 0.0;
       const unsigned long long m = __ballot(nz);
       const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
       if (nz) out[n + before] = (uint16_t)k;                                       // n + before < number of non-zeros <= K
@@ -52,6 +59,8 @@ __global__ __launch_bounds__(kWordListBlock) void word_list_build_kernel(WordLis
     if (lane == 0) p.nw[w] = n;
   }
 }
+__global__ __launch_bounds__(kWordListBlock) void word_list_build_kernel(WordListParams p) { word_list_build_body<false>(p); }
+__global__ __launch_bounds__(kWordListBlock) void word_list_mask_kernel(WordListParams p) { word_list_build_body<true>(p); }
 
 // ---- the z step ------------------------------------------------------------------------------------------------------
 struct PolyaurnSparseParams : SpaliasParams {
@@ -63,5 +72,8 @@ struct PolyaurnSparseParams : SpaliasParams {
 inline size_t polyaurn_sparse_lds_bytes(int K, int cap) { return spalias_lds_bytes(K, cap); }
 
 __global__ __launch_bounds__(64) void polyaurn_sparse_wave_kernel(PolyaurnSparseParams sp) { sparse_wave_body<true>(sp); }
+// scheme nzvsspalias (NZVSSpaliasUncollapsedParallelLDA.java:157-315): the same step over the variable-selection Phi and
+// the drawn cells' lists, except that a token without a candidate draws from its word's alias table (:252-254)
+__global__ __launch_bounds__(64) void nzvs_wave_kernel(PolyaurnSparseParams sp) { sparse_wave_body<true, PolyaurnSparseParams, true>(sp); }
 
 }  // namespace ggs

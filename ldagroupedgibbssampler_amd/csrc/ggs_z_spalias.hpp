@@ -62,7 +62,9 @@ inline size_t spalias_lds_bytes(int K, int cap) { return (size_t)cap * 8 + (size
 
 // WORD_LISTS: polyaurn_sparse (Params = PolyaurnSparseParams: the words' lists exist, the counters are kept); without:
 // spalias (SpaliasParams).  Every difference between the two is an `if constexpr (WORD_LISTS)` or a condition on it below.
-template <bool WORD_LISTS, class Params>
+// N0_ALIAS (nzvsspalias, with WORD_LISTS): a token without a candidate draws sample(w, U) from its word's alias table instead of
+// polyaurn's floor(U * K); a draw with i == K is GGS_ERR_INVALID_TOPIC.
+template <bool WORD_LISTS, class Params, bool N0_ALIAS = false>
 __device__ __forceinline__ void sparse_wave_body(const Params &sp) {
   const PcgsParams &p = sp.b;
   const uint16_t *nzw = nullptr;                                                   // [V][K]: the words' lists,
@@ -193,8 +195,20 @@ __device__ __forceinline__ void sparse_wave_body(const Params &sp) {
       };
 
       int new_topic = -1;
-      if (WORD_LISTS && n == 0) {                                                  // no candidate: polyaurn's uniform draw
-        new_topic = polyaurn_uniform_topic(U, K);
+      if (WORD_LISTS && n == 0) {                                                  // no candidate: polyaurn's uniform draw, or (N0_ALIAS) the word's alias table
+        if constexpr (N0_ALIAS) {
+          const double ups = U * (double)K;
+          const int i = (int)ups;
+          if (i >= K) {
+            if (lane == 0) atomicOr(p.status, ST_INVALID_TOPIC);
+            new_topic = K - 1;
+          } else {
+            const size_t o = (size_t)w * K + i;
+            new_topic = (ups - (double)i) > sp.ps[o] ? sp.a[o] : i;
+          }
+        } else {
+          new_topic = polyaurn_uniform_topic(U, K);
+        }
         n_unif += 1;
       } else {
         if constexpr (WORD_LISTS) {

@@ -11,6 +11,7 @@ ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_INVARIANT = 5, 6, 7, 8
 FLAG_PARANOID, FLAG_SAVE_PHI_MEAN, FLAG_PCGS, FLAG_COLLAPSED, FLAG_POLYAURN, FLAG_SPALIAS, FLAG_LIGHTPCLDA = 1, 2, 4, 8, 16, 32, 64
 FLAG_POLYAURN_SPARSE = 128
 FLAG_LIGHTCOLLAPSED = 256
+FLAG_NZVSSPALIAS = 512
 PURPOSE_Z, PURPOSE_THETA, PURPOSE_PHI, PURPOSE_INIT_PHI = 1, 2, 3, 4
 
 
@@ -301,6 +302,18 @@ class GGSHandle:
         self._chk(self._L.ggs_get_sparse_stats(self._h, _lp(out)))
         return out
 
+    def set_variable_selection_prior(self, pi):
+        """scheme=nzvsspalias: the prior probability that a cell without tokens keeps its place in its topic (0.5 until set); a
+        FLAG_NZVSSPALIAS handle, before its first Phi."""
+        self._chk(self._L.ggs_set_variable_selection_prior(self._h, float(pi)))
+
+    def vs_stats(self):
+        """scheme=nzvsspalias: the cells the last Phi draw left undrawn, the cells of the current Phi that are 0.0 and the largest
+        number of rounds a topic's indicator chain took in that draw (int64 [3])."""
+        out = np.zeros(3, np.int64)
+        self._chk(self._L.ggs_get_vs_stats(self._h, _lp(out)))
+        return out
+
     def get_theta(self, doc_begin=0, doc_end=None):
         doc_end = self.D if doc_end is None else doc_end
         out = np.empty((doc_end - doc_begin, self.K), np.float64)
@@ -370,7 +383,8 @@ class GGSHandle:
 Z_KERNEL_NAMES = {0: "z_kernel (whole-row tiles)", 1: "z_sliced_kernel + z_hot_kernel (score registers)", 2: "z_stream1_kernel (one pass)",
                   3: "z_stream_kernel (two passes)", 4: "pcgs_sliced_kernel (lane per document)", 5: "pcgs_wave_kernel (wave per document)",
                   6: "spalias_wave_kernel (wave per document)", 7: "lightpc_wave_kernel (wave per document)",
-                  8: "polyaurn_sparse_wave_kernel (wave per document)", 9: "lightcollapsed_wave_kernel (wave per document)"}
+                  8: "polyaurn_sparse_wave_kernel (wave per document)", 9: "lightcollapsed_wave_kernel (wave per document)",
+                  10: "nzvs_wave_kernel (wave per document)"}
 
 
 class GGSGroup:
@@ -452,7 +466,7 @@ def debug_math(op, x, y=None, device_id=0):
     x = np.ascontiguousarray(x, np.float64)
     y = x if y is None else np.ascontiguousarray(y, np.float64)
     out = np.empty_like(x)
-    rc = L.ggs_debug_math(device_id, {"log": 0, "pow": 1, "sqrt": 2, "div": 3}[op], x.size, _dp(x), _dp(y), _dp(out))
+    rc = L.ggs_debug_math(device_id, {"log": 0, "pow": 1, "sqrt": 2, "div": 3, "exp": 4}[op], x.size, _dp(x), _dp(y), _dp(out))
     if rc:
         raise GGSError(rc, "ggs_debug_math")
     return out
@@ -494,6 +508,27 @@ def debug_alias(phi, alpha, device_id=0):
     if rc:
         raise GGSError(rc, "ggs_debug_alias")
     return ps, a, tn
+
+
+def debug_vs_indicators(counts, prev_phi, beta, pi, seed, iteration, u=None, device_id=0):
+    """scheme=nzvsspalias's indicator chain alone, for counts [K][V] and prev_phi [K][V]: (drawn [K][V] bool, s_end [K], rounds [K]).
+    u [K][V], if given, replaces the Philox uniforms."""
+    L = _lib.load()
+    counts = np.ascontiguousarray(counts, np.int32)
+    prev_phi = np.ascontiguousarray(prev_phi, np.float64)
+    K, V = counts.shape
+    if prev_phi.shape != (K, V):
+        raise ValueError("prev_phi must have the shape of counts")
+    if u is not None:
+        u = np.ascontiguousarray(u, np.float64)
+        if u.shape != (K, V):
+            raise ValueError("u must have the shape of counts")
+    drawn, s_end, rounds = np.empty((K, V), np.uint8), np.empty(K, np.int32), np.empty(K, np.int32)
+    rc = L.ggs_debug_vs_indicators(device_id, V, K, _ip(counts), _dp(prev_phi), float(beta), float(pi), seed, iteration, _dp(u) if u is not None else None,
+                                   drawn.ctypes.data_as(C.POINTER(C.c_uint8)), _ip(s_end), _ip(rounds))
+    if rc:
+        raise GGSError(rc, "ggs_debug_vs_indicators")
+    return drawn.astype(bool), s_end, rounds
 
 
 def debug_column_sum(x=None, counts=None, beta=0.0, device_id=0):

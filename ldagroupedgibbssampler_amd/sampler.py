@@ -39,6 +39,7 @@ class SimpleLDAConfiguration:
         self.phi_mean_thin = int(kw.pop("phi_mean_thin", 1))         # PHI_THIN_DEFAULT
         self.alias_poisson_threshold = int(kw.pop("alias_poisson_threshold", 100))   # ALIAS_POISSON_DEFAULT_THRESHOLD; scheme=polyaurn and polyaurn_sparse only
         self.topic_prior_filename = kw.pop("topic_prior_filename", None)   # TOPIC_PRIOR_FILENAME, default none; scheme=spalias_priors only
+        self.variable_selection_prior = float(kw.pop("variable_selection_prior", 0.5))   # VARIABLE_SELECTION_PRIOR_DEFAULT; scheme=nzvsspalias only
         self.paranoid = bool(kw.pop("paranoid", False))              # run the UPLDA:299-338 invariants every sweep
         self.device_id = int(kw.pop("device_id", 0))                 # optional gpu_* key; default first visible GPU
         # the diagnostics of the sampling loop (UPLDA:695-905), computed on the device and written in the Java driver's formats
@@ -486,6 +487,37 @@ class PolyaUrnSparseLDA(LDAPartiallyCollapsedGibbsSampler):
     def getSparseStats(self):
         """tokens that walked the word's list, the document's list, tokens drawn uniformly, the sum of candidates (cumulative)"""
         return self._h.sparse_stats()
+
+
+class NZVSSpaliasUncollapsedParallelLDA(LDAPartiallyCollapsedGibbsSampler):
+    """scheme=nzvsspalias (topics/NZVSSpaliasUncollapsedParallelLDA.java over types/VSDirichlet.java): the pcgs model with a
+    variable-selection Dirichlet for Phi -- a cell without tokens keeps or loses its place in the topic by a Bernoulli
+    indicator, so Phi has exact zeros -- and the doubly sparse z step over the shorter of the word's list of drawn topics and
+    the document's list.  Config key variable_selection_prior (default 0.5).  Constructed directly: create_model() keeps
+    refusing the name "nzvsspalias" (tests/test_spalias_model.py pins that refusal)."""
+    _scheme_flags = native.FLAG_NZVSSPALIAS
+
+    def _before_initial_state(self, training):
+        self._h.set_variable_selection_prior(self.config.variable_selection_prior)
+
+    def getTheta(self):
+        raise NotImplementedError("scheme=nzvsspalias never draws theta; use getThetaEstimate() (UPLDA:716-720 does the same)")
+
+    def getAliasTables(self):
+        """(ps [V][K], a [V][K], typeNorm [V]) of the current Phi"""
+        return self._h.alias_tables()
+
+    def getWordTopicLists(self):
+        """(nw [V], topics [V][K]): per word the topics whose cell the last Phi draw drew, ascending, -1 behind them"""
+        return self._h.word_topic_lists()
+
+    def getSparseStats(self):
+        """tokens that walked the word's list, the document's list, tokens drawn from the alias table alone, the sum of candidates"""
+        return self._h.sparse_stats()
+
+    def getVSStats(self):
+        """cells the last Phi draw left undrawn, zero cells of the current Phi, the most rounds a topic's indicator chain took"""
+        return self._h.vs_stats()
 
 
 class SerialCollapsedLDA(LDAGroupedGibbsSampler):
