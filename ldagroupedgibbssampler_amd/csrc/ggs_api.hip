@@ -192,6 +192,7 @@ struct ggs_handle {
   double *d_pr_pref = nullptr, *d_pr_fn = nullptr;     // that sum's own guess and segment functions: d_sum_pref stays the magnitudes'
   // scheme=lightpclda (ggs_z_lightpc.hpp): the pcgs model and spalias's tables, a Metropolis-Hastings z step
   double alpha_sum = 0;                                // the k-order sum of alpha
+  bool alpha_symmetric = false;                        // every alpha[k] has the bits of alpha[0]: the theta draw's count-0 cells share their gamma constants per document
   unsigned long long *d_mh = nullptr;                  // [3]: ggs_get_mh_stats, zeroed by ggs_set_corpus
   int32_t *d_tpt = nullptr;                            // scheme=lightcollapsed (ggs_z_lightcollapsed.hpp): [V] tokensPerType of the sweep-start counts
   // scheme=polyaurn_sparse (ggs_z_polyaurn_sparse.hpp): polyaurn's Phi, spalias's tables and document lists, and per word the
@@ -985,6 +986,7 @@ int launch_theta(ggs_handle *h, hipStream_t stream, double *dst, int32_t iterati
   tp.doc_ptr = h->d_doc_ptr + d0; tp.z = h->d_z; tp.alpha = h->d_alpha; tp.theta = dst + (size_t)d0 * h->K; tp.status = h->d_status;
   tp.num_docs = d1 - d0; tp.doc_base = h->doc_base + d0; tp.seed = h->seed; tp.iteration = (uint32_t)iteration;
   tp.K = h->K; tp.docs_per_block = docs_per_block; tp.queue_cap = std::min(kGammaQueue, h->gamma_queue_cap);
+  tp.sym_alpha = h->alpha_symmetric ? 1 : 0;
   const int64_t grid = (d1 - d0 + docs_per_block - 1) / docs_per_block;
   void *args[] = {&tp};
   HIP_TRY(h, hipLaunchKernel(h->plan.theta.fn, dim3((unsigned)grid), dim3(kThetaBlock), args, (size_t)(lds ? lds : h->cfg->theta_lds), stream));
@@ -1143,8 +1145,13 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
     }
   }
   // ---- the theta draw: of every sweep for scheme ggs, of the log posterior's diagnostic theta for the pcgs family
+  // The documents per workgroup: by the cells alone (theta_cells_lds_bytes: the 32 KiB were measured before the cell list
+  // and the class-A table came beside the cells); 32 or more are halved where the whole workgroup would pass the quarter
+  // of the CU's LDS below (K = 96 - 115: 16 instead of 32, at K = 100 35.4 KiB; K = 46 - 57: 32 instead of 64).  Not below 16: with 8
+  // documents the two serial K-chains of a workgroup take over (K = 200, 18 846 documents: the draw 0.48 ms instead of 0.25).
+  const int theta_quarter = (kMaxLdsBytes - 24 * 1024) / 4;
   int B = 64;
-  while (B > 1 && theta_lds_bytes(K, B) > 32 * 1024) B >>= 1;
+  while (B > 1 && (theta_cells_lds_bytes(K, B) > 32 * 1024 || (B > 16 && theta_lds_bytes(K, B) > theta_quarter))) B >>= 1;
   if (theta_lds_bytes(K, B) > kMaxLdsBytes) return GGS_ERR_UNSUPPORTED;
   pl.theta.fn = reinterpret_cast<const void *>(theta_kernel<kThetaBlock>); pl.theta.block = kThetaBlock;
   // The request is padded to a quarter of the CU's LDS: at most 4 workgroups (16 waves) of the theta draw per CU.
@@ -1152,9 +1159,11 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
   // not running waves, and measured with 5-6 resident workgroups theta finishes early (0.53 ms instead of 0.75)
   // while the Phi phase it starves gets longer (0.67 -> 0.72 ms).
   // ... and 24 KiB of every CU stay free for the main stream's own LDS users (the walk of the exact column sums,
-  // 14.5 KiB per workgroup: with the CU's LDS handed out to theta workgroups to the last granule it waited for the
-  // theta draw to END -- 5 ms at K = 1024).
-  const int theta_quarter = (kMaxLdsBytes - 24 * 1024) / 4;
+  // 20.5 KiB of static LDS per workgroup, 22 KiB allocated: with the CU's LDS handed out to theta workgroups to the last
+  // granule it waited for the theta draw to END -- 5 ms at K = 1024).  Workgroups of 16 documents at K = 193 - 227 pass
+  // the quarter with their list (K = 200: 35.3 KiB, 36 allocated): four of them leave 16 KiB, and the walk takes the 36 KiB
+  // that one of them frees when it ends.  That configuration draws theta only where the z step is in one part (D <= V: few
+  // rounds of theta workgroups; measured there, 1.005 -> 0.989 ms per sweep against the build without the list).
   pl.cfg_plain = {1, pl.z.per_cu, B, std::max(theta_lds_bytes(K, B), theta_quarter), 0};
   // ... unless the theta draw is the critical leg itself (theta_main): then five workgroups per CU, of 16 documents
   // each.  Measured at K = 100 on one box, ms per sweep (documents per workgroup x workgroups per CU): 32x4 1.60-1.61,
@@ -1171,11 +1180,18 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
     int parts = kn.zparts.set ? std::max(1, std::min(8, kn.zparts.v)) : pl.kernel == 2 ? 8 : 1;   // measured at K = 1024: 1 part 18.4 ms per sweep, 2: 18.1, 4: 16.5, 8: 15.9
     if (parts > 1 && pl.kernel == 2) {
       const int kBeside = kn.beside.set ? std::max(1, kn.beside.v) : 4;   // measured at K = 1024 (sweep): 2 -> 16.9 ms, 3 -> 16.1, 4 -> 15.0, 5 -> 15.0
+      // The z waves and the documents per workgroup are the ones the cells alone allow (as measured, before the cell
+      // list came beside the cells).  Where the list takes the request over a granule that the z waves' remainder does not
+      // have four times (K = 161-164, 234-256, 513-572, 769-828, 1153-1280), three theta workgroups sit beside the z waves
+      // instead of kBeside.  Measured against the other two ways at K = 161 / 256 / 520, ms per sweep (without the list
+      // 2.881 / 3.600 / 8.993): this 2.884 / 3.581 / 8.704, a z wave less 2.969 / 3.674 / 8.931, half the documents 4.12 at 256.
+      const int z_alloc = lds_alloc_of(pl.z.lds);
+      auto z_waves_beside = [&](int theta_lds) { return std::min(pl.z.per_cu, (kMaxLdsBytes - kLdsGranule - kBeside * lds_alloc_of(theta_lds)) / z_alloc); };
       int Bt = 64;
-      while (Bt > 1 && theta_lds_bytes(K, Bt) > 10 * 1024) Bt >>= 1;
-      const int t_lds = theta_lds_bytes(K, Bt), z_alloc = lds_alloc_of(pl.z.lds);
-      const int zw = std::min(pl.z.per_cu, (kMaxLdsBytes - kLdsGranule - kBeside * lds_alloc_of(t_lds)) / z_alloc);
-      if (t_lds <= 12 * 1024 && zw >= 2)
+      while (Bt > 1 && theta_cells_lds_bytes(K, Bt) > 10 * 1024) Bt >>= 1;
+      const int zw = z_waves_beside(theta_cells_lds_bytes(K, Bt));
+      const int t_lds = theta_lds_bytes(K, Bt);
+      if (theta_cells_lds_bytes(K, Bt) <= 12 * 1024 && zw >= 2)
         pl.cfg_parts = {parts, zw, Bt, std::max(t_lds, theta_quarter), std::max(t_lds, (kMaxLdsBytes - kLdsGranule - zw * z_alloc) / kBeside / kLdsGranule * kLdsGranule)};
       else
         parts = 1;
@@ -1805,6 +1821,7 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
   for (double a : h->alpha)
     if (!(a > 0)) { delete h; return GGS_ERR_BAD_ARG; }
   for (double a : h->alpha) h->alpha_sum = h->alpha_sum + a;
+  h->alpha_symmetric = std::all_of(h->alpha.begin(), h->alpha.end(), [&](double a) { return std::memcmp(&a, &h->alpha[0], sizeof a) == 0; });
   // 2. the handle's own switches
   // GGS_DEBUG_MARGIN: above 1 the margins force the exact replays in tests.  Below 1 voids the proof, so only the float32 cold
   // kernel takes it (its decided draw is a count of partial sums, always a topic < K); the checkpoint-and-refine walks of the

@@ -334,10 +334,29 @@ struct DrawStream {
   }
 };
 
+// What a gamma draw needs of its shape and of nothing else: the boost decision of ParallelRandoms.java:61-66 and the
+// constants of the Marsaglia-Tsang loop (ParallelRandoms.java:149-150).  Cells with the same shape have bit-equal constants,
+// so a draw may take them from a table that another lane filled (the theta and Phi draws: one entry per document or tile
+// column for the cells with count 0) instead of spending a square root and three divisions on its own.
+struct GammaConsts {
+  double shape;       // as given: Gamma(shape) is what is drawn
+  double d, c;        // of the boosted shape: 1 + shape where shape < 1
+  double inv_alpha;   // 1.0 / shape, the boost's exponent: set where boost is
+  bool boost;
+};
+__device__ __forceinline__ GammaConsts gamma_consts(double alpha) {
+  GammaConsts k;
+  k.shape = alpha;
+  k.boost = alpha < 1;
+  const double shape = k.boost ? 1 + alpha : alpha;
+  k.d = shape - (1.0 / 3.0);
+  k.c = 1.0 / sqrt(9.0 * k.d);
+  k.inv_alpha = k.boost ? 1.0 / alpha : 0.0;
+  return k;
+}
+
 // ParallelRandoms.java:148-159
-__device__ __forceinline__ double prgamma(DrawStream &r, double alpha) {
-  const double d = alpha - (1.0 / 3.0);
-  const double c = 1.0 / sqrt(9.0 * d);
+__device__ __forceinline__ double prgamma(DrawStream &r, const double d, const double c) {
   for (;;) {
     double x, v;
     do {
@@ -358,12 +377,12 @@ __device__ __forceinline__ double prgamma(DrawStream &r, double alpha) {
 // element's first draw whatever the shape (stream layout, see oracle/ggs_oracle.c rgamma): every
 // lane is then at the same stream position at every call site and new Philox blocks are needed
 // by all lanes together.
-__device__ __forceinline__ double rgamma(DrawStream &r, double alpha) {
-  const bool boost = alpha < 1;
+__device__ __forceinline__ double rgamma(DrawStream &r, const GammaConsts &k) {
   const double u = r.next_double();                  // drawn BEFORE the Marsaglia-Tsang loop, as at ParallelRandoms.java:62
-  const double g = prgamma(r, boost ? 1 + alpha : alpha);
-  return boost ? g * strict_pow(u, 1.0 / alpha) : g;
+  const double g = prgamma(r, k.d, k.c);
+  return k.boost ? g * strict_pow(u, k.inv_alpha) : g;
 }
+__device__ __forceinline__ double rgamma(DrawStream &r, double alpha) { return rgamma(r, gamma_consts(alpha)); }
 
 // The same draw when nothing is rejected twice -- straight-line code for a whole wave.  rgamma's loops cost a wave the
 // MAXIMUM over its 64 lanes: the polar method rejects 21 % of its pairs (3.3 rounds until all lanes hold one), and one
@@ -372,7 +391,8 @@ __device__ __forceinline__ double rgamma(DrawStream &r, double alpha) {
 // 3-4: Philox blocks 0-2) and the squeeze test once, with exactly the operations rgamma would perform on that path;
 // a lane for which that does not settle the draw (both pairs rejected 4.6 %, squeeze failed ~9 %, v <= 0) returns false
 // and its element is drawn by rgamma from the start of its stream -- by the caller, gathered into full waves.
-__device__ __forceinline__ bool rgamma_first_try(uint64_t seed, uint32_t iter, uint32_t purpose, uint64_t elem, double alpha, double &g) {
+// `k` may live in LDS (a table entry): its fields are read where they are used.
+__device__ __forceinline__ bool rgamma_first_try(uint64_t seed, uint32_t iter, uint32_t purpose, uint64_t elem, const GammaConsts &k, double &g) {
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), c0 = (uint32_t)elem, c1 = (uint32_t)(elem >> 32), c2 = purpose << 24;
   const U4 b0 = philox4x32_10(c0, c1, c2, iter, k0, k1), b1 = philox4x32_10(c0, c1, c2 | 1u, iter, k0, k1),
            b2 = philox4x32_10(c0, c1, c2 | 2u, iter, k0, k1);
@@ -386,17 +406,16 @@ __device__ __forceinline__ bool rgamma_first_try(uint64_t seed, uint32_t iter, u
   const double u = ok_a ? w : u53(b2.z, b2.w);                        // position 3 or 5
   const double multiplier = sqrt(-2 * strict_log(s) / s);
   const double x = v1 * multiplier;
-  const bool boost = alpha < 1;
-  const double shape = boost ? 1 + alpha : alpha;
-  const double d = shape - (1.0 / 3.0);
-  const double c = 1.0 / sqrt(9.0 * d);
-  double v = 1.0 + c * x;
+  double v = 1.0 + k.c * x;
   if (!(v > 0.0)) return false;                                       // rgamma: the cached second Gaussian comes next
   v = v * v * v;
   if (!(u < (1.0 - 0.0331 * (x * x) * (x * x)))) return false;        // rgamma: the log test, perhaps another round
-  const double r = d * v;
-  g = boost ? r * strict_pow(u0, 1.0 / alpha) : r;
+  const double r = k.d * v;
+  g = k.boost ? r * strict_pow(u0, k.inv_alpha) : r;
   return true;
+}
+__device__ __forceinline__ bool rgamma_first_try(uint64_t seed, uint32_t iter, uint32_t purpose, uint64_t elem, double alpha, double &g) {
+  return rgamma_first_try(seed, iter, purpose, elem, gamma_consts(alpha), g);
 }
 
 }  // namespace ggs

@@ -54,7 +54,8 @@ enum StatusBits : uint32_t {
 // K1+K2: per-document theta draw (GGS:57-72 + ParallelDirichlet.java:46-70).
 // One workgroup owns `docs_per_block` consecutive documents.
 //   phase 1  histogram of the current z per document (LDS atomics)
-//   phase 2  one lane per document: magnitude = sum_k (n_dk + alpha_k), in k order
+//   phase 2  one lane per document: magnitude = sum_k (n_dk + alpha_k), in k order, and the constants of the document's
+//            count-0 cells; all lanes: the cell list, in shape-class order
 //   phase 3  all lanes: Gamma(partition*magnitude) draws, one (doc, k) pair each: straight-line first try, then the
 //            general rejection loops for the elements it left over, gathered into full waves
 //   phase 4  one lane per document: sum of the gammas, in k order
@@ -62,6 +63,14 @@ enum StatusBits : uint32_t {
 // LDS: one 8-byte cell per (k, document), [K][BP] with BP = docs_per_block | 1 (odd => the
 // k-major walks of phases 2, 4, 5 are bank-conflict free): the count n_dk (int32, low word) until
 // its lane has drawn the gamma that replaces it.
+//
+// Shape classes.  What a draw needs of its shape alone (GammaConsts: a square root and three divisions) is the same for
+// every count-0 cell of a document when alpha is symmetric -- ((0 + alpha) / m_d) * m_d -- and two thirds of the cells have
+// count 0 once the chain has settled.  Class A = those cells, class B = the others; a cell is classified by its COUNT, the
+// shape is not computed for it.  Phase 3 walks a list of the workgroup's cells with class A at the front and class B at the
+// back, 64 consecutive positions per wave: a wave that holds class A only takes the constants from the document's table
+// entry, one that holds class B only never boosts (count >= 1: shape > 1) and skips the pow; at most two waves of a
+// workgroup are mixed and cost what every wave cost in index order.  Which lane draws a cell changes no bit of it.
 // ------------------------------------------------------------------------------
 struct ThetaParams {
   const int64_t *doc_ptr;
@@ -74,13 +83,16 @@ struct ThetaParams {
   uint32_t iteration;
   int32_t K, docs_per_block;
   int32_t queue_cap;   // <= kGammaQueue (smaller only in tests: the draw-on-the-spot path of a full queue)
+  int32_t sym_alpha;   // every alpha[k] has the bits of alpha[0]: count-0 cells are class A (0: every cell is class B)
 };
 
 constexpr int kGammaQueue = 768;             // uint16 element indices: a workgroup's cells number < 65536 (LDS / 8)
 constexpr int kThetaQueueBytes = 8 + 2 * kGammaQueue;
 // LDS of theta_kernel with b documents per workgroup: gam [K][b | 1] doubles, mag, tot [b] doubles, len [b] int32, the queue
-// (mirrors the carve-up at the top of the kernel, whose B is a run-time parameter)
-constexpr int theta_lds_bytes(const int K, const int b) { return (int)((size_t)K * (b | 1) * 8 + (size_t)b * 20 + kThetaQueueBytes); }
+// -- theta_cells_lds_bytes, what the planner's thresholds were measured with -- and the class-A constants [b] and the
+// cell list [K * b] uint16 (mirrors the carve-up at the top of the kernel, whose B is a run-time parameter)
+constexpr int theta_cells_lds_bytes(const int K, const int b) { return (int)((size_t)K * (b | 1) * 8 + (size_t)b * 20 + kThetaQueueBytes); }
+constexpr int theta_lds_bytes(const int K, const int b) { return theta_cells_lds_bytes(K, b) + (int)((size_t)b * sizeof(GammaConsts) + (size_t)K * b * 2); }
 
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void theta_kernel(ThetaParams p) {
@@ -90,16 +102,18 @@ __global__ __launch_bounds__(BLOCK) void theta_kernel(ThetaParams p) {
   int32_t *hist = reinterpret_cast<int32_t *>(smem);                 // the same cells: count in word 0 of cell i = hist[2 * i]
   double *mag = gam + (size_t)K * BP;                                // [B]
   double *tot = mag + B;                                             // [B]
-  int32_t *len = reinterpret_cast<int32_t *>(tot + B);               // [B]
-  int32_t *qn = len + B;                                             // [2] (one used) fill of the queue below
+  GammaConsts *ctab = reinterpret_cast<GammaConsts *>(tot + B);      // [B] of the document's count-0 cells (class A)
+  int32_t *len = reinterpret_cast<int32_t *>(ctab + B);              // [B]
+  int32_t *qn = len + B;                                             // [2] fill of the queue below; the list's cursors: class A's in the low half, class B's in the high half
   uint16_t *queue = reinterpret_cast<uint16_t *>(qn + 2);            // [kGammaQueue] elements left to the general draw
+  uint16_t *list = queue + kGammaQueue;                              // [K * B] cell indices: class A from the front, class B from the back
 
   const int tid = threadIdx.x;
   const int64_t d0 = (int64_t)blockIdx.x * B;
   const int nb = (int)min((int64_t)B, p.num_docs - d0);
 
   for (int i = tid; i < K * BP; i += BLOCK) hist[2 * i] = 0;
-  if (tid == 0) *qn = 0;
+  if (tid < 2) qn[tid] = 0;
   __syncthreads();
 
   constexpr int NW = BLOCK / 64;
@@ -115,8 +129,32 @@ __global__ __launch_bounds__(BLOCK) void theta_kernel(ThetaParams p) {
     double m = 0;
     for (int k = 0; k < K; ++k) m += (double)hist[2 * (k * BP + tid)] + p.alpha[k];  // Dirichlet(double[]): magnitude
     mag[tid] = m;
+    const double pk = (double)0 + p.alpha[0];                        // shape_of below, of a cell with count 0
+    ctab[tid] = gamma_consts((pk / m) * m);
+  }
+  // the cell list: whole waves over the nb * K cell indices (k-major, as phase 3 has always split them), each appending its
+  // class-A cells at the front cursor and its class-B cells at the back cursor.  Cells of empty documents are not listed.
+  const uint32_t m_nb = udiv_magic((uint32_t)max(nb, 1)), m_K = udiv_magic((uint32_t)K);     // nb * K cells: < 2^16
+  const int ncell = nb * K;
+  for (int i0 = wave * 64; i0 < ncell; i0 += BLOCK) {
+    const int i = i0 + lane;
+    bool listed = false, a = false;
+    if (i < ncell) {
+      const int k = udiv_small(i, m_nb), b = i - k * nb;
+      listed = len[b] > 0;
+      a = listed && p.sym_alpha && hist[2 * (k * BP + b)] == 0;
+    }
+    const unsigned long long ma = __ballot(a), mb = __ballot(listed && !a);
+    uint32_t base = 0;                                               // both counts stay below 2^16, as the cells do
+    if (lane == 0) base = atomicAdd(reinterpret_cast<uint32_t *>(qn + 1), (uint32_t)__popcll(ma) | (uint32_t)__popcll(mb) << 16);
+    base = (uint32_t)__shfl((int)base, 0);
+    const unsigned long long mine = a ? ma : mb;
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
+    if (a) list[(int)(base & 0xffffu) + rank] = (uint16_t)i;
+    else if (listed) list[ncell - 1 - ((int)(base >> 16) + rank)] = (uint16_t)i;
   }
   __syncthreads();
+  const int n_a = (int)((uint32_t)qn[1] & 0xffffu), n_b = (int)((uint32_t)qn[1] >> 16);
 
   // phase 3a: every lane tries the straight-line draw (rgamma_first_try); the ~14 % of elements it does not settle are
   // queued and drawn by the general rgamma in full waves (3b) -- or on the spot when the queue is full
@@ -131,14 +169,17 @@ __global__ __launch_bounds__(BLOCK) void theta_kernel(ThetaParams p) {
     if (rs.exhausted) atomicOr(p.status, ST_RNG_EXHAUSTED);
     return g;
   };
-  const uint32_t m_nb = udiv_magic((uint32_t)max(nb, 1)), m_K = udiv_magic((uint32_t)K);     // nb * K cells: < 2^16
-  for (int i = tid; i < nb * K; i += BLOCK) {
+  for (int pos = tid; pos < n_a + n_b; pos += BLOCK) {
+    const int i = list[pos < n_a ? pos : ncell - n_b + (pos - n_a)];
     const int k = udiv_small(i, m_nb), b = i - k * nb;
-    if (len[b] == 0) continue;                                       // GGS:52-53
-    const double shape = shape_of(k, b);
+    const bool table = __ballot(pos >= n_a) == 0;                    // wave-uniform: all of this wave's cells are class A
+    const double shape = table ? ctab[b].shape : shape_of(k, b);
     double g;
     if (shape > 0) {
-      if (!rgamma_first_try(p.seed, p.iteration, GGS_PURPOSE_THETA, (uint64_t)(p.doc_base + d0 + b) * (uint64_t)K + (uint64_t)k, shape, g)) {
+      const uint64_t elem = (uint64_t)(p.doc_base + d0 + b) * (uint64_t)K + (uint64_t)k;
+      const bool drawn = table ? rgamma_first_try(p.seed, p.iteration, GGS_PURPOSE_THETA, elem, ctab[b], g)
+                               : rgamma_first_try(p.seed, p.iteration, GGS_PURPOSE_THETA, elem, shape, g);
+      if (!drawn) {
         const int slot = atomicAdd(qn, 1);
         if (slot < p.queue_cap) { queue[slot] = (uint16_t)i; continue; }   // the cell keeps its count until 3b
         g = draw_general(k, b, shape);
@@ -500,19 +541,21 @@ __device__ __forceinline__ void phi_gamma_body(const PhiGammaParams &p) {
   // after the Phi chain and the sweep was 0.02 ms longer).
   if (p.prio) __builtin_amdgcn_s_setprio(1);
   __shared__ uint16_t queue[kPhiQueue];
+  __shared__ uint16_t list[64 * kPhiCols];   // the tile's drawn cells in shape-class order: class A (count 0) from the front, class B from the back
+  __shared__ GammaConsts ctab[kPhiCols];     // of a column's count-0 cells
   __shared__ int32_t qn;
   __shared__ double acc_lo[kPhiCols], acc_hi[kPhiCols];
   __shared__ int32_t e_los[kPhiCols], aheads[kPhiCols], flag_s[kPhiCols];
   const int lane = threadIdx.x;
   const int64_t tiles = (int64_t)(p.seg_end - p.seg_begin) * p.ncg;
-  auto shape_of = [&](int v, int k) {
-    const int32_t cnt = p.n_wk[(size_t)v * p.cnt_pitch + k];
+  auto shape_of_count = [&](int32_t cnt, int k) {
     if (p.initial) return (cnt == 0) ? p.prior_pm : p.prior_pm + (double)cnt;   // MarsagliaSparseDirichlet.java:37-41
     const double pk = p.beta + (double)cnt;                                     // GGS:188
     if constexpr (MODE == kDrawVS) return pk;
     const double m = p.mag[k];
     return (pk / m) * m;
   };
+  auto shape_of = [&](int v, int k) { return shape_of_count(p.n_wk[(size_t)v * p.cnt_pitch + k], k); };
   auto draw_general = [&](int v, int k, double shape) {
     DrawStream rs(p.seed, p.iteration, p.purpose, (uint64_t)(p.k0 + k) * (uint64_t)p.V + (uint64_t)v);
     const double g = rgamma(rs, shape);
@@ -530,8 +573,35 @@ __device__ __forceinline__ void phi_gamma_body(const PhiGammaParams &p) {
       SegCand c{kSegNoGuess, true};
       if (p.guess) c = seg_candidates(p.guess[(size_t)seg * p.K + kb + lane], p.guess[(size_t)(seg + 1) * p.K + kb + lane]);
       e_los[lane] = c.e_lo; aheads[lane] = c.ahead ? 1 : 0; acc_lo[lane] = 0; acc_hi[lane] = 0; flag_s[lane] = 0;
+      ctab[lane] = gamma_consts(shape_of_count(0, kb + lane));
     }
     if (lane == 0) qn = 0;
+    // The cell list, as in theta_kernel: every count-0 cell of a column has the column's shape, so a wave of such cells
+    // (class A, ~9 in 10 of a sparse n_wk) takes its constants from ctab; a cell with a count is class B.  Classified by
+    // the count alone.  A masked cell is written here and is in neither class.
+    int n_a = 0, n_b = 0;
+#pragma unroll 1
+    for (int j0 = 0; j0 < n; j0 += 64) {
+      const int j = j0 + lane;
+      bool listed = false, a = false;
+      if (j < n) {
+        const int dv = udiv_small(j, m_kw), v = v0 + dv, k = kb + (j - dv * kw);
+        listed = true;
+        if constexpr (MASKED) {
+          const int kg = p.k0 + k;
+          if ((p.zero_mask[(size_t)v * p.mask_pitch + (kg >> 5)] >> (kg & 31)) & 1u) {
+            p.phiT[(size_t)v * p.Kp + k] = (MODE == kDrawVS && p.undrawn_negative) ? -0.0 : 0.0;
+            listed = false;
+          }
+        }
+        a = listed && p.n_wk[(size_t)v * p.cnt_pitch + k] == 0;
+      }
+      const unsigned long long ma = __ballot(a), mb = __ballot(listed && !a), mine = a ? ma : mb;
+      const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
+      if (a) list[n_a + rank] = (uint16_t)j;
+      else if (listed) list[n - 1 - (n_b + rank)] = (uint16_t)j;
+      n_a += (int)__popcll(ma); n_b += (int)__popcll(mb);
+    }
     __syncthreads();
     auto emit = [&](int v, int c, double g) {                            // the gamma to memory, its quantised value to the segment functions
       if constexpr (PRIORS) { if (g <= 0) g = kConditionalMinGamma; }
@@ -544,19 +614,17 @@ __device__ __forceinline__ void phi_gamma_body(const PhiGammaParams &p) {
       seg_accumulate(&acc_lo[c], &acc_hi[c], &flag_s[c], q_lo, q_hi, fl);
     };
 #pragma unroll 1
-    for (int j = lane; j < n; j += 64) {
+    for (int pos = lane; pos < n_a + n_b; pos += 64) {
+      const int j = list[pos < n_a ? pos : n - n_b + (pos - n_a)];
       const int dv = udiv_small(j, m_kw), v = v0 + dv, c = j - dv * kw, k = kb + c;
-      if constexpr (MASKED) {
-        const int kg = p.k0 + k;
-        if ((p.zero_mask[(size_t)v * p.mask_pitch + (kg >> 5)] >> (kg & 31)) & 1u) {
-          p.phiT[(size_t)v * p.Kp + k] = (MODE == kDrawVS && p.undrawn_negative) ? -0.0 : 0.0;
-          continue;
-        }
-      }
-      const double shape = shape_of(v, k);
+      const bool table = __ballot(pos >= n_a) == 0;                      // wave-uniform: all of these cells are class A
+      const double shape = table ? ctab[c].shape : shape_of(v, k);
       double g;
       if (shape > 0) {
-        if (!rgamma_first_try(p.seed, p.iteration, p.purpose, (uint64_t)(p.k0 + k) * (uint64_t)p.V + (uint64_t)v, shape, g)) {
+        const uint64_t elem = (uint64_t)(p.k0 + k) * (uint64_t)p.V + (uint64_t)v;
+        const bool drawn = table ? rgamma_first_try(p.seed, p.iteration, p.purpose, elem, ctab[c], g)
+                                 : rgamma_first_try(p.seed, p.iteration, p.purpose, elem, shape, g);
+        if (!drawn) {
           const int slot = atomicAdd(&qn, 1);
           if (slot < p.queue_cap) { queue[slot] = (uint16_t)j; continue; }
           g = draw_general(v, k, shape);
