@@ -2,7 +2,7 @@
 // tui/ParallelLDA.java:173-296 drives the Java sampler.  Reads an integer corpus
 //   line 1: D V      then D lines: len tok tok ...
 // runs `iterations` sweeps and prints z and tokensPerTopic so a test can compare it with the
-// ctypes path.   usage: ggs_host_demo corpus.txt K alpha beta seed iterations [log_dir [ggs|collapsed|lightpclda|lightcollapsed]]
+// ctypes path.   usage: ggs_host_demo corpus.txt K alpha beta seed iterations [log_dir [ggs|collapsed|lightpclda|lightcollapsed|adlda]]
 // With a log_dir the corpus doubles as the test set and the loop's diagnostics are on (compute_likelihood,
 // start_diagnostic = 1, log_topic_indicators): the files of the Java driver appear there (ggs_formats.hpp).
 #include <cstdio>
@@ -14,7 +14,7 @@
 #include "ggs_sampler.hpp"
 
 int main(int argc, char **argv) {
-  if (argc < 7 || argc > 9) { std::fprintf(stderr, "usage: %s corpus.txt K alpha beta seed iterations [log_dir [ggs|collapsed|lightpclda|lightcollapsed]]\n", argv[0]); return 2; }
+  if (argc < 7 || argc > 9) { std::fprintf(stderr, "usage: %s corpus.txt K alpha beta seed iterations [log_dir [ggs|collapsed|lightpclda|lightcollapsed|adlda]]\n", argv[0]); return 2; }
   std::ifstream in(argv[1]);
   ggs::InstanceList inst;
   int64_t D;
@@ -33,6 +33,7 @@ int main(int argc, char **argv) {
   cfg.collapsed = argc >= 9 && std::string(argv[8]) == "collapsed";
   cfg.lightpclda = argc >= 9 && std::string(argv[8]) == "lightpclda";
   cfg.lightcollapsed = argc >= 9 && std::string(argv[8]) == "lightcollapsed";
+  cfg.adlda = argc >= 9 && std::string(argv[8]) == "adlda";
   struct Counting : ggs::LDAGroupedGibbsSampler {
     using LDAGroupedGibbsSampler::LDAGroupedGibbsSampler;
     int pre = 0, post = 0;
@@ -56,7 +57,7 @@ int main(int argc, char **argv) {
     std::printf("theta_estimate_doc0_sum %.17g\n", s);
     if (!logging) model.addTestInstances(inst);         // the diagnostics of the sampling loop, on the device
     std::printf("heldout %.17g\nloglik %.17g\n", model.heldOutLogLikelihood(100), model.modelLogLikelihood());
-    if (!cfg.collapsed && !cfg.lightcollapsed) std::printf("logposterior %.17g\n", model.computeLogPosterior());
+    if (!cfg.collapsed && !cfg.lightcollapsed && !cfg.adlda) std::printf("logposterior %.17g\n", model.computeLogPosterior());
   } catch (const ggs::SamplerError &e) {
     std::fprintf(stderr, "SamplerError %d: %s\n", e.code, e.what());
     return 1;

@@ -21,7 +21,7 @@ def main():
     ap.add_argument("dataset")
     ap.add_argument("--stoplist", default=None, help="one stop word per line (LDAConfiguration: stoplist.txt)")
     ap.add_argument("--rare-threshold", type=int, default=0)
-    ap.add_argument("--scheme", default="ggs", choices=["ggs", "pcgs", "collapsed", "polyaurn", "spalias", "spalias_priors", "lightpclda", "polyaurn_sparse", "lightcollapsed", "nzvsspalias"])
+    ap.add_argument("--scheme", default="ggs", choices=["ggs", "pcgs", "collapsed", "polyaurn", "spalias", "spalias_priors", "lightpclda", "polyaurn_sparse", "lightcollapsed", "nzvsspalias", "adlda"])
     ap.add_argument("--topic-priors", default=None, metavar="FILE",
                     help="scheme spalias_priors: lines `topic,word,word,...`; those words may only belong to that topic (topic_prior_filename)")
     ap.add_argument("--vs-prior", type=float, default=0.5, metavar="X",
@@ -52,6 +52,9 @@ def main():
     if args.scheme == "nzvsspalias":                          # not in create_model's registry: the class itself
         from ldagroupedgibbssampler_amd.sampler import NZVSSpaliasUncollapsedParallelLDA
         model = NZVSSpaliasUncollapsedParallelLDA(cfg)
+    elif args.scheme == "adlda":
+        from ldagroupedgibbssampler_amd.sampler import ADLDA
+        model = ADLDA(cfg)
     else:
         model = create_model(cfg)
     model.setRandomSeed(cfg.get_seed())

@@ -152,7 +152,7 @@ enum {
                                      length.  With any of GGS_FLAG_COLLAPSED, GGS_FLAG_PCGS, GGS_FLAG_POLYAURN, GGS_FLAG_SPALIAS,
                                      GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE: GGS_ERR_BAD_ARG.  A new bit, not a new ABI
                                      version. */
-  GGS_FLAG_NZVSSPALIAS = 1 << 9   /* scheme=nzvsspalias (NZVSSpaliasUncollapsedParallelLDA, ParallelLDA.java; types/VSDirichlet.java:34-112):
+  GGS_FLAG_NZVSSPALIAS = 1 << 9,  /* scheme=nzvsspalias (NZVSSpaliasUncollapsedParallelLDA, ParallelLDA.java; types/VSDirichlet.java:34-112):
                                      the pcgs model (implied: GGS_FLAG_PCGS is set internally; initial Phi, counts and alias tables as
                                      under GGS_FLAG_SPALIAS) with a VARIABLE-SELECTION Dirichlet for Phi, which has exact zeros.
                                      Phi of a sweep, per topic k: n_k = the topic's int token count, s = the zeros of the old row; the
@@ -183,6 +183,31 @@ enum {
                                      Results are bit-identical to one handle.  K up to 4096, any document length.  With any of GGS_FLAG_COLLAPSED,
                                      GGS_FLAG_POLYAURN, GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE,
                                      GGS_FLAG_LIGHTCOLLAPSED: GGS_ERR_BAD_ARG.  A new bit, not a new ABI version. */
+  GGS_FLAG_ADLDA = 1 << 10        /* scheme=adlda (ADLDA, ParallelLDA.java:409-412; MyWorkerRunnable.sampleTopicsForOneDoc,
+                                     MyWorkerRunnable.java:32-409): the collapsed model -- no theta, no Phi; ggs_get_phi, the exchange,
+                                     the likelihoods and ggs_check_invariants exactly as under GGS_FLAG_COLLAPSED -- under the SparseLDA
+                                     bucket z step of Yao, Mimno and McCallum: the exact conditional of GGS_FLAG_COLLAPSED's parallel
+                                     schedule (AD-LDA, one worker per document, every token against the counts N, T of the sweep start
+                                     minus itself) at O(nnz_d + nnz_w) per token.  At the head of every sweep: den0[k] = (double)T[k] +
+                                     betaSum; S0 = the k-order sum from 0.0 of (alpha_k * beta) / den0[k]; per word the ascending list
+                                     L_w of its topics with N[w][k] > 0 (ggs_get_word_topic_lists).  Per token (word w, old topic z0,
+                                     U the first uniform of Philox block 0 of its GGS_PURPOSE_Z stream; counts converted to double,
+                                     every expression left to right): n_d[z0]-- (a count of 0 leaves the document's list, the last
+                                     entry fills the hole); den(k) = (double)(T[k] - [k == z0]) + betaSum, G'(k) = N[w][k] - [k == z0];
+                                     S = S0 - (alpha_z0 * beta) / den0[z0] + (alpha_z0 * beta) / den(z0); R = the list-order sum of
+                                     (beta * n_d[c]) / den(c) over the document's list; Q = the list-order sum over L_w of score_j =
+                                     ((alpha_k + n_d[k]) / den(k)) * G'(k); sample = U * (S + R + Q).  sample < Q: i = -1, while
+                                     sample > 0: i++, sample -= score_i; the topic is L_w[i] (past the last entry:
+                                     GGS_ERR_INVALID_TOPIC, clamped to it).  Else sample -= Q; sample < R: sample /= beta, over the
+                                     document's list sample -= n_d[c] / den(c), the first c with sample <= 0.0, K - 1 if none (no
+                                     error).  Else sample -= R, sample /= beta, k = 0, sample -= alpha_0 / den(0), while sample > 0.0:
+                                     k++, sample -= alpha_k / den(k) (k == K: GGS_ERR_INVALID_TOPIC, clamped to K - 1).  Then
+                                     n_d[new]++, z = new.  ggs_get_sparse_stats counts the buckets.  ggs_sample_z_given_phi,
+                                     ggs_get_alias_tables and ggs_get_mh_stats: GGS_ERR_UNSUPPORTED; ggs_collapsed_serial_sweep:
+                                     GGS_ERR_STATE.  Sharded runs are bit-identical to one handle.  K up to 4096, any document
+                                     length.  With any of GGS_FLAG_COLLAPSED, GGS_FLAG_PCGS, GGS_FLAG_POLYAURN, GGS_FLAG_SPALIAS,
+                                     GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE, GGS_FLAG_LIGHTCOLLAPSED, GGS_FLAG_NZVSSPALIAS:
+                                     GGS_ERR_BAD_ARG.  A new bit, not a new ABI version. */
 };
 
 /* RNG stream addressing.  The reference draws from ThreadLocalRandom and a
@@ -509,13 +534,15 @@ int ggs_get_mh_stats(ggs_handle *h, int64_t out[3]);
  * topics[w][0 .. nw[w]) those topics in ascending order, -1 behind them.  Either output may be null.  GGS_ERR_STATE without
  * GGS_FLAG_POLYAURN_SPARSE or before the first Phi.  GGS_FLAG_LIGHTCOLLAPSED: the lists of the handle's current counts, nw[w] = the
  * number of topics with n_wk > 0 (0 for a word without tokens); the same rebuild and, with an exchange, the same collective as
- * ggs_get_alias_tables under that flag.  GGS_FLAG_NZVSSPALIAS: the lists as that flag defines them (the drawn cells). */
+ * ggs_get_alias_tables under that flag.  GGS_FLAG_ADLDA: the same lists of the current counts.  GGS_FLAG_NZVSSPALIAS: the lists
+ * as that flag defines them (the drawn cells). */
 int ggs_get_word_topic_lists(ggs_handle *h, int32_t *nw /*V*/, int32_t *topics /*[V][K]*/);
 /* scheme=polyaurn_sparse's counters, cumulative since ggs_set_corpus, every token in exactly one of the first three:
  * out[0] tokens that walked the word's list, out[1] tokens that walked the document's list, out[2] tokens drawn uniformly
  * (no candidate), out[3] the sum of n, the number of candidates, over all tokens.  GGS_ERR_STATE without
  * GGS_FLAG_POLYAURN_SPARSE or GGS_FLAG_NZVSSPALIAS (there out[2] counts the tokens drawn from the alias table for want of a
- * candidate). */
+ * candidate).  GGS_FLAG_ADLDA: out[0] tokens drawn from the word bucket Q, out[1] from the document bucket R, out[2] from the
+ * smoothing bucket S, out[3] the sum of nnz_w + nnz_d (the document's list after the token's removal) over all tokens. */
 int ggs_get_sparse_stats(ggs_handle *h, int64_t out[4]);
 /* scheme=nzvsspalias: pi, the prior probability that a cell without tokens keeps its place in the topic (vsPrior of
  * VSDirichlet; 0.5 until set).  Callable until the handle has a Phi (afterwards GGS_ERR_STATE); pi outside (0, 1):

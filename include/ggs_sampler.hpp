@@ -52,6 +52,7 @@ struct LDAConfiguration {
   bool spalias = false;           // scheme=spalias (ParallelLDA.java:439-442, SpaliasUncollapsedParallelLDA): the pcgs model, a sparse z step over alias tables
   bool lightpclda = false;        // scheme=lightpclda (ParallelLDA.java:469-473, LightPCLDA): the pcgs model, a Metropolis-Hastings z step over alias tables
   bool polyaurn_sparse = false;   // scheme=polyaurn_sparse (PolyaUrnSpaliasLDA.java:180-334): polyaurn's model, the doubly sparse z step
+  bool adlda = false;             // scheme=adlda (ParallelLDA.java:409-412, ADLDA): the collapsed model, the SparseLDA bucket z step over the counts
   bool lightcollapsed = false;    // scheme=lightcollapsed (ParallelLDA.java:429-433, CollapsedLightLDA): the collapsed model, a Metropolis-Hastings z step over the counts
   int alias_poisson_threshold = 100;   // ALIAS_POISSON_DEFAULT_THRESHOLD (LDAConfiguration.java:44); read under polyaurn and polyaurn_sparse only
   int device_id = 0;
@@ -90,7 +91,7 @@ class LDAGroupedGibbsSampler {
     c.flags = (config_.paranoid ? GGS_FLAG_PARANOID : 0) | (config_.save_phi_mean ? GGS_FLAG_SAVE_PHI_MEAN : 0) |
               (config_.pcgs ? GGS_FLAG_PCGS : 0) | (config_.collapsed ? GGS_FLAG_COLLAPSED : 0) | (config_.polyaurn ? GGS_FLAG_POLYAURN : 0) |
               (config_.spalias ? GGS_FLAG_SPALIAS : 0) | (config_.lightpclda ? GGS_FLAG_LIGHTPCLDA : 0) |
-              (config_.polyaurn_sparse ? GGS_FLAG_POLYAURN_SPARSE : 0) | (config_.lightcollapsed ? GGS_FLAG_LIGHTCOLLAPSED : 0);
+              (config_.polyaurn_sparse ? GGS_FLAG_POLYAURN_SPARSE : 0) | (config_.lightcollapsed ? GGS_FLAG_LIGHTCOLLAPSED : 0) | (config_.adlda ? GGS_FLAG_ADLDA : 0);
     c.alias_poisson_threshold = config_.alias_poisson_threshold;
     c.phi_burn_in = (int32_t)(((double)config_.phi_mean_burnin / 100) * config_.iterations);   // UPLDA:206-207
     c.phi_mean_thin = config_.phi_mean_thin;
@@ -262,7 +263,7 @@ class LDAGroupedGibbsSampler {
   std::vector<double> loglikelihood, heldOutLoglikelihood, logPosterior;    // MSLDA:114-115; UPLDA:591,843,849
   void diagnostics(int iteration) {
     const bool files = !config_.log_dir.empty();
-    if (config_.start_diagnostic > 0 && iteration >= config_.start_diagnostic && !config_.collapsed && !config_.lightcollapsed) {   // pcgs: with a fresh theta, UPLDA:710-714
+    if (config_.start_diagnostic > 0 && iteration >= config_.start_diagnostic && !config_.collapsed && !config_.lightcollapsed && !config_.adlda) {   // pcgs: with a fresh theta, UPLDA:710-714
       const double lp = computeLogPosterior();                              // UPLDA:818-821
       logPosterior.push_back(lp);
       if (files)

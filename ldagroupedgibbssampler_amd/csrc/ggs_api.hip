@@ -26,6 +26,7 @@
 #include "ggs_phi_vs.hpp"
 #include "ggs_z_lightpc.hpp"
 #include "ggs_z_lightcollapsed.hpp"
+#include "ggs_z_adlda.hpp"
 #include "ggs_loglik.hpp"
 #include "ggs_heldout.hpp"
 #include "ggs_exchange.hpp"
@@ -70,13 +71,15 @@ constexpr int kThetaBlock = 256;
 
 // What a handle samples and how: derived once from ggs_config::flags (scheme_of).  Every scheme but ggs runs the pcgs
 // machinery: no theta in the chain, a document order instead of chunk lists, the plan's lane / wave / ... entries.
-enum class Scheme { ggs, pcgs, collapsed, polyaurn, spalias, lightpclda, polyaurn_sparse, lightcollapsed, nzvsspalias };
+enum class Scheme { ggs, pcgs, collapsed, polyaurn, spalias, lightpclda, polyaurn_sparse, lightcollapsed, nzvsspalias, adlda };
 constexpr bool pcgs_family(Scheme s) { return s != Scheme::ggs; }
 constexpr bool has_alias(Scheme s) { return s == Scheme::spalias || s == Scheme::lightpclda || s == Scheme::polyaurn_sparse || s == Scheme::nzvsspalias; }
 // the count form: no Phi, the model is the type-topic counts and tokensPerTopic; the sweep's merge is the (word, z) histogram
-constexpr bool count_form(Scheme s) { return s == Scheme::collapsed || s == Scheme::lightcollapsed; }
+constexpr bool count_form(Scheme s) { return s == Scheme::collapsed || s == Scheme::lightcollapsed || s == Scheme::adlda; }
+// ... and, of these, the schemes whose z step never reads a Phi-shaped matrix or a theta: neither is allocated
+constexpr bool counts_only(Scheme s) { return s == Scheme::lightcollapsed || s == Scheme::adlda; }
 constexpr bool has_tables(Scheme s) { return has_alias(s) || s == Scheme::lightcollapsed; }   // ps / a / type_norm [V][K]: over Phi, or (lightcollapsed) over the counts
-constexpr bool has_word_lists(Scheme s) { return s == Scheme::polyaurn_sparse || s == Scheme::lightcollapsed || s == Scheme::nzvsspalias; }
+constexpr bool has_word_lists(Scheme s) { return s == Scheme::polyaurn_sparse || s == Scheme::lightcollapsed || s == Scheme::nzvsspalias || s == Scheme::adlda; }
 constexpr bool doubly_sparse(Scheme s) { return s == Scheme::polyaurn_sparse || s == Scheme::nzvsspalias; }   // sparse_wave_body<true>: the words' lists and the counters
 constexpr bool sparse_walk(Scheme s) { return s == Scheme::spalias || doubly_sparse(s); }                      // sparse_wave_body: LDS sized by the corpus
 constexpr bool has_mh(Scheme s) { return s == Scheme::lightpclda || s == Scheme::lightcollapsed; }
@@ -122,9 +125,11 @@ struct LaunchPlan {
   // nzvsspalias (ggs_phi_vs.hpp): the indicator chain's three kernels (its LDS comes with V), the list build from the drawn
   // cells (wordlist stays the build from phi != 0.0, after ggs_set_phi) and the z step
   KernelLaunch vsbits, vschain, wordmask, nzvs;
+  // adlda (ggs_z_adlda.hpp): the sweep head (den0 and S0; the words' lists of the counts) and the bucket z step (LDS per corpus)
+  KernelLaunch adhead, adlists, adlda;
   bool wave_forced = false;            // ... because of K; otherwise per corpus (a document of 32 768 tokens or more)
   int32_t alias_wpb = 0;
-  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse, &countalias, &lightcol, &vsbits, &wordmask, &nzvs}; }   // not vschain: it has static LDS, and its dynamic LDS stays below the default cap
+  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse, &countalias, &lightcol, &vsbits, &wordmask, &nzvs, &adlda}; }   // not vschain: it has static LDS, and its dynamic LDS stays below the default cap
 };
 
 // The phase events of one sweep.  Sweeps are settled (waited for, checked, timed) in batches, so a ring of them:
@@ -194,6 +199,7 @@ struct ggs_handle {
   double alpha_sum = 0;                                // the k-order sum of alpha
   bool alpha_symmetric = false;                        // every alpha[k] has the bits of alpha[0]: the theta draw's count-0 cells share their gamma constants per document
   unsigned long long *d_mh = nullptr;                  // [3]: ggs_get_mh_stats, zeroed by ggs_set_corpus
+  double *d_ad_den0 = nullptr, *d_ad_s0 = nullptr;     // scheme=adlda (ggs_z_adlda.hpp): [K] den0 and [1] S0 of the sweep-start counts
   int32_t *d_tpt = nullptr;                            // scheme=lightcollapsed (ggs_z_lightcollapsed.hpp): [V] tokensPerType of the sweep-start counts
   // scheme=polyaurn_sparse (ggs_z_polyaurn_sparse.hpp): polyaurn's Phi, spalias's tables and document lists, and per word the
   // ascending list of its topics with phi != 0, rebuilt with the tables
@@ -409,7 +415,7 @@ int check_status(ggs_handle *h) {
   if (!st) return GGS_OK;
   HIP_TRY(h, hipMemsetAsync(h->d_status, 0, sizeof(uint32_t), h->stream));
   if (st & ST_INVALID_TOPIC)
-    return set_err(h, GGS_ERR_INVALID_TOPIC, h->scheme == Scheme::collapsed ? "SimpleLDA: New topic not sampled." /* MSLDA:216-218 */ : h->scheme == Scheme::lightcollapsed ? "Collapsed Light-LDA: Sampled invalid topic." /* CollapsedLightLDA.java:957-959 */ : "LDAGroupedGibbsSampler: Topic sampled is invalid!");
+    return set_err(h, GGS_ERR_INVALID_TOPIC, h->scheme == Scheme::collapsed ? "SimpleLDA: New topic not sampled." /* MSLDA:216-218 */ : h->scheme == Scheme::lightcollapsed ? "Collapsed Light-LDA: Sampled invalid topic." /* CollapsedLightLDA.java:957-959 */ : h->scheme == Scheme::adlda ? "ADLDA: New topic not sampled." /* MyWorkerRunnable.java:332-336 */ : "LDAGroupedGibbsSampler: Topic sampled is invalid!");
   if (st & ST_NEGATIVE_COUNT) return set_err(h, GGS_ERR_NEGATIVE_COUNT, "Negative count for topic (Invalid count!)");
   if (st & ST_BAD_SHAPE) return set_err(h, GGS_ERR_BAD_ARG, "alpha and beta must be strictly positive (gamma shape <= 0)");
   if (st & ST_INVARIANT) return set_err(h, GGS_ERR_INVARIANT, "Inconsistent Indicator probability");   // VSDirichlet.java:55
@@ -951,6 +957,22 @@ int launch_count_alias_build(ggs_handle *h) {
   return GGS_OK;
 }
 
+// scheme=adlda: den0, S0 and the words' lists of the corpus-wide counts now in d_n_wk / d_n_k, on the handle's stream: at the head
+// of every z step, and for the list getter.  With an exchange every rank holds the gathered counts and builds all for itself.
+int launch_adlda_head(ggs_handle *h) {
+  int rc = launch_magnitude(h);                        // the counts gathered, tokensPerTopic in step with them
+  if (rc) return rc;
+  AdldaHeadParams hp{};
+  hp.n_k = h->d_n_k; hp.alpha = h->d_alpha; hp.den0 = h->d_ad_den0; hp.s0 = h->d_ad_s0; hp.beta = h->beta; hp.beta_sum = h->beta * (double)h->V; hp.K = h->K;
+  void *hargs[] = {&hp};
+  HIP_TRY(h, launch(h, h->plan.adhead, 1, hargs, h->stream));
+  WordListParams wp{};
+  wp.counts = h->d_n_wk; wp.nzw = h->d_nzw; wp.nw = h->d_nw; wp.V = h->V; wp.K = h->K; wp.Kp = h->Kp;
+  void *wargs[] = {&wp};
+  HIP_TRY(h, launch(h, h->plan.adlists, h->V, wargs, h->stream));
+  return GGS_OK;
+}
+
 // Phi draw: initial (K8) or per sweep (K6).  One GPU: the whole matrix in place (and tokensPerTopic refreshed);
 // with an exchange: steps A, B, C above.
 int launch_phi(ggs_handle *h, bool initial, bool accumulate_mean, Events *E = nullptr) {
@@ -1259,11 +1281,16 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, pl.lightcol.fn, 64, (size_t)pl.lightcol.lds) != hipSuccess || by_regs < 1) by_regs = 1;
     pl.lightcol.per_cu = lds_workgroups_per_cu(pl.lightcol.lds, std::min(by_regs, 32));
   }
+  if (scheme == Scheme::adlda) {                       // one wave for the head, a wave per word for the lists; the z kernel's LDS comes with the corpus
+    pl.adhead = {reinterpret_cast<const void *>(adlda_head_kernel), 64, 0, 1};
+    pl.adlists = {reinterpret_cast<const void *>(word_list_counts_kernel), kWordListBlock, 0, 8};
+    pl.adlda.fn = reinterpret_cast<const void *>(adlda_wave_kernel);
+  }
   return GGS_OK;
 }
 
 const KernelLaunch &pcgs_entry(const LaunchPlan &pl, Scheme s, bool wave) {
-  return s == Scheme::lightcollapsed ? pl.lightcol : s == Scheme::lightpclda ? pl.lightpc : s == Scheme::spalias ? pl.spalias : s == Scheme::polyaurn_sparse ? pl.pusparse : s == Scheme::nzvsspalias ? pl.nzvs : wave ? pl.wave : pl.lane;
+  return s == Scheme::adlda ? pl.adlda : s == Scheme::lightcollapsed ? pl.lightcol : s == Scheme::lightpclda ? pl.lightpc : s == Scheme::spalias ? pl.spalias : s == Scheme::polyaurn_sparse ? pl.pusparse : s == Scheme::nzvsspalias ? pl.nzvs : wave ? pl.wave : pl.lane;
 }
 int launch_pcgs_z(ggs_handle *h) {
   if (h->N == 0) return GGS_OK;
@@ -1277,6 +1304,7 @@ int launch_pcgs_z(ggs_handle *h) {
   PolyaurnSparseParams sp{};                           // spalias's kernel takes its base, SpaliasParams
   LightpcParams lp{};
   LightCollapsedParams lc{};
+  AdldaParams ad{};
   void *args[] = {&pp, &h->margin_scale};              // the wave-per-document kernel takes both, the lane-per-document kernels the first
   if (sparse_walk(h->scheme)) {
     // one wave per document over its non-zero topics (ggs_z_spalias.hpp), or over the word's where they are fewer
@@ -1292,6 +1320,11 @@ int launch_pcgs_z(ggs_handle *h) {
     pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;   // betaSum as the collapsed path forms it
     lc.b = pp; lc.ps = h->d_alias_ps; lc.a = h->d_alias_a; lc.nzw = h->d_nzw; lc.nw = h->d_nw; lc.tpt = h->d_tpt; lc.mh = h->d_mh; lc.alpha_sum = h->alpha_sum;
     args[0] = &lc;
+  } else if (h->scheme == Scheme::adlda) {             // den0, S0 and the lists of the sweep-start counts, then one wave per document (ggs_z_adlda.hpp)
+    if ((rc = launch_adlda_head(h))) return rc;
+    pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;   // betaSum as the collapsed path forms it
+    ad.b = pp; ad.den0 = h->d_ad_den0; ad.s0 = h->d_ad_s0; ad.nzw = h->d_nzw; ad.nw = h->d_nw; ad.stats = h->d_ps_stats; ad.cap = h->sp_cap; ad.margin_scale = h->margin_scale;
+    args[0] = &ad;
   } else if (h->scheme == Scheme::collapsed) {
     // the sweep-start ratios (beta + n_wk)/(betaSum + n_k) of the corpus-wide counts, then the pcgs loop over them
     if ((rc = launch_magnitude(h))) return rc;
@@ -1780,11 +1813,13 @@ int scheme_of(const ggs_config *cfg, Scheme &scheme, int32_t &poisson_L) {
   if ((f & GGS_FLAG_LIGHTCOLLAPSED) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_PCGS | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA | GGS_FLAG_POLYAURN_SPARSE))) return GGS_ERR_BAD_ARG;
   // nzvsspalias is the pcgs model under a Phi draw and a z step of its own
   if ((f & GGS_FLAG_NZVSSPALIAS) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA | GGS_FLAG_POLYAURN_SPARSE | GGS_FLAG_LIGHTCOLLAPSED))) return GGS_ERR_BAD_ARG;
-  scheme = (f & GGS_FLAG_NZVSSPALIAS) ? Scheme::nzvsspalias : (f & GGS_FLAG_LIGHTCOLLAPSED) ? Scheme::lightcollapsed : (f & GGS_FLAG_POLYAURN_SPARSE) ? Scheme::polyaurn_sparse : (f & GGS_FLAG_LIGHTPCLDA) ? Scheme::lightpclda : (f & GGS_FLAG_SPALIAS) ? Scheme::spalias : (f & GGS_FLAG_POLYAURN) ? Scheme::polyaurn
+  // adlda is the collapsed model under a z step of its own: none of the other schemes' flags beside it
+  if ((f & GGS_FLAG_ADLDA) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_PCGS | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA | GGS_FLAG_POLYAURN_SPARSE | GGS_FLAG_LIGHTCOLLAPSED | GGS_FLAG_NZVSSPALIAS))) return GGS_ERR_BAD_ARG;
+  scheme = (f & GGS_FLAG_ADLDA) ? Scheme::adlda : (f & GGS_FLAG_NZVSSPALIAS) ? Scheme::nzvsspalias : (f & GGS_FLAG_LIGHTCOLLAPSED) ? Scheme::lightcollapsed : (f & GGS_FLAG_POLYAURN_SPARSE) ? Scheme::polyaurn_sparse : (f & GGS_FLAG_LIGHTPCLDA) ? Scheme::lightpclda : (f & GGS_FLAG_SPALIAS) ? Scheme::spalias : (f & GGS_FLAG_POLYAURN) ? Scheme::polyaurn
          : (f & GGS_FLAG_COLLAPSED) ? Scheme::collapsed : (f & GGS_FLAG_PCGS) ? Scheme::pcgs : Scheme::ggs;
   poisson_L = cfg->alias_poisson_threshold == 0 ? 100 : cfg->alias_poisson_threshold;   // LDAConfiguration.java:44
   if (poisson_phi(scheme) && ((f & GGS_FLAG_COLLAPSED) || poisson_L < 1 || poisson_L > kPoissonMaxThreshold)) return GGS_ERR_BAD_ARG;
-  if (has_tables(scheme) && cfg->num_topics > kPcgsWaveMaxTopics) return GGS_ERR_UNSUPPORTED;
+  if ((has_tables(scheme) || scheme == Scheme::adlda) && cfg->num_topics > kPcgsWaveMaxTopics) return GGS_ERR_UNSUPPORTED;
   return GGS_OK;
 }
 
@@ -1859,8 +1894,8 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
   for (const void *f : {reinterpret_cast<const void *>(ll_docs_kernel), reinterpret_cast<const void *>(lp_docs_kernel)})
     if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes) != hipSuccess) return bail(GGS_ERR_HIP);
   // 4. the model's buffers
-  // (a lightcollapsed handle has no Phi: ggs_get_phi allocates the buffer of its point estimate when it is first asked for one)
-  const bool with_phi = h->scheme != Scheme::lightcollapsed;
+  // (a lightcollapsed or adlda handle has no Phi: ggs_get_phi allocates the buffer of its point estimate when it is first asked for one)
+  const bool with_phi = !counts_only(h->scheme);
   const size_t kv = (size_t)h->K * h->V, phi_elems = (size_t)h->V * h->Kp + kPhiTailPadBytes / 8;
   if ((rc = dev_alloc(h, &h->d_alpha, h->K)) || (with_phi && (rc = dev_alloc(h, &h->d_phiT, phi_elems))) ||
       (rc = dev_alloc(h, &h->d_mag, h->K)) || (rc = dev_alloc(h, &h->d_tot, h->K)) || (rc = dev_alloc(h, &h->d_n_wk, kv)) ||
@@ -1918,6 +1953,15 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     if (hipMemset(h->d_nzw, 0, kv * sizeof(uint16_t)) != hipSuccess || hipMemset(h->d_nw, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess ||
         hipMemset(h->d_tpt, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess || hipMemset(h->d_alias_ps, 0, kv * sizeof(double)) != hipSuccess ||
         hipMemset(h->d_alias_a, 0, kv * sizeof(int32_t)) != hipSuccess || hipMemset(h->d_alias_tn, 0, (size_t)h->V * sizeof(double)) != hipSuccess)
+      return bail(GGS_ERR_HIP);
+  }
+  if (h->scheme == Scheme::adlda) {                    // lists and counters start zeroed: no entry is ever read that the head did not write
+    if ((rc = dev_alloc(h, &h->d_nzw, kv)) || (rc = dev_alloc(h, &h->d_nw, (size_t)h->V)) || (rc = dev_alloc(h, &h->d_ps_stats, 4)) ||
+        (rc = dev_alloc(h, &h->d_ad_den0, (size_t)h->K)) || (rc = dev_alloc(h, &h->d_ad_s0, 1)))
+      return bail(rc);
+    if (hipMemset(h->d_nzw, 0, kv * sizeof(uint16_t)) != hipSuccess || hipMemset(h->d_nw, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess ||
+        hipMemset(h->d_ps_stats, 0, 4 * sizeof(unsigned long long)) != hipSuccess || hipMemset(h->d_ad_den0, 0, (size_t)h->K * sizeof(double)) != hipSuccess ||
+        hipMemset(h->d_ad_s0, 0, sizeof(double)) != hipSuccess)
       return bail(GGS_ERR_HIP);
   }
   if (h->scheme == Scheme::collapsed && (rc = dev_alloc(h, &h->d_lcg, 2))) return bail(rc);
@@ -2034,7 +2078,7 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
     h->pcgs_wave = pl.wave_forced || L.longest > kPcgsMaxDocLen;
     if (h->pcgs_wave && !pl.wave.fn) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=pcgs: a document of 32768 tokens or more with more than 4096 topics");
     h->pcgs_z = pcgs_entry(pl, h->scheme, h->pcgs_wave);
-    h->pcgs_items = (has_tables(h->scheme) || h->pcgs_wave) ? (int64_t)L.order.size() : ((int64_t)L.order.size() + 63) / 64;   // a wave or a lane per entry
+    h->pcgs_items = (has_tables(h->scheme) || h->scheme == Scheme::adlda || h->pcgs_wave) ? (int64_t)L.order.size() : ((int64_t)L.order.size() + 63) / 64;   // a wave or a lane per entry
     if (sparse_walk(h->scheme)) {
       // the list of a document's non-zero topics holds at most min(K, its length) entries; the resident waves are what LDS allows,
       // at most the CU's 32
@@ -2048,6 +2092,14 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, h->pcgs_z.fn, 64, (size_t)h->pcgs_z.lds) != hipSuccess || by_regs < 1) by_regs = 1;
         h->pcgs_z.per_cu = std::min(h->pcgs_z.per_cu, by_regs);
       }
+      if (const char *e = debug_env("GGS_DEBUG_SPALIAS_WPC")) h->pcgs_z.per_cu = std::max(1, std::min(h->pcgs_z.per_cu, std::atoi(e)));
+    }
+    if (h->scheme == Scheme::adlda) {                  // the same list, beside den0, alpha and a block of terms; resident waves by LDS and by registers
+      h->sp_cap = (int32_t)std::max<int64_t>(1, std::min<int64_t>(h->K, L.longest));
+      h->pcgs_z.lds = (int)adlda_lds_bytes(h->K, h->sp_cap);
+      int by_regs = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, h->pcgs_z.fn, 64, (size_t)h->pcgs_z.lds) != hipSuccess || by_regs < 1) by_regs = 1;
+      h->pcgs_z.per_cu = lds_workgroups_per_cu(h->pcgs_z.lds, std::min(by_regs, 32));
       if (const char *e = debug_env("GGS_DEBUG_SPALIAS_WPC")) h->pcgs_z.per_cu = std::max(1, std::min(h->pcgs_z.per_cu, std::atoi(e)));
     }
   }
@@ -2076,7 +2128,7 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   if (L.warm_tiers > 0 && ((rc = upload(h, &h->d_wt_pack, L.wt_pack)) || (rc = upload(h, &h->d_w_docs, L.w_docs)) ||
                            (rc = upload(h, &h->d_warm_words, L.warm_words)) || (rc = upload(h, &h->d_warm_meta, L.warm_meta))))
     return rc;
-  const bool with_theta = h->scheme != Scheme::lightcollapsed;   // no theta in its chain and none for a diagnostic (ggs_log_posterior is unsupported)
+  const bool with_theta = !counts_only(h->scheme);   // no theta in its chain and none for a diagnostic (ggs_log_posterior is unsupported)
   if ((rc = dev_alloc(h, &h->d_z, (size_t)N)) || (rc = dev_alloc(h, &h->d_zw, (size_t)N)) ||
       (with_theta && (rc = dev_alloc(h, &h->d_theta, theta_elems))) || (!pcgs && (rc = dev_alloc(h, &h->d_theta_next, theta_elems))))   // theta_next: what the ggs z phase swaps in
     return rc;
@@ -2229,7 +2281,7 @@ int ggs_sample_z_given_phi(ggs_handle *h, int32_t n_sweeps) {
   int rc = require_ready(h, true);
   if (rc) return rc;
   if (h->in_sweep) return set_err(h, GGS_ERR_STATE, "inside a split sweep");
-  if (count_form(h->scheme)) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed and scheme=lightcollapsed have no Phi to condition on");
+  if (count_form(h->scheme)) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed, scheme=lightcollapsed and scheme=adlda have no Phi to condition on");
   for (int32_t i = 0; i < n_sweeps; ++i) {
     h->iteration += 1;                                 // UPLDA:980
     h->force_detail = true;
@@ -2600,7 +2652,7 @@ int ggs_set_phi(ggs_handle *h, const double *phi) {
   if (!h || !phi) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (h->scheme == Scheme::lightcollapsed) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=lightcollapsed has no Phi to set");
+  if (counts_only(h->scheme)) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=lightcollapsed and scheme=adlda have no Phi to set");
   const size_t kv = (size_t)h->K * h->V;
   if (h->have_priors) {   // the z step leaves the prior factor out because Phi is exactly zero wherever the prior is (ggs_hip.h)
     for (int32_t v = 0; v < h->V; ++v)
@@ -2680,6 +2732,7 @@ int ggs_get_alias_tables(ggs_handle *h, double *ps, int32_t *a, double *type_nor
   if (!h) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
+  if (h->scheme == Scheme::adlda) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=adlda builds no alias tables");
   if (!has_tables(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE, GGS_FLAG_LIGHTCOLLAPSED or GGS_FLAG_NZVSSPALIAS");
   const size_t kv = (size_t)h->K * h->V;
   if (h->scheme == Scheme::lightcollapsed) {           // the tables of the current counts: what the next sweep builds at its head
@@ -2709,6 +2762,7 @@ int ggs_get_mh_stats(ggs_handle *h, int64_t out[3]) {
   if (!h || !out) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
+  if (h->scheme == Scheme::adlda) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=adlda has no Metropolis-Hastings step");
   if (!has_mh(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_mh_stats needs GGS_FLAG_LIGHTPCLDA or GGS_FLAG_LIGHTCOLLAPSED");
   unsigned long long v[3];
   HIP_TRY(h, hipMemcpyAsync(v, h->d_mh, sizeof(v), hipMemcpyDeviceToHost, h->stream));
@@ -2720,9 +2774,11 @@ int ggs_get_word_topic_lists(ggs_handle *h, int32_t *nw, int32_t *topics) {
   if (!h) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (!has_word_lists(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_word_topic_lists needs GGS_FLAG_POLYAURN_SPARSE, GGS_FLAG_LIGHTCOLLAPSED or GGS_FLAG_NZVSSPALIAS");
+  if (!has_word_lists(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_word_topic_lists needs GGS_FLAG_POLYAURN_SPARSE, GGS_FLAG_LIGHTCOLLAPSED, GGS_FLAG_NZVSSPALIAS or GGS_FLAG_ADLDA");
   if (h->scheme == Scheme::lightcollapsed) {           // of the current counts
     if ((rc = require_ready(h, false)) || (rc = launch_count_alias_build(h))) return rc;
+  } else if (h->scheme == Scheme::adlda) {             // of the current counts
+    if ((rc = require_ready(h, false)) || (rc = launch_adlda_head(h))) return rc;
   } else {
     if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
     if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
@@ -2743,7 +2799,7 @@ int ggs_get_sparse_stats(ggs_handle *h, int64_t out[4]) {
   if (!h || !out) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (!doubly_sparse(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_sparse_stats needs GGS_FLAG_POLYAURN_SPARSE or GGS_FLAG_NZVSSPALIAS");
+  if (!doubly_sparse(h->scheme) && h->scheme != Scheme::adlda) return set_err(h, GGS_ERR_STATE, "ggs_get_sparse_stats needs GGS_FLAG_POLYAURN_SPARSE, GGS_FLAG_NZVSSPALIAS or GGS_FLAG_ADLDA");
   unsigned long long v[4];
   HIP_TRY(h, hipMemcpyAsync(v, h->d_ps_stats, sizeof(v), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2793,7 +2849,7 @@ int ggs_get_theta(ggs_handle *h, int64_t doc_begin, int64_t doc_end, double *the
   int rc = require_ready(h, false);
   if (rc) return rc;
   if (doc_begin < 0 || doc_end > h->D || doc_begin > doc_end || (!theta && doc_end > doc_begin)) return set_err(h, GGS_ERR_BAD_ARG, "bad document range");
-  if (h->scheme == Scheme::lightcollapsed) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=lightcollapsed keeps no theta");
+  if (counts_only(h->scheme)) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=lightcollapsed and scheme=adlda keep no theta");
   return copy_out(h, theta, h->d_theta + (size_t)doc_begin * h->K, sizeof(double) * (size_t)(doc_end - doc_begin) * h->K);
 }
 int ggs_get_doc_topic_counts(ggs_handle *h, int64_t doc_begin, int64_t doc_end, int32_t *n_dk) {
@@ -3097,7 +3153,7 @@ int ggs_get_warm_tiers(ggs_handle *h, int32_t *tiers, int32_t *warm_words, int32
 int ggs_get_z_form(ggs_handle *h, int32_t *kernel, int32_t *form, int32_t *calibrated) {
   if (!h) return GGS_ERR_BAD_ARG;
   const bool splittable = h->plan.sliced() && h->Cs > h->Cc && h->Cc > 0;
-  if (kernel) *kernel = h->scheme == Scheme::nzvsspalias ? 10 : h->scheme == Scheme::lightcollapsed ? 9 : h->scheme == Scheme::polyaurn_sparse ? 8 : h->scheme == Scheme::lightpclda ? 7 : h->scheme == Scheme::spalias ? 6 : pcgs_family(h->scheme) ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
+  if (kernel) *kernel = h->scheme == Scheme::adlda ? 11 : h->scheme == Scheme::nzvsspalias ? 10 : h->scheme == Scheme::lightcollapsed ? 9 : h->scheme == Scheme::polyaurn_sparse ? 8 : h->scheme == Scheme::lightpclda ? 7 : h->scheme == Scheme::spalias ? 6 : pcgs_family(h->scheme) ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
   if (form) *form = h->plan.sliced() ? (splittable && h->z_split ? 1 : 2) : 0;
   if (calibrated) *calibrated = (splittable && h->z_split_tried && !h->plan.split_forced && h->plan.split) ? 1 : 0;
   return GGS_OK;

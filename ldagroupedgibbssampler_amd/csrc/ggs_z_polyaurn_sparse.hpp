@@ -35,11 +35,13 @@ struct WordListParams {
   // zero_mask[w * mask_pitch + (k >> 5)] clear -- not phi != 0.0: a drawn gamma that underflowed to 0.0 stays listed
   const uint32_t *zero_mask;
   int32_t mask_pitch;
+  // FROM_COUNTS (scheme adlda, ggs_z_adlda.hpp): the list is the topics with counts[w * K + k] > 0, the corpus-wide counts
+  const int32_t *counts;       // [V][K]
 };
 
 constexpr int kWordListBlock = 256;
 
-template <bool FROM_MASK>
+template <bool FROM_MASK, bool FROM_COUNTS = false>
 __device__ __forceinline__ void word_list_build_body(const WordListParams &p) {
   const int lane = threadIdx.x & 63, waves = kWordListBlock / 64;
   for (int64_t w = (int64_t)blockIdx.x * waves + (threadIdx.x >> 6); w < p.V; w += (int64_t)gridDim.x * waves) {
@@ -49,7 +51,8 @@ __device__ __forceinline__ void word_list_build_body(const WordListParams &p) {
     for (int k0 = 0; k0 < p.K; k0 += 64) {
       const int k = k0 + lane;
       bool nz;
-      if constexpr (FROM_MASK) nz = k < p.K && !((p.zero_mask[(size_t)w * p.mask_pitch + (k >> 5)] >> (k & 31)) & 1u);
+      if constexpr (FROM_COUNTS) nz = k < p.K && p.counts[(size_t)w * p.K + k] > 0;
+      else if constexpr (FROM_MASK) nz = k < p.K && !((p.zero_mask[(size_t)w * p.mask_pitch + (k >> 5)] >> (k & 31)) & 1u);
       else nz = k < p.K && row[k] != 0.0;
       const unsigned long long m = __ballot(nz);
       const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -61,6 +64,7 @@ __device__ __forceinline__ void word_list_build_body(const WordListParams &p) {
 }
 __global__ __launch_bounds__(kWordListBlock) void word_list_build_kernel(WordListParams p) { word_list_build_body<false>(p); }
 __global__ __launch_bounds__(kWordListBlock) void word_list_mask_kernel(WordListParams p) { word_list_build_body<true>(p); }
+__global__ __launch_bounds__(kWordListBlock) void word_list_counts_kernel(WordListParams p) { word_list_build_body<false, true>(p); }
 
 // ---- the z step ------------------------------------------------------------------------------------------------------
 struct PolyaurnSparseParams : SpaliasParams {

@@ -12,6 +12,7 @@ FLAG_PARANOID, FLAG_SAVE_PHI_MEAN, FLAG_PCGS, FLAG_COLLAPSED, FLAG_POLYAURN, FLA
 FLAG_POLYAURN_SPARSE = 128
 FLAG_LIGHTCOLLAPSED = 256
 FLAG_NZVSSPALIAS = 512
+FLAG_ADLDA = 1024
 PURPOSE_Z, PURPOSE_THETA, PURPOSE_PHI, PURPOSE_INIT_PHI = 1, 2, 3, 4
 
 
@@ -290,14 +291,15 @@ class GGSHandle:
     def word_topic_lists(self):
         """scheme=polyaurn_sparse: (nw [V], topics [V][K]) of the current Phi -- per word the number of topics with
         phi[k][w] != 0 and those topics in ascending order, -1 behind them.  scheme=lightcollapsed: of the current counts, the
-        topics with n_wk > 0."""
+        topics with n_wk > 0; scheme=adlda: the same lists of the current counts."""
         nw, topics = np.empty(self.V, np.int32), np.empty((self.V, self.K), np.int32)
         self._chk(self._L.ggs_get_word_topic_lists(self._h, _ip(nw), _ip(topics)))
         return nw, topics
 
     def sparse_stats(self):
         """scheme=polyaurn_sparse: tokens that walked the word's list, the document's list, tokens drawn uniformly (no
-        candidate) and the sum of the candidates' number over all tokens, cumulative since set_corpus (int64 [4])."""
+        candidate) and the sum of the candidates' number over all tokens, cumulative since set_corpus (int64 [4]).  scheme=adlda:
+        tokens drawn from the word bucket Q, the document bucket R, the smoothing bucket S, and the sum of nnz_w + nnz_d."""
         out = np.zeros(4, np.int64)
         self._chk(self._L.ggs_get_sparse_stats(self._h, _lp(out)))
         return out
@@ -384,7 +386,7 @@ Z_KERNEL_NAMES = {0: "z_kernel (whole-row tiles)", 1: "z_sliced_kernel + z_hot_k
                   3: "z_stream_kernel (two passes)", 4: "pcgs_sliced_kernel (lane per document)", 5: "pcgs_wave_kernel (wave per document)",
                   6: "spalias_wave_kernel (wave per document)", 7: "lightpc_wave_kernel (wave per document)",
                   8: "polyaurn_sparse_wave_kernel (wave per document)", 9: "lightcollapsed_wave_kernel (wave per document)",
-                  10: "nzvs_wave_kernel (wave per document)"}
+                  10: "nzvs_wave_kernel (wave per document)", 11: "adlda_wave_kernel (wave per document)"}
 
 
 class GGSGroup:

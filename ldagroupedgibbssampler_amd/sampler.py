@@ -220,7 +220,7 @@ class LDAGroupedGibbsSampler:
         indicators; each value is kept in the Java-named list and, with a log_dir, appended in the Java file format."""
         cfg = self.config
         from . import formats as F
-        if cfg.start_diagnostic > 0 and iteration >= cfg.start_diagnostic and not (self._scheme_flags & (native.FLAG_COLLAPSED | native.FLAG_LIGHTCOLLAPSED)):   # pcgs: with a fresh theta, UPLDA:710-714
+        if cfg.start_diagnostic > 0 and iteration >= cfg.start_diagnostic and not (self._scheme_flags & (native.FLAG_COLLAPSED | native.FLAG_LIGHTCOLLAPSED | native.FLAG_ADLDA)):   # pcgs: with a fresh theta, UPLDA:710-714
             lp = self.computeLogPosterior()                               # UPLDA:818-821
             self.logPosterior.append(lp)
             if cfg.log_dir:
@@ -584,9 +584,35 @@ class CollapsedLightLDA(LDAGroupedGibbsSampler):
         return self._h.mh_stats()
 
 
+class ADLDA(LDAGroupedGibbsSampler):
+    """scheme=adlda (topics/ADLDA.java, ParallelLDA.java:409-412; MyWorkerRunnable.sampleTopicsForOneDoc): the collapsed model --
+    no theta and no Phi are drawn, getPhi() is the point estimate (beta + n_wk)/(betaSum + n_k) -- under the SparseLDA bucket z
+    step: the conditional split into a smoothing, a document and a word mass, walked over the document's and the word's
+    non-zero topics only.  The exact conditional and the schedule of scheme=collapsed's parallel (AD-LDA) schedule, at
+    O(nnz_d + nnz_w) per token.  Constructed directly: create_model does not know the name."""
+    _scheme_flags = native.FLAG_ADLDA
+
+    def getTheta(self):
+        raise NotImplementedError("scheme=adlda never draws theta; use getThetaEstimate()")
+
+    def sampleZGivenPhi(self, iterations):
+        raise NotImplementedError("scheme=adlda has no Phi to condition on")
+
+    def getWordTopicLists(self):
+        """(nw [V], topics [V][K]): per word the topics with n_wk > 0 in ascending order, -1 behind them"""
+        self._need_data()
+        return self._h.word_topic_lists()
+
+    def getSparseStats(self):
+        """tokens drawn from the word bucket, the document bucket, the smoothing bucket; the sum of nnz_w + nnz_d (cumulative)"""
+        return self._h.sparse_stats()
+
+
 def create_model(config, scheme=None):
     """The `case "ggs"` / `case "pcgs"` / `case "collapsed"` / `case "lightcollapsed"` / `case "polyaurn"` / `case "spalias"` / `case "lightpclda"` of tui/ParallelLDA.createModel
-    (ParallelLDA.java:401-490); "spalias_priors" is :464-468; "polyaurn_sparse" is this build's name for polyaurn over the sparse z step the reference's class holds."""
+    (ParallelLDA.java:401-490); "spalias_priors" is :464-468; "polyaurn_sparse" is this build's name for polyaurn over the sparse z step the reference's class holds.
+    "adlda" (:409-412) is not in this registry, as "nzvsspalias" is not (tests/test_host_mirror.py pins the refusal of the name):
+    construct ADLDA(config) itself."""
     scheme = scheme or config.scheme
     if scheme == "ggs":
         return LDAGroupedGibbsSampler(config)
