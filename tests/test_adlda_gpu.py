@@ -5,8 +5,10 @@ schedule; the driver and the host mirrors.
 
 adlda_wave_kernel proposes by wave scans and replays the undecided tokens exactly (ggs_z_adlda.hpp); the smoothing bucket is
 always replayed.  test_debug_margin_sends_every_token_through_the_replay runs with the margins scaled so that nothing is
-decided by a scan: the same bits.  The knife-edge rows (uniforms on sample == Q, sample == R, a walk's <= 0.0, the 63 / 64
-seam of a walk) are left to a follow-up; tests/test_adlda_model.py has the edges on the CPU."""
+decided by a scan: the same bits.  The knife-edge rows (sample == Q, sample - Q == R, a walk's rest of exactly 0.0, the
+63 / 64 seam of each walk, the entries next to a zero score) are tests/adlda_knife_edge.py's: tests/test_adlda_knife_edge_gpu.py
+puts them through the device, tests/test_adlda_knife_edge_model.py shows what they tell; tests/test_adlda_model.py has the
+restatement's own edges on the CPU."""
 import os
 import socket
 import subprocess
