@@ -17,11 +17,13 @@ sys.path.insert(0, ROOT)
 
 
 def main():
+    from ldagroupedgibbssampler_amd.native import SCHEME_FLAGS
+
     ap = argparse.ArgumentParser()
     ap.add_argument("dataset")
     ap.add_argument("--stoplist", default=None, help="one stop word per line (LDAConfiguration: stoplist.txt)")
     ap.add_argument("--rare-threshold", type=int, default=0)
-    ap.add_argument("--scheme", default="ggs", choices=["ggs", "pcgs", "collapsed", "polyaurn", "spalias", "spalias_priors", "lightpclda", "polyaurn_sparse", "lightcollapsed", "nzvsspalias", "adlda"])
+    ap.add_argument("--scheme", default="ggs", choices=list(SCHEME_FLAGS) + ["spalias_priors"])   # spalias_priors: spalias's flag and --topic-priors
     ap.add_argument("--topic-priors", default=None, metavar="FILE",
                     help="scheme spalias_priors: lines `topic,word,word,...`; those words may only belong to that topic (topic_prior_filename)")
     ap.add_argument("--vs-prior", type=float, default=0.5, metavar="X",

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -70,20 +71,9 @@ struct Knobs {
 constexpr int kThetaBlock = 256;
 
 // What a handle samples and how: derived once from ggs_config::flags (scheme_of).  Every scheme but ggs runs the pcgs
-// machinery: no theta in the chain, a document order instead of chunk lists, the plan's lane / wave / ... entries.
+// machinery: no theta in the chain, a document order instead of chunk lists, the plan's lane / wave / ... entries.  What a
+// scheme is stands in its row of kSchemes, below the launch plan.
 enum class Scheme { ggs, pcgs, collapsed, polyaurn, spalias, lightpclda, polyaurn_sparse, lightcollapsed, nzvsspalias, adlda };
-constexpr bool pcgs_family(Scheme s) { return s != Scheme::ggs; }
-constexpr bool has_alias(Scheme s) { return s == Scheme::spalias || s == Scheme::lightpclda || s == Scheme::polyaurn_sparse || s == Scheme::nzvsspalias; }
-// the count form: no Phi, the model is the type-topic counts and tokensPerTopic; the sweep's merge is the (word, z) histogram
-constexpr bool count_form(Scheme s) { return s == Scheme::collapsed || s == Scheme::lightcollapsed || s == Scheme::adlda; }
-// ... and, of these, the schemes whose z step never reads a Phi-shaped matrix or a theta: neither is allocated
-constexpr bool counts_only(Scheme s) { return s == Scheme::lightcollapsed || s == Scheme::adlda; }
-constexpr bool has_tables(Scheme s) { return has_alias(s) || s == Scheme::lightcollapsed; }   // ps / a / type_norm [V][K]: over Phi, or (lightcollapsed) over the counts
-constexpr bool has_word_lists(Scheme s) { return s == Scheme::polyaurn_sparse || s == Scheme::lightcollapsed || s == Scheme::nzvsspalias || s == Scheme::adlda; }
-constexpr bool doubly_sparse(Scheme s) { return s == Scheme::polyaurn_sparse || s == Scheme::nzvsspalias; }   // sparse_wave_body<true>: the words' lists and the counters
-constexpr bool sparse_walk(Scheme s) { return s == Scheme::spalias || doubly_sparse(s); }                      // sparse_wave_body: LDS sized by the corpus
-constexpr bool has_mh(Scheme s) { return s == Scheme::lightpclda || s == Scheme::lightcollapsed; }
-constexpr bool poisson_phi(Scheme s) { return s == Scheme::polyaurn || s == Scheme::polyaurn_sparse; }   // Phi drawn as polyaurn draws it
 
 // One kernel as a handle launches it: the function, its workgroup, its dynamic LDS and the workgroups per CU of its
 // persistent grid.  The table kernels' LDS is given without table rows (they differ by corpus).
@@ -131,6 +121,66 @@ struct LaunchPlan {
   int32_t alias_wpb = 0;
   std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse, &countalias, &lightcol, &vsbits, &wordmask, &nzvs, &adlda}; }   // not vschain: it has static LDS, and its dynamic LDS stays below the default cap
 };
+
+// One row per scheme, indexed by the enum: everything the host code asks about a scheme that is not its own buffers or its own
+// launches.  A new scheme is a row here, its kernel header, its plan entry (plan_launches) and its own buffers (ggs_create).
+enum : uint32_t { kHasAlias = 1, kHasTables = 2, kCountForm = 4, kCountsOnly = 8, kHasWordLists = 16, kDoublySparse = 32, kSparseWalk = 64, kHasMh = 128,
+                  kPoissonPhi = 256, kSparseStats = 512 };   // SchemeRow::caps: what the predicates below the table ask
+struct SchemeRow {
+  const char *name;                       // as the documentation spells it; the flag is GGS_FLAG_<NAME>
+  int32_t flag, refused;                  // its own bit of ggs_config::flags (ggs: none), the bits that are GGS_ERR_BAD_ARG beside it
+  int32_t z_kernel;                       // as ggs_get_z_form numbers it; 0: chosen per handle (ggs: plan.kernel) or per corpus (4 lane, 5 wave)
+  KernelLaunch LaunchPlan::*entry;        // the wave-per-document z kernel of its own (K <= kPcgsWaveMaxTopics, a wave per order entry), or null: plan.lane / plan.wave
+  size_t (*corpus_lds)(int K, int cap);   // ... whose LDS comes with the corpus: lists of sp_cap entries; or null
+  const char *invalid_topic;              // the reference's message for GGS_ERR_INVALID_TOPIC
+  uint32_t caps;
+};
+constexpr const char *kGgsInvalidTopic = "LDAGroupedGibbsSampler: Topic sampled is invalid!";
+constexpr int32_t kModelFlags = GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN, kLightFlags = kModelFlags | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA | GGS_FLAG_POLYAURN_SPARSE;
+// `refused`: one z step per handle.  spalias, lightpclda, polyaurn_sparse and nzvsspalias run over the pcgs model only (GGS_FLAG_PCGS
+// beside them is accepted); lightcollapsed and adlda are the collapsed model under a z step of their own: no older scheme's flag
+// beside them.  (GGS_FLAG_POLYAURN | GGS_FLAG_COLLAPSED is polyaurn, refused by the Poisson check of scheme_of.)
+constexpr SchemeRow kSchemes[] = {
+    {"ggs", 0, 0, 0, nullptr, nullptr, kGgsInvalidTopic, 0},
+    {"pcgs", GGS_FLAG_PCGS, 0, 0, nullptr, nullptr, kGgsInvalidTopic, 0},
+    {"collapsed", GGS_FLAG_COLLAPSED, 0, 0, nullptr, nullptr, "SimpleLDA: New topic not sampled." /* MSLDA:216-218 */, kCountForm},
+    {"polyaurn", GGS_FLAG_POLYAURN, 0, 0, nullptr, nullptr, kGgsInvalidTopic, kPoissonPhi},
+    {"spalias", GGS_FLAG_SPALIAS, kModelFlags, 6, &LaunchPlan::spalias, spalias_lds_bytes, kGgsInvalidTopic, kHasAlias | kHasTables | kSparseWalk},
+    {"lightpclda", GGS_FLAG_LIGHTPCLDA, kModelFlags | GGS_FLAG_SPALIAS, 7, &LaunchPlan::lightpc, nullptr, kGgsInvalidTopic, kHasAlias | kHasTables | kHasMh},
+    {"polyaurn_sparse", GGS_FLAG_POLYAURN_SPARSE, kModelFlags | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA, 8, &LaunchPlan::pusparse, spalias_lds_bytes, kGgsInvalidTopic,
+     kHasAlias | kHasTables | kHasWordLists | kDoublySparse | kSparseWalk | kPoissonPhi | kSparseStats},
+    {"lightcollapsed", GGS_FLAG_LIGHTCOLLAPSED, kLightFlags | GGS_FLAG_PCGS, 9, &LaunchPlan::lightcol, nullptr, "Collapsed Light-LDA: Sampled invalid topic." /* CollapsedLightLDA.java:957-959 */,
+     kHasTables | kCountForm | kCountsOnly | kHasWordLists | kHasMh},
+    {"nzvsspalias", GGS_FLAG_NZVSSPALIAS, kLightFlags | GGS_FLAG_LIGHTCOLLAPSED, 10, &LaunchPlan::nzvs, spalias_lds_bytes, kGgsInvalidTopic,
+     kHasAlias | kHasTables | kHasWordLists | kDoublySparse | kSparseWalk | kSparseStats},
+    {"adlda", GGS_FLAG_ADLDA, kLightFlags | GGS_FLAG_PCGS | GGS_FLAG_LIGHTCOLLAPSED | GGS_FLAG_NZVSSPALIAS, 11, &LaunchPlan::adlda, adlda_lds_bytes, "ADLDA: New topic not sampled." /* MyWorkerRunnable.java:332-336 */,
+     kCountForm | kCountsOnly | kHasWordLists | kSparseStats},
+};
+constexpr int kNumSchemes = (int)(sizeof(kSchemes) / sizeof(kSchemes[0]));
+static_assert(kNumSchemes == (int)Scheme::adlda + 1, "one row per Scheme, in the enum's order");
+constexpr const SchemeRow &row_of(Scheme s) { return kSchemes[(int)s]; }
+constexpr bool has(Scheme s, uint32_t cap) { return (row_of(s).caps & cap) != 0; }
+constexpr bool pcgs_family(Scheme s) { return row_of(s).flag != 0; }
+constexpr bool has_alias(Scheme s) { return has(s, kHasAlias); }             // alias_build_kernel's tables over Phi
+constexpr bool count_form(Scheme s) { return has(s, kCountForm); }           // no Phi, the model is the type-topic counts and tokensPerTopic; the sweep's merge is the (word, z) histogram
+constexpr bool counts_only(Scheme s) { return has(s, kCountsOnly); }         // ... and the z step never reads a Phi-shaped matrix or a theta: neither is allocated
+constexpr bool has_tables(Scheme s) { return has(s, kHasTables); }           // ps / a / type_norm [V][K]: over Phi, or (lightcollapsed) over the counts
+constexpr bool has_word_lists(Scheme s) { return has(s, kHasWordLists); }    // d_nzw / d_nw: per word the ascending list of its topics
+constexpr bool doubly_sparse(Scheme s) { return has(s, kDoublySparse); }     // sparse_wave_body<true>: the words' lists and the counters
+constexpr bool sparse_walk(Scheme s) { return has(s, kSparseWalk); }         // sparse_wave_body: SpaliasParams
+constexpr bool has_mh(Scheme s) { return has(s, kHasMh); }                   // d_mh: a Metropolis-Hastings z step
+constexpr bool poisson_phi(Scheme s) { return has(s, kPoissonPhi); }         // Phi drawn as polyaurn draws it
+constexpr bool has_sparse_stats(Scheme s) { return has(s, kSparseStats); }   // d_ps_stats: ggs_get_sparse_stats
+constexpr bool wave_only(Scheme s) { return row_of(s).entry != nullptr; }   // no lane-per-document form: K <= kPcgsWaveMaxTopics, a wave per order entry
+// "F needs GGS_FLAG_A, GGS_FLAG_B or GGS_FLAG_C": the flags of the schemes with `cap`, for the getters that only they answer
+std::string needs_flag(const char *fn, uint32_t cap) {
+  std::vector<std::string> names;
+  for (const SchemeRow &r : kSchemes)
+    if (r.caps & cap) { names.push_back("GGS_FLAG_"); for (const char *c = r.name; *c; ++c) names.back() += (char)std::toupper((unsigned char)*c); }
+  std::string msg = std::string(fn) + " needs ";
+  for (size_t i = 0; i < names.size(); ++i) msg += (i == 0 ? "" : i + 1 == names.size() ? " or " : ", ") + names[i];
+  return msg;
+}
 
 // The phase events of one sweep.  Sweeps are settled (waited for, checked, timed) in batches, so a ring of them:
 // sweep i records into slot i % kEvRing; the theta drawn ahead for sweep i + 1 records th0/th1 of THAT slot.
@@ -333,7 +383,7 @@ int set_err(ggs_handle *h, int code, const std::string &msg) {
   return code;
 }
 
-#define HIP_TRY(h, expr)                                                                        \
+#define HIP_TRY(h, expr)                                                                       \
   do {                                                                                          \
     hipError_t _e = (expr);                                                                     \
     if (_e != hipSuccess)                                                                       \
@@ -352,6 +402,14 @@ int dev_alloc(ggs_handle *h, T **p, size_t count) {
   if (std::find(h->owned.begin(), h->owned.end(), slot) == h->owned.end()) h->owned.push_back(slot);
   if (*p) { (void)hipFree(*p); *p = nullptr; }
   HIP_TRY(h, hipMalloc(slot, std::max<size_t>(count, 1) * sizeof(T)));
+  return GGS_OK;
+}
+// ... and zeroed (on the null stream)
+template <typename T>
+int dev_alloc_zeroed(ggs_handle *h, T **p, size_t count) {
+  const int rc = dev_alloc(h, p, count);
+  if (rc) return rc;
+  HIP_TRY(h, hipMemset(*p, 0, sizeof(T) * count));
   return GGS_OK;
 }
 // ... and filled from the host (on the null stream)
@@ -414,8 +472,7 @@ int check_status(ggs_handle *h) {
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (!st) return GGS_OK;
   HIP_TRY(h, hipMemsetAsync(h->d_status, 0, sizeof(uint32_t), h->stream));
-  if (st & ST_INVALID_TOPIC)
-    return set_err(h, GGS_ERR_INVALID_TOPIC, h->scheme == Scheme::collapsed ? "SimpleLDA: New topic not sampled." /* MSLDA:216-218 */ : h->scheme == Scheme::lightcollapsed ? "Collapsed Light-LDA: Sampled invalid topic." /* CollapsedLightLDA.java:957-959 */ : h->scheme == Scheme::adlda ? "ADLDA: New topic not sampled." /* MyWorkerRunnable.java:332-336 */ : "LDAGroupedGibbsSampler: Topic sampled is invalid!");
+  if (st & ST_INVALID_TOPIC) return set_err(h, GGS_ERR_INVALID_TOPIC, row_of(h->scheme).invalid_topic);
   if (st & ST_NEGATIVE_COUNT) return set_err(h, GGS_ERR_NEGATIVE_COUNT, "Negative count for topic (Invalid count!)");
   if (st & ST_BAD_SHAPE) return set_err(h, GGS_ERR_BAD_ARG, "alpha and beta must be strictly positive (gamma shape <= 0)");
   if (st & ST_INVARIANT) return set_err(h, GGS_ERR_INVARIANT, "Inconsistent Indicator probability");   // VSDirichlet.java:55
@@ -682,6 +739,10 @@ int launch_magnitude(ggs_handle *h) {
 bool conditional_phi(const ggs_handle *h, bool initial) { return h->have_priors && !initial; }
 // scheme=nzvsspalias: the sweep draw is the variable-selection one (ggs_phi_vs.hpp); the initial draw is pcgs's
 bool vs_phi(const ggs_handle *h, bool initial) { return h->scheme == Scheme::nzvsspalias && !initial; }
+// ... and what a draw leaves the words' lists to be built from: nothing (the initial Phi), or its drawn cells
+void vs_note_draw(ggs_handle *h, bool initial) {
+  if (h->scheme == Scheme::nzvsspalias) { h->vs_lists = initial ? ggs_handle::VsLists::empty : ggs_handle::VsLists::drawn; if (initial) h->vs_drawn = false; }
+}
 // The indicator chain of the topics [k0, k0 + Ks) from their counts cnt [V][cnt_pitch] (tokensPerTopic in n_k) and the Phi now
 // in d_phiT: the undrawn cells into d_vs_und (by topic) and d_vs_mask (by word).  Before anything overwrites phiT.
 int launch_vs_chain(ggs_handle *h, const int32_t *cnt, int32_t cnt_pitch, int32_t Ks, int32_t k0, const int32_t *n_k) {
@@ -912,7 +973,7 @@ int phi_step_c(ggs_handle *h, bool initial, bool accumulate_mean) {
   HIP_TRY(h, hipGetLastError());
   h->have_phi = true;
   h->alias_stale = true;
-  if (h->scheme == Scheme::nzvsspalias) { h->vs_lists = initial ? ggs_handle::VsLists::empty : ggs_handle::VsLists::drawn; if (initial) h->vs_drawn = false; }
+  vs_note_draw(h, initial);
   if (h->have_priors && initial) return phi_apply_priors(h);
   return GGS_OK;
 }
@@ -931,7 +992,7 @@ int launch_alias_build(ggs_handle *h) {
   if (h->scheme == Scheme::nzvsspalias && h->vs_lists == ggs_handle::VsLists::empty) {   // the reference fills no list before its first samplePhi
     HIP_TRY(h, hipMemsetAsync(h->d_nw, 0, (size_t)h->V * sizeof(int32_t), h->stream));
   } else if (doubly_sparse(h->scheme)) {               // the words' lists of non-zero topics, of the same Phi (nzvsspalias after a sweep: of its drawn cells)
-    const bool from_mask = h->scheme == Scheme::nzvsspalias && h->vs_lists == ggs_handle::VsLists::drawn;
+    const bool from_mask = h->vs_lists == ggs_handle::VsLists::drawn;   // nzvsspalias alone has them (vs_note_draw)
     WordListParams wp{};
     wp.phiT = h->d_phiT; wp.nzw = h->d_nzw; wp.nw = h->d_nw; wp.V = h->V; wp.K = h->K; wp.Kp = h->Kp;
     wp.zero_mask = h->d_vs_mask; wp.mask_pitch = h->vs_pitch;
@@ -942,12 +1003,10 @@ int launch_alias_build(ggs_handle *h) {
   return GGS_OK;
 }
 
-// scheme=lightcollapsed: the words' lists and tables of the corpus-wide counts now in d_n_wk / d_n_k (count_alias_build_kernel),
-// on the handle's stream: at the head of every z step, and for the getters.  With an exchange every rank holds the gathered
-// counts and builds all V words for itself.
+// The head of a count-form scheme's z step (launch_sweep_head), on the handle's stream: what the step conditions on, of the
+// corpus-wide counts now in d_n_wk / d_n_k; also run for the getters.  With an exchange every rank holds the gathered counts and
+// builds all for itself.  scheme=lightcollapsed: the words' lists and tables (count_alias_build_kernel)
 int launch_count_alias_build(ggs_handle *h) {
-  int rc = launch_magnitude(h);                        // the counts gathered, tokensPerTopic in step with them
-  if (rc) return rc;
   CountAliasParams cp{};
   cp.n_wk = h->d_n_wk; cp.n_k = h->d_n_k; cp.ps = h->d_alias_ps; cp.a = h->d_alias_a; cp.type_norm = h->d_alias_tn;
   cp.nzw = h->d_nzw; cp.nw = h->d_nw; cp.tpt = h->d_tpt; cp.beta_sum = h->beta * (double)h->V;
@@ -957,11 +1016,8 @@ int launch_count_alias_build(ggs_handle *h) {
   return GGS_OK;
 }
 
-// scheme=adlda: den0, S0 and the words' lists of the corpus-wide counts now in d_n_wk / d_n_k, on the handle's stream: at the head
-// of every z step, and for the list getter.  With an exchange every rank holds the gathered counts and builds all for itself.
+// scheme=adlda: den0, S0 and the words' lists
 int launch_adlda_head(ggs_handle *h) {
-  int rc = launch_magnitude(h);                        // the counts gathered, tokensPerTopic in step with them
-  if (rc) return rc;
   AdldaHeadParams hp{};
   hp.n_k = h->d_n_k; hp.alpha = h->d_alpha; hp.den0 = h->d_ad_den0; hp.s0 = h->d_ad_s0; hp.beta = h->beta; hp.beta_sum = h->beta * (double)h->V; hp.K = h->K;
   void *hargs[] = {&hp};
@@ -970,6 +1026,18 @@ int launch_adlda_head(ggs_handle *h) {
   wp.counts = h->d_n_wk; wp.nzw = h->d_nzw; wp.nw = h->d_nw; wp.V = h->V; wp.K = h->K; wp.Kp = h->Kp;
   void *wargs[] = {&wp};
   HIP_TRY(h, launch(h, h->plan.adlists, h->V, wargs, h->stream));
+  return GGS_OK;
+}
+
+int launch_sweep_head(ggs_handle *h) {
+  const int rc = launch_magnitude(h);                  // the counts gathered, tokensPerTopic in step with them
+  if (rc) return rc;
+  if (h->scheme == Scheme::lightcollapsed) return launch_count_alias_build(h);
+  if (h->scheme == Scheme::adlda) return launch_adlda_head(h);
+  // collapsed: the ratios (beta + n_wk)/(betaSum + n_k) into phiT, for the pcgs loop over them
+  hipLaunchKernelGGL(psi_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, h->d_n_wk, h->d_n_k, h->beta, h->beta * (double)h->V, h->d_phiT,
+                     h->K, h->Kp, h->V);
+  HIP_TRY(h, hipGetLastError());
   return GGS_OK;
 }
 
@@ -994,7 +1062,7 @@ int launch_phi(ggs_handle *h, bool initial, bool accumulate_mean, Events *E = nu
     return rc;
   h->n_k_valid = true;
   h->have_phi = true;
-  if (h->scheme == Scheme::nzvsspalias) { h->vs_lists = initial ? ggs_handle::VsLists::empty : ggs_handle::VsLists::drawn; if (initial) h->vs_drawn = false; }
+  vs_note_draw(h, initial);
   if (h->have_priors && initial && (rc = phi_apply_priors(h))) return rc;
   return launch_alias_build(h);
 }
@@ -1084,6 +1152,15 @@ const void *stream_kernel_for(bool two_pass, bool regck, int group) {
 const void *pcgs_lane_kernel_for(int K, bool sliced, bool collapsed, bool polyaurn) {
   if (sliced) return collapsed ? collapsed_kernel_for(K) : polyaurn ? polyaurn_kernel_for(K) : pcgs_kernel_for(K);
   return collapsed ? reinterpret_cast<const void *>(pcgs_z_kernel<true>) : polyaurn ? reinterpret_cast<const void *>(polyaurn_z_kernel) : reinterpret_cast<const void *>(pcgs_z_kernel<false>);
+}
+
+// The resident single-wave workgroups per CU of a persistent grid (exactly what is resident: a workgroup that is not would walk
+// its share only after the others have finished theirs): what the kernel's registers allow (asked of the runtime, whose answer
+// ignores the LDS allocation granule) and what LDS allows, at most the CU's 32.
+int resident_waves_per_cu(const void *fn, int lds) {
+  int by_regs = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, fn, 64, (size_t)lds) != hipSuccess || by_regs < 1) by_regs = 1;
+  return lds_workgroups_per_cu(lds, std::min(by_regs, 32));
 }
 
 // Every launch a handle of (K, V, scheme) can make on the device: which kernel, how much LDS (the layout functions beside
@@ -1231,9 +1308,7 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
     const int nb = pcgs_wave_blocks(Kp);
     pl.wave.fn = pcgs_wave_kernel_for(nb, collapsed, polyaurn);
     pl.wave.lds = pcgs_wave_lds_bytes(nb);
-    int by_regs = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, pl.wave.fn, 64, (size_t)pl.wave.lds) != hipSuccess || by_regs < 1) by_regs = 1;
-    pl.wave.per_cu = lds_workgroups_per_cu(pl.wave.lds, std::min(by_regs, 32));
+    pl.wave.per_cu = resident_waves_per_cu(pl.wave.fn, pl.wave.lds);
   }
   pl.wave_forced = kn.pcgs_wave.set ? kn.pcgs_wave.v != 0 : K > (collapsed ? kCollapsedWaveFromTopics : polyaurn ? kPolyaurnWaveFromTopics : kPcgsWaveFromTopics);
   if (pl.wave_forced && !pl.wave.fn) return GGS_ERR_UNSUPPORTED;   // more than 4096 topics
@@ -1249,13 +1324,11 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
     pl.alias = {reinterpret_cast<const void *>(alias_build_kernel), 64, (int)alias_lds_bytes(K, pl.alias_wpb), 0};
     pl.alias.per_cu = lds_workgroups_per_cu(pl.alias.lds, 16);
   }
+  if (doubly_sparse(scheme)) pl.wordlist = {reinterpret_cast<const void *>(word_list_build_kernel), kWordListBlock, 0, 8};   // a wave per word, four to a workgroup
+  // the z kernels of the sparse walks and of adlda: their LDS comes with the corpus
   if (scheme == Scheme::spalias) pl.spalias.fn = reinterpret_cast<const void *>(spalias_wave_kernel);
-  if (scheme == Scheme::polyaurn_sparse) {             // a wave per word, four to a workgroup; the z kernel's LDS comes with the corpus
-    pl.wordlist = {reinterpret_cast<const void *>(word_list_build_kernel), kWordListBlock, 0, 8};
-    pl.pusparse.fn = reinterpret_cast<const void *>(polyaurn_sparse_wave_kernel);
-  }
-  if (scheme == Scheme::nzvsspalias) {                 // both list builds, the chain's kernels (LDS by V, a workgroup per topic) and the z step
-    pl.wordlist = {reinterpret_cast<const void *>(word_list_build_kernel), kWordListBlock, 0, 8};
+  if (scheme == Scheme::polyaurn_sparse) pl.pusparse.fn = reinterpret_cast<const void *>(polyaurn_sparse_wave_kernel);
+  if (scheme == Scheme::nzvsspalias) {                 // the list build from the drawn cells, the chain's kernels (LDS by V, a workgroup per topic) and the z step
     pl.wordmask = {reinterpret_cast<const void *>(word_list_mask_kernel), kWordListBlock, 0, 8};
     pl.vsbits = {reinterpret_cast<const void *>(vs_bits_kernel), 64, 0, 32};
     const bool global = V > kVsLdsMaxV || (kn.vs_global.set && kn.vs_global.v != 0);
@@ -1264,12 +1337,9 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
     pl.nzvs.fn = reinterpret_cast<const void *>(nzvs_wave_kernel);
   }
   if (scheme == Scheme::lightpclda) {
-    // the resident single-wave workgroups: what the kernel's registers allow (asked of the runtime) and what LDS allows, at
-    // most the CU's 32 -- a lone wave issues at a fraction of a SIMD's rate, and the step is a chain of dependent operations
+    // as many resident waves as fit: a lone wave issues at a fraction of a SIMD's rate, and the step is a chain of dependent operations
     pl.lightpc = {reinterpret_cast<const void *>(lightpc_wave_kernel), 64, (int)lightpc_lds_bytes(K), 0};
-    int by_regs = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, pl.lightpc.fn, 64, (size_t)pl.lightpc.lds) != hipSuccess || by_regs < 1) by_regs = 1;
-    pl.lightpc.per_cu = lds_workgroups_per_cu(pl.lightpc.lds, std::min(by_regs, 32));
+    pl.lightpc.per_cu = resident_waves_per_cu(pl.lightpc.fn, pl.lightpc.lds);
   }
   if (scheme == Scheme::lightcollapsed) {
     // the tables over the counts: alias_build_kernel's words per workgroup and residency; the z step: lightpc's rule
@@ -1277,9 +1347,7 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
     pl.countalias = {reinterpret_cast<const void *>(count_alias_build_kernel), 64, (int)count_alias_lds_bytes(K, pl.alias_wpb), 0};
     pl.countalias.per_cu = lds_workgroups_per_cu(pl.countalias.lds, 16);
     pl.lightcol = {reinterpret_cast<const void *>(lightcollapsed_wave_kernel), 64, (int)lightcollapsed_lds_bytes(K), 0};
-    int by_regs = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, pl.lightcol.fn, 64, (size_t)pl.lightcol.lds) != hipSuccess || by_regs < 1) by_regs = 1;
-    pl.lightcol.per_cu = lds_workgroups_per_cu(pl.lightcol.lds, std::min(by_regs, 32));
+    pl.lightcol.per_cu = resident_waves_per_cu(pl.lightcol.fn, pl.lightcol.lds);
   }
   if (scheme == Scheme::adlda) {                       // one wave for the head, a wave per word for the lists; the z kernel's LDS comes with the corpus
     pl.adhead = {reinterpret_cast<const void *>(adlda_head_kernel), 64, 0, 1};
@@ -1290,7 +1358,7 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
 }
 
 const KernelLaunch &pcgs_entry(const LaunchPlan &pl, Scheme s, bool wave) {
-  return s == Scheme::adlda ? pl.adlda : s == Scheme::lightcollapsed ? pl.lightcol : s == Scheme::lightpclda ? pl.lightpc : s == Scheme::spalias ? pl.spalias : s == Scheme::polyaurn_sparse ? pl.pusparse : s == Scheme::nzvsspalias ? pl.nzvs : wave ? pl.wave : pl.lane;
+  return row_of(s).entry ? pl.*row_of(s).entry : wave ? pl.wave : pl.lane;
 }
 int launch_pcgs_z(ggs_handle *h) {
   if (h->N == 0) return GGS_OK;
@@ -1300,11 +1368,13 @@ int launch_pcgs_z(ggs_handle *h) {
   pp.num_docs = h->pcgs_order_len; pp.tok_base = h->tok_base; pp.seed = h->seed; pp.iteration = (uint32_t)h->iteration;   // the length of the (padded) order list
   pp.K = h->K; pp.Kp = h->Kp;
   int rc;
-  if (h->alias_stale && (rc = launch_alias_build(h))) return rc;   // spalias, lightpclda, polyaurn_sparse
+  if (h->alias_stale && (rc = launch_alias_build(h))) return rc;   // the schemes with tables over Phi
+  if (count_form(h->scheme)) {
+    if ((rc = launch_sweep_head(h))) return rc;
+    pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;   // betaSum = beta * numTypes, MSLDA:136
+  }
   PolyaurnSparseParams sp{};                           // spalias's kernel takes its base, SpaliasParams
-  LightpcParams lp{};
-  LightCollapsedParams lc{};
-  AdldaParams ad{};
+  LightpcParams lp{}; LightCollapsedParams lc{}; AdldaParams ad{};
   void *args[] = {&pp, &h->margin_scale};              // the wave-per-document kernel takes both, the lane-per-document kernels the first
   if (sparse_walk(h->scheme)) {
     // one wave per document over its non-zero topics (ggs_z_spalias.hpp), or over the word's where they are fewer
@@ -1315,23 +1385,12 @@ int launch_pcgs_z(ggs_handle *h) {
   } else if (h->scheme == Scheme::lightpclda) {        // one wave per document, two proposals per token (ggs_z_lightpc.hpp)
     lp.b = pp; lp.ps = h->d_alias_ps; lp.a = h->d_alias_a; lp.mh = h->d_mh; lp.alpha_sum = h->alpha_sum;
     args[0] = &lp;
-  } else if (h->scheme == Scheme::lightcollapsed) {    // the tables of the sweep-start counts, then one wave per document (ggs_z_lightcollapsed.hpp)
-    if ((rc = launch_count_alias_build(h))) return rc;
-    pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;   // betaSum as the collapsed path forms it
+  } else if (h->scheme == Scheme::lightcollapsed) {    // one wave per document over the tables of the sweep-start counts
     lc.b = pp; lc.ps = h->d_alias_ps; lc.a = h->d_alias_a; lc.nzw = h->d_nzw; lc.nw = h->d_nw; lc.tpt = h->d_tpt; lc.mh = h->d_mh; lc.alpha_sum = h->alpha_sum;
     args[0] = &lc;
-  } else if (h->scheme == Scheme::adlda) {             // den0, S0 and the lists of the sweep-start counts, then one wave per document (ggs_z_adlda.hpp)
-    if ((rc = launch_adlda_head(h))) return rc;
-    pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;   // betaSum as the collapsed path forms it
+  } else if (h->scheme == Scheme::adlda) {             // one wave per document over den0, S0 and the lists of the sweep-start counts
     ad.b = pp; ad.den0 = h->d_ad_den0; ad.s0 = h->d_ad_s0; ad.nzw = h->d_nzw; ad.nw = h->d_nw; ad.stats = h->d_ps_stats; ad.cap = h->sp_cap; ad.margin_scale = h->margin_scale;
     args[0] = &ad;
-  } else if (h->scheme == Scheme::collapsed) {
-    // the sweep-start ratios (beta + n_wk)/(betaSum + n_k) of the corpus-wide counts, then the pcgs loop over them
-    if ((rc = launch_magnitude(h))) return rc;
-    pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;   // betaSum = beta * numTypes, MSLDA:136
-    hipLaunchKernelGGL(psi_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, h->d_n_wk, h->d_n_k, pp.beta, pp.beta_sum, h->d_phiT,
-                       h->K, h->Kp, h->V);
-    HIP_TRY(h, hipGetLastError());
   }
   HIP_TRY(h, launch(h, h->pcgs_z, h->pcgs_items, args, h->stream));
   return GGS_OK;
@@ -1803,23 +1862,15 @@ int group_collective(ggs_handle **hs, int32_t n, Step step) {
 // answered before any device is asked for.
 int scheme_of(const ggs_config *cfg, Scheme &scheme, int32_t &poisson_L) {
   const int32_t f = cfg->flags;
-  // spalias runs over the pcgs model only (polyaurn over the sparse z step is not provided); lightpclda likewise, and it is
-  // not spalias: one z step per handle
-  if ((f & GGS_FLAG_SPALIAS) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN))) return GGS_ERR_BAD_ARG;
-  if ((f & GGS_FLAG_LIGHTPCLDA) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS))) return GGS_ERR_BAD_ARG;
-  // polyaurn_sparse is a scheme of its own: polyaurn's Phi under the doubly sparse step, none of the other z steps beside it
-  if ((f & GGS_FLAG_POLYAURN_SPARSE) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA))) return GGS_ERR_BAD_ARG;
-  // lightcollapsed is the collapsed model under a z step of its own: none of the other schemes' flags beside it
-  if ((f & GGS_FLAG_LIGHTCOLLAPSED) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_PCGS | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA | GGS_FLAG_POLYAURN_SPARSE))) return GGS_ERR_BAD_ARG;
-  // nzvsspalias is the pcgs model under a Phi draw and a z step of its own
-  if ((f & GGS_FLAG_NZVSSPALIAS) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA | GGS_FLAG_POLYAURN_SPARSE | GGS_FLAG_LIGHTCOLLAPSED))) return GGS_ERR_BAD_ARG;
-  // adlda is the collapsed model under a z step of its own: none of the other schemes' flags beside it
-  if ((f & GGS_FLAG_ADLDA) && (f & (GGS_FLAG_COLLAPSED | GGS_FLAG_PCGS | GGS_FLAG_POLYAURN | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA | GGS_FLAG_POLYAURN_SPARSE | GGS_FLAG_LIGHTCOLLAPSED | GGS_FLAG_NZVSSPALIAS))) return GGS_ERR_BAD_ARG;
-  scheme = (f & GGS_FLAG_ADLDA) ? Scheme::adlda : (f & GGS_FLAG_NZVSSPALIAS) ? Scheme::nzvsspalias : (f & GGS_FLAG_LIGHTCOLLAPSED) ? Scheme::lightcollapsed : (f & GGS_FLAG_POLYAURN_SPARSE) ? Scheme::polyaurn_sparse : (f & GGS_FLAG_LIGHTPCLDA) ? Scheme::lightpclda : (f & GGS_FLAG_SPALIAS) ? Scheme::spalias : (f & GGS_FLAG_POLYAURN) ? Scheme::polyaurn
-         : (f & GGS_FLAG_COLLAPSED) ? Scheme::collapsed : (f & GGS_FLAG_PCGS) ? Scheme::pcgs : Scheme::ggs;
+  scheme = Scheme::ggs;
+  for (int i = 0; i < kNumSchemes; ++i) {              // the rows stand in the order of their bits: the highest bit set names the scheme
+    if (!(f & kSchemes[i].flag)) continue;
+    if (f & kSchemes[i].refused) return GGS_ERR_BAD_ARG;
+    scheme = (Scheme)i;
+  }
   poisson_L = cfg->alias_poisson_threshold == 0 ? 100 : cfg->alias_poisson_threshold;   // LDAConfiguration.java:44
   if (poisson_phi(scheme) && ((f & GGS_FLAG_COLLAPSED) || poisson_L < 1 || poisson_L > kPoissonMaxThreshold)) return GGS_ERR_BAD_ARG;
-  if ((has_tables(scheme) || scheme == Scheme::adlda) && cfg->num_topics > kPcgsWaveMaxTopics) return GGS_ERR_UNSUPPORTED;
+  if (wave_only(scheme) && cfg->num_topics > kPcgsWaveMaxTopics) return GGS_ERR_UNSUPPORTED;
   return GGS_OK;
 }
 
@@ -1897,50 +1948,31 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
   // (a lightcollapsed or adlda handle has no Phi: ggs_get_phi allocates the buffer of its point estimate when it is first asked for one)
   const bool with_phi = !counts_only(h->scheme);
   const size_t kv = (size_t)h->K * h->V, phi_elems = (size_t)h->V * h->Kp + kPhiTailPadBytes / 8;
-  if ((rc = dev_alloc(h, &h->d_alpha, h->K)) || (with_phi && (rc = dev_alloc(h, &h->d_phiT, phi_elems))) ||
-      (rc = dev_alloc(h, &h->d_mag, h->K)) || (rc = dev_alloc(h, &h->d_tot, h->K)) || (rc = dev_alloc(h, &h->d_n_wk, kv)) ||
-      (rc = dev_alloc(h, &h->d_n_k, h->K)) || (rc = dev_alloc(h, &h->d_status, 4)))
+  if ((rc = upload(h, &h->d_alpha, h->alpha)) || (with_phi && (rc = dev_alloc_zeroed(h, &h->d_phiT, phi_elems))) ||
+      (rc = dev_alloc(h, &h->d_mag, h->K)) || (rc = dev_alloc(h, &h->d_tot, h->K)) || (rc = dev_alloc_zeroed(h, &h->d_n_wk, kv)) ||
+      (rc = dev_alloc_zeroed(h, &h->d_n_k, h->K)) || (rc = dev_alloc_zeroed(h, &h->d_status, 4)))
     return bail(rc);
-  if ((h->flags & GGS_FLAG_SAVE_PHI_MEAN) && (rc = dev_alloc(h, &h->d_phi_mean, kv))) return bail(rc);
+  if ((h->flags & GGS_FLAG_SAVE_PHI_MEAN) && (rc = dev_alloc_zeroed(h, &h->d_phi_mean, kv))) return bail(rc);
   if (h->plan.sliced() && h->plan.f32) {
-    const size_t n32 = (size_t)h->V * h->plan.Kp32 + kPhiTailPadBytes / 4;
-    if ((rc = dev_alloc(h, &h->d_phiT32, n32))) return bail(rc);
-    if (hipMemset(h->d_phiT32, 0, sizeof(float) * n32) != hipSuccess) return bail(GGS_ERR_HIP);
-    if (kn.replays.is(1)) {
-      if ((rc = dev_alloc(h, &h->d_replays, 1))) return bail(rc);
-      if (hipMemset(h->d_replays, 0, sizeof(unsigned long long)) != hipSuccess) return bail(GGS_ERR_HIP);
-    }
+    if ((rc = dev_alloc_zeroed(h, &h->d_phiT32, (size_t)h->V * h->plan.Kp32 + kPhiTailPadBytes / 4))) return bail(rc);
+    if (kn.replays.is(1) && (rc = dev_alloc_zeroed(h, &h->d_replays, 1))) return bail(rc);
   }
   if (h->exact_sum && ((rc = dev_alloc(h, &h->d_sum_pref, ((size_t)h->sum_nseg + 1) * h->K)) ||
                        (rc = dev_alloc(h, &h->d_sum_fn, (size_t)h->sum_nseg * h->K * 4))))
     return bail(rc);
-  if (hipMemcpy(h->d_alpha, h->alpha.data(), sizeof(double) * h->K, hipMemcpyHostToDevice) != hipSuccess ||
-      (with_phi && hipMemset(h->d_phiT, 0, sizeof(double) * phi_elems) != hipSuccess) ||
-      hipMemset(h->d_n_wk, 0, sizeof(int32_t) * kv) != hipSuccess ||
-      hipMemset(h->d_n_k, 0, sizeof(int32_t) * h->K) != hipSuccess || hipMemset(h->d_status, 0, 16) != hipSuccess ||
-      (h->d_phi_mean && hipMemset(h->d_phi_mean, 0, sizeof(double) * kv) != hipSuccess))
-    return bail(GGS_ERR_HIP);
-  if (has_tables(h->scheme) && ((rc = dev_alloc(h, &h->d_alias_ps, kv)) || (rc = dev_alloc(h, &h->d_alias_a, kv)) || (rc = dev_alloc(h, &h->d_alias_tn, (size_t)h->V)))) return bail(rc);
-  if (has_mh(h->scheme) && ((rc = dev_alloc(h, &h->d_mh, 3)) || hipMemset(h->d_mh, 0, 3 * sizeof(unsigned long long)) != hipSuccess)) return bail(rc ? rc : GGS_ERR_HIP);
-  if (h->scheme == Scheme::polyaurn_sparse) {          // lists and counters start zeroed: no entry is ever read that the build did not write
-    if ((rc = dev_alloc(h, &h->d_nzw, kv)) || (rc = dev_alloc(h, &h->d_nw, (size_t)h->V)) || (rc = dev_alloc(h, &h->d_ps_stats, 4))) return bail(rc);
-    if (hipMemset(h->d_nzw, 0, kv * sizeof(uint16_t)) != hipSuccess || hipMemset(h->d_nw, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess ||
-        hipMemset(h->d_ps_stats, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
-      return bail(GGS_ERR_HIP);
-  }
-  if (h->scheme == Scheme::nzvsspalias) {              // the lists and counters as polyaurn_sparse's; the chain's rows, the mask, its outputs
+  // tables, lists and counters start zeroed: no entry is ever read that the build (adlda: the head) did not write
+  if (has_tables(h->scheme) && ((rc = dev_alloc_zeroed(h, &h->d_alias_ps, kv)) || (rc = dev_alloc_zeroed(h, &h->d_alias_a, kv)) || (rc = dev_alloc_zeroed(h, &h->d_alias_tn, (size_t)h->V)))) return bail(rc);
+  if (has_mh(h->scheme) && (rc = dev_alloc_zeroed(h, &h->d_mh, 3))) return bail(rc);
+  if (has_word_lists(h->scheme) && ((rc = dev_alloc_zeroed(h, &h->d_nzw, kv)) || (rc = dev_alloc_zeroed(h, &h->d_nw, (size_t)h->V)))) return bail(rc);
+  if (has_sparse_stats(h->scheme) && (rc = dev_alloc_zeroed(h, &h->d_ps_stats, 4))) return bail(rc);
+  if (h->scheme == Scheme::nzvsspalias) {              // the chain's rows, the mask, its outputs
     h->vs_W = (h->V + 31) / 32; h->vs_pitch = (h->K + 31) / 32;
     h->vs_global = h->plan.vschain.lds == 0;
     const size_t kw = (size_t)h->K * h->vs_W, vm = (size_t)h->V * h->vs_pitch;
-    if ((rc = dev_alloc(h, &h->d_nzw, kv)) || (rc = dev_alloc(h, &h->d_nw, (size_t)h->V)) || (rc = dev_alloc(h, &h->d_ps_stats, 4)) ||
-        (rc = dev_alloc(h, &h->d_vs_cz, kw)) || (rc = dev_alloc(h, &h->d_vs_pz, kw)) || (rc = dev_alloc(h, &h->d_vs_und, kw)) ||
-        (rc = dev_alloc(h, &h->d_vs_mask, vm)) || (rc = dev_alloc(h, &h->d_vs_s_end, (size_t)h->K)) || (rc = dev_alloc(h, &h->d_vs_rounds, (size_t)h->K)) ||
+    if ((rc = dev_alloc(h, &h->d_vs_cz, kw)) || (rc = dev_alloc(h, &h->d_vs_pz, kw)) || (rc = dev_alloc_zeroed(h, &h->d_vs_und, kw)) ||
+        (rc = dev_alloc_zeroed(h, &h->d_vs_mask, vm)) || (rc = dev_alloc(h, &h->d_vs_s_end, (size_t)h->K)) || (rc = dev_alloc_zeroed(h, &h->d_vs_rounds, (size_t)h->K)) ||
         (rc = dev_alloc(h, &h->d_vs_zero, 1)) || (h->vs_global && (rc = dev_alloc(h, &h->d_vs_work, 2 * kw))))
       return bail(rc);
-    if (hipMemset(h->d_nzw, 0, kv * sizeof(uint16_t)) != hipSuccess || hipMemset(h->d_nw, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess ||
-        hipMemset(h->d_ps_stats, 0, 4 * sizeof(unsigned long long)) != hipSuccess || hipMemset(h->d_vs_und, 0, kw * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(h->d_vs_mask, 0, vm * sizeof(uint32_t)) != hipSuccess || hipMemset(h->d_vs_rounds, 0, (size_t)h->K * sizeof(int32_t)) != hipSuccess)
-      return bail(GGS_ERR_HIP);
   }
   if (poisson_phi(h->scheme)) {
     std::vector<double> T;
@@ -1948,22 +1980,8 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     h->pa_t00 = T[0];
     if ((rc = upload(h, &h->d_pa_table, T)) || (rc = dev_alloc(h, &h->d_pa_acc, (size_t)h->K * kPoissonAccStride))) return bail(rc);
   }
-  if (h->scheme == Scheme::lightcollapsed) {           // lists and tables start zeroed: no entry is ever read that the build did not write
-    if ((rc = dev_alloc(h, &h->d_nzw, kv)) || (rc = dev_alloc(h, &h->d_nw, (size_t)h->V)) || (rc = dev_alloc(h, &h->d_tpt, (size_t)h->V))) return bail(rc);
-    if (hipMemset(h->d_nzw, 0, kv * sizeof(uint16_t)) != hipSuccess || hipMemset(h->d_nw, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess ||
-        hipMemset(h->d_tpt, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess || hipMemset(h->d_alias_ps, 0, kv * sizeof(double)) != hipSuccess ||
-        hipMemset(h->d_alias_a, 0, kv * sizeof(int32_t)) != hipSuccess || hipMemset(h->d_alias_tn, 0, (size_t)h->V * sizeof(double)) != hipSuccess)
-      return bail(GGS_ERR_HIP);
-  }
-  if (h->scheme == Scheme::adlda) {                    // lists and counters start zeroed: no entry is ever read that the head did not write
-    if ((rc = dev_alloc(h, &h->d_nzw, kv)) || (rc = dev_alloc(h, &h->d_nw, (size_t)h->V)) || (rc = dev_alloc(h, &h->d_ps_stats, 4)) ||
-        (rc = dev_alloc(h, &h->d_ad_den0, (size_t)h->K)) || (rc = dev_alloc(h, &h->d_ad_s0, 1)))
-      return bail(rc);
-    if (hipMemset(h->d_nzw, 0, kv * sizeof(uint16_t)) != hipSuccess || hipMemset(h->d_nw, 0, (size_t)h->V * sizeof(int32_t)) != hipSuccess ||
-        hipMemset(h->d_ps_stats, 0, 4 * sizeof(unsigned long long)) != hipSuccess || hipMemset(h->d_ad_den0, 0, (size_t)h->K * sizeof(double)) != hipSuccess ||
-        hipMemset(h->d_ad_s0, 0, sizeof(double)) != hipSuccess)
-      return bail(GGS_ERR_HIP);
-  }
+  if (h->scheme == Scheme::lightcollapsed && (rc = dev_alloc_zeroed(h, &h->d_tpt, (size_t)h->V))) return bail(rc);
+  if (h->scheme == Scheme::adlda && ((rc = dev_alloc_zeroed(h, &h->d_ad_den0, (size_t)h->K)) || (rc = dev_alloc_zeroed(h, &h->d_ad_s0, 1)))) return bail(rc);
   if (h->scheme == Scheme::collapsed && (rc = dev_alloc(h, &h->d_lcg, 2))) return bail(rc);
   // 5. events and streams
   for (auto &e : h->ev_part)
@@ -2078,28 +2096,15 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
     h->pcgs_wave = pl.wave_forced || L.longest > kPcgsMaxDocLen;
     if (h->pcgs_wave && !pl.wave.fn) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=pcgs: a document of 32768 tokens or more with more than 4096 topics");
     h->pcgs_z = pcgs_entry(pl, h->scheme, h->pcgs_wave);
-    h->pcgs_items = (has_tables(h->scheme) || h->scheme == Scheme::adlda || h->pcgs_wave) ? (int64_t)L.order.size() : ((int64_t)L.order.size() + 63) / 64;   // a wave or a lane per entry
-    if (sparse_walk(h->scheme)) {
-      // the list of a document's non-zero topics holds at most min(K, its length) entries; the resident waves are what LDS allows,
-      // at most the CU's 32
+    h->pcgs_items = (wave_only(h->scheme) || h->pcgs_wave) ? (int64_t)L.order.size() : ((int64_t)L.order.size() + 63) / 64;   // a wave or a lane per entry
+    if (const auto corpus_lds = row_of(h->scheme).corpus_lds) {
+      // the list of a document's non-zero topics holds at most min(K, its length) entries (adlda: beside den0, alpha and a block of
+      // terms); the resident waves by LDS and, but for spalias, by the kernel's registers.  (The doubly sparse walks took
+      // min(lds_workgroups_per_cu(lds, 32), by_regs): with Q = what LDS allows and by_regs >= 1, min(max(1, min(32, Q)), by_regs) =
+      // max(1, min(by_regs, 32, Q)) whether min(32, Q) is 0 or not, which is resident_waves_per_cu.)
       h->sp_cap = (int32_t)std::max<int64_t>(1, std::min<int64_t>(h->K, L.longest));
-      h->pcgs_z.lds = (int)spalias_lds_bytes(h->K, h->sp_cap);
-      h->pcgs_z.per_cu = lds_workgroups_per_cu(h->pcgs_z.lds, 32);
-      if (doubly_sparse(h->scheme)) {
-        // ... and what its registers allow (asked of the runtime): a workgroup of the persistent grid that is not resident
-        // would walk its share of the documents only after the others have finished theirs
-        int by_regs = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, h->pcgs_z.fn, 64, (size_t)h->pcgs_z.lds) != hipSuccess || by_regs < 1) by_regs = 1;
-        h->pcgs_z.per_cu = std::min(h->pcgs_z.per_cu, by_regs);
-      }
-      if (const char *e = debug_env("GGS_DEBUG_SPALIAS_WPC")) h->pcgs_z.per_cu = std::max(1, std::min(h->pcgs_z.per_cu, std::atoi(e)));
-    }
-    if (h->scheme == Scheme::adlda) {                  // the same list, beside den0, alpha and a block of terms; resident waves by LDS and by registers
-      h->sp_cap = (int32_t)std::max<int64_t>(1, std::min<int64_t>(h->K, L.longest));
-      h->pcgs_z.lds = (int)adlda_lds_bytes(h->K, h->sp_cap);
-      int by_regs = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, h->pcgs_z.fn, 64, (size_t)h->pcgs_z.lds) != hipSuccess || by_regs < 1) by_regs = 1;
-      h->pcgs_z.per_cu = lds_workgroups_per_cu(h->pcgs_z.lds, std::min(by_regs, 32));
+      h->pcgs_z.lds = (int)corpus_lds(h->K, h->sp_cap);
+      h->pcgs_z.per_cu = h->scheme == Scheme::spalias ? lds_workgroups_per_cu(h->pcgs_z.lds, 32) : resident_waves_per_cu(h->pcgs_z.fn, h->pcgs_z.lds);
       if (const char *e = debug_env("GGS_DEBUG_SPALIAS_WPC")) h->pcgs_z.per_cu = std::max(1, std::min(h->pcgs_z.per_cu, std::atoi(e)));
     }
   }
@@ -2728,42 +2733,41 @@ int ggs_get_topic_priors(ggs_handle *h, double *priors) {
   return GGS_OK;
 }
 
+// What ggs_get_alias_tables and ggs_get_word_topic_lists read, brought up to date: of the current counts (a count-form scheme: what
+// the next sweep builds at its head), or of the current Phi
+static int refresh_tables(ggs_handle *h) {
+  int rc;
+  if (count_form(h->scheme)) return (rc = require_ready(h, false)) ? rc : launch_sweep_head(h);
+  if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
+  return h->alias_stale ? launch_alias_build(h) : GGS_OK;
+}
 int ggs_get_alias_tables(ggs_handle *h, double *ps, int32_t *a, double *type_norm) {
   if (!h) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (h->scheme == Scheme::adlda) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=adlda builds no alias tables");
-  if (!has_tables(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_alias_tables needs GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE, GGS_FLAG_LIGHTCOLLAPSED or GGS_FLAG_NZVSSPALIAS");
+  if (!has_tables(h->scheme))                          // adlda: lightcollapsed's sibling has them; promised GGS_ERR_UNSUPPORTED in ggs_hip.h
+    return counts_only(h->scheme) ? set_err(h, GGS_ERR_UNSUPPORTED, "scheme=adlda builds no alias tables") : set_err(h, GGS_ERR_STATE, needs_flag("ggs_get_alias_tables", kHasTables));
+  if ((rc = refresh_tables(h))) return rc;
   const size_t kv = (size_t)h->K * h->V;
-  if (h->scheme == Scheme::lightcollapsed) {           // the tables of the current counts: what the next sweep builds at its head
-    if ((rc = require_ready(h, false)) || (rc = launch_count_alias_build(h))) return rc;
-    std::vector<int32_t> n((size_t)h->V);
-    HIP_TRY(h, hipMemcpyAsync(n.data(), h->d_nw, n.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (ps) HIP_TRY(h, hipMemcpyAsync(ps, h->d_alias_ps, kv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (a) HIP_TRY(h, hipMemcpyAsync(a, h->d_alias_a, kv * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (type_norm) HIP_TRY(h, hipMemcpyAsync(type_norm, h->d_alias_tn, (size_t)h->V * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int32_t w = 0; w < h->V; ++w)                 // the kernel writes a row's first nw[w] entries: behind them ps = 1.0, a = the index
-      for (int32_t i = n[(size_t)w]; i < h->K; ++i) {
-        if (ps) ps[(size_t)w * h->K + i] = 1.0;
-        if (a) a[(size_t)w * h->K + i] = i;
-      }
-    return GGS_OK;
-  }
-  if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
-  if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
+  std::vector<int32_t> n(count_form(h->scheme) ? (size_t)h->V : 0);   // lightcollapsed: the kernel writes a row's first nw[w] entries
+  if (!n.empty()) HIP_TRY(h, hipMemcpyAsync(n.data(), h->d_nw, n.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   if (ps) HIP_TRY(h, hipMemcpyAsync(ps, h->d_alias_ps, kv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (a) HIP_TRY(h, hipMemcpyAsync(a, h->d_alias_a, kv * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   if (type_norm) HIP_TRY(h, hipMemcpyAsync(type_norm, h->d_alias_tn, (size_t)h->V * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (size_t w = 0; w < n.size(); ++w)                // ... behind them ps = 1.0, a = the index
+    for (int32_t i = n[w]; i < h->K; ++i) {
+      if (ps) ps[w * h->K + i] = 1.0;
+      if (a) a[w * h->K + i] = i;
+    }
   return GGS_OK;
 }
 int ggs_get_mh_stats(ggs_handle *h, int64_t out[3]) {
   if (!h || !out) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (h->scheme == Scheme::adlda) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=adlda has no Metropolis-Hastings step");
-  if (!has_mh(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_mh_stats needs GGS_FLAG_LIGHTPCLDA or GGS_FLAG_LIGHTCOLLAPSED");
+  if (!has_mh(h->scheme))                              // adlda: as in ggs_get_alias_tables
+    return counts_only(h->scheme) ? set_err(h, GGS_ERR_UNSUPPORTED, "scheme=adlda has no Metropolis-Hastings step") : set_err(h, GGS_ERR_STATE, needs_flag("ggs_get_mh_stats", kHasMh));
   unsigned long long v[3];
   HIP_TRY(h, hipMemcpyAsync(v, h->d_mh, sizeof(v), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2774,15 +2778,8 @@ int ggs_get_word_topic_lists(ggs_handle *h, int32_t *nw, int32_t *topics) {
   if (!h) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (!has_word_lists(h->scheme)) return set_err(h, GGS_ERR_STATE, "ggs_get_word_topic_lists needs GGS_FLAG_POLYAURN_SPARSE, GGS_FLAG_LIGHTCOLLAPSED, GGS_FLAG_NZVSSPALIAS or GGS_FLAG_ADLDA");
-  if (h->scheme == Scheme::lightcollapsed) {           // of the current counts
-    if ((rc = require_ready(h, false)) || (rc = launch_count_alias_build(h))) return rc;
-  } else if (h->scheme == Scheme::adlda) {             // of the current counts
-    if ((rc = require_ready(h, false)) || (rc = launch_adlda_head(h))) return rc;
-  } else {
-    if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
-    if (h->alias_stale && (rc = launch_alias_build(h))) return rc;
-  }
+  if (!has_word_lists(h->scheme)) return set_err(h, GGS_ERR_STATE, needs_flag("ggs_get_word_topic_lists", kHasWordLists));
+  if ((rc = refresh_tables(h))) return rc;
   const size_t kv = (size_t)h->K * h->V;
   std::vector<int32_t> n((size_t)h->V);
   std::vector<uint16_t> l(topics ? kv : 0);
@@ -2799,7 +2796,7 @@ int ggs_get_sparse_stats(ggs_handle *h, int64_t out[4]) {
   if (!h || !out) return GGS_ERR_BAD_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  if (!doubly_sparse(h->scheme) && h->scheme != Scheme::adlda) return set_err(h, GGS_ERR_STATE, "ggs_get_sparse_stats needs GGS_FLAG_POLYAURN_SPARSE, GGS_FLAG_NZVSSPALIAS or GGS_FLAG_ADLDA");
+  if (!has_sparse_stats(h->scheme)) return set_err(h, GGS_ERR_STATE, needs_flag("ggs_get_sparse_stats", kSparseStats));
   unsigned long long v[4];
   HIP_TRY(h, hipMemcpyAsync(v, h->d_ps_stats, sizeof(v), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -3153,7 +3150,8 @@ int ggs_get_warm_tiers(ggs_handle *h, int32_t *tiers, int32_t *warm_words, int32
 int ggs_get_z_form(ggs_handle *h, int32_t *kernel, int32_t *form, int32_t *calibrated) {
   if (!h) return GGS_ERR_BAD_ARG;
   const bool splittable = h->plan.sliced() && h->Cs > h->Cc && h->Cc > 0;
-  if (kernel) *kernel = h->scheme == Scheme::adlda ? 11 : h->scheme == Scheme::nzvsspalias ? 10 : h->scheme == Scheme::lightcollapsed ? 9 : h->scheme == Scheme::polyaurn_sparse ? 8 : h->scheme == Scheme::lightpclda ? 7 : h->scheme == Scheme::spalias ? 6 : pcgs_family(h->scheme) ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
+  const int32_t own = row_of(h->scheme).z_kernel;
+  if (kernel) *kernel = own ? own : pcgs_family(h->scheme) ? (h->pcgs_wave ? 5 : 4) : h->plan.kernel;
   if (form) *form = h->plan.sliced() ? (splittable && h->z_split ? 1 : 2) : 0;
   if (calibrated) *calibrated = (splittable && h->z_split_tried && !h->plan.split_forced && h->plan.split) ? 1 : 0;
   return GGS_OK;

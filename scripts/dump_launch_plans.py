@@ -18,8 +18,7 @@ from ldagroupedgibbssampler_amd import native  # noqa: E402
 from ldagroupedgibbssampler_amd.corpus import zipf_unigram_corpus  # noqa: E402
 
 TOPICS = (8, 20, 100, 160, 161, 176, 192, 200, 256, 512, 1024, 2048, 4096)
-SCHEMES = {"ggs": 0, "pcgs": native.FLAG_PCGS, "collapsed": native.FLAG_COLLAPSED, "polyaurn": native.FLAG_POLYAURN, "spalias": native.FLAG_SPALIAS,
-           "lightpclda": native.FLAG_LIGHTPCLDA, "polyaurn_sparse": native.FLAG_POLYAURN_SPARSE, "lightcollapsed": native.FLAG_LIGHTCOLLAPSED, "nzvsspalias": native.FLAG_NZVSSPALIAS, "adlda": native.FLAG_ADLDA}
+SCHEMES = native.SCHEME_FLAGS
 
 
 def main():

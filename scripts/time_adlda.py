@@ -32,7 +32,7 @@ from ldagroupedgibbssampler_amd.corpus import synthetic_lda_corpus  # noqa: E402
 
 SEED, ALPHA, BETA = 2019, 0.1, 0.01
 SCHEMES = ("adlda", "collapsed", "lightcollapsed")
-FLAGS = {"adlda": native.FLAG_ADLDA, "collapsed": native.FLAG_COLLAPSED, "lightcollapsed": native.FLAG_LIGHTCOLLAPSED}
+FLAGS = {s: native.SCHEME_FLAGS[s] for s in SCHEMES}
 
 
 def timed(h, steps):

@@ -58,8 +58,7 @@ def build_ms(h, steps):
 
 
 def handle(scheme, corpus, K):
-    flags = {"lightcollapsed": native.FLAG_LIGHTCOLLAPSED, "collapsed": native.FLAG_COLLAPSED}[scheme]
-    h = native.GGSHandle(K, corpus.num_types, ALPHA, BETA, SEED, flags=flags)
+    h = native.GGSHandle(K, corpus.num_types, ALPHA, BETA, SEED, flags=native.SCHEME_FLAGS[scheme])
     h.set_corpus(corpus.doc_ptr, corpus.tokens)
     return h
 

@@ -28,7 +28,7 @@ from ldagroupedgibbssampler_amd import native  # noqa: E402
 from ldagroupedgibbssampler_amd.corpus import synthetic_lda_corpus  # noqa: E402
 
 SEED, ALPHA, BETA = 2019, 0.1, 0.01
-FLAGS = {"nzvsspalias": native.FLAG_NZVSSPALIAS, "spalias": native.FLAG_SPALIAS, "polyaurn_sparse": native.FLAG_POLYAURN_SPARSE}
+FLAGS = {s: native.SCHEME_FLAGS[s] for s in ("nzvsspalias", "spalias", "polyaurn_sparse")}
 PHASES = ("theta_ms", "z_ms", "merge_ms", "phi_ms", "exchange_ms")
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "nzvs_bench.jsonl")
 

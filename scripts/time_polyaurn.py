@@ -23,8 +23,7 @@ SEED, ALPHA, BETA = 2019, 0.1, 0.01
 
 
 def run(leg, scheme, corpus, K, steps, warmup, world=1, rank=0, tok_base=0, doc_base=0, total_tokens=None):
-    flags = {"polyaurn": native.FLAG_POLYAURN, "pcgs": native.FLAG_PCGS}[scheme]
-    h = native.GGSHandle(K, corpus.num_types, ALPHA, BETA, SEED, flags=flags)
+    h = native.GGSHandle(K, corpus.num_types, ALPHA, BETA, SEED, flags=native.SCHEME_FLAGS[scheme])
     if world > 1:
         h.attach_null_exchange(rank, world)
     h.set_corpus(corpus.doc_ptr, corpus.tokens, doc_base, tok_base)

@@ -26,7 +26,7 @@ from ldagroupedgibbssampler_amd import native  # noqa: E402
 from ldagroupedgibbssampler_amd.corpus import synthetic_lda_corpus  # noqa: E402
 
 SEED, ALPHA, BETA = 2019, 0.1, 0.01
-FLAGS = {"polyaurn_sparse": native.FLAG_POLYAURN_SPARSE, "polyaurn": native.FLAG_POLYAURN, "spalias": native.FLAG_SPALIAS}
+FLAGS = {s: native.SCHEME_FLAGS[s] for s in ("polyaurn_sparse", "polyaurn", "spalias")}
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "polyaurn_sparse_bench.jsonl")
 
 

@@ -43,7 +43,7 @@ def timed(h, steps):
 
 
 def handle(scheme, corpus, K):
-    h = native.GGSHandle(K, corpus.num_types, ALPHA, BETA, SEED, flags={"spalias": native.FLAG_SPALIAS, "pcgs": native.FLAG_PCGS}[scheme])
+    h = native.GGSHandle(K, corpus.num_types, ALPHA, BETA, SEED, flags=native.SCHEME_FLAGS[scheme])
     h.set_corpus(corpus.doc_ptr, corpus.tokens)
     return h
 
