@@ -130,7 +130,8 @@ class Probabilities:
     def __call__(self, s):
         s = int(s)
         if s not in self.known:
-            want = [t for t in range(max(0, s - 48), s + 49) if t not in self.known]
+            half = max(48, len(self.known) // 2)                    # a chain that has wandered far goes on wandering
+            want = [t for t in range(max(0, s - half), s + half + 1) if t not in self.known]
             for t, p in zip(want, indicator_probability(np.array(want), self.n_k, self.beta, self.pi)):
                 self.known[t] = float(p)
         return self.known[s]
@@ -167,11 +168,12 @@ def sequential_chain(counts, prev_phi, U, beta, pi):
     return drawn, s, bad
 
 
-def rounds_chain(counts, prev_phi, U, beta, pi, confirm=True):
+def rounds_chain(counts, prev_phi, U, beta, pi, confirm=True, max_rounds=None):
     """vs_chain_kernel's rounds: s is kept at the start of every 32-cell word (s0 everywhere before the first round); a round
     walks every word cell by cell from its start, then the starts become s0 + the exclusive scan of the words' steps; rounds
     repeat until one changes no decision and no start.  confirm=False ends at the first round that changes no DECISION,
-    without confirming that the starts it has just moved leave the decisions standing (the tests show that this is wrong).
+    without confirming that the starts it has just moved leave the decisions standing (the tests show that this is wrong);
+    max_rounds ends after that many rounds whatever they changed (wrong too: tests/test_nzvs_knife_edge_model.py).
     Returns (drawn [V] bool, s behind the last cell, rounds)."""
     counts = np.asarray(counts)
     V = counts.size
@@ -183,9 +185,10 @@ def rounds_chain(counts, prev_phi, U, beta, pi, confirm=True):
     P = Probabilities(n_k, beta, pi)
     sw, und = np.full(W, s0, np.int64), np.zeros((W, 32), bool)
     rounds = 0
+    live = [b for b in range(32) if cz[:, b].any()]                 # a position at which no word has a cell without a count decides nothing
     while True:
         s, un = sw.copy(), np.zeros((W, 32), bool)
-        for b in range(32):
+        for b in live:
             with np.errstate(invalid="ignore"):
                 above = Uw[:, b] > P.many(s)                        # false for a NaN p
             undrawn, kept = cz[:, b] & above, cz[:, b] & ~above
@@ -196,7 +199,7 @@ def rounds_chain(counts, prev_phi, U, beta, pi, confirm=True):
         changed = bool((un != und).any()) or (confirm and bool((new_sw != sw).any()))
         und, sw, s_end = un, new_sw, s0 + int(d.sum())
         rounds += 1
-        if not changed:
+        if not changed or rounds == max_rounds:
             break
         assert rounds <= V + 2
     return ~und.reshape(-1)[:V], s_end, rounds

@@ -235,6 +235,7 @@ def test_the_phi_mean_stays_zero_and_n_sampled_counts(native, oracle, cats):
 
 # ---- sharded: bit-identical to one handle ---------------------------------------------------------------------------
 # Each rank runs the indicator chain of its own topic slice; the drawn sets travel as the sign of zero of the gathered gammas.
+# A drawn cell whose gamma underflowed holds +0.0 and stays listed: every case asserts that it has one.
 def _rank(native, tr, rank, world, whole, K, mode, sweeps, out, errs):
     import torch
     from ldagroupedgibbssampler_amd.sharded import _DevPtr
@@ -292,9 +293,8 @@ def _rank(native, tr, rank, world, whole, K, mode, sweeps, out, errs):
         tr.bar.abort()
 
 
-@pytest.mark.parametrize("mode", ["dense", "sparse"])
-def test_two_ranks_equal_one_handle(native, oracle, mode):
-    world, sweeps, K, V = 2, 3, 40, 900
+def ranks_equal_one_handle(native, world, K, mode):
+    sweeps, V = 3, 900
     whole = random_corpus(310, V, 90, seed=K + V, empty_every=9)
     tr, out, errs = ThreadTransport(world), [None] * world, []
     ts = [threading.Thread(target=_rank, args=(native, tr, r, world, whole, K, mode, sweeps, out, errs)) for r in range(world)]
@@ -324,8 +324,28 @@ def test_two_ranks_equal_one_handle(native, oracle, mode):
             assert_bit_equal(out[r]["lists"][i], ref["lists"][i], "%s rank %d" % (name, r))
         assert tuple(out[r]["vs"][:2]) == tuple(ref["vs"][:2]), "undrawn and zero cells, rank %d" % r
     assert max(out[r]["vs"][2] for r in range(world)) == ref["vs"][2]   # a rank reports the rounds of its own topics' chains
-    assert_bit_equal(out[0]["stats"] + out[1]["stats"], ref["stats"], "sparse_stats summed over the ranks")
+    assert_bit_equal(np.sum([out[r]["stats"] for r in range(world)], axis=0), ref["stats"], "sparse_stats summed over the ranks")
     assert ref["vs"][0] > 0 and ref["stats"][0] > 0 and ref["stats"][1] > 0
+    # a drawn cell whose Gamma(beta) underflowed: +0.0 and listed.  The sign of zero that carries the drawn set between the ranks
+    # must not take it for an undrawn cell (-0.0 on the way); the lists above are already equal on every rank.
+    nw, topics = ref["lists"]
+    listed = np.zeros((K, V), bool)
+    for w in range(V):
+        listed[topics[w, :nw[w]], w] = True
+    underflowed = int((listed & (ref["phi"] == 0.0)).sum())
+    print("world=%d K=%d %s: %d drawn cells hold +0.0, %d cells undrawn" % (world, K, mode, underflowed, ref["vs"][0]))
+    assert underflowed >= 1 and int((~listed).sum()) == ref["vs"][0]
+
+
+@pytest.mark.parametrize("mode", ["dense", "sparse"])
+def test_two_ranks_equal_one_handle(native, oracle, mode):
+    ranks_equal_one_handle(native, 2, 40, mode)
+
+
+def test_three_ranks_whose_slices_straddle_the_mask_words(native, oracle):
+    """K = 70 over three ranks: slices of 24, 23 and 23 topics, so k0 = 24 and 47 fall inside the 32-bit words of the masks that
+    vs_bits_kernel and vs_mask_kernel write by topic"""
+    ranks_equal_one_handle(native, 3, 70, "dense")
 
 
 # ---- misuse and the launch plan -------------------------------------------------------------------------------------
