@@ -34,6 +34,9 @@ def main():
     ap.add_argument("--iterations", type=int, default=200)
     ap.add_argument("--seed", type=int, default=4711)
     ap.add_argument("--top-words", type=int, default=8)
+    ap.add_argument("--doc-topic-distances", action="store_true",
+                    help="compute_doc_topic_distances: min_doc_distances.csv and min_topic_distances.csv in --out, one line per iteration from --start-diagnostic on")
+    ap.add_argument("--start-diagnostic", type=int, default=500, help="start_diagnostic: first iteration of the log posterior and the distances")
     ap.add_argument("--out", default=None, help="directory for the driver's files (phi / theta / counts / likelihood)")
     args = ap.parse_args()
     if args.topic_priors and args.scheme != "spalias_priors":
@@ -50,7 +53,8 @@ def main():
         os.makedirs(args.out, exist_ok=True)
     cfg = SimpleLDAConfiguration(scheme=args.scheme, topics=args.topics, alpha=args.alpha, beta=args.beta, iterations=args.iterations,
                                  seed=args.seed, exec_time=None, compute_likelihood=bool(args.out), log_dir=args.out,
-                                 topic_prior_filename=args.topic_priors, variable_selection_prior=args.vs_prior)
+                                 topic_prior_filename=args.topic_priors, variable_selection_prior=args.vs_prior,
+                                 compute_doc_topic_distances=args.doc_topic_distances, start_diagnostic=args.start_diagnostic)
     if args.scheme == "nzvsspalias":                          # not in create_model's registry: the class itself
         from ldagroupedgibbssampler_amd.sampler import NZVSSpaliasUncollapsedParallelLDA
         model = NZVSSpaliasUncollapsedParallelLDA(cfg)

@@ -284,6 +284,14 @@ inline void append_heldout_log_likelihood(const std::string &log_dir, int iterat
 inline void append_log_posterior(const std::string &log_dir, int iteration, double value, long long millis) {   // LDAUtils.java:955-968
   append_line(log_dir + "/log-posterior.txt", std::to_string(iteration) + "\t" + java_format_fixed(value, 6) + "\t" + std::to_string(millis));
 }
+inline void append_min_doc_distances(const std::string &log_dir, int iteration, const double *values, int64_t n) {   // UPLDA:724-748
+  std::string line = std::to_string(iteration);
+  for (int64_t i = 0; i < n; ++i) { line += ","; line += java_double_to_string(values[i]); }
+  append_line(log_dir + "/min_doc_distances.csv", line);
+}
+inline void append_min_topic_distance(const std::string &log_dir, int iteration, double value) {                    // UPLDA:799-801
+  append_line(log_dir + "/min_topic_distances.csv", std::to_string(iteration) + "," + java_double_to_string(value));
+}
 
 }  // namespace formats
 }  // namespace ggs

@@ -581,6 +581,28 @@ int ggs_model_log_likelihood(ggs_handle *h, double *doc_side, double *topic_side
  * under the Philox stream GGS_PURPOSE_THETA at the current iteration (reproducible; ggs_get_theta returns it afterwards).
  * GGS_ERR_UNSUPPORTED for scheme collapsed (no Phi). */
 int ggs_log_posterior(ggs_handle *h, double *doc_side, double *topic_side);
+/* replaces: the two distance loops of the diagnostics (compute_doc_topic_distances; UPLDA:723-753 "Quantity A" and :778-806
+ * "Quantity B"; the same code in SerialCollapsedLDA.java:221-305 and ADLDA.java:414 ff.), on the device-resident state.
+ * Per pair: s = 0.0; for k in index order t = a[k] - b[k], s = s + t * t (product and sum rounded separately, never fused:
+ * Math.pow(t, 2.0) is t * t on HotSpot from JDK 9 on -- an assumption for older JVMs and StrictMath); dist = sqrt(s); the minimum
+ * starts at 1e+20 and is replaced only when dist < min, so a NaN distance never enters and a row without a partner reports 1e+20.
+ * sqrt is correctly rounded, hence monotone: the kernels minimise the sums and take one square root per output
+ * (csrc/ggs_distances.hpp).  Bit-identical to that loop.
+ * ggs_min_doc_distances: min_dist[d], d in [0, D): the smallest distance of this handle's theta row d to
+ *   other == NULL (n_other must be 0): every OTHER row of this handle's theta -- the reference's loop (min_doc_distances.csv);
+ *   other given: the n_other rows of the foreign block other [n_other][K] (host memory; nothing is skipped).  A doc-sharded run
+ *   calls once with NULL and once per foreign shard's theta block and takes the element-wise minimum: bit-identical to one handle.
+ *   The block travels to the device in pieces of at most 64 MiB.
+ * theta: scheme ggs -- the thetaMatrix of the last z step (UPLDA:716-720); the pcgs family -- the diagnostic draw of
+ * ggs_log_posterior (UPLDA:710-714: the stream GGS_PURPOSE_THETA at the current iteration; both calls redraw the same bits, and
+ * ggs_get_theta returns them afterwards).  D == 0 writes nothing.
+ * ggs_min_topic_distance: *min_dist = the smallest distance between two rows of the current Phi (min_topic_distances.csv), 1e+20
+ * for K == 1.  Phi is replicated on every rank of an exchange: any rank's value is the model's.
+ * Both: GGS_ERR_UNSUPPORTED for schemes collapsed, lightcollapsed and adlda (their augmented theta and Phi draws,
+ * LDAUtils.drawDirichlets, are not part of this library); GGS_ERR_STATE before a corpus and a Phi exist; GGS_ERR_BAD_ARG for a
+ * null output or a negative size. */
+int ggs_min_doc_distances(ggs_handle *h, const double *other /*[n_other][K] host, or NULL*/, int64_t n_other, double *min_dist /*[D]*/);
+int ggs_min_topic_distance(ggs_handle *h, double *min_dist);
 /* replaces: addTestInstances (UPLDA:340-343; the test set of the held-out estimator).  CSR like ggs_set_corpus; token
  * ids are indices of the TRAINING alphabet, ids >= num_types are out of vocabulary and skipped as at MPE:341-345.
  * doc_base = global index of the first test document (RNG element ids only; for a sharded test set).  Documents longer
@@ -608,6 +630,13 @@ int ggs_debug_column_sum(int32_t device_id, int32_t V, int32_t K, const double *
  * running sums the walk leaves behind; n_k_out (K, or NULL; counts only) = the integer column sums (tokensPerTopic). */
 int ggs_debug_column_sum_guided(int32_t device_id, int32_t V, int32_t K, const double *x, const int32_t *counts, double beta,
                                 const double *guess, double *out, double *pref_out, int32_t *n_k_out);
+/* The distance kernels on their own, for arbitrary inputs: min_dist[i], i in [0, n) = min(1e+20, sqrt(min_sq[i])), min_sq[i]
+ * (or NULL) = the smallest in-order sum of squared differences of row i of a over its partners, NaN sums ignored, +inf where
+ * there is none.  element_major == 0: a is [n][len]; the partners are the m rows of b [m][len], or with b == NULL the other rows
+ * of a (the diagonal skipped; m is not read) -- the document kernel.  element_major == 1: a is [len][n], b must be NULL -- the
+ * topic kernel, which ggs_min_topic_distance follows with the minimum over i.  n, len (and m with b) must be positive. */
+int ggs_debug_min_distances(int32_t device_id, const double *a, int64_t n, const double *b /*or NULL*/, int64_t m, int64_t len, int32_t element_major,
+                            double *min_dist /*[n]*/, double *min_sq /*[n] or NULL*/);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,7 @@ struct LDAConfiguration {
   // the diagnostics of the sampling loop (UPLDA:695-905), computed on the device, written as the Java driver writes them
   bool compute_likelihood = false;   // model LL (+ held-out LL with a test set) every iteration, UPLDA:838-850
   int start_diagnostic = 500;        // START_DIAG_DEFAULT; log posterior from this iteration on, UPLDA:706,818-821
+  bool compute_doc_topic_distances = false;   // COMPUTE_DOC_TOPIC_DISTANCES_DEFAULT; min_doc_distances.csv / min_topic_distances.csv, UPLDA:723-753,778-806
   bool log_topic_indicators = false; // z_<iteration>.csv, UPLDA:637-638,871-872
   std::string log_dir;               // where the files go (LoggingUtils' run directory in Java); empty = no files
 };
@@ -244,6 +245,18 @@ class LDAGroupedGibbsSampler {
     chk(ggs_log_posterior(h_, &a, &b));
     return a + b;
   }
+  std::vector<double> minDocumentDistances() {                              // "Quantity A", UPLDA:723-753, on the device
+    need();
+    std::vector<double> d((size_t)D_);
+    chk(ggs_min_doc_distances(h_, nullptr, 0, d.data()));
+    return d;
+  }
+  double minTopicDistance() {                                               // "Quantity B", UPLDA:778-806, on the device
+    need();
+    double v = 0;
+    chk(ggs_min_topic_distance(h_, &v));
+    return v;
+  }
   void addTestInstances(const InstanceList &testSet) {                      // MSLDA:918-923; ids of the training alphabet
     need();
     chk(ggs_set_test_corpus(h_, testSet.size(), testSet.doc_ptr.data(), testSet.tokens.data(), 0));
@@ -261,9 +274,19 @@ class LDAGroupedGibbsSampler {
   // The per-iteration diagnostics of UPLDA:695-905 that have a device implementation, in the Java order; each value is
   // kept in the Java-named list and, with a log_dir, appended in the Java file format.
   std::vector<double> loglikelihood, heldOutLoglikelihood, logPosterior;    // MSLDA:114-115; UPLDA:591,843,849
+  std::vector<std::vector<double>> minDocDistances;                         // per diagnostic iteration: the line of min_doc_distances.csv
+  std::vector<double> minTopicDistances;                                    // ... and of min_topic_distances.csv
   void diagnostics(int iteration) {
     const bool files = !config_.log_dir.empty();
     if (config_.start_diagnostic > 0 && iteration >= config_.start_diagnostic && !config_.collapsed && !config_.lightcollapsed && !config_.adlda) {   // pcgs: with a fresh theta, UPLDA:710-714
+      if (config_.compute_doc_topic_distances) {                            // theta, document distances, topic distance: UPLDA:710-806
+        minDocDistances.push_back(minDocumentDistances());
+        minTopicDistances.push_back(minTopicDistance());
+        if (files) {
+          formats::append_min_doc_distances(config_.log_dir, iteration, minDocDistances.back().data(), D_);
+          formats::append_min_topic_distance(config_.log_dir, iteration, minTopicDistances.back());
+        }
+      }
       const double lp = computeLogPosterior();                              // UPLDA:818-821
       logPosterior.push_back(lp);
       if (files)

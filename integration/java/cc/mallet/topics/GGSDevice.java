@@ -180,6 +180,43 @@ final class GGSDevice {
 		return lp;
 	}
 
+	/** The body of the document loop of compute_doc_topic_distances (UPLDA:723-743, "Quantity A"): per document the smallest
+	 *  Euclidean distance of its theta row to any other document's, on the device-resident theta (under pcgs: the diagnostic
+	 *  draw, as logPosterior()).  Several GPUs: every shard against itself, then against every other shard's theta block. */
+	double[] minDocDistances() {
+		settle();
+		int K = model.numTopics, n = handles.length;
+		double[] result = new double[model.data.size()];
+		double[][] own = new double[n][];
+		double[][] blocks = new double[n][];
+		for (int r = 0; r < n; r++) {
+			int docs = (int) (shardDocBase[r + 1] - shardDocBase[r]);
+			own[r] = new double[docs];
+			GGSNative.nMinDocDistances(handles[r], null, 0, own[r]);      // also leaves the theta the next call reads
+			if (n > 1) {
+				blocks[r] = new double[docs * K];
+				GGSNative.nGetTheta(handles[r], 0, docs, blocks[r]);
+			}
+		}
+		for (int r = 0; r < n; r++) {
+			int docs = own[r].length;
+			double[] against = new double[docs];
+			for (int s = 0; s < n; s++) {
+				if (s == r || own[s].length == 0 || docs == 0) continue;
+				GGSNative.nMinDocDistances(handles[r], blocks[s], own[s].length, against);
+				for (int d = 0; d < docs; d++) own[r][d] = Math.min(own[r][d], against[d]);
+			}
+			System.arraycopy(own[r], 0, result, (int) shardDocBase[r], docs);
+		}
+		return result;
+	}
+
+	/** The topic loop of compute_doc_topic_distances (UPLDA:782-796, "Quantity B"); Phi is replicated: any rank. */
+	double minTopicDistance() {
+		settle();
+		return GGSNative.nMinTopicDistance(handles[0]);
+	}
+
 	/** addTestInstances (MSLDA:918-923): ids are indices of the shared training alphabet. */
 	void uploadTestSet(InstanceList testSet) {
 		long[] docPtr = new long[testSet.size() + 1];

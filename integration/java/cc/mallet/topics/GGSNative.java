@@ -39,6 +39,8 @@ final class GGSNative {
 	static native double[] nGetTimings(long h);                                           // ggs_get_timings: theta, z, merge, phi, exchange (ms, cumulative)
 	static native double[] nModelLogLikelihood(long h);                                   // ggs_model_log_likelihood: {doc side, topic side} of ONE evaluation
 	static native double[] nLogPosterior(long h);                                         // ggs_log_posterior: {doc side, topic side} of ONE evaluation
+	static native void nMinDocDistances(long h, double[] other, long nOther, double[] minDist);   // ggs_min_doc_distances; other == null: the handle's documents against each other
+	static native double nMinTopicDistance(long h);                                       // ggs_min_topic_distance
 	static native void nSetTestCorpus(long h, long[] docPtr, int[] tokens);               // ggs_set_test_corpus
 	static native double nHeldOutLogLikelihood(long h, int numParticles);                 // ggs_heldout_log_likelihood
 	static native void nSetGlobalTokenCount(long h, long n);                              // ggs_set_global_token_count

@@ -118,6 +118,20 @@ JNIEXPORT jdoubleArray JNICALL Java_cc_mallet_topics_GGSNative_nModelLogLikeliho
 JNIEXPORT jdoubleArray JNICALL Java_cc_mallet_topics_GGSNative_nLogPosterior(JNIEnv *env, jclass c, jlong h) {
   double a = 0, b = 0; CHECK_RET(H(h), ggs_log_posterior(H(h), &a, &b), 0); return pair_of(env, a, b);          /* UPLDA:1573-1634 */
 }
+/* the distances of compute_doc_topic_distances (UPLDA:723-753, 778-806): D doubles and one double cross JNI, no matrices --
+ * except the foreign theta block of a sharded run, which is `other` (null: the handle's documents against each other) */
+JNIEXPORT void JNICALL Java_cc_mallet_topics_GGSNative_nMinDocDistances(JNIEnv *env, jclass c, jlong h, jdoubleArray other, jlong nOther,
+                                                                                        jdoubleArray out) {
+  jdouble *o = other ? (*env)->GetDoubleArrayElements(env, other, 0) : 0;
+  jdouble *p = (*env)->GetDoubleArrayElements(env, out, 0);
+  int rc = ggs_min_doc_distances(H(h), o, other ? nOther : 0, p);
+  (*env)->ReleaseDoubleArrayElements(env, out, p, 0);
+  if (other) (*env)->ReleaseDoubleArrayElements(env, other, o, JNI_ABORT);
+  if (rc) throw_for(env, H(h), rc);
+}
+JNIEXPORT jdouble JNICALL Java_cc_mallet_topics_GGSNative_nMinTopicDistance(JNIEnv *env, jclass c, jlong h) {
+  double v = 0; CHECK_RET(H(h), ggs_min_topic_distance(H(h), &v), 0.0); return v;
+}
 JNIEXPORT void JNICALL Java_cc_mallet_topics_GGSNative_nSetTestCorpus(JNIEnv *env, jclass c, jlong h,
                                                                                       jlongArray docPtr, jintArray tokens) {
   jsize D = (*env)->GetArrayLength(env, docPtr) - 1;

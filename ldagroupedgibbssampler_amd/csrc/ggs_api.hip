@@ -32,6 +32,7 @@
 #include "ggs_heldout.hpp"
 #include "ggs_exchange.hpp"
 #include "ggs_corpus_lists.hpp"
+#include "ggs_distances.hpp"
 
 using namespace ggs;
 
@@ -2925,6 +2926,80 @@ int ggs_log_posterior(ggs_handle *h, double *doc_side, double *topic_side) {
   *doc_side = out[0]; *topic_side = out[1];
   return GGS_OK;
 }
+// ---- min document / topic distances (csrc/ggs_distances.hpp) ---------------------------------------------------------------
+namespace {
+// One launch covers at most 2^30 tiles: bands of whole tile rows.
+int64_t dist_band_rows(int64_t tiles_b) { return std::max<int64_t>(1, ((int64_t)1 << 30) / std::max<int64_t>(tiles_b, 1)); }
+// min_bits[n] (preset by the caller) <- the minimal sums of the rows of A [n][len] over the rows of B [m][len]; B == A with diag
+void launch_min_row_dist(hipStream_t st, const double *A, int64_t n, const double *B, int64_t m, int64_t len, bool diag, unsigned long long *min_bits) {
+  if (n <= 0 || m <= 0) return;
+  constexpr int T = dist_tile_edge(kDistRowR);
+  const int64_t ta = (n + T - 1) / T, tb = (m + T - 1) / T, band = dist_band_rows(tb);
+  for (int64_t t0 = 0; t0 < ta; t0 += band)
+    hipLaunchKernelGGL(min_row_dist_kernel, dim3((unsigned)(std::min(band, ta - t0) * tb)), dim3(kDistBlock), 0, st, A, n, B, m, len, diag ? 1 : 0, t0 * tb, tb, min_bits);
+}
+// the same for the columns of A [len][pitch] against each other
+void launch_min_topic_dist(hipStream_t st, const double *A, int64_t n, int64_t pitch, int64_t len, unsigned long long *min_bits) {
+  if (n <= 1) return;
+  constexpr int T = dist_tile_edge(kDistTopR);
+  const int64_t ta = (n + T - 1) / T, band = dist_band_rows(ta);
+  for (int64_t t0 = 0; t0 < ta; t0 += band)
+    hipLaunchKernelGGL(min_topic_dist_kernel, dim3((unsigned)(std::min(band, ta - t0) * ta)), dim3(kDistBlock), 0, st, A, n, pitch, len, t0 * ta, ta, min_bits);
+}
+constexpr size_t kDistPieceBytes = (size_t)64 << 20;   // a foreign block travels to scratch in pieces of at most this
+}  // namespace
+
+int ggs_min_doc_distances(ggs_handle *h, const double *other, int64_t n_other, double *min_dist) {
+  int rc = require_ready(h, false);
+  if (rc) return rc;
+  if (count_form(h->scheme))
+    return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed, lightcollapsed and adlda draw no theta: the document distances of UPLDA:723-753 do not apply");
+  if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi: call ggs_init_phi / ggs_set_z / ggs_set_phi first");
+  const int64_t D = h->D, K = h->K;
+  if (n_other < 0 || (!other && n_other != 0) || (!min_dist && D > 0)) return set_err(h, GGS_ERR_BAD_ARG, "null output or negative size");
+  if (D == 0) return GGS_OK;
+  if (pcgs_family(h->scheme)) {
+    // UPLDA:710-714: one fresh theta per diagnostic iteration for the distances and the log posterior together; here both
+    // calls redraw the same bits (the stream GGS_PURPOSE_THETA at the current iteration), as ggs_log_posterior does
+    if ((rc = drop_theta_ahead(h)) || (rc = launch_theta(h, h->stream, h->d_theta, h->iteration))) return rc;
+  }
+  const int64_t piece_rows = other ? std::max<int64_t>(1, std::min<int64_t>(n_other, (int64_t)(kDistPieceBytes / (sizeof(double) * (size_t)K)))) : 0;
+  const size_t head = sizeof(double) * 2 * (size_t)D;     // [D] minimal sums as bit patterns, [D] distances
+  if ((rc = ensure_scratch(h, head + sizeof(double) * (size_t)piece_rows * (size_t)K))) return rc;
+  auto *d_bits = static_cast<unsigned long long *>(h->d_scratch);
+  auto *d_out = reinterpret_cast<double *>(d_bits + D);
+  double *d_piece = d_out + D;
+  const int grid = grid_for(D, 256);
+  hipLaunchKernelGGL(min_dist_preset_kernel, dim3(grid), dim3(256), 0, h->stream, d_bits, D);
+  if (!other) launch_min_row_dist(h->stream, h->d_theta, D, h->d_theta, D, K, true, d_bits);
+  for (int64_t r0 = 0; other && r0 < n_other; r0 += piece_rows) {
+    const int64_t rows = std::min(piece_rows, n_other - r0);
+    HIP_TRY(h, hipMemcpyAsync(d_piece, other + r0 * K, sizeof(double) * (size_t)rows * (size_t)K, hipMemcpyHostToDevice, h->stream));
+    launch_min_row_dist(h->stream, h->d_theta, D, d_piece, rows, K, false, d_bits);
+    if (r0 + piece_rows < n_other) HIP_TRY(h, hipStreamSynchronize(h->stream));   // the piece is overwritten next
+  }
+  hipLaunchKernelGGL(min_dist_finish_kernel, dim3(grid), dim3(256), 0, h->stream, d_bits, D, d_out, static_cast<double *>(nullptr));
+  HIP_TRY(h, hipGetLastError());
+  return copy_out(h, min_dist, d_out, sizeof(double) * (size_t)D);
+}
+
+int ggs_min_topic_distance(ggs_handle *h, double *min_dist) {
+  int rc = require_ready(h, false);
+  if (rc) return rc;
+  if (count_form(h->scheme))
+    return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed, lightcollapsed and adlda draw no Phi: the topic distances of UPLDA:778-806 do not apply");
+  if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi: call ggs_init_phi / ggs_set_z / ggs_set_phi first");
+  if (!min_dist) return set_err(h, GGS_ERR_BAD_ARG, "null output");
+  const int64_t K = h->K;
+  if ((rc = ensure_scratch(h, sizeof(double) * ((size_t)K + 1)))) return rc;
+  auto *d_bits = static_cast<unsigned long long *>(h->d_scratch);
+  auto *d_out = reinterpret_cast<double *>(d_bits + K);
+  hipLaunchKernelGGL(min_dist_preset_kernel, dim3(grid_for(K, 256)), dim3(256), 0, h->stream, d_bits, K);
+  launch_min_topic_dist(h->stream, h->d_phiT, K, h->Kp, h->V, d_bits);
+  hipLaunchKernelGGL(min_dist_reduce_kernel, dim3(1), dim3(kDistBlock), 0, h->stream, d_bits, K, d_out);
+  HIP_TRY(h, hipGetLastError());
+  return copy_out(h, min_dist, d_out, sizeof(double));
+}
 int ggs_set_test_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32_t *tokens, int64_t doc_base) {
   if (!h || D < 0 || !doc_ptr || doc_base < 0) return set_err(h, GGS_ERR_BAD_ARG, "bad test corpus arguments");
   if (doc_ptr[0] != 0) return set_err(h, GGS_ERR_BAD_ARG, "doc_ptr[0] must be 0");
@@ -3333,6 +3408,27 @@ int ggs_debug_column_sum_guided(int32_t device_id, int32_t V, int32_t K, const d
 
 int ggs_debug_column_sum(int32_t device_id, int32_t V, int32_t K, const double *x, const int32_t *counts, double beta, double *out) {
   return ggs_debug_column_sum_guided(device_id, V, K, x, counts, beta, nullptr, out, nullptr, nullptr);
+}
+
+int ggs_debug_min_distances(int32_t device_id, const double *a, int64_t n, const double *b, int64_t m, int64_t len, int32_t element_major, double *min_dist,
+                            double *min_sq) {
+  if (!a || !min_dist || n <= 0 || len <= 0 || (b && m <= 0) || (element_major && b) || hipSetDevice(device_id) != hipSuccess) return GGS_ERR_BAD_ARG;
+  TmpDev t;
+  auto *da = static_cast<double *>(t.get(sizeof(double) * (size_t)n * (size_t)len));
+  auto *db = b ? static_cast<double *>(t.get(sizeof(double) * (size_t)m * (size_t)len)) : da;
+  auto *dbits = static_cast<unsigned long long *>(t.get(sizeof(double) * (size_t)n));
+  auto *dout = static_cast<double *>(t.get(sizeof(double) * (size_t)n)), *dsq = static_cast<double *>(t.get(sizeof(double) * (size_t)n));
+  if (!da || !db || !dbits || !dout || !dsq) return GGS_ERR_HIP;
+  if (hipMemcpy(da, a, sizeof(double) * (size_t)n * (size_t)len, hipMemcpyHostToDevice) != hipSuccess) return GGS_ERR_HIP;
+  if (b && hipMemcpy(db, b, sizeof(double) * (size_t)m * (size_t)len, hipMemcpyHostToDevice) != hipSuccess) return GGS_ERR_HIP;
+  const int grid = (int)std::min<int64_t>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(min_dist_preset_kernel, dim3(grid), dim3(256), 0, nullptr, dbits, n);
+  if (element_major) launch_min_topic_dist(nullptr, da, n, n, len, dbits);
+  else launch_min_row_dist(nullptr, da, n, db, b ? m : n, len, b == nullptr, dbits);
+  hipLaunchKernelGGL(min_dist_finish_kernel, dim3(grid), dim3(256), 0, nullptr, dbits, n, dout, dsq);
+  if (hipGetLastError() != hipSuccess || hipMemcpy(min_dist, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return GGS_ERR_HIP;
+  if (min_sq && hipMemcpy(min_sq, dsq, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return GGS_ERR_HIP;
+  return GGS_OK;
 }
 
 }  // extern "C"

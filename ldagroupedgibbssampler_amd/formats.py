@@ -239,3 +239,16 @@ def append_log_posterior(log_dir, iteration, value, millis):
     """LDAUtils.logPosteriorToFile (LDAUtils.java:955-968): ``%d\\t%.6f\\t%d%n`` with System.currentTimeMillis()."""
     with open(os.path.join(log_dir, "log-posterior.txt"), "a", newline="") as f:
         f.write("%d\t%s\t%d%s" % (iteration, java_format_fixed(value, 6), millis, os.linesep))
+
+
+def append_min_doc_distances(log_dir, iteration, values):
+    """UPLDA:724-748: ``iteration,d0,d1,...`` -- every value as StringBuilder.append(double), i.e. Double.toString -- appended
+    to min_doc_distances.csv."""
+    with open(os.path.join(log_dir, "min_doc_distances.csv"), "a", newline="") as f:
+        f.write(",".join([str(int(iteration))] + [java_double_to_string(v) for v in np.asarray(values, np.float64).tolist()]) + os.linesep)
+
+
+def append_min_topic_distance(log_dir, iteration, value):
+    """UPLDA:799-801: ``iteration,value`` appended to min_topic_distances.csv."""
+    with open(os.path.join(log_dir, "min_topic_distances.csv"), "a", newline="") as f:
+        f.write("%d,%s%s" % (iteration, java_double_to_string(value), os.linesep))

@@ -354,6 +354,27 @@ class GGSHandle:
         self._chk(self._L.ggs_log_posterior(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def min_doc_distances(self, other=None):
+        """min_doc_distances.csv (UPLDA:723-753), on the device: per document of this handle the smallest Euclidean distance
+        of its theta row to every other row (other=None: the reference's loop), or to the rows of the foreign block
+        `other` [n][K] (a doc-sharded run: once with None, once per foreign shard, element-wise minimum).  1e20 without a partner."""
+        out = np.empty(self.D, np.float64)
+        if other is None:
+            op, n = None, 0
+        else:
+            other = np.ascontiguousarray(other, np.float64)
+            if other.ndim != 2 or other.shape[1] != self.K:
+                raise ValueError("other must be [n][K]")
+            op, n = _dp(other), other.shape[0]
+        self._chk(self._L.ggs_min_doc_distances(self._h, op, n, _dp(out)))
+        return out
+
+    def min_topic_distance(self):
+        """min_topic_distances.csv (UPLDA:778-806), on the device: the smallest Euclidean distance between two rows of Phi."""
+        v = C.c_double()
+        self._chk(self._L.ggs_min_topic_distance(self._h, C.byref(v)))
+        return v.value
+
     def set_test_corpus(self, doc_ptr, tokens, doc_base=0):
         """addTestInstances (MSLDA:918-923): the held-out estimator's test set; ids >= num_types are out of vocabulary."""
         doc_ptr = np.ascontiguousarray(doc_ptr, np.int64)
@@ -584,3 +605,24 @@ def debug_column_sum_guided(x=None, counts=None, beta=0.0, guess=None, device_id
     if rc:
         raise GGSError(rc, "ggs_debug_column_sum_guided")
     return out, pref, (n_k if counts is not None else None)
+
+
+def debug_min_distances(a, b=None, element_major=False, device_id=0):
+    """The distance kernels on arbitrary inputs: (min_dist [n], min_sq [n]).  a is [n][len] (element_major: [len][n]); b [m][len]
+    or None = a against itself with the diagonal skipped."""
+    L = _lib.load()
+    a = np.ascontiguousarray(a, np.float64)
+    if a.ndim != 2:
+        raise ValueError("a must be a matrix")
+    length, n = a.shape if element_major else a.shape[::-1]
+    bp, m = None, 0
+    if b is not None:
+        b = np.ascontiguousarray(b, np.float64)
+        if b.ndim != 2 or b.shape[1] != length:
+            raise ValueError("b must be [m][len]")
+        bp, m = _dp(b), b.shape[0]
+    dist, sq = np.empty(n, np.float64), np.empty(n, np.float64)
+    rc = L.ggs_debug_min_distances(device_id, _dp(a), n, bp, m, length, 1 if element_major else 0, _dp(dist), _dp(sq))
+    if rc:
+        raise GGSError(rc, "ggs_debug_min_distances")
+    return dist, sq

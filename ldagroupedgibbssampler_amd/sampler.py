@@ -45,6 +45,7 @@ class SimpleLDAConfiguration:
         # the diagnostics of the sampling loop (UPLDA:695-905), computed on the device and written in the Java driver's formats
         self.compute_likelihood = bool(kw.pop("compute_likelihood", False))   # model LL (+ held-out LL with a test set) every iteration, UPLDA:838-850
         self.start_diagnostic = int(kw.pop("start_diagnostic", 500))          # START_DIAG_DEFAULT; log posterior from this iteration on, UPLDA:706,818-821
+        self.compute_doc_topic_distances = bool(kw.pop("compute_doc_topic_distances", False))   # COMPUTE_DOC_TOPIC_DISTANCES_DEFAULT; min_doc_distances.csv / min_topic_distances.csv from start_diagnostic on, UPLDA:723-753,778-806
         self.log_topic_indicators = bool(kw.pop("log_topic_indicators", False))  # z_<iteration>.csv, UPLDA:637-638,871-872
         self.log_dir = kw.pop("log_dir", None)                       # where the files go (LoggingUtils' run directory in Java); None = no files
         if kw:
@@ -126,6 +127,7 @@ class LDAGroupedGibbsSampler:
         self.zSamplingTimeCum = 0.0      # ms, as UPLDA:642-693 accumulates them
         self.phiSamplingTimeCum = 0.0
         self.loglikelihood, self.heldOutLoglikelihood, self.logPosterior = [], [], []   # the Java lists (MSLDA:114-115; UPLDA:591,843,849) + the posterior values
+        self.minDocDistances, self.minTopicDistances = [], []    # per diagnostic iteration: the line of min_doc_distances.csv ([D]) and of min_topic_distances.csv
 
     # ---- LDAGibbsSampler ----
     def setConfiguration(self, config):
@@ -215,12 +217,20 @@ class LDAGroupedGibbsSampler:
         self._h.sweep_end()
 
     def _diagnostics(self, iteration):
-        """The per-iteration diagnostics of UPLDA:695-905 that have a device implementation, in the Java order: log
+        """The per-iteration diagnostics of UPLDA:695-905 that have a device implementation, in the Java order: document and
+        topic distances (compute_doc_topic_distances) and log
         posterior (ggs and pcgs, from start_diagnostic on), held-out and model log likelihood (compute_likelihood), topic
         indicators; each value is kept in the Java-named list and, with a log_dir, appended in the Java file format."""
         cfg = self.config
         from . import formats as F
         if cfg.start_diagnostic > 0 and iteration >= cfg.start_diagnostic and not (self._scheme_flags & (native.FLAG_COLLAPSED | native.FLAG_LIGHTCOLLAPSED | native.FLAG_ADLDA)):   # pcgs: with a fresh theta, UPLDA:710-714
+            if getattr(cfg, "compute_doc_topic_distances", False):        # theta, document distances, topic distance: UPLDA:710-806
+                dd, td = self.minDocumentDistances(), self.minTopicDistance()
+                self.minDocDistances.append(dd)
+                self.minTopicDistances.append(td)
+                if cfg.log_dir:
+                    F.append_min_doc_distances(cfg.log_dir, iteration, dd)
+                    F.append_min_topic_distance(cfg.log_dir, iteration, td)
             lp = self.computeLogPosterior()                               # UPLDA:818-821
             self.logPosterior.append(lp)
             if cfg.log_dir:
@@ -328,6 +338,19 @@ class LDAGroupedGibbsSampler:
         self._need_data()
         doc_side, topic_side = self._h.log_posterior()
         return doc_side + topic_side
+
+    def minDocumentDistances(self):
+        """"Quantity A" (UPLDA:723-753), on the device (ggs_min_doc_distances): per document the smallest Euclidean distance of
+        its theta row to any other document's; scheme ggs on the thetaMatrix of the last z step, the pcgs family on the
+        diagnostic theta draw the log posterior makes too (UPLDA:710-714).  One line of min_doc_distances.csv."""
+        self._need_data()
+        return self._h.min_doc_distances()
+
+    def minTopicDistance(self):
+        """"Quantity B" (UPLDA:778-806), on the device (ggs_min_topic_distance): the smallest Euclidean distance between two
+        rows of Phi.  One line of min_topic_distances.csv."""
+        self._need_data()
+        return self._h.min_topic_distance()
 
     def getBeta(self):
         return self.beta

@@ -133,6 +133,27 @@ class ShardedGGS:
             total += v
         return total, doc_ll
 
+    def min_doc_distances(self, gather=None):
+        """min_doc_distances.csv of a doc-sharded run: this rank's documents against the whole corpus.  Every rank computes
+        its documents against each other (engine.min_doc_distances()), the ranks gather their theta blocks (``gather`` as
+        for heldout_log_likelihood), and every foreign block is one more call whose result enters by element-wise minimum:
+        bit-identical to one handle, minima of identical doubles being exact.  Returns this rank's [local D] values."""
+        out = np.asarray(self.engine.min_doc_distances(), np.float64).copy()   # draws the diagnostic theta where the scheme has none
+        if gather is None:
+            import torch.distributed as dist
+
+            def gather(a):
+                res = [None] * self.world
+                dist.all_gather_object(res, a)
+                return res
+        blocks = gather(np.asarray(self.engine.get_theta(), np.float64))
+        for r, blk in enumerate(blocks):
+            blk = np.asarray(blk, np.float64)
+            if r == self.rank or blk.shape[0] == 0 or out.size == 0:
+                continue
+            out = np.minimum(out, self.engine.min_doc_distances(blk))
+        return out
+
     def sweep(self, n=1):
         """n sweeps, one count exchange each; only the last one is waited for (device-side error flags are sticky)."""
         end_async = getattr(self.engine, "sweep_end_async", self.engine.sweep_end)
