@@ -33,11 +33,12 @@ def main():
     ap.add_argument("--beta", type=float, default=0.01)
     ap.add_argument("--iterations", type=int, default=200)
     ap.add_argument("--seed", type=int, default=4711)
-    ap.add_argument("--top-words", type=int, default=8)
+    ap.add_argument("--top-words", type=int, default=8, help="nr_top_words: words per topic, printed and in TopWords.txt / RelevanceWords.txt (clamped to the vocabulary size, as the driver clamps)")
+    ap.add_argument("--lambda", dest="lambda_", type=float, default=0.6, help="lambda: the relevance weight of RelevanceWords.txt")
     ap.add_argument("--doc-topic-distances", action="store_true",
                     help="compute_doc_topic_distances: min_doc_distances.csv and min_topic_distances.csv in --out, one line per iteration from --start-diagnostic on")
     ap.add_argument("--start-diagnostic", type=int, default=500, help="start_diagnostic: first iteration of the log posterior and the distances")
-    ap.add_argument("--out", default=None, help="directory for the driver's files (phi / theta / counts / likelihood)")
+    ap.add_argument("--out", default=None, help="directory for the driver's files (phi / theta / counts / likelihood / TopWords.txt / RelevanceWords.txt)")
     args = ap.parse_args()
     if args.topic_priors and args.scheme != "spalias_priors":
         ap.error("--topic-priors belongs to --scheme spalias_priors")
@@ -54,7 +55,8 @@ def main():
     cfg = SimpleLDAConfiguration(scheme=args.scheme, topics=args.topics, alpha=args.alpha, beta=args.beta, iterations=args.iterations,
                                  seed=args.seed, exec_time=None, compute_likelihood=bool(args.out), log_dir=args.out,
                                  topic_prior_filename=args.topic_priors, variable_selection_prior=args.vs_prior,
-                                 compute_doc_topic_distances=args.doc_topic_distances, start_diagnostic=args.start_diagnostic)
+                                 compute_doc_topic_distances=args.doc_topic_distances, start_diagnostic=args.start_diagnostic,
+                                 nr_top_words=args.top_words, **{"lambda": args.lambda_})
     if args.scheme == "nzvsspalias":                          # not in create_model's registry: the class itself
         from ldagroupedgibbssampler_amd.sampler import NZVSSpaliasUncollapsedParallelLDA
         model = NZVSSpaliasUncollapsedParallelLDA(cfg)
@@ -69,13 +71,16 @@ def main():
     print("%d iterations: z %.1f ms, Phi %.1f ms in all; model log likelihood %.2f" %
           (model.getCurrentIteration(), model.zSamplingTimeCum, model.phiSamplingTimeCum, model.modelLogLikelihood()))
 
-    n_wk = np.asarray(model.getTypeTopicMatrix())           # [V][K] counts, as LDAUtils.getTopWords ranks them
+    requested = min(cfg.nr_top_words, c.num_types)          # tui/ParallelLDA.java:272-274
+    top = model.getTopWords(requested)                      # LDAUtils.getTopWords on the device-resident counts: ties by falling id
     for k in range(args.topics):
-        top = np.argsort(-n_wk[:, k], kind="stable")[:args.top_words]
-        print("topic %2d: %s" % (k, " ".join(c.vocab[i] for i in top if n_wk[i, k] > 0)))
+        print("topic %2d: %s" % (k, " ".join(top[k])))
 
     if args.out:
         K, V, D, it = args.topics, c.num_types, c.num_docs, model.getCurrentIteration()
+        n_wk = np.asarray(model.getTypeTopicMatrix())       # [V][K] counts, for type_topic_counts.csv
+        F.write_top_words(top, os.path.join(args.out, "TopWords.txt"))
+        F.write_top_words(model.getTopRelevanceWords(requested, cfg.lambda_), os.path.join(args.out, "RelevanceWords.txt"))
         if args.scheme != "collapsed":
             F.write_binary_double_matrix(np.asarray(model.getPhi()), F.binary_matrix_name(os.path.join(args.out, "phi"), K, V, it))
         F.write_ascii_double_matrix(np.asarray(model.getThetaEstimate()), F.ascii_matrix_name(args.out, "Theta_DxK", D, K, it))

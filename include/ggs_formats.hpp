@@ -292,6 +292,20 @@ inline void append_min_doc_distances(const std::string &log_dir, int iteration, 
 inline void append_min_topic_distance(const std::string &log_dir, int iteration, double value) {                    // UPLDA:799-801
   append_line(log_dir + "/min_topic_distances.csv", std::to_string(iteration) + "," + java_double_to_string(value));
 }
+// LDAUtils.formatTopWordsAsCsv (LDAUtils.java:1429-1443): one line per topic, the words joined by ",", the lines by "\n"
+inline std::string format_top_words_csv(const std::vector<std::vector<std::string>> &rows) {
+  std::string out;
+  for (size_t i = 0; i < rows.size(); ++i) {
+    for (size_t j = 0; j < rows[i].size(); ++j) { out += rows[i][j]; if (j + 1 < rows[i].size()) out += ","; }
+    if (i + 1 < rows.size()) out += "\n";
+  }
+  return out;
+}
+// TopWords.txt / RelevanceWords.txt: println of the CSV (tui/ParallelLDA.java:272-296)
+inline void write_top_words(const std::vector<std::vector<std::string>> &rows, const std::string &fn) {
+  std::ofstream f(fn, std::ios::binary | std::ios::trunc);
+  f << format_top_words_csv(rows) << "\n";
+}
 
 }  // namespace formats
 }  // namespace ggs

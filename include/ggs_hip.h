@@ -603,6 +603,32 @@ int ggs_log_posterior(ggs_handle *h, double *doc_side, double *topic_side);
  * null output or a negative size. */
 int ggs_min_doc_distances(ggs_handle *h, const double *other /*[n_other][K] host, or NULL*/, int64_t n_other, double *min_dist /*[D]*/);
 int ggs_min_topic_distance(ggs_handle *h, double *min_dist);
+/* replaces: LDAUtils.getTopWords / getTopWordIndices (LDAUtils.java:874-911; TopWords.txt, tui/ParallelLDA.java:272-283),
+ * getTopRelevanceWords (:566-590; RelevanceWords.txt, ParallelLDA.java:285-296), getTopDistinctiveWords (:592-617),
+ * getTopSalientWords (:619-644) and getK1ReWeightedWords (:752-801) on the handle's CURRENT corpus-wide type-topic counts (with
+ * an exchange: gathered as ggs_get_type_topic_counts gathers them -- a collective call; every rank returns the model's answer).
+ * Works under every scheme.  idx[k][r], r in [0, n_words): the word ids of topic k in IDSorter's order -- falling score, equal
+ * scores (-0.0 == +0.0) by FALLING id; score (or NULL): their scores.  The score of (word w, topic k) by kind:
+ *   GGS_TOP_WORDS        (double) n_wk
+ *   GGS_TOP_RELEVANCE    lambda * L + (1 - lambda) * (L - log(p_w[w])), L = log(p_wk)            (Sievert & Shirley)
+ *   GGS_TOP_DISTINCTIVE  0.0 + P * log(P / p_w[w]), P = p_wk * (mass_k / total) / p_w[w] left to right
+ *   GGS_TOP_SALIENT      p_w[w] * distinctive
+ *   GGS_TOP_K1           p_wk / (sum over k in index order, from 0.0, of p_wk)
+ * with p_wk = (n_wk + beta) / mass_k, p_w[w] = rowsum_w / total and the three Java running sums, each from 0.0 over
+ * (double) n_wk + beta in index order: mass_k over w, rowsum_w over k, total over all V * K cells (w outer, k inner).  Every
+ * operation is rounded on its own in the Java order; log is the library's fdlibm log (StrictMath.log; Math.log on a JVM is
+ * parity-unpinned, as everywhere here).  Bit-identical to those loops restated (tests/topic_summaries_restatement.py).
+ * lambda is read by GGS_TOP_RELEVANCE only.  Nothing the sweep reads is written: a call between sweeps leaves the chain's bits.
+ * GGS_ERR_BAD_ARG: null idx, n_words < 1 or > V (the Java IllegalArgumentException), an unknown kind, a lambda that is not
+ * finite, beta == 0 with a kind other than GGS_TOP_WORDS (NaN scores, which IDSorter cannot order);
+ * GGS_ERR_UNSUPPORTED: n_words > GGS_TOP_WORDS_MAX, or V * K >= 2^31 - 256; GGS_ERR_STATE before a corpus. */
+#define GGS_TOP_WORDS 0
+#define GGS_TOP_RELEVANCE 1
+#define GGS_TOP_DISTINCTIVE 2
+#define GGS_TOP_SALIENT 3
+#define GGS_TOP_K1 4
+#define GGS_TOP_WORDS_MAX 128
+int ggs_top_words(ggs_handle *h, int32_t kind, int32_t n_words, double lambda, int32_t *idx /*[K][n_words]*/, double *score /*[K][n_words] or NULL*/);
 /* replaces: addTestInstances (UPLDA:340-343; the test set of the held-out estimator).  CSR like ggs_set_corpus; token
  * ids are indices of the TRAINING alphabet, ids >= num_types are out of vocabulary and skipped as at MPE:341-345.
  * doc_base = global index of the first test document (RNG element ids only; for a sharded test set).  Documents longer
@@ -637,6 +663,16 @@ int ggs_debug_column_sum_guided(int32_t device_id, int32_t V, int32_t K, const d
  * topic kernel, which ggs_min_topic_distance follows with the minimum over i.  n, len (and m with b) must be positive. */
 int ggs_debug_min_distances(int32_t device_id, const double *a, int64_t n, const double *b /*or NULL*/, int64_t m, int64_t len, int32_t element_major,
                             double *min_dist /*[n]*/, double *min_sq /*[n] or NULL*/);
+/* The topic-summary kernels on their own, for an arbitrary count matrix [V][K] (host): idx / score as ggs_top_words, and (each
+ * or NULL) the normalisers mass_k [K], rowsum_w [V], *total and every score all_scores [V][K].  Same error codes. */
+int ggs_debug_topic_summaries(int32_t device_id, int32_t V, int32_t K, const int32_t *counts /*[V][K]*/, double beta, double lambda, int32_t kind,
+                              int32_t n_words, int32_t *idx /*[K][n_words]*/, double *score /*[K][n_words] or NULL*/, double *mass_k /*[K] or NULL*/,
+                              double *rowsum_w /*[V] or NULL*/, double *total /*or NULL*/, double *all_scores /*[V][K] or NULL*/);
+/* Where a ggs_top_words call spends its device time (scripts/time_topic_summaries.py): the same launches on the handle's counts
+ * with events between them; ms[4] = mass_k, total, the words' statistics (rowsum_w, p_w, log p_w), selection and merge.  The
+ * first three are 0 for GGS_TOP_WORDS.  element_chain != 0: both column sums by the element-by-element chain kernel (one
+ * lane per sum: what the total chain costs without ggs_exact_sum.hpp).  Nothing is copied back. */
+int ggs_debug_top_words_phases(ggs_handle *h, int32_t kind, int32_t n_words, double lambda, int32_t element_chain, double *ms /*[4]*/);
 
 #ifdef __cplusplus
 }

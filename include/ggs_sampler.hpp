@@ -60,6 +60,8 @@ struct LDAConfiguration {
   bool compute_likelihood = false;   // model LL (+ held-out LL with a test set) every iteration, UPLDA:838-850
   int start_diagnostic = 500;        // START_DIAG_DEFAULT; log posterior from this iteration on, UPLDA:706,818-821
   bool compute_doc_topic_distances = false;   // COMPUTE_DOC_TOPIC_DISTANCES_DEFAULT; min_doc_distances.csv / min_topic_distances.csv, UPLDA:723-753,778-806
+  int nr_top_words = 20;             // NO_TOP_WORDS_DEFAULT (LDAConfiguration.java:38): words per topic of TopWords.txt / RelevanceWords.txt
+  double lambda = 0.6;               // LAMBDA_DEFAULT (LDAConfiguration.java:41): the relevance weight
   bool log_topic_indicators = false; // z_<iteration>.csv, UPLDA:637-638,871-872
   std::string log_dir;               // where the files go (LoggingUtils' run directory in Java); empty = no files
 };
@@ -257,6 +259,29 @@ class LDAGroupedGibbsSampler {
     chk(ggs_min_topic_distance(h_, &v));
     return v;
   }
+  // The topic summaries of LDAUtils.java:566-911 on the device-resident counts (ggs_top_words): [K][n] word ids in IDSorter's
+  // order; kind = GGS_TOP_WORDS (getTopWordIndices / getTopWords), GGS_TOP_RELEVANCE (getTopRelevanceWords, config lambda),
+  // GGS_TOP_DISTINCTIVE, GGS_TOP_SALIENT, GGS_TOP_K1.
+  std::vector<std::vector<int32_t>> getTopWordIndices(int n, int kind = GGS_TOP_WORDS) {
+    need();
+    if (n > V_)                                                             // LDAUtils.java:568-570
+      throw std::invalid_argument("Asked for more words (" + std::to_string(n) + ") than there are types (unique words = noTypes = " + std::to_string(V_) + ").");
+    std::vector<int32_t> flat((size_t)config_.topics * (size_t)(n > 0 ? n : 0));
+    chk(ggs_top_words(h_, kind, n, config_.lambda, flat.data(), nullptr));
+    std::vector<std::vector<int32_t>> out((size_t)config_.topics);
+    for (int k = 0; k < config_.topics; ++k) out[(size_t)k].assign(flat.begin() + (size_t)k * n, flat.begin() + (size_t)(k + 1) * n);
+    return out;
+  }
+  // ... and as strings of the alphabet (id -> word): the rows formats::write_top_words takes
+  std::vector<std::vector<std::string>> getTopWords(int n, const std::vector<std::string> &alphabet, int kind = GGS_TOP_WORDS) {
+    std::vector<std::vector<std::string>> out;
+    for (const auto &row : getTopWordIndices(n, kind)) {
+      out.emplace_back();
+      for (int32_t id : row) out.back().push_back(alphabet.at((size_t)id));
+    }
+    return out;
+  }
+  std::vector<std::vector<std::string>> getTopRelevanceWords(int n, const std::vector<std::string> &alphabet) { return getTopWords(n, alphabet, GGS_TOP_RELEVANCE); }
   void addTestInstances(const InstanceList &testSet) {                      // MSLDA:918-923; ids of the training alphabet
     need();
     chk(ggs_set_test_corpus(h_, testSet.size(), testSet.doc_ptr.data(), testSet.tokens.data(), 0));

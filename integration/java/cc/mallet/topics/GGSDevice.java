@@ -217,6 +217,20 @@ final class GGSDevice {
 		return GGSNative.nMinTopicDistance(handles[0]);
 	}
 
+	/** LDAUtils.getTopWordIndices and its four siblings (LDAUtils.java:566-911) on the device-resident counts: [K][nWords] word
+	 *  ids in IDSorter's order; kind 0 top, 1 relevance (lambda), 2 distinctive, 3 salient, 4 K1.  No copy-back of
+	 *  typeTopicCounts; several GPUs: the counts are gathered first, every rank then holds the model's answer. */
+	int[][] topWordIndices(int kind, int nWords, double lambda) {
+		settle();
+		if (multi()) GGSNative.nGroupGatherCounts(handles);
+		int K = model.numTopics;
+		int[] flat = new int[K * nWords];
+		GGSNative.nTopWords(handles[0], kind, nWords, lambda, flat, null);
+		int[][] result = new int[K][nWords];
+		for (int k = 0; k < K; k++) System.arraycopy(flat, k * nWords, result[k], 0, nWords);
+		return result;
+	}
+
 	/** addTestInstances (MSLDA:918-923): ids are indices of the shared training alphabet. */
 	void uploadTestSet(InstanceList testSet) {
 		long[] docPtr = new long[testSet.size() + 1];

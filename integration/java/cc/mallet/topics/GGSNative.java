@@ -41,6 +41,7 @@ final class GGSNative {
 	static native double[] nLogPosterior(long h);                                         // ggs_log_posterior: {doc side, topic side} of ONE evaluation
 	static native void nMinDocDistances(long h, double[] other, long nOther, double[] minDist);   // ggs_min_doc_distances; other == null: the handle's documents against each other
 	static native double nMinTopicDistance(long h);                                       // ggs_min_topic_distance
+	static native void nTopWords(long h, int kind, int nWords, double lambda, int[] idx, double[] score);   // ggs_top_words; idx [K][nWords], score the same or null
 	static native void nSetTestCorpus(long h, long[] docPtr, int[] tokens);               // ggs_set_test_corpus
 	static native double nHeldOutLogLikelihood(long h, int numParticles);                 // ggs_heldout_log_likelihood
 	static native void nSetGlobalTokenCount(long h, long n);                              // ggs_set_global_token_count

@@ -132,6 +132,16 @@ JNIEXPORT void JNICALL Java_cc_mallet_topics_GGSNative_nMinDocDistances(JNIEnv *
 JNIEXPORT jdouble JNICALL Java_cc_mallet_topics_GGSNative_nMinTopicDistance(JNIEnv *env, jclass c, jlong h) {
   double v = 0; CHECK_RET(H(h), ggs_min_topic_distance(H(h), &v), 0.0); return v;
 }
+/* the topic summaries of LDAUtils.java:566-911 (TopWords.txt, RelevanceWords.txt): K * nWords ids cross JNI, no count matrix */
+JNIEXPORT void JNICALL Java_cc_mallet_topics_GGSNative_nTopWords(JNIEnv *env, jclass c, jlong h, jint kind, jint nWords, jdouble lambda,
+                                                                                 jintArray idx, jdoubleArray score) {
+  jint *ip = (*env)->GetIntArrayElements(env, idx, 0);
+  jdouble *sp = score ? (*env)->GetDoubleArrayElements(env, score, 0) : 0;
+  int rc = ggs_top_words(H(h), kind, nWords, lambda, (int32_t *)ip, sp);
+  if (score) (*env)->ReleaseDoubleArrayElements(env, score, sp, 0);
+  (*env)->ReleaseIntArrayElements(env, idx, ip, 0);
+  if (rc) throw_for(env, H(h), rc);
+}
 JNIEXPORT void JNICALL Java_cc_mallet_topics_GGSNative_nSetTestCorpus(JNIEnv *env, jclass c, jlong h,
                                                                                       jlongArray docPtr, jintArray tokens) {
   jsize D = (*env)->GetArrayLength(env, docPtr) - 1;

@@ -33,6 +33,7 @@
 #include "ggs_exchange.hpp"
 #include "ggs_corpus_lists.hpp"
 #include "ggs_distances.hpp"
+#include "ggs_topic_summaries.hpp"
 
 using namespace ggs;
 
@@ -3000,6 +3001,109 @@ int ggs_min_topic_distance(ggs_handle *h, double *min_dist) {
   HIP_TRY(h, hipGetLastError());
   return copy_out(h, min_dist, d_out, sizeof(double));
 }
+// ---- top words per topic (csrc/ggs_topic_summaries.hpp) --------------------------------------------------------------------
+namespace {
+// the device work space of one call, carved from one allocation
+struct TsPlan {
+  int32_t V = 0, K = 0, n = 0, nseg = 0, sum_nseg = 0, tot_nseg = 0;
+  size_t mass = 0, total = 0, rowsum = 0, k1mass = 0, pw = 0, logpw = 0, guess = 0, fn = 0, tguess = 0, tfn = 0, cand_s = 0, cand_i = 0, idx = 0, score = 0, bytes = 0;
+  TsPlan(int32_t V, int32_t K, int32_t n);
+};
+TsPlan::TsPlan(int32_t V, int32_t K, int32_t n) {
+  TsPlan &q = *this;
+  q.V = V; q.K = K; q.n = n;
+  q.nseg = (V + kTsSegWords - 1) / kTsSegWords;
+  q.sum_nseg = (V + kSumSegRows - 1) / kSumSegRows;
+  q.tot_nseg = (int32_t)(((int64_t)V * K + kSumSegRows - 1) / kSumSegRows);
+  size_t at = 0;
+  auto take = [&](size_t b) { const size_t o = at; at += (b + 255) & ~(size_t)255; return o; };
+  q.mass = take(8 * (size_t)K); q.total = take(8);
+  q.rowsum = take(8 * (size_t)V); q.k1mass = take(8 * (size_t)V); q.pw = take(8 * (size_t)V); q.logpw = take(8 * (size_t)V);
+  q.guess = take(8 * ((size_t)q.sum_nseg + 1) * K); q.fn = take(32 * (size_t)q.sum_nseg * K);
+  q.tguess = take(8 * ((size_t)q.tot_nseg + 1)); q.tfn = take(32 * (size_t)q.tot_nseg);
+  q.cand_s = take(8 * (size_t)q.nseg * n * K); q.cand_i = take(4 * (size_t)q.nseg * n * K);
+  q.idx = take(4 * (size_t)K * n); q.score = take(8 * (size_t)K * n);
+  q.bytes = at;
+}
+int ts_check_args(ggs_handle *h, int32_t V, int32_t K, double beta, int32_t kind, int32_t n, double lambda, const int32_t *idx) {
+  if (!idx) return set_err(h, GGS_ERR_BAD_ARG, "null idx");
+  if (kind < 0 || kind >= kTsKinds) return set_err(h, GGS_ERR_BAD_ARG, "unknown kind: 0 top, 1 relevance, 2 distinctive, 3 salient, 4 k1");
+  if (n < 1 || n > V) return set_err(h, GGS_ERR_BAD_ARG, "Asked for more words (" + std::to_string(n) + ") than there are types (unique words = noTypes = " + std::to_string(V) + ").");
+  if (!std::isfinite(lambda)) return set_err(h, GGS_ERR_BAD_ARG, "lambda must be finite");
+  if (kind != kTsTop && !(beta > 0.0)) return set_err(h, GGS_ERR_BAD_ARG, "beta must be positive for the probability rankings (the scores of empty cells are NaN otherwise)");
+  if (n > kTsMaxWords) return set_err(h, GGS_ERR_UNSUPPORTED, "at most " + std::to_string(kTsMaxWords) + " words per topic");
+  if ((int64_t)V * K > ((int64_t)1 << 31) - 256 || (V + kTsSegWords - 1) / kTsSegWords > 16000)
+    return set_err(h, GGS_ERR_UNSUPPORTED, "the topic summaries index the V * K cells with 32 bits and keep V / 256 list heads in LDS");
+  return GGS_OK;
+}
+// cnt [V][K] on the device -> idx / score in the work space; norms: the normalisers and the words' statistics whatever the kind
+// ev (or NULL): five events recorded around mass_k | total | the words' statistics | selection and merge
+void ts_launch(hipStream_t st, bool exact_sum, const int32_t *cnt, double beta, double lambda, int32_t kind, const TsPlan &q, char *work, bool norms, double *all_scores,
+               hipEvent_t *ev = nullptr) {
+  auto mark = [&](int i) { if (ev) (void)hipEventRecord(ev[i], st); };
+  auto D = [&](size_t o) { return reinterpret_cast<double *>(work + o); };
+  TsParams p{};
+  p.cnt = cnt; p.mass = D(q.mass); p.total = D(q.total); p.rowsum = D(q.rowsum); p.k1mass = D(q.k1mass); p.pw = D(q.pw); p.logpw = D(q.logpw);
+  p.cand_score = D(q.cand_s); p.cand_id = reinterpret_cast<int32_t *>(work + q.cand_i); p.idx = reinterpret_cast<int32_t *>(work + q.idx); p.score = D(q.score);
+  p.all_scores = all_scores; p.beta = beta; p.lambda = lambda; p.one_minus_lambda = 1 - lambda;
+  p.pitch = q.K; p.V = q.V; p.K = q.K; p.kind = kind; p.n = q.n; p.nseg = q.nseg;
+  if (norms || kind != kTsTop) {
+    // mass_k: the Dirichlet magnitude sum; total: the same sum over the one column of the V * K cells flattened.  Unguided, in
+    // work space of their own: the handle's running sums (the Phi phase's guess) are neither read nor written.
+    ggs_handle col;
+    col.K = q.K; col.V = q.V; col.beta = beta; col.stream = st; col.exact_sum = exact_sum; col.sum_nseg = q.sum_nseg;
+    mark(0);
+    launch_column_sum<int32_t, true>(&col, cnt, q.K, q.K, D(q.mass), nullptr, false, false, D(q.guess), D(q.fn));
+    mark(1);
+    col.K = 1; col.V = (int32_t)((int64_t)q.V * q.K); col.sum_nseg = q.tot_nseg;
+    launch_column_sum<int32_t, true>(&col, cnt, 1, 1, D(q.total), nullptr, false, false, D(q.tguess), D(q.tfn));
+    mark(2);
+    hipLaunchKernelGGL(ts_words_kernel, dim3((unsigned)((q.V + 63) / 64)), dim3(64), 0, st, p);
+  } else {
+    mark(0); mark(1); mark(2);
+  }
+  mark(3);
+  if (all_scores) hipLaunchKernelGGL(ts_scores_kernel, dim3((unsigned)((q.K + 255) / 256), (unsigned)std::min(q.V, 4096)), dim3(256), 0, st, p);
+  const dim3 grid((unsigned)q.nseg, (unsigned)((q.K + kTsTopics - 1) / kTsTopics));
+  if (q.n <= kTsLdsWords) hipLaunchKernelGGL(ts_select_kernel<true>, grid, dim3(64), (size_t)q.n * 64 * 12, st, p);
+  else hipLaunchKernelGGL(ts_select_kernel<false>, grid, dim3(64), 0, st, p);
+  hipLaunchKernelGGL(ts_merge_kernel, dim3((unsigned)q.K), dim3(64), sizeof(int32_t) * (size_t)q.nseg, st, p);
+  mark(4);
+}
+}  // namespace
+
+int ggs_top_words(ggs_handle *h, int32_t kind, int32_t n_words, double lambda, int32_t *idx, double *score) {
+  int rc = require_ready(h, false);
+  if (rc) return rc;
+  if ((rc = ts_check_args(h, h->V, h->K, h->beta, kind, n_words, lambda, idx))) return rc;
+  if ((rc = ensure_global_counts(h))) return rc;
+  const TsPlan q(h->V, h->K, n_words);
+  if ((rc = ensure_scratch(h, q.bytes))) return rc;
+  char *work = static_cast<char *>(h->d_scratch);
+  ts_launch(h->stream, h->exact_sum, h->d_n_wk, h->beta, lambda, kind, q, work, false, nullptr);
+  HIP_TRY(h, hipGetLastError());
+  if ((rc = copy_out(h, idx, work + q.idx, sizeof(int32_t) * (size_t)h->K * n_words))) return rc;
+  return score ? copy_out(h, score, work + q.score, sizeof(double) * (size_t)h->K * n_words) : GGS_OK;
+}
+int ggs_debug_top_words_phases(ggs_handle *h, int32_t kind, int32_t n_words, double lambda, int32_t element_chain, double *ms) {
+  int rc = require_ready(h, false);
+  if (rc) return rc;
+  int32_t dummy = 0;
+  if (!ms) return set_err(h, GGS_ERR_BAD_ARG, "null output");
+  if ((rc = ts_check_args(h, h->V, h->K, h->beta, kind, n_words, lambda, &dummy))) return rc;
+  if ((rc = ensure_global_counts(h))) return rc;
+  const TsPlan q(h->V, h->K, n_words);
+  if ((rc = ensure_scratch(h, q.bytes))) return rc;
+  hipEvent_t ev[5] = {};
+  for (auto &e : ev) HIP_TRY(h, hipEventCreate(&e));
+  ts_launch(h->stream, element_chain ? false : h->exact_sum, h->d_n_wk, h->beta, lambda, kind, q, static_cast<char *>(h->d_scratch), false, nullptr, ev);
+  hipError_t err = hipGetLastError();
+  if (err == hipSuccess) err = hipStreamSynchronize(h->stream);
+  for (int i = 0; i < 4 && err == hipSuccess; ++i) { float f = 0; err = hipEventElapsedTime(&f, ev[i], ev[i + 1]); ms[i] = f; }
+  for (auto &e : ev) (void)hipEventDestroy(e);
+  HIP_TRY(h, err);
+  return GGS_OK;
+}
 int ggs_set_test_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32_t *tokens, int64_t doc_base) {
   if (!h || D < 0 || !doc_ptr || doc_base < 0) return set_err(h, GGS_ERR_BAD_ARG, "bad test corpus arguments");
   if (doc_ptr[0] != 0) return set_err(h, GGS_ERR_BAD_ARG, "doc_ptr[0] must be 0");
@@ -3428,6 +3532,29 @@ int ggs_debug_min_distances(int32_t device_id, const double *a, int64_t n, const
   hipLaunchKernelGGL(min_dist_finish_kernel, dim3(grid), dim3(256), 0, nullptr, dbits, n, dout, dsq);
   if (hipGetLastError() != hipSuccess || hipMemcpy(min_dist, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return GGS_ERR_HIP;
   if (min_sq && hipMemcpy(min_sq, dsq, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return GGS_ERR_HIP;
+  return GGS_OK;
+}
+
+int ggs_debug_topic_summaries(int32_t device_id, int32_t V, int32_t K, const int32_t *counts, double beta, double lambda, int32_t kind, int32_t n_words,
+                              int32_t *idx, double *score, double *mass_k, double *rowsum_w, double *total, double *all_scores) {
+  if (V <= 0 || K <= 0 || !counts || hipSetDevice(device_id) != hipSuccess) return GGS_ERR_BAD_ARG;
+  int rc = ts_check_args(nullptr, V, K, beta, kind, n_words, lambda, idx);
+  if (rc) return rc;
+  TmpDev t;
+  const TsPlan q(V, K, n_words);
+  const size_t kv = (size_t)V * K;
+  char *work = static_cast<char *>(t.get(q.bytes));
+  auto *dcnt = static_cast<int32_t *>(t.get(kv * 4));
+  double *dall = all_scores ? static_cast<double *>(t.get(kv * 8)) : nullptr;
+  if (!work || !dcnt || (all_scores && !dall)) return GGS_ERR_HIP;
+  if (hipMemcpy(dcnt, counts, kv * 4, hipMemcpyHostToDevice) != hipSuccess) return GGS_ERR_HIP;
+  // GGS_DEBUG_CHAIN=1: both column sums walked element by element
+  ts_launch(nullptr, !Knob("GGS_DEBUG_CHAIN").is(1), dcnt, beta, lambda, kind, q, work, true, dall);
+  auto fetch = [&](void *dst, const void *src, size_t bytes) { return !dst || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+  if (hipGetLastError() != hipSuccess || !fetch(idx, work + q.idx, 4 * (size_t)K * n_words) || !fetch(score, work + q.score, 8 * (size_t)K * n_words) ||
+      !fetch(mass_k, work + q.mass, 8 * (size_t)K) || !fetch(rowsum_w, work + q.rowsum, 8 * (size_t)V) || !fetch(total, work + q.total, 8) ||
+      !fetch(all_scores, dall, kv * 8))
+    return GGS_ERR_HIP;
   return GGS_OK;
 }
 

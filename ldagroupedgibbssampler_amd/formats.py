@@ -252,3 +252,15 @@ def append_min_topic_distance(log_dir, iteration, value):
     """UPLDA:799-801: ``iteration,value`` appended to min_topic_distances.csv."""
     with open(os.path.join(log_dir, "min_topic_distances.csv"), "a", newline="") as f:
         f.write("%d,%s%s" % (iteration, java_double_to_string(value), os.linesep))
+
+
+def format_top_words_csv(rows):
+    """LDAUtils.formatTopWordsAsCsv (LDAUtils.java:1429-1443): one line per topic, the words joined by ``,``, the lines by
+    ``\\n``, none after the last."""
+    return "\n".join(",".join(row) for row in rows)
+
+
+def write_top_words(rows, fn):
+    """TopWords.txt / RelevanceWords.txt as the driver writes them (tui/ParallelLDA.java:272-296): println of the CSV."""
+    with open(fn, "w", newline="") as f:
+        f.write(format_top_words_csv(rows) + os.linesep)

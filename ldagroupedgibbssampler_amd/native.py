@@ -17,6 +17,9 @@ FLAG_ADLDA = 1024
 SCHEME_FLAGS = {"ggs": 0, "pcgs": FLAG_PCGS, "collapsed": FLAG_COLLAPSED, "polyaurn": FLAG_POLYAURN, "spalias": FLAG_SPALIAS, "lightpclda": FLAG_LIGHTPCLDA,
                 "polyaurn_sparse": FLAG_POLYAURN_SPARSE, "lightcollapsed": FLAG_LIGHTCOLLAPSED, "nzvsspalias": FLAG_NZVSSPALIAS, "adlda": FLAG_ADLDA}
 PURPOSE_Z, PURPOSE_THETA, PURPOSE_PHI, PURPOSE_INIT_PHI = 1, 2, 3, 4
+# the rankings of ggs_top_words (GGS_TOP_*), and its cap on the words per topic (GGS_TOP_WORDS_MAX)
+TOP_KINDS = {"top": 0, "relevance": 1, "distinctive": 2, "salient": 3, "k1": 4}
+TOP_WORDS_MAX = 128
 
 
 class GGSError(RuntimeError):
@@ -71,6 +74,14 @@ def rccl_unique_id():
     if rc:
         raise GGSError(rc, "ggs_rccl_unique_id failed (librccl not loadable?)")
     return buf.raw
+
+
+def _top_kind(kind):
+    if isinstance(kind, str):
+        if kind not in TOP_KINDS:
+            raise ValueError("kind must be one of %s" % ", ".join(TOP_KINDS))
+        return TOP_KINDS[kind]
+    return int(kind)
 
 
 class GGSHandle:
@@ -375,6 +386,22 @@ class GGSHandle:
         self._chk(self._L.ggs_min_topic_distance(self._h, C.byref(v)))
         return v.value
 
+    def top_words(self, kind, n, lam=0.6, scores=False):
+        """The n best words of every topic (ggs_top_words) on the corpus-wide counts: idx [K][n] in IDSorter's order (falling
+        score, ties by falling id); kind = "top" (LDAUtils.getTopWords, TopWords.txt), "relevance" (getTopRelevanceWords with
+        lambda = lam, RelevanceWords.txt), "distinctive", "salient" or "k1".  scores=True: (idx, score [K][n])."""
+        idx = np.empty((self.K, int(n)), np.int32)
+        sc = np.empty((self.K, int(n)), np.float64) if scores else None
+        self._chk(self._L.ggs_top_words(self._h, _top_kind(kind), int(n), float(lam), _ip(idx), _dp(sc) if scores else None))
+        return (idx, sc) if scores else idx
+
+    def top_words_phases(self, kind, n, lam=0.6, element_chain=False):
+        """Device milliseconds of one top_words call by phase (ggs_debug_top_words_phases): mass_k, total, the words'
+        statistics, selection and merge.  element_chain: the column sums by the one-lane chain kernel."""
+        ms = np.zeros(4, np.float64)
+        self._chk(self._L.ggs_debug_top_words_phases(self._h, _top_kind(kind), int(n), float(lam), int(bool(element_chain)), _dp(ms)))
+        return dict(zip(("mass_k", "total", "words", "select_merge"), ms.tolist()))
+
     def set_test_corpus(self, doc_ptr, tokens, doc_base=0):
         """addTestInstances (MSLDA:918-923): the held-out estimator's test set; ids >= num_types are out of vocabulary."""
         doc_ptr = np.ascontiguousarray(doc_ptr, np.int64)
@@ -626,3 +653,21 @@ def debug_min_distances(a, b=None, element_major=False, device_id=0):
     if rc:
         raise GGSError(rc, "ggs_debug_min_distances")
     return dist, sq
+
+
+def debug_topic_summaries(counts, beta, kind, n, lam=0.6, device_id=0):
+    """The topic-summary kernels on an arbitrary count matrix [V][K]: a dict with idx [K][n], score [K][n], mass_k [K],
+    rowsum_w [V], total and all_scores [V][K] (ggs_debug_topic_summaries)."""
+    L = _lib.load()
+    counts = np.ascontiguousarray(counts, np.int32)
+    if counts.ndim != 2:
+        raise ValueError("counts must be [V][K]")
+    V, K = counts.shape
+    n = int(n)
+    idx, score = np.empty((K, max(n, 0)), np.int32), np.empty((K, max(n, 0)), np.float64)
+    mass, rowsum, total, every = np.empty(K, np.float64), np.empty(V, np.float64), np.empty(1, np.float64), np.empty((V, K), np.float64)
+    rc = L.ggs_debug_topic_summaries(device_id, V, K, _ip(counts), float(beta), float(lam), _top_kind(kind), n, _ip(idx), _dp(score), _dp(mass), _dp(rowsum),
+                                     _dp(total), _dp(every))
+    if rc:
+        raise GGSError(rc, "ggs_debug_topic_summaries")
+    return {"idx": idx, "score": score, "mass_k": mass, "rowsum_w": rowsum, "total": float(total[0]), "all_scores": every}

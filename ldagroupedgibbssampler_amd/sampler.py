@@ -46,6 +46,8 @@ class SimpleLDAConfiguration:
         self.compute_likelihood = bool(kw.pop("compute_likelihood", False))   # model LL (+ held-out LL with a test set) every iteration, UPLDA:838-850
         self.start_diagnostic = int(kw.pop("start_diagnostic", 500))          # START_DIAG_DEFAULT; log posterior from this iteration on, UPLDA:706,818-821
         self.compute_doc_topic_distances = bool(kw.pop("compute_doc_topic_distances", False))   # COMPUTE_DOC_TOPIC_DISTANCES_DEFAULT; min_doc_distances.csv / min_topic_distances.csv from start_diagnostic on, UPLDA:723-753,778-806
+        self.nr_top_words = int(kw.pop("nr_top_words", 20))                   # NO_TOP_WORDS_DEFAULT (LDAConfiguration.java:38): the words per topic of TopWords.txt / RelevanceWords.txt
+        self.lambda_ = float(kw.pop("lambda", 0.6))                           # LAMBDA_DEFAULT (LDAConfiguration.java:41), the relevance weight; `lambda` is a Python keyword: pass **{"lambda": x}
         self.log_topic_indicators = bool(kw.pop("log_topic_indicators", False))  # z_<iteration>.csv, UPLDA:637-638,871-872
         self.log_dir = kw.pop("log_dir", None)                       # where the files go (LoggingUtils' run directory in Java); None = no files
         if kw:
@@ -351,6 +353,45 @@ class LDAGroupedGibbsSampler:
         rows of Phi.  One line of min_topic_distances.csv."""
         self._need_data()
         return self._h.min_topic_distance()
+
+    # ---- the topic summaries of LDAUtils.java:566-911, on the device-resident counts (ggs_top_words) ----
+    def _top(self, kind, n, lam=0.6, words=True):
+        self._need_data()
+        n, V = int(n), self._corpus.num_types
+        if n > V:                                                     # the Java IllegalArgumentException, LDAUtils.java:568-570
+            raise ValueError("Asked for more words (%d) than there are types (unique words = noTypes = %d)." % (n, V))
+        idx = self._h.top_words(kind, n, lam)
+        if not words:
+            return idx
+        vocab = self._corpus.vocab
+        if vocab is None:
+            raise ValueError("the corpus has no vocabulary: getTopWordIndices returns the ids")
+        return [[vocab[i] for i in row] for row in idx.tolist()]
+
+    def getTopWordIndices(self, n):
+        """LDAUtils.getTopWordIndices (:895-911): [K][n] word ids by falling count, equal counts by falling id."""
+        return self._top("top", n, words=False)
+
+    def getTopWords(self, n):
+        """LDAUtils.getTopWords (:874-893), the rows of TopWords.txt (tui/ParallelLDA.java:272-283)."""
+        return self._top("top", n)
+
+    def getTopRelevanceWords(self, n, lam=None):
+        """LDAUtils.getTopRelevanceWords (:566-590; Sievert & Shirley's relevance), the rows of RelevanceWords.txt
+        (tui/ParallelLDA.java:285-296).  lam: the configuration's `lambda` unless given."""
+        return self._top("relevance", n, getattr(self.config, "lambda_", 0.6) if lam is None else lam)
+
+    def getTopDistinctiveWords(self, n):
+        """LDAUtils.getTopDistinctiveWords (:592-617; Chuang, Manning & Heer's distinctiveness)."""
+        return self._top("distinctive", n)
+
+    def getTopSalientWords(self, n):
+        """LDAUtils.getTopSalientWords (:619-644)."""
+        return self._top("salient", n)
+
+    def getK1ReWeightedWords(self, n):
+        """LDAUtils.getK1ReWeightedWords (:752-801; Song et al.'s keyword re-ranking)."""
+        return self._top("k1", n)
 
     def getBeta(self):
         return self.beta
