@@ -38,10 +38,15 @@ def main():
     ap.add_argument("--doc-topic-distances", action="store_true",
                     help="compute_doc_topic_distances: min_doc_distances.csv and min_topic_distances.csv in --out, one line per iteration from --start-diagnostic on")
     ap.add_argument("--start-diagnostic", type=int, default=500, help="start_diagnostic: first iteration of the log posterior and the distances")
+    ap.add_argument("--topic-diagnostics", default=None, metavar="FILE",
+                    help="save_doc_topic_diagnostics / doc_topic_diagnostics_filename: TopicModelDiagnosticsPlain's CSV (eleven quality scores per topic) "
+                         "as FILE in --out; the coherence column is printed")
     ap.add_argument("--out", default=None, help="directory for the driver's files (phi / theta / counts / likelihood / TopWords.txt / RelevanceWords.txt)")
     args = ap.parse_args()
     if args.topic_priors and args.scheme != "spalias_priors":
         ap.error("--topic-priors belongs to --scheme spalias_priors")
+    if args.topic_diagnostics and not args.out:
+        ap.error("--topic-diagnostics writes into --out")
 
     from ldagroupedgibbssampler_amd import formats as F
     from ldagroupedgibbssampler_amd.frontend import load_dataset
@@ -56,7 +61,8 @@ def main():
                                  seed=args.seed, exec_time=None, compute_likelihood=bool(args.out), log_dir=args.out,
                                  topic_prior_filename=args.topic_priors, variable_selection_prior=args.vs_prior,
                                  compute_doc_topic_distances=args.doc_topic_distances, start_diagnostic=args.start_diagnostic,
-                                 nr_top_words=args.top_words, **{"lambda": args.lambda_})
+                                 nr_top_words=args.top_words, save_doc_topic_diagnostics=bool(args.topic_diagnostics),
+                                 doc_topic_diagnostics_filename=args.topic_diagnostics, **{"lambda": args.lambda_})
     if args.scheme == "nzvsspalias":                          # not in create_model's registry: the class itself
         from ldagroupedgibbssampler_amd.sampler import NZVSSpaliasUncollapsedParallelLDA
         model = NZVSSpaliasUncollapsedParallelLDA(cfg)
@@ -81,6 +87,10 @@ def main():
         n_wk = np.asarray(model.getTypeTopicMatrix())       # [V][K] counts, for type_topic_counts.csv
         F.write_top_words(top, os.path.join(args.out, "TopWords.txt"))
         F.write_top_words(model.getTopRelevanceWords(requested, cfg.lambda_), os.path.join(args.out, "RelevanceWords.txt"))
+        if cfg.save_doc_topic_diagnostics:                  # tui/ParallelLDA.java:218-225, with nr_top_words clamped first
+            tmd = model.getTopicModelDiagnostics(requested)
+            F.write_topic_diagnostics(tmd.names, [tmd.scores[x] for x in tmd.names], os.path.join(args.out, cfg.doc_topic_diagnostics_filename))
+            print("coherence: %s" % " ".join("%d:%s" % (k, F.java_format_fixed(v, 4)) for k, v in enumerate(tmd.scores["coherence"])))
         if args.scheme != "collapsed":
             F.write_binary_double_matrix(np.asarray(model.getPhi()), F.binary_matrix_name(os.path.join(args.out, "phi"), K, V, it))
         F.write_ascii_double_matrix(np.asarray(model.getThetaEstimate()), F.ascii_matrix_name(args.out, "Theta_DxK", D, K, it))

@@ -306,6 +306,25 @@ inline void write_top_words(const std::vector<std::vector<std::string>> &rows, c
   std::ofstream f(fn, std::ios::binary | std::ios::trunc);
   f << format_top_words_csv(rows) << "\n";
 }
+// TopicModelDiagnosticsPlain.topicsToCsv (TopicModelDiagnosticsPlain.java:576-605): "Topic," and the names joined by ","; per topic
+// "%d," and the "%.4f" scores joined by ","; every line ends in "\n".  columns[i][k]: the score names[i] of topic k.
+inline std::string format_topic_diagnostics_csv(const std::vector<std::string> &names, const std::vector<std::vector<double>> &columns) {
+  std::string out = "Topic,";
+  for (size_t i = 0; i < names.size(); ++i) { out += names[i]; if (i + 1 < names.size()) out += ","; }
+  out += "\n";
+  const size_t K = columns.empty() ? 0 : columns[0].size();
+  for (size_t k = 0; k < K; ++k) {
+    out += std::to_string(k) + ",";
+    for (size_t i = 0; i < columns.size(); ++i) { out += java_format_fixed(columns[i][k], 4); if (i + 1 < columns.size()) out += ","; }
+    out += "\n";
+  }
+  return out;
+}
+// the save_doc_topic_diagnostics file: println of the CSV (tui/ParallelLDA.java:218-225)
+inline void write_topic_diagnostics(const std::vector<std::string> &names, const std::vector<std::vector<double>> &columns, const std::string &fn) {
+  std::ofstream f(fn, std::ios::binary | std::ios::trunc);
+  f << format_topic_diagnostics_csv(names, columns) << "\n";
+}
 
 }  // namespace formats
 }  // namespace ggs

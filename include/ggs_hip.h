@@ -629,6 +629,61 @@ int ggs_min_topic_distance(ggs_handle *h, double *min_dist);
 #define GGS_TOP_K1 4
 #define GGS_TOP_WORDS_MAX 128
 int ggs_top_words(ggs_handle *h, int32_t kind, int32_t n_words, double lambda, int32_t *idx /*[K][n_words]*/, double *score /*[K][n_words] or NULL*/);
+/* replaces: new TopicModelDiagnosticsPlain(model, numTopWords).topicsToCsv() (topics/TopicModelDiagnosticsPlain.java; the file
+ * save_doc_topic_diagnostics makes tui/ParallelLDA.java:218-225 write), in two calls: the statistics over the documents (z), then
+ * the scores from the corpus-wide counts and those statistics.  Notation: n = n_words; T_k[r], r < n: the top words of topic k,
+ * exactly ggs_top_words(GGS_TOP_WORDS); c_dk: tokens of document d with z = k; n_wk, n_k: the corpus-wide counts;
+ * wtc[w] = sum_k n_wk and numTokens = sum_k n_k (integers); P = {0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.5}.  Every product, quotient
+ * and sum is rounded on its own in the Java order; log is the library's fdlibm log (Math.log on a JVM is parity-unpinned).
+ *
+ * ggs_topic_doc_statistics (collectDocumentStatistics :108-220) covers THIS handle's documents; integers add across shards:
+ *   doc_stats[k][0] nonzero   documents with c_dk > 0
+ *   doc_stats[k][1] rank1     documents whose largest c_dk is at k (strict > walking k upwards: the lowest k among equal maxima)
+ *   doc_stats[k][2 + i] at_prop[k][i]: for each document with c_dk > 0, prop = (alpha_k + c_dk) / (alphaSum + len_d), alphaSum the
+ *                   running sum of alpha_k from 0.0 in index order; counters i = 0, 1, ... incremented until the first prop < P[i]
+ *   codoc[k][i][j]  S_dk = { i : some token of d has type T_k[i] and z = k }; for each d with c_dk > 0 and each i in S_dk
+ *                   codoc[k][i][i]++, for i < j both in S_dk [i][j]++ and [j][i]++ (a word under another topic does not count,
+ *                   a word twice in a document counts once)
+ *   clogc_out[k]    from 0.0 (or clogc_in[k], what the shards before this one left), over the documents in index order:
+ *                   s = s + (double) c_dk * log((double) c_dk) for every d with c_dk > 0 -- one rounding chain per topic
+ * idx [K][n_words] (host): the corpus-wide top words, or NULL for the handle's own ggs_top_words (then a collective call with an
+ * exchange).  A doc-sharded run calls it rank after rank in document order with the same idx, clogc_out of one rank being the
+ * next rank's clogc_in, and adds the integers: bit-identical to one handle over the whole corpus.
+ *
+ * ggs_topic_scores: topic_scores[row][k], the CSV's columns without word-length (host: it needs the alphabet), from the handle's
+ * CURRENT corpus-wide counts (gathered as ggs_top_words gathers them: a collective call with an exchange) and the (summed)
+ * statistics passed in.  Every division is in doubles, ints cast first.
+ *   0 tokens            (double) n_k
+ *   1 document_entropy  -clogc[k] / n_k + log(n_k)
+ *   2 coherence         for row = 0..n-1, col < row: score = log((codoc[row][col] + beta) / (codoc[col][col] + beta)),
+ *                       rowScore += score, min = score if score < min (from 0.0); topic += rowScore; word score of row = min
+ *   3 uniform_dist      the words of k in IDSorter order (all V, falling count, ties by falling id):
+ *                       score = (c / n_k) * log((c * V) / n_k), running sum from 0.0; word scores: the first n addends
+ *   4 corpus_dist       same order: coef = (double) numTokens / n_k; score = (c / n_k) * log(coef * c / wtc[w]); running sum
+ *   5 eff_num_words     same order: p = c / n_k; s += p * p; 1.0 / s
+ *   6 token-doc-diff    over r < n: w_r = (double) n_{T_k[r],k}, d_r = codoc[r][r], running sums wordSum, docSum; per r:
+ *                       p = w_r / wordSum, q = d_r / docSum, m = 0.5 * (p + q), score = 0.0, += 0.5 * p * log(p / m) if p > 0,
+ *                       += 0.5 * q * log(q / m) if q > 0; word score; topic = running sum
+ *   7 rank_1_docs       (double) rank1 / nonzero
+ *   8 allocation_ratio  (double) at_prop[k][6] / at_prop[k][1]
+ *   9 allocation_count  (double) at_prop[k][5] / nonzero
+ * word_scores[4][K][n_words] (or NULL): coherence, uniform_dist, corpus_dist, token-doc-diff.  As in the Java, a zero cell's addend
+ * of uniform_dist / corpus_dist is 0.0 * log(0.0) = NaN: those two topic scores are NaN unless the topic's column has no zero
+ * cell, and a top word with count 0 has word score NaN; eff_num_words is unaffected (+ 0.0); n_k == 0 gives IEEE's NaNs and
+ * infinities.  NaNs are NaN whatever their bits; everything else equals the Java loops restated
+ * (tests/topic_diagnostics_restatement.py) bit for bit.  One deviation: the Java driver builds the diagnostics before it clamps
+ * nr_top_words to V and then reads word id 0 for the missing positions; here n_words must be in [1, min(V, GGS_TOP_WORDS_MAX)].
+ * Works under every scheme; nothing a sweep reads is written: a call between sweeps leaves the chain's bits.
+ * GGS_ERR_STATE before a corpus; GGS_ERR_BAD_ARG: a null argument, n_words < 1 or > V, an idx entry outside [0, V);
+ * GGS_ERR_UNSUPPORTED: n_words > GGS_TOP_WORDS_MAX, or (document statistics) K > GGS_TOPIC_DIAGNOSTICS_MAX_TOPICS: a document's
+ * K-long histogram and masks no longer fit 60 KiB of LDS. */
+#define GGS_TOPIC_DIAGNOSTICS_MAX_TOPICS 3072
+#define GGS_TOPIC_SCORE_ROWS 10
+#define GGS_TOPIC_WORD_SCORE_ROWS 4
+int ggs_topic_doc_statistics(ggs_handle *h, int32_t n_words, const int32_t *idx /*[K][n_words] host, or NULL*/, const double *clogc_in /*[K] or NULL*/,
+                             int32_t *codoc /*[K][n_words][n_words]*/, int32_t *doc_stats /*[K][9]*/, double *clogc_out /*[K]*/);
+int ggs_topic_scores(ggs_handle *h, int32_t n_words, const int32_t *idx /*[K][n_words] host, or NULL*/, const int32_t *codoc, const int32_t *doc_stats,
+                     const double *clogc, double *topic_scores /*[10][K]*/, double *word_scores /*[4][K][n_words] or NULL*/);
 /* replaces: addTestInstances (UPLDA:340-343; the test set of the held-out estimator).  CSR like ggs_set_corpus; token
  * ids are indices of the TRAINING alphabet, ids >= num_types are out of vocabulary and skipped as at MPE:341-345.
  * doc_base = global index of the first test document (RNG element ids only; for a sharded test set).  Documents longer
@@ -674,6 +729,19 @@ int ggs_debug_topic_summaries(int32_t device_id, int32_t V, int32_t K, const int
  * lane per sum: what the total chain costs without ggs_exact_sum.hpp).  Nothing is copied back. */
 int ggs_debug_top_words_phases(ggs_handle *h, int32_t kind, int32_t n_words, double lambda, int32_t element_chain, double *ms /*[4]*/);
 
+/* The topic-diagnostics kernels on their own, for an arbitrary corpus with its z (doc_ptr [D + 1] from 0, tokens < V, z < K; host)
+ * and an arbitrary count matrix [V][K] (host): outputs as ggs_topic_doc_statistics / ggs_topic_scores; sorted_ids [K][n_words] (or
+ * NULL): the first n_words cells of every topic's sorted non-zero cells, -1 beyond them.  Same error codes. */
+int ggs_debug_topic_doc_statistics(int32_t device_id, int64_t D, const int64_t *doc_ptr, const int32_t *tokens, const int32_t *z, int32_t V, int32_t K,
+                                   const double *alpha /*[K]*/, int32_t n_words, const int32_t *idx, const double *clogc_in /*[K] or NULL*/, int32_t *codoc,
+                                   int32_t *doc_stats, double *clogc_out);
+int ggs_debug_topic_scores(int32_t device_id, int32_t V, int32_t K, const int32_t *counts /*[V][K]*/, double beta, int32_t n_words, const int32_t *idx,
+                           const int32_t *codoc, const int32_t *doc_stats, const double *clogc, double *topic_scores, double *word_scores /*or NULL*/,
+                           int32_t *sorted_ids /*or NULL*/);
+/* Where ggs_topic_doc_statistics + ggs_topic_scores spend their device time (scripts/time_topic_diagnostics.py): both calls on the
+ * handle's own top words with events between the launches; ms[7] = membership (host CSR and its upload), document pass (with the
+ * mirror), column statistics and c log c addends, the clogc chain, n_k and wtc, compaction + sort + sorted chains, small scores. */
+int ggs_debug_topic_diagnostics_phases(ggs_handle *h, int32_t n_words, double *ms /*[7]*/);
 #ifdef __cplusplus
 }
 #endif

@@ -151,12 +151,17 @@ SIGNATURES = {
     "ggs_min_doc_distances": (C.c_int, [_vp, _dp, C.c_int64, _dp]),
     "ggs_min_topic_distance": (C.c_int, [_vp, _dp]),
     "ggs_top_words": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, _ip, _dp]),
+    "ggs_topic_doc_statistics": (C.c_int, [_vp, C.c_int32, _ip, _dp, _ip, _ip, _dp]),
+    "ggs_topic_scores": (C.c_int, [_vp, C.c_int32, _ip, _ip, _ip, _dp, _dp, _dp]),
     "ggs_set_test_corpus": (C.c_int, [_vp, C.c_int64, _lp, _ip, C.c_int64]),
     "ggs_heldout_log_likelihood": (C.c_int, [_vp, C.c_int32, _dp, _dp]),
     "ggs_debug_column_sum": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _ip, C.c_double, _dp]),
     "ggs_debug_column_sum_guided": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _ip, C.c_double, _dp, _dp, _dp, _ip]),
     "ggs_debug_min_distances": (C.c_int, [C.c_int32, _dp, C.c_int64, _dp, C.c_int64, C.c_int64, C.c_int32, _dp, _dp]),
     "ggs_debug_top_words_phases": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, _dp]),
+    "ggs_debug_topic_doc_statistics": (C.c_int, [C.c_int32, C.c_int64, _lp, _ip, _ip, C.c_int32, C.c_int32, _dp, C.c_int32, _ip, _dp, _ip, _ip, _dp]),
+    "ggs_debug_topic_scores": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _ip, C.c_double, C.c_int32, _ip, _ip, _ip, _dp, _dp, _dp, _ip]),
+    "ggs_debug_topic_diagnostics_phases": (C.c_int, [_vp, C.c_int32, _dp]),
     "ggs_debug_topic_summaries": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _ip, C.c_double, C.c_double, C.c_int32, C.c_int32, _ip, _dp, _dp, _dp, _dp, _dp]),
 }
 

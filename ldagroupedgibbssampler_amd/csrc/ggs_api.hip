@@ -34,6 +34,7 @@
 #include "ggs_corpus_lists.hpp"
 #include "ggs_distances.hpp"
 #include "ggs_topic_summaries.hpp"
+#include "ggs_topic_diagnostics.hpp"
 
 using namespace ggs;
 
@@ -3104,6 +3105,225 @@ int ggs_debug_top_words_phases(ggs_handle *h, int32_t kind, int32_t n_words, dou
   HIP_TRY(h, err);
   return GGS_OK;
 }
+// ---- topic diagnostics (csrc/ggs_topic_diagnostics.hpp) ---------------------------------------------------------------------
+namespace {
+constexpr size_t kTdPieceBytes = (size_t)64 << 20;     // the dense rows of a piece of documents / the sort buffers of a group of topics
+// events between the phases of a call (ggs_debug_topic_diagnostics_phases); without it, nothing is recorded
+struct TdTimer {
+  hipStream_t st;
+  std::vector<std::pair<int, hipEvent_t>> marks;       // (phase that ends here, or -1 for a start; event)
+  void mark(int phase) {
+    hipEvent_t e = nullptr;
+    if (hipEventCreate(&e) != hipSuccess) return;
+    (void)hipEventRecord(e, st);
+    marks.emplace_back(phase, e);
+  }
+  // after a synchronize: adds every span to ms[phase]
+  void collect(double *ms) {
+    for (size_t i = 1; i < marks.size(); ++i) {
+      float f = 0;
+      if (marks[i].first >= 0 && hipEventElapsedTime(&f, marks[i - 1].second, marks[i].second) == hipSuccess) ms[marks[i].first] += f;
+    }
+  }
+  ~TdTimer() { for (auto &m : marks) (void)hipEventDestroy(m.second); }
+};
+inline void td_mark(TdTimer *t, int phase) { if (t) t->mark(phase); }
+enum { kTdPhMembership = 0, kTdPhDocs = 1, kTdPhColumns = 2, kTdPhChain = 3, kTdPhTotals = 4, kTdPhSorted = 5, kTdPhSmall = 6, kTdPhases = 7 };
+
+int td_check_args(ggs_handle *h, int32_t V, int32_t K, int32_t n, const int32_t *idx) {
+  if (n < 1 || n > V) return set_err(h, GGS_ERR_BAD_ARG, "Asked for more words (" + std::to_string(n) + ") than there are types (unique words = noTypes = " + std::to_string(V) + ").");
+  if (n > kTdMaxWords) return set_err(h, GGS_ERR_UNSUPPORTED, "at most " + std::to_string(kTdMaxWords) + " words per topic");
+  if (idx)
+    for (size_t i = 0; i < (size_t)K * n; ++i)
+      if (idx[i] < 0 || idx[i] >= V) return set_err(h, GGS_ERR_BAD_ARG, "idx holds a word id outside [0, V)");
+  return GGS_OK;
+}
+int td_check_topics(ggs_handle *h, int32_t K) {
+  if (K > kTdMaxTopics)
+    return set_err(h, GGS_ERR_UNSUPPORTED, "the topic diagnostics keep a document's topic counts and top-word masks in LDS (20 bytes per topic): at most " +
+                                               std::to_string(kTdMaxTopics) + " topics fit 60 KiB, this model has " + std::to_string(K));
+  return GGS_OK;
+}
+
+// the device work space of ggs_topic_doc_statistics
+struct TdDocPlan {
+  int64_t D = 0, piece = 0;
+  int32_t V = 0, K = 0, n = 0;
+  size_t mem_ptr = 0, mem = 0, codoc = 0, stats = 0, clogc = 0, maxtopic = 0, crow = 0, addend = 0, bytes = 0;
+  TdDocPlan(int64_t D_, int32_t V_, int32_t K_, int32_t n_) : D(D_), V(V_), K(K_), n(n_) {
+    // a piece's dense rows (4 + 8 bytes per cell) stay within kTdPieceBytes, but hold at least one wave's 256 documents
+    piece = (int64_t)(kTdPieceBytes / (12 * (size_t)K)) / kTdSegDocs * kTdSegDocs;
+    piece = std::max<int64_t>(piece, kTdSegDocs);
+    piece = std::min<int64_t>(piece, std::max<int64_t>(D, 1));
+    size_t at = 0;
+    auto take = [&](size_t b) { const size_t o = at; at += (b + 255) & ~(size_t)255; return o; };
+    mem_ptr = take(4 * ((size_t)V + 1)); mem = take(4 * (size_t)K * n); codoc = take(4 * (size_t)K * n * n); stats = take(4 * (size_t)K * kTdStats);
+    clogc = take(8 * (size_t)K); maxtopic = take(4 * (size_t)piece); crow = take(4 * (size_t)piece * K); addend = take(8 * (size_t)piece * K);
+    bytes = at;
+  }
+};
+// idx [K][n] (host) -> the CSR by word of the (topic, position) pairs
+void td_membership(const int32_t *idx, int32_t V, int32_t K, int32_t n, std::vector<int32_t> &ptr, std::vector<int32_t> &mem) {
+  ptr.assign((size_t)V + 1, 0);
+  mem.assign((size_t)K * n, 0);
+  for (size_t i = 0; i < (size_t)K * n; ++i) ptr[(size_t)idx[i] + 1] += 1;
+  for (int32_t w = 0; w < V; ++w) ptr[(size_t)w + 1] += ptr[w];
+  std::vector<int32_t> cur(ptr.begin(), ptr.end() - 1);
+  for (int32_t k = 0; k < K; ++k)
+    for (int32_t r = 0; r < n; ++r) mem[(size_t)cur[idx[(size_t)k * n + r]]++] = k * 128 + r;
+}
+// Enqueues the whole document pass; the results are left in work (q.codoc, q.stats, q.clogc).  The uploads are synchronous.
+hipError_t td_doc_launch(hipStream_t st, const TdDocPlan &q, char *work, const int64_t *d_doc_ptr, const int32_t *d_tok, const int32_t *d_z, const double *d_alpha,
+                         double alpha_sum, const int32_t *idx, const double *clogc_in, TdTimer *tm) {
+  td_mark(tm, -1);
+  std::vector<int32_t> ptr, mem;
+  td_membership(idx, q.V, q.K, q.n, ptr, mem);
+  hipError_t e;
+  if ((e = hipMemcpyAsync(work + q.mem_ptr, ptr.data(), 4 * ptr.size(), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(work + q.mem, mem.data(), 4 * mem.size(), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(work + q.codoc, 0, q.stats + 4 * (size_t)q.K * kTdStats - q.codoc, st)) != hipSuccess) return e;
+  if (clogc_in) e = hipMemcpyAsync(work + q.clogc, clogc_in, 8 * (size_t)q.K, hipMemcpyHostToDevice, st);
+  else e = hipMemsetAsync(work + q.clogc, 0, 8 * (size_t)q.K, st);
+  if (e != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;           // ptr / mem / clogc_in are pageable host memory
+  td_mark(tm, kTdPhMembership);
+  TdDocParams p{};
+  p.doc_ptr = d_doc_ptr; p.tok = d_tok; p.z = d_z;
+  p.mem_ptr = reinterpret_cast<int32_t *>(work + q.mem_ptr); p.mem = reinterpret_cast<int32_t *>(work + q.mem);
+  p.crow = reinterpret_cast<int32_t *>(work + q.crow); p.maxtopic = reinterpret_cast<int32_t *>(work + q.maxtopic);
+  p.codoc = reinterpret_cast<int32_t *>(work + q.codoc); p.alpha = d_alpha; p.alpha_sum = alpha_sum;
+  p.addend = reinterpret_cast<double *>(work + q.addend); p.doc_stats = reinterpret_cast<int32_t *>(work + q.stats);
+  p.K = q.K; p.n = q.n;
+  double *clogc = reinterpret_cast<double *>(work + q.clogc);
+  const unsigned kblocks = (unsigned)((q.K + 63) / 64);
+  for (int64_t d0 = 0; d0 < q.D; d0 += q.piece) {
+    p.d0 = d0; p.nd = std::min<int64_t>(q.piece, q.D - d0);
+    hipLaunchKernelGGL(td_docs_kernel, dim3((unsigned)std::min<int64_t>(p.nd, 4096)), dim3(64), (size_t)kTdLdsPerTopic * q.K, st, p);
+    td_mark(tm, kTdPhDocs);
+    hipLaunchKernelGGL(td_columns_kernel, dim3(kblocks, (unsigned)((p.nd + kTdSegDocs - 1) / kTdSegDocs)), dim3(64), 0, st, p);
+    td_mark(tm, kTdPhColumns);
+    hipLaunchKernelGGL(td_clogc_kernel, dim3(kblocks), dim3(64), 0, st, p.addend, p.nd, q.K, clogc);
+    td_mark(tm, kTdPhChain);
+  }
+  hipLaunchKernelGGL(td_mirror_kernel, dim3((unsigned)grid_for((int64_t)q.K * q.n * q.n, 256)), dim3(256), 0, st, p.codoc, q.K, q.n);
+  td_mark(tm, kTdPhDocs);
+  return hipGetLastError();
+}
+
+// the device work space of ggs_topic_scores
+struct TdScorePlan {
+  int32_t V = 0, K = 0, n = 0, group = 0;
+  size_t n_k = 0, wtc = 0, idx = 0, codoc = 0, stats = 0, clogc = 0, head = 0, ts = 0, ws = 0, key_a = 0, id_a = 0, key_b = 0, id_b = 0, bytes = 0;
+  TdScorePlan(int32_t V_, int32_t K_, int32_t n_) : V(V_), K(K_), n(n_) {
+    group = (int32_t)std::min<size_t>((size_t)K, std::max<size_t>(1, kTdPieceBytes / (16 * (size_t)V)));   // the sort's four [group][V] buffers within kTdPieceBytes
+    size_t at = 0;
+    auto take = [&](size_t b) { const size_t o = at; at += (b + 255) & ~(size_t)255; return o; };
+    n_k = take(4 * (size_t)K); wtc = take(4 * (size_t)V); idx = take(4 * (size_t)K * n); codoc = take(4 * (size_t)K * n * n); stats = take(4 * (size_t)K * kTdStats);
+    clogc = take(8 * (size_t)K); head = take(4 * (size_t)K * n); ts = take(8 * (size_t)kTdScoreRows * K); ws = take(8 * (size_t)kTdWordRows * K * n);
+    const size_t buf = 4 * (size_t)group * V;
+    key_a = take(buf); id_a = take(buf); key_b = take(buf); id_b = take(buf);
+    bytes = at;
+  }
+};
+hipError_t td_score_launch(hipStream_t st, const TdScorePlan &q, char *work, const int32_t *d_cnt, int32_t pitch, double beta, const int32_t *idx, const int32_t *codoc,
+                           const int32_t *doc_stats, const double *clogc, bool words, TdTimer *tm) {
+  hipError_t e;
+  td_mark(tm, -1);
+  if ((e = hipMemcpyAsync(work + q.idx, idx, 4 * (size_t)q.K * q.n, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(work + q.codoc, codoc, 4 * (size_t)q.K * q.n * q.n, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(work + q.stats, doc_stats, 4 * (size_t)q.K * kTdStats, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(work + q.clogc, clogc, 8 * (size_t)q.K, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(work + q.n_k, 0, 4 * (size_t)q.K, st)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+  td_mark(tm, -1);
+  auto I = [&](size_t o) { return reinterpret_cast<int32_t *>(work + o); };
+  TdScoreParams p{};
+  p.cnt = d_cnt; p.n_k = I(q.n_k); p.wtc = I(q.wtc); p.idx = I(q.idx); p.codoc = I(q.codoc); p.doc_stats = I(q.stats);
+  p.clogc = reinterpret_cast<double *>(work + q.clogc); p.key_a = I(q.key_a); p.id_a = I(q.id_a); p.key_b = I(q.key_b); p.id_b = I(q.id_b);
+  p.sorted_head = I(q.head); p.topic_scores = reinterpret_cast<double *>(work + q.ts); p.word_scores = words ? reinterpret_cast<double *>(work + q.ws) : nullptr;
+  p.beta = beta; p.pitch = pitch; p.V = q.V; p.K = q.K; p.n = q.n;
+  hipLaunchKernelGGL(td_nk_kernel, dim3((unsigned)((q.K + 63) / 64), (unsigned)std::min(q.V, 256)), dim3(64), 0, st, p);
+  hipLaunchKernelGGL(td_wtc_kernel, dim3((unsigned)std::min(q.V, 8192)), dim3(64), 0, st, p);
+  td_mark(tm, kTdPhTotals);
+  for (int32_t k0 = 0; k0 < q.K; k0 += q.group) {
+    p.k0 = k0;
+    hipLaunchKernelGGL(td_sorted_kernel, dim3((unsigned)std::min(q.group, q.K - k0)), dim3(64), 0, st, p);
+  }
+  td_mark(tm, kTdPhSorted);
+  hipLaunchKernelGGL(td_small_kernel, dim3((unsigned)q.K), dim3(64), 0, st, p);
+  td_mark(tm, kTdPhSmall);
+  return hipGetLastError();
+}
+double td_alpha_sum(const double *alpha, int32_t K) {
+  double s = 0;
+  for (int32_t k = 0; k < K; ++k) s += alpha[k];
+  return s;
+}
+// idx, or the handle's own top words into own
+int td_resolve_idx(ggs_handle *h, int32_t n, const int32_t *&idx, std::vector<int32_t> &own) {
+  int rc = td_check_args(h, h->V, h->K, n, idx);
+  if (rc || idx) return rc;
+  own.resize((size_t)h->K * n);
+  if ((rc = ggs_top_words(h, GGS_TOP_WORDS, n, 0.0, own.data(), nullptr))) return rc;
+  idx = own.data();
+  return GGS_OK;
+}
+int td_doc_statistics(ggs_handle *h, int32_t n, const int32_t *idx, const double *clogc_in, int32_t *codoc, int32_t *doc_stats, double *clogc_out, TdTimer *tm) {
+  int rc = require_ready(h, false);
+  if (rc) return rc;
+  if (!codoc || !doc_stats || !clogc_out) return set_err(h, GGS_ERR_BAD_ARG, "null output");
+  std::vector<int32_t> own;
+  if ((rc = td_resolve_idx(h, n, idx, own)) || (rc = td_check_topics(h, h->K))) return rc;
+  const TdDocPlan q(h->D, h->V, h->K, n);
+  if ((rc = ensure_scratch(h, q.bytes))) return rc;
+  char *work = static_cast<char *>(h->d_scratch);
+  HIP_TRY(h, td_doc_launch(h->stream, q, work, h->d_doc_ptr, h->d_tok, h->d_z, h->d_alpha, td_alpha_sum(h->alpha.data(), h->K), idx, clogc_in, tm));
+  if ((rc = copy_out(h, codoc, work + q.codoc, 4 * (size_t)h->K * n * n)) || (rc = copy_out(h, doc_stats, work + q.stats, 4 * (size_t)h->K * kTdStats))) return rc;
+  return copy_out(h, clogc_out, work + q.clogc, 8 * (size_t)h->K);
+}
+int td_scores(ggs_handle *h, int32_t n, const int32_t *idx, const int32_t *codoc, const int32_t *doc_stats, const double *clogc, double *topic_scores,
+              double *word_scores, TdTimer *tm) {
+  int rc = require_ready(h, false);
+  if (rc) return rc;
+  if (!codoc || !doc_stats || !clogc || !topic_scores) return set_err(h, GGS_ERR_BAD_ARG, "null argument");
+  std::vector<int32_t> own;
+  if ((rc = td_resolve_idx(h, n, idx, own)) || (rc = ensure_global_counts(h))) return rc;
+  const TdScorePlan q(h->V, h->K, n);
+  if ((rc = ensure_scratch(h, q.bytes))) return rc;
+  char *work = static_cast<char *>(h->d_scratch);
+  HIP_TRY(h, td_score_launch(h->stream, q, work, h->d_n_wk, h->K, h->beta, idx, codoc, doc_stats, clogc, word_scores != nullptr, tm));
+  if ((rc = copy_out(h, topic_scores, work + q.ts, 8 * (size_t)kTdScoreRows * h->K))) return rc;
+  return word_scores ? copy_out(h, word_scores, work + q.ws, 8 * (size_t)kTdWordRows * h->K * n) : GGS_OK;
+}
+}  // namespace
+
+int ggs_topic_doc_statistics(ggs_handle *h, int32_t n_words, const int32_t *idx, const double *clogc_in, int32_t *codoc, int32_t *doc_stats, double *clogc_out) {
+  return td_doc_statistics(h, n_words, idx, clogc_in, codoc, doc_stats, clogc_out, nullptr);
+}
+int ggs_topic_scores(ggs_handle *h, int32_t n_words, const int32_t *idx, const int32_t *codoc, const int32_t *doc_stats, const double *clogc, double *topic_scores,
+                     double *word_scores) {
+  return td_scores(h, n_words, idx, codoc, doc_stats, clogc, topic_scores, word_scores, nullptr);
+}
+int ggs_debug_topic_diagnostics_phases(ggs_handle *h, int32_t n_words, double *ms) {
+  int rc = require_ready(h, false);
+  if (rc) return rc;
+  if (!ms) return set_err(h, GGS_ERR_BAD_ARG, "null output");
+  if ((rc = td_check_args(h, h->V, h->K, n_words, nullptr))) return rc;
+  const size_t K = (size_t)h->K, n = (size_t)n_words;
+  std::vector<int32_t> idx(K * n), codoc(K * n * n), stats(K * kTdStats);
+  std::vector<double> clogc(K), ts(kTdScoreRows * K);
+  if ((rc = ggs_top_words(h, GGS_TOP_WORDS, n_words, 0.0, idx.data(), nullptr))) return rc;
+  for (int i = 0; i < kTdPhases; ++i) ms[i] = 0;
+  {
+    TdTimer tm{h->stream, {}};
+    if ((rc = td_doc_statistics(h, n_words, idx.data(), nullptr, codoc.data(), stats.data(), clogc.data(), &tm))) return rc;
+    tm.collect(ms);
+  }
+  TdTimer tm{h->stream, {}};
+  if ((rc = td_scores(h, n_words, idx.data(), codoc.data(), stats.data(), clogc.data(), ts.data(), nullptr, &tm))) return rc;
+  tm.collect(ms);
+  return GGS_OK;
+}
 int ggs_set_test_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32_t *tokens, int64_t doc_base) {
   if (!h || D < 0 || !doc_ptr || doc_base < 0) return set_err(h, GGS_ERR_BAD_ARG, "bad test corpus arguments");
   if (doc_ptr[0] != 0) return set_err(h, GGS_ERR_BAD_ARG, "doc_ptr[0] must be 0");
@@ -3554,6 +3774,61 @@ int ggs_debug_topic_summaries(int32_t device_id, int32_t V, int32_t K, const int
   if (hipGetLastError() != hipSuccess || !fetch(idx, work + q.idx, 4 * (size_t)K * n_words) || !fetch(score, work + q.score, 8 * (size_t)K * n_words) ||
       !fetch(mass_k, work + q.mass, 8 * (size_t)K) || !fetch(rowsum_w, work + q.rowsum, 8 * (size_t)V) || !fetch(total, work + q.total, 8) ||
       !fetch(all_scores, dall, kv * 8))
+    return GGS_ERR_HIP;
+  return GGS_OK;
+}
+
+int ggs_debug_topic_doc_statistics(int32_t device_id, int64_t D, const int64_t *doc_ptr, const int32_t *tokens, const int32_t *z, int32_t V, int32_t K,
+                                   const double *alpha, int32_t n_words, const int32_t *idx, const double *clogc_in, int32_t *codoc, int32_t *doc_stats,
+                                   double *clogc_out) {
+  if (D < 0 || V <= 0 || K <= 0 || !doc_ptr || !alpha || !idx || !codoc || !doc_stats || !clogc_out || doc_ptr[0] != 0) return GGS_ERR_BAD_ARG;
+  for (int64_t d = 0; d < D; ++d)
+    if (doc_ptr[d + 1] < doc_ptr[d]) return GGS_ERR_BAD_ARG;
+  const int64_t N = doc_ptr[D];
+  if (N > 0 && (!tokens || !z)) return GGS_ERR_BAD_ARG;
+  for (int64_t t = 0; t < N; ++t)
+    if (tokens[t] < 0 || tokens[t] >= V || z[t] < 0 || z[t] >= K) return GGS_ERR_BAD_ARG;
+  int rc = td_check_args(nullptr, V, K, n_words, idx);
+  if (rc || (rc = td_check_topics(nullptr, K))) return rc;
+  if (hipSetDevice(device_id) != hipSuccess) return GGS_ERR_BAD_ARG;
+  TmpDev t;
+  const TdDocPlan q(D, V, K, n_words);
+  char *work = static_cast<char *>(t.get(q.bytes));
+  auto *dptr = static_cast<int64_t *>(t.get(8 * ((size_t)D + 1)));
+  auto *dtok = static_cast<int32_t *>(t.get(4 * (size_t)N)), *dz = static_cast<int32_t *>(t.get(4 * (size_t)N));
+  auto *dalpha = static_cast<double *>(t.get(8 * (size_t)K));
+  if (!work || !dptr || !dtok || !dz || !dalpha) return GGS_ERR_HIP;
+  if (hipMemcpy(dptr, doc_ptr, 8 * ((size_t)D + 1), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dalpha, alpha, 8 * (size_t)K, hipMemcpyHostToDevice) != hipSuccess ||
+      (N > 0 && (hipMemcpy(dtok, tokens, 4 * (size_t)N, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dz, z, 4 * (size_t)N, hipMemcpyHostToDevice) != hipSuccess)))
+    return GGS_ERR_HIP;
+  if (td_doc_launch(nullptr, q, work, dptr, dtok, dz, dalpha, td_alpha_sum(alpha, K), idx, clogc_in, nullptr) != hipSuccess) return GGS_ERR_HIP;
+  if (hipMemcpy(codoc, work + q.codoc, 4 * (size_t)K * n_words * n_words, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(doc_stats, work + q.stats, 4 * (size_t)K * kTdStats, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(clogc_out, work + q.clogc, 8 * (size_t)K, hipMemcpyDeviceToHost) != hipSuccess)
+    return GGS_ERR_HIP;
+  return GGS_OK;
+}
+
+int ggs_debug_topic_scores(int32_t device_id, int32_t V, int32_t K, const int32_t *counts, double beta, int32_t n_words, const int32_t *idx, const int32_t *codoc,
+                           const int32_t *doc_stats, const double *clogc, double *topic_scores, double *word_scores, int32_t *sorted_ids) {
+  if (V <= 0 || K <= 0 || !counts || !idx || !codoc || !doc_stats || !clogc || !topic_scores) return GGS_ERR_BAD_ARG;
+  int rc = td_check_args(nullptr, V, K, n_words, idx);
+  if (rc) return rc;
+  if ((int64_t)V * K > ((int64_t)1 << 31) - 256) return GGS_ERR_UNSUPPORTED;
+  for (size_t i = 0; i < (size_t)V * K; ++i)
+    if (counts[i] < 0) return GGS_ERR_BAD_ARG;
+  if (hipSetDevice(device_id) != hipSuccess) return GGS_ERR_BAD_ARG;
+  TmpDev t;
+  const TdScorePlan q(V, K, n_words);
+  const size_t kv = (size_t)V * K;
+  char *work = static_cast<char *>(t.get(q.bytes));
+  auto *dcnt = static_cast<int32_t *>(t.get(kv * 4));
+  if (!work || !dcnt) return GGS_ERR_HIP;
+  if (hipMemcpy(dcnt, counts, kv * 4, hipMemcpyHostToDevice) != hipSuccess) return GGS_ERR_HIP;
+  if (td_score_launch(nullptr, q, work, dcnt, K, beta, idx, codoc, doc_stats, clogc, word_scores != nullptr, nullptr) != hipSuccess) return GGS_ERR_HIP;
+  auto fetch = [&](void *dst, const void *src, size_t bytes) { return !dst || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+  if (!fetch(topic_scores, work + q.ts, 8 * (size_t)kTdScoreRows * K) || !fetch(word_scores, work + q.ws, 8 * (size_t)kTdWordRows * K * n_words) ||
+      !fetch(sorted_ids, work + q.head, 4 * (size_t)K * n_words))
     return GGS_ERR_HIP;
   return GGS_OK;
 }

@@ -264,3 +264,21 @@ def write_top_words(rows, fn):
     """TopWords.txt / RelevanceWords.txt as the driver writes them (tui/ParallelLDA.java:272-296): println of the CSV."""
     with open(fn, "w", newline="") as f:
         f.write(format_top_words_csv(rows) + os.linesep)
+
+
+def format_topic_diagnostics_csv(names, columns):
+    """TopicModelDiagnosticsPlain.topicsToCsv (:576-605): the header ``Topic,`` and the names joined by ``,``; per topic ``%d,``
+    and the ``%.4f`` scores joined by ``,``; every line ends in ``\n``.  columns[i][k]: the score names[i] of topic k."""
+    columns = [list(c) for c in columns]
+    if len(columns) != len(names) or len({len(c) for c in columns}) > 1:
+        raise ValueError("one column of K scores per name")
+    out = ["Topic," + ",".join(names) + "\n"]
+    for k in range(len(columns[0]) if columns else 0):
+        out.append("%d," % k + ",".join(java_format_fixed(c[k], 4) for c in columns) + "\n")
+    return "".join(out)
+
+
+def write_topic_diagnostics(names, columns, fn):
+    """The save_doc_topic_diagnostics file as the driver writes it (tui/ParallelLDA.java:218-225): println of the CSV."""
+    with open(fn, "w", newline="") as f:
+        f.write(format_topic_diagnostics_csv(names, columns) + os.linesep)

@@ -20,6 +20,11 @@ PURPOSE_Z, PURPOSE_THETA, PURPOSE_PHI, PURPOSE_INIT_PHI = 1, 2, 3, 4
 # the rankings of ggs_top_words (GGS_TOP_*), and its cap on the words per topic (GGS_TOP_WORDS_MAX)
 TOP_KINDS = {"top": 0, "relevance": 1, "distinctive": 2, "salient": 3, "k1": 4}
 TOP_WORDS_MAX = 128
+# the columns of TopicModelDiagnosticsPlain.topicsToCsv in its order; ggs_topic_scores' rows are these without word-length
+TOPIC_DIAGNOSTIC_NAMES = ("tokens", "document_entropy", "word-length", "coherence", "uniform_dist", "corpus_dist", "eff_num_words", "token-doc-diff",
+                          "rank_1_docs", "allocation_ratio", "allocation_count")
+TOPIC_SCORE_ROWS = tuple(x for x in TOPIC_DIAGNOSTIC_NAMES if x != "word-length")
+TOPIC_WORD_SCORE_ROWS = ("coherence", "uniform_dist", "corpus_dist", "token-doc-diff")
 
 
 class GGSError(RuntimeError):
@@ -82,6 +87,33 @@ def _top_kind(kind):
             raise ValueError("kind must be one of %s" % ", ".join(TOP_KINDS))
         return TOP_KINDS[kind]
     return int(kind)
+
+
+class TopicDiagnostics:
+    """What `new TopicModelDiagnosticsPlain(model, n)` holds (topics/TopicModelDiagnosticsPlain.java): ``names`` (the columns of
+    topicsToCsv in its order), ``scores[name]`` ([K] doubles), ``word_scores[name]`` ([K][n], for coherence, uniform_dist,
+    corpus_dist, token-doc-diff and -- with an alphabet -- word-length), ``idx`` ([K][n] top word ids), the document statistics
+    ``codoc`` / ``doc_stats`` / ``clogc``.  word-length needs the words themselves: without an alphabet that column is left out
+    of ``names`` (and of the CSV) instead of being filled with NaNs."""
+
+    def __init__(self, idx, codoc, doc_stats, clogc, topic_scores, word_scores, alphabet=None):
+        self.idx, self.codoc, self.doc_stats, self.clogc = idx, codoc, doc_stats, clogc
+        self.n = idx.shape[1]
+        self.scores = dict(zip(TOPIC_SCORE_ROWS, topic_scores))
+        self.word_scores = dict(zip(TOPIC_WORD_SCORE_ROWS, word_scores)) if word_scores is not None else {}
+        if alphabet is not None:                                  # getWordLengthScores (:399-418): String.length() is UTF-16 code units
+            lengths = np.array([[len(alphabet[i].encode("utf-16-le")) // 2 for i in row] for row in idx.tolist()], np.float64)
+            self.word_scores["word-length"] = lengths
+            self.scores["word-length"] = np.array([float(int(r.sum())) for r in lengths]) / float(self.n)
+        self.names = tuple(x for x in TOPIC_DIAGNOSTIC_NAMES if x in self.scores)
+
+    def codocument_matrix(self, k):
+        """getCodocumentMatrix(topic): [n][n], the diagonal = documents with the word under the topic"""
+        return self.codoc[k]
+
+    def topics_to_csv(self):
+        from . import formats
+        return formats.format_topic_diagnostics_csv(self.names, [self.scores[x] for x in self.names])
 
 
 class GGSHandle:
@@ -402,6 +434,53 @@ class GGSHandle:
         self._chk(self._L.ggs_debug_top_words_phases(self._h, _top_kind(kind), int(n), float(lam), int(bool(element_chain)), _dp(ms)))
         return dict(zip(("mass_k", "total", "words", "select_merge"), ms.tolist()))
 
+    def topic_doc_statistics(self, n, idx=None, clogc_in=None):
+        """collectDocumentStatistics of TopicModelDiagnosticsPlain over THIS handle's documents (ggs_topic_doc_statistics):
+        (codoc [K][n][n] int32, doc_stats [K][9] int32 = nonzero, rank1, at_prop[7], clogc [K]).  idx [K][n]: the corpus-wide top
+        words (default: this handle's own top_words("top", n)); clogc_in: the chain value the shards before this one left."""
+        n = int(n)
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, np.int32)
+            if idx.shape != (self.K, n):
+                raise ValueError("idx must be [K][n]")
+        if clogc_in is not None:
+            clogc_in = np.ascontiguousarray(clogc_in, np.float64)
+            if clogc_in.shape != (self.K,):
+                raise ValueError("clogc_in must be [K]")
+        m = max(n, 0)
+        codoc, stats, clogc = np.empty((self.K, m, m), np.int32), np.empty((self.K, 9), np.int32), np.empty(self.K, np.float64)
+        self._chk(self._L.ggs_topic_doc_statistics(self._h, n, _ip(idx) if idx is not None else None, _dp(clogc_in) if clogc_in is not None else None,
+                                                   _ip(codoc), _ip(stats), _dp(clogc)))
+        return codoc, stats, clogc
+
+    def topic_scores(self, n, idx, codoc, doc_stats, clogc, word_scores=False):
+        """The topic scores from the corpus-wide counts and the (summed) document statistics (ggs_topic_scores): [10][K] in
+        TOPIC_SCORE_ROWS' order; word_scores=True: (that, [4][K][n] in TOPIC_WORD_SCORE_ROWS' order)."""
+        n = int(n)
+        m = max(n, 0)
+        idx, codoc = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(codoc, np.int32)
+        doc_stats, clogc = np.ascontiguousarray(doc_stats, np.int32), np.ascontiguousarray(clogc, np.float64)
+        if idx.shape != (self.K, m) or codoc.shape != (self.K, m, m) or doc_stats.shape != (self.K, 9) or clogc.shape != (self.K,):
+            raise ValueError("idx [K][n], codoc [K][n][n], doc_stats [K][9], clogc [K]")
+        ts = np.empty((len(TOPIC_SCORE_ROWS), self.K), np.float64)
+        ws = np.empty((len(TOPIC_WORD_SCORE_ROWS), self.K, m), np.float64) if word_scores else None
+        self._chk(self._L.ggs_topic_scores(self._h, n, _ip(idx), _ip(codoc), _ip(doc_stats), _dp(clogc), _dp(ts), _dp(ws) if word_scores else None))
+        return (ts, ws) if word_scores else ts
+
+    def topic_diagnostics(self, n, alphabet=None):
+        """TopicModelDiagnosticsPlain(model, n) of a one-handle run: top words, document statistics, scores -> TopicDiagnostics.
+        alphabet (the words by id) adds the word-length column; without it that column is left out."""
+        idx = self.top_words("top", n)
+        codoc, stats, clogc = self.topic_doc_statistics(n, idx)
+        ts, ws = self.topic_scores(n, idx, codoc, stats, clogc, word_scores=True)
+        return TopicDiagnostics(idx, codoc, stats, clogc, ts, ws, alphabet)
+
+    def topic_diagnostics_phases(self, n):
+        """Device milliseconds of topic_doc_statistics + topic_scores by phase (ggs_debug_topic_diagnostics_phases)."""
+        ms = np.zeros(7, np.float64)
+        self._chk(self._L.ggs_debug_topic_diagnostics_phases(self._h, int(n), _dp(ms)))
+        return dict(zip(("membership", "document_pass", "column_statistics", "clogc_chain", "totals", "sort_and_sorted_chains", "small_scores"), ms.tolist()))
+
     def set_test_corpus(self, doc_ptr, tokens, doc_base=0):
         """addTestInstances (MSLDA:918-923): the held-out estimator's test set; ids >= num_types are out of vocabulary."""
         doc_ptr = np.ascontiguousarray(doc_ptr, np.int64)
@@ -671,3 +750,42 @@ def debug_topic_summaries(counts, beta, kind, n, lam=0.6, device_id=0):
     if rc:
         raise GGSError(rc, "ggs_debug_topic_summaries")
     return {"idx": idx, "score": score, "mass_k": mass, "rowsum_w": rowsum, "total": float(total[0]), "all_scores": every}
+
+
+def debug_topic_doc_statistics(doc_ptr, tokens, z, V, K, alpha, n, idx, clogc_in=None, device_id=0):
+    """The document-statistics kernels on an arbitrary corpus and assignment (ggs_debug_topic_doc_statistics):
+    (codoc [K][n][n], doc_stats [K][9], clogc [K])."""
+    L = _lib.load()
+    doc_ptr, tokens, z = np.ascontiguousarray(doc_ptr, np.int64), np.ascontiguousarray(tokens, np.int32), np.ascontiguousarray(z, np.int32)
+    alpha = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, np.float64), (K,)))
+    idx = np.ascontiguousarray(idx, np.int32)
+    n = int(n)
+    if idx.shape != (K, max(n, 0)) or len(tokens) != len(z) or len(tokens) != int(doc_ptr[-1]):
+        raise ValueError("idx must be [K][n], tokens and z as long as doc_ptr says")
+    clogc_in = None if clogc_in is None else np.ascontiguousarray(clogc_in, np.float64)
+    m = max(n, 0)
+    codoc, stats, clogc = np.empty((K, m, m), np.int32), np.empty((K, 9), np.int32), np.empty(K, np.float64)
+    rc = L.ggs_debug_topic_doc_statistics(device_id, len(doc_ptr) - 1, _lp(doc_ptr), _ip(tokens), _ip(z), int(V), int(K), _dp(alpha), n,
+                                          _ip(idx), _dp(clogc_in) if clogc_in is not None else None, _ip(codoc), _ip(stats), _dp(clogc))
+    if rc:
+        raise GGSError(rc, "ggs_debug_topic_doc_statistics")
+    return codoc, stats, clogc
+
+
+def debug_topic_scores(counts, beta, n, idx, codoc, doc_stats, clogc, device_id=0):
+    """The topic-score kernels on an arbitrary count matrix [V][K] (ggs_debug_topic_scores): (topic_scores [10][K],
+    word_scores [4][K][n], sorted_ids [K][n])."""
+    L = _lib.load()
+    counts = np.ascontiguousarray(counts, np.int32)
+    V, K = counts.shape
+    n = int(n)
+    m = max(n, 0)
+    idx, codoc = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(codoc, np.int32)
+    doc_stats, clogc = np.ascontiguousarray(doc_stats, np.int32), np.ascontiguousarray(clogc, np.float64)
+    if idx.shape != (K, m) or codoc.shape != (K, m, m) or doc_stats.shape != (K, 9) or clogc.shape != (K,):
+        raise ValueError("idx [K][n], codoc [K][n][n], doc_stats [K][9], clogc [K]")
+    ts, ws, head = np.empty((len(TOPIC_SCORE_ROWS), K), np.float64), np.empty((len(TOPIC_WORD_SCORE_ROWS), K, m), np.float64), np.empty((K, m), np.int32)
+    rc = L.ggs_debug_topic_scores(device_id, V, K, _ip(counts), float(beta), n, _ip(idx), _ip(codoc), _ip(doc_stats), _dp(clogc), _dp(ts), _dp(ws), _ip(head))
+    if rc:
+        raise GGSError(rc, "ggs_debug_topic_scores")
+    return ts, ws, head

@@ -48,6 +48,8 @@ class SimpleLDAConfiguration:
         self.compute_doc_topic_distances = bool(kw.pop("compute_doc_topic_distances", False))   # COMPUTE_DOC_TOPIC_DISTANCES_DEFAULT; min_doc_distances.csv / min_topic_distances.csv from start_diagnostic on, UPLDA:723-753,778-806
         self.nr_top_words = int(kw.pop("nr_top_words", 20))                   # NO_TOP_WORDS_DEFAULT (LDAConfiguration.java:38): the words per topic of TopWords.txt / RelevanceWords.txt
         self.lambda_ = float(kw.pop("lambda", 0.6))                           # LAMBDA_DEFAULT (LDAConfiguration.java:41), the relevance weight; `lambda` is a Python keyword: pass **{"lambda": x}
+        self.save_doc_topic_diagnostics = bool(kw.pop("save_doc_topic_diagnostics", False))   # ParsedLDAConfiguration.java:324-327: the driver writes TopicModelDiagnosticsPlain.topicsToCsv, tui/ParallelLDA.java:218-225
+        self.doc_topic_diagnostics_filename = kw.pop("doc_topic_diagnostics_filename", None)   # ParsedLDAConfiguration.java:330-332: its file name in the run directory (no default in Java either)
         self.log_topic_indicators = bool(kw.pop("log_topic_indicators", False))  # z_<iteration>.csv, UPLDA:637-638,871-872
         self.log_dir = kw.pop("log_dir", None)                       # where the files go (LoggingUtils' run directory in Java); None = no files
         if kw:
@@ -392,6 +394,18 @@ class LDAGroupedGibbsSampler:
     def getK1ReWeightedWords(self, n):
         """LDAUtils.getK1ReWeightedWords (:752-801; Song et al.'s keyword re-ranking)."""
         return self._top("k1", n)
+
+    def getTopicModelDiagnostics(self, n=None):
+        """new TopicModelDiagnosticsPlain(model, n) on the device-resident z and counts (ggs_topic_doc_statistics,
+        ggs_topic_scores): native.TopicDiagnostics with the eleven scores per topic, the word scores, the codocument matrices
+        and topics_to_csv().  n: the configuration's nr_top_words unless given.  Unlike the Java (which reads word 0 for the
+        positions beyond the vocabulary), n > V is refused: the driver clamps first."""
+        self._need_data()
+        n = int(getattr(self.config, "nr_top_words", 20) if n is None else n)
+        V = self._corpus.num_types
+        if n > V:
+            raise ValueError("Asked for more words (%d) than there are types (unique words = noTypes = %d)." % (n, V))
+        return self._h.topic_diagnostics(n, self._corpus.vocab)
 
     def getBeta(self):
         return self.beta

@@ -154,6 +154,33 @@ class ShardedGGS:
             out = np.minimum(out, self.engine.min_doc_distances(blk))
         return out
 
+    def topic_diagnostics(self, n, alphabet=None, gather=None):
+        """TopicModelDiagnosticsPlain of a doc-sharded run, on every rank (a collective call).  The top words come from the
+        corpus-wide counts, the same on every rank.  The clogc chain is ONE rounding chain per topic over all documents in
+        index order, so the ranks take their documents' statistics in rank order: in round r rank r runs
+        engine.topic_doc_statistics from the chain value rank r - 1 left, and the ranks gather it (``gather`` as for
+        heldout_log_likelihood).  The integers are added (exact in any order).  Bit-identical to one handle over the whole
+        corpus."""
+        from .native import TopicDiagnostics
+        if gather is None:
+            import torch.distributed as dist
+
+            def gather(a):
+                res = [None] * self.world
+                dist.all_gather_object(res, a)
+                return res
+        idx = self.engine.top_words("top", n)
+        mine, chain = None, None
+        for r in range(self.world):
+            if self.rank == r:
+                mine = self.engine.topic_doc_statistics(n, idx, chain)
+            chain = np.asarray(gather(mine[2] if mine is not None else None)[r], np.float64)
+        parts = gather(mine[:2])
+        codoc = np.sum([np.asarray(p[0], np.int64) for p in parts], axis=0).astype(np.int32)
+        stats = np.sum([np.asarray(p[1], np.int64) for p in parts], axis=0).astype(np.int32)
+        ts, ws = self.engine.topic_scores(n, idx, codoc, stats, chain, word_scores=True)
+        return TopicDiagnostics(idx, codoc, stats, chain, ts, ws, alphabet)
+
     def sweep(self, n=1):
         """n sweeps, one count exchange each; only the last one is waited for (device-side error flags are sticky)."""
         end_async = getattr(self.engine, "sweep_end_async", self.engine.sweep_end)
