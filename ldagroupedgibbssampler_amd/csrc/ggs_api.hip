@@ -47,10 +47,18 @@ const char *debug_env(const char *name) {
   static const bool enabled = [] { const char *e = std::getenv("GGS_DEBUG"); return e && std::atoi(e) == 1; }();
   return enabled ? std::getenv(name) : nullptr;
 }
+// A size that a test may shrink: the knob's value clamped to [1, built_in], the built-in constant without it.  Read at every
+// call, as GGS_DEBUG_HELDOUT_CELLS is: pieces, groups and bands only get smaller, no result changes.
+int64_t debug_shrunk(const char *name, int64_t built_in) {
+  const char *e = debug_env(name);
+  return e ? std::max<int64_t>(1, std::min<int64_t>(built_in, std::atoll(e))) : built_in;
+}
 
 // The knobs ggs_create reads, all at its top: what the launch planner takes instead of an environment, and the handle's
 // own switches.  (The knobs of other entry points are read there: the exchange's at its set-up, GGS_DEBUG_SPALIAS_WPC at
-// ggs_set_corpus, GGS_DEBUG_PHICOLS at a Phi draw, GGS_DEBUG_HELDOUT_CELLS at every held-out call.)
+// ggs_set_corpus, GGS_DEBUG_PHICOLS at a Phi draw, GGS_DEBUG_HELDOUT_CELLS at every held-out call, GGS_DEBUG_TD_PIECE_BYTES
+// at every topic-diagnostics call, GGS_DEBUG_DIST_PIECE_BYTES and GGS_DEBUG_DIST_BAND_TILES at every distance call: the last
+// three through debug_shrunk, which can only make a piece, a group or a band smaller.)
 struct Knob {
   bool set = false;
   int v = 0;
@@ -2930,8 +2938,11 @@ int ggs_log_posterior(ggs_handle *h, double *doc_side, double *topic_side) {
 }
 // ---- min document / topic distances (csrc/ggs_distances.hpp) ---------------------------------------------------------------
 namespace {
-// One launch covers at most 2^30 tiles: bands of whole tile rows.
-int64_t dist_band_rows(int64_t tiles_b) { return std::max<int64_t>(1, ((int64_t)1 << 30) / std::max<int64_t>(tiles_b, 1)); }
+// One launch covers at most 2^30 tiles (GGS_DEBUG_DIST_BAND_TILES: fewer): bands of whole tile rows.
+constexpr int64_t kDistBandTiles = (int64_t)1 << 30;
+int64_t dist_band_rows(int64_t tiles_b) {
+  return std::max<int64_t>(1, debug_shrunk("GGS_DEBUG_DIST_BAND_TILES", kDistBandTiles) / std::max<int64_t>(tiles_b, 1));
+}
 // min_bits[n] (preset by the caller) <- the minimal sums of the rows of A [n][len] over the rows of B [m][len]; B == A with diag
 void launch_min_row_dist(hipStream_t st, const double *A, int64_t n, const double *B, int64_t m, int64_t len, bool diag, unsigned long long *min_bits) {
   if (n <= 0 || m <= 0) return;
@@ -2949,6 +2960,7 @@ void launch_min_topic_dist(hipStream_t st, const double *A, int64_t n, int64_t p
     hipLaunchKernelGGL(min_topic_dist_kernel, dim3((unsigned)(std::min(band, ta - t0) * ta)), dim3(kDistBlock), 0, st, A, n, pitch, len, t0 * ta, ta, min_bits);
 }
 constexpr size_t kDistPieceBytes = (size_t)64 << 20;   // a foreign block travels to scratch in pieces of at most this
+size_t dist_piece_bytes() { return (size_t)debug_shrunk("GGS_DEBUG_DIST_PIECE_BYTES", (int64_t)kDistPieceBytes); }   // tests: several pieces
 }  // namespace
 
 int ggs_min_doc_distances(ggs_handle *h, const double *other, int64_t n_other, double *min_dist) {
@@ -2965,7 +2977,7 @@ int ggs_min_doc_distances(ggs_handle *h, const double *other, int64_t n_other, d
     // calls redraw the same bits (the stream GGS_PURPOSE_THETA at the current iteration), as ggs_log_posterior does
     if ((rc = drop_theta_ahead(h)) || (rc = launch_theta(h, h->stream, h->d_theta, h->iteration))) return rc;
   }
-  const int64_t piece_rows = other ? std::max<int64_t>(1, std::min<int64_t>(n_other, (int64_t)(kDistPieceBytes / (sizeof(double) * (size_t)K)))) : 0;
+  const int64_t piece_rows = other ? std::max<int64_t>(1, std::min<int64_t>(n_other, (int64_t)(dist_piece_bytes() / (sizeof(double) * (size_t)K)))) : 0;
   const size_t head = sizeof(double) * 2 * (size_t)D;     // [D] minimal sums as bit patterns, [D] distances
   if ((rc = ensure_scratch(h, head + sizeof(double) * (size_t)piece_rows * (size_t)K))) return rc;
   auto *d_bits = static_cast<unsigned long long *>(h->d_scratch);
@@ -3108,6 +3120,8 @@ int ggs_debug_top_words_phases(ggs_handle *h, int32_t kind, int32_t n_words, dou
 // ---- topic diagnostics (csrc/ggs_topic_diagnostics.hpp) ---------------------------------------------------------------------
 namespace {
 constexpr size_t kTdPieceBytes = (size_t)64 << 20;     // the dense rows of a piece of documents / the sort buffers of a group of topics
+// what both planners below size by, wherever they are constructed (a handle's call or its ggs_debug_* twin)
+size_t td_piece_bytes() { return (size_t)debug_shrunk("GGS_DEBUG_TD_PIECE_BYTES", (int64_t)kTdPieceBytes); }   // tests: several pieces / groups
 // events between the phases of a call (ggs_debug_topic_diagnostics_phases); without it, nothing is recorded
 struct TdTimer {
   hipStream_t st;
@@ -3152,7 +3166,7 @@ struct TdDocPlan {
   size_t mem_ptr = 0, mem = 0, codoc = 0, stats = 0, clogc = 0, maxtopic = 0, crow = 0, addend = 0, bytes = 0;
   TdDocPlan(int64_t D_, int32_t V_, int32_t K_, int32_t n_) : D(D_), V(V_), K(K_), n(n_) {
     // a piece's dense rows (4 + 8 bytes per cell) stay within kTdPieceBytes, but hold at least one wave's 256 documents
-    piece = (int64_t)(kTdPieceBytes / (12 * (size_t)K)) / kTdSegDocs * kTdSegDocs;
+    piece = (int64_t)(td_piece_bytes() / (12 * (size_t)K)) / kTdSegDocs * kTdSegDocs;
     piece = std::max<int64_t>(piece, kTdSegDocs);
     piece = std::min<int64_t>(piece, std::max<int64_t>(D, 1));
     size_t at = 0;
@@ -3215,7 +3229,7 @@ struct TdScorePlan {
   int32_t V = 0, K = 0, n = 0, group = 0;
   size_t n_k = 0, wtc = 0, idx = 0, codoc = 0, stats = 0, clogc = 0, head = 0, ts = 0, ws = 0, key_a = 0, id_a = 0, key_b = 0, id_b = 0, bytes = 0;
   TdScorePlan(int32_t V_, int32_t K_, int32_t n_) : V(V_), K(K_), n(n_) {
-    group = (int32_t)std::min<size_t>((size_t)K, std::max<size_t>(1, kTdPieceBytes / (16 * (size_t)V)));   // the sort's four [group][V] buffers within kTdPieceBytes
+    group = (int32_t)std::min<size_t>((size_t)K, std::max<size_t>(1, td_piece_bytes() / (16 * (size_t)V)));   // the sort's four [group][V] buffers within kTdPieceBytes
     size_t at = 0;
     auto take = [&](size_t b) { const size_t o = at; at += (b + 255) & ~(size_t)255; return o; };
     n_k = take(4 * (size_t)K); wtc = take(4 * (size_t)V); idx = take(4 * (size_t)K * n); codoc = take(4 * (size_t)K * n * n); stats = take(4 * (size_t)K * kTdStats);

@@ -13,6 +13,9 @@ of `waves` waves, an item per wave and trip.  per_cu is what the plan allows at 
   CAP_ALIAS     16   alias_build_kernel, alias_words_per_block(K) words per workgroup and trip (:1129, ggs_alias.hpp:39)
   CAP_POISSON    2   phi_poisson_kernel: tiles of rows_per_tile rows, two workgroups per CU (:738-741)
   CAP_SLICED     1   the ggs score-register kernels: one workgroup of SLICED_WAVES = 4 waves per CU (:1036-1039)
+  CAP_VSBITS    32   vs_bits_kernel (nzvsspalias): a wave per 32-cell word of 64 topics (plan_launches, pl.vsbits)
+  CAP_WORDMASK   8   word_list_mask_kernel (nzvsspalias): as word_list_build_kernel, a word per wave (pl.wordmask)
+nzvs_wave_kernel takes CAP_WAVE like the other sparse walks (resident_waves_per_cu: 32 at most).
 
 A plan may give fewer than the cap (LDS, registers), never more: a bound computed with the cap holds for the real grid."""
 import numpy as np
@@ -20,6 +23,7 @@ import numpy as np
 from ldagroupedgibbssampler_amd.corpus import Corpus
 
 CAP_WAVE, CAP_LANE, CAP_WORDLIST, CAP_ALIAS, CAP_POISSON, CAP_SLICED = 32, 8, 8, 16, 2, 1
+CAP_VSBITS, CAP_WORDMASK = 32, 8
 WORDLIST_WAVES, SLICED_WAVES = 4, 4
 POISSON_THREADS = 1024                  # kPoissonThreads (ggs_phi_poisson.hpp:23)
 KNOB = "GGS_DEBUG_NUM_CUS"
@@ -43,6 +47,10 @@ def alias_words_per_block(K):
 
 def alias_items(V, K):
     return -(-V // alias_words_per_block(K))                      # launch_alias_build, ggs_api.hip:859
+
+
+def vs_bits_items(V, K):
+    return -(-V // 32) * -(-K // 64)                               # launch_vs_chain: vs_W words x ceil(Ks / 64) (ggs_api.hip)
 
 
 def poisson_tiles(V, K, cus):

@@ -18,7 +18,11 @@ enough for a second item, so:
 The Phi-phase kernels are covered through handles only (ggs_debug_alias has a fixed grid of its own and ggs_debug_poisson
 runs debug_poisson_kernel, a thread per draw): alias_build_kernel by the K = 1024 rows (4 words per workgroup and trip,
 V = 210: 53 trips over at most 16 workgroups, the last one of 2 words), word_list_build_kernel by the polyaurn_sparse rows,
-phi_poisson_kernel by the polyaurn and polyaurn_sparse rows; each of those rows writes the inequality out from V and K."""
+phi_poisson_kernel by the polyaurn and polyaurn_sparse rows; each of those rows writes the inequality out from V and K.
+nzvsspalias' two persistent Phi-phase kernels, vs_bits_kernel and word_list_mask_kernel, go through launch() with the handle's
+CU count like its z kernel (ggs_api.hip: launch_vs_chain and the list build behind the alias tables): the K = 130 row gives
+each of the three at least three trips on one CU, the last one ragged (the z kernel's 200 documents come as the padded
+two-round order of 384 entries there: its last round is ragged by the entries that hold no document)."""
 import os
 import threading
 
@@ -29,6 +33,7 @@ from ldagroupedgibbssampler_amd import priors
 from ldagroupedgibbssampler_amd.corpus import even_split
 from ldagroupedgibbssampler_amd.sharded import java_lcg_initial_z
 from tests import lightpclda_restatement as LR
+from tests import nzvs_restatement as NR
 from tests import persistent_grid as PG
 from tests import polyaurn_restatement as PR
 from tests import polyaurn_sparse_restatement as PSR
@@ -41,7 +46,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PRIORS_FILE = os.path.join(ROOT, "tests", "golden", "priors", "topic_priors_SmallTexts.txt")
 SEED, ZSEED, ALPHA, BETA, SWEEPS = 777, 5, 0.1, 0.01, 2
-ALIAS_SCHEMES = ("spalias", "spalias_priors", "lightpclda", "polyaurn_sparse")
+ALIAS_SCHEMES = ("spalias", "spalias_priors", "lightpclda", "polyaurn_sparse", "nzvsspalias")
 ORACLE_SCHEMES = ("ggs", "pcgs", "collapsed")
 
 
@@ -78,6 +83,10 @@ ROWS = [
     Row("lightpclda", 100, "wave", 210, "lightpc_wave_kernel", PG.CAP_WAVE),
     Row("polyaurn_sparse", 8, "wave", 800, "polyaurn_sparse_wave_kernel", PG.CAP_WAVE, phases=("poisson", "wordlist")),
     Row("polyaurn_sparse", 160, "wave", 210, "polyaurn_sparse_wave_kernel", PG.CAP_WAVE, phases=("poisson", "wordlist")),
+    # nzvsspalias: the z kernel on the wave corpus (K = 8: tokens without a candidate draw from the alias table); K = 130 and
+    # V = 1030: 33 x 3 = 99 items of vs_bits_kernel on 32 workgroups, 258 groups of four words on 8 workgroups of word_list_mask_kernel
+    Row("nzvsspalias", 8, "wave", 210, "nzvs_wave_kernel", PG.CAP_WAVE, phases=("no candidate",)),
+    Row("nzvsspalias", 130, "wave", 1030, "nzvs_wave_kernel", PG.CAP_WAVE, phases=("vsbits", "wordmask", "ragged z")),
     # ggs is bit-compared at size elsewhere; these pin the knob.  The score-register kernels run one workgroup of four waves
     # per CU over up to three chunk lists (cold, hot, warm): the count asked of num_chunks is per list
     Row("ggs", 100, "wave", 210, "z_sliced_kernel", PG.CAP_SLICED, dict(SLICED, GGS_DEBUG_SPLIT="0"), waves=PG.SLICED_WAVES, lists=3, form="fused"),
@@ -95,11 +104,12 @@ MARGIN_ROWS = [r.id for r in ROWS if (r.scheme, r.K) in (("spalias", 8), ("polya
 
 def flags_of(native, scheme):
     return {"ggs": 0, "pcgs": native.FLAG_PCGS, "collapsed": native.FLAG_COLLAPSED, "polyaurn": native.FLAG_POLYAURN, "spalias": native.FLAG_SPALIAS,
-            "spalias_priors": native.FLAG_SPALIAS, "lightpclda": native.FLAG_LIGHTPCLDA, "polyaurn_sparse": native.FLAG_POLYAURN_SPARSE}[scheme]
+            "spalias_priors": native.FLAG_SPALIAS, "lightpclda": native.FLAG_LIGHTPCLDA, "polyaurn_sparse": native.FLAG_POLYAURN_SPARSE,
+            "nzvsspalias": native.FLAG_NZVSSPALIAS}[scheme]
 
 
 def has_mean(scheme):
-    return scheme != "collapsed"                                    # counts only: Phi is a point estimate of them
+    return scheme not in ("collapsed", "nzvsspalias")               # counts only: Phi is a point estimate of them; nzvsspalias keeps no mean
 
 
 _corpora = {}
@@ -152,9 +162,11 @@ def snapshot(g, scheme, mean=True):
         s["priors"] = g.get_topic_priors()
     if scheme == "lightpclda":
         s["mh_stats"] = np.asarray(g.mh_stats(), np.int64)
-    if scheme == "polyaurn_sparse":
+    if scheme in ("polyaurn_sparse", "nzvsspalias"):
         s["nw"], s["word lists"] = g.word_topic_lists()
         s["sparse_stats"] = np.asarray(g.sparse_stats(), np.int64)
+    if scheme == "nzvsspalias":
+        s["vs_stats"] = np.asarray(g.vs_stats(), np.int64)[:2]      # undrawn cells of the last draw, zero cells of Phi
     if mean and has_mean(scheme):
         s["phi mean"], n = g.get_phi_mean()
         s["phi mean samples"] = np.array([n], np.int64)
@@ -187,8 +199,18 @@ def device_run(native, monkeypatch, row, cus, margin=None, trips=True):
             PG.assert_trips(row.V, cus, PG.CAP_WORDLIST, "word_list_build_kernel", waves=PG.WORDLIST_WAVES)
         if "poisson" in row.phases:
             PG.assert_trips(PG.poisson_tiles(row.V, row.K, cus), cus, PG.CAP_POISSON, "phi_poisson_kernel")
+        if "vsbits" in row.phases:                                  # ceil(V / 32) words of 32 cells x ceil(K / 64) waves of topics
+            PG.assert_trips(PG.vs_bits_items(row.V, row.K), cus, PG.CAP_VSBITS, "vs_bits_kernel")
+            assert PG.vs_bits_items(row.V, row.K) == -(-row.V // 32) * -(-row.K // 64) and PG.vs_bits_items(row.V, row.K) % (cus * PG.CAP_VSBITS) != 0
+        if "wordmask" in row.phases:                                # a word per wave, four waves a workgroup
+            PG.assert_trips(row.V, cus, PG.CAP_WORDMASK, "word_list_mask_kernel", waves=PG.WORDLIST_WAVES)
+            assert -(-row.V // PG.WORDLIST_WAVES) % (cus * PG.CAP_WORDMASK) != 0 and row.V % PG.WORDLIST_WAVES != 0
+        if "ragged z" in row.phases:                                # the last round is not full: by its count, or by the padded order's -1 entries
+            assert info["num_chunks"] % (cus * row.cap) != 0 or info["num_chunks"] > c.num_docs, info
     g.sweep(SWEEPS)
     s = snapshot(g, row.scheme)
+    if "no candidate" in row.phases:                                # the first sweep draws every token from the alias tables (no list yet); the second some
+        assert c.num_tokens < s["sparse_stats"][2] < 2 * c.num_tokens and s["sparse_stats"][:2].sum() > 0, s["sparse_stats"]
     g.check_invariants()
     g.close()
     return s
@@ -234,6 +256,8 @@ def authority(oracle, row):
             m = LR.Model(K, V, ALPHA, BETA, SEED, c.doc_ptr, c.tokens, z0, **mean)
         elif row.scheme == "polyaurn":
             m = PR.Model(K, V, ALPHA, BETA, SEED, c.doc_ptr, c.tokens, z0, **mean)
+        elif row.scheme == "nzvsspalias":
+            m = NR.Model(K, V, ALPHA, BETA, SEED, c.doc_ptr, c.tokens, z0)
         else:
             m = PSR.Model(K, V, ALPHA, BETA, SEED, c.doc_ptr, c.tokens, z0, **mean)
         m.init_phi()
@@ -250,11 +274,14 @@ def authority(oracle, row):
         if row.scheme == "lightpclda":
             s["mh_stats"] = np.asarray(m.stats, np.int64)
             assert_bit_equal(np.asarray(m.topic_totals(), np.int32), s["n_k"], "the restatement's own n_k")
-        if row.scheme == "polyaurn_sparse":
+        if row.scheme in ("polyaurn_sparse", "nzvsspalias"):
             s["nw"], s["word lists"], s["sparse_stats"] = m.nw, PSR.padded(m.lists, K), np.asarray(m.stats, np.int64)
-        pm = m.phi_mean()
-        s["phi mean"], n = pm if isinstance(pm, tuple) else (pm, m.n_sampled)
-        s["phi mean samples"] = np.array([n], np.int64)
+        if row.scheme == "nzvsspalias":
+            s["vs_stats"] = np.asarray(m.vs_stats_first_two(), np.int64)
+        if has_mean(row.scheme):
+            pm = m.phi_mean()
+            s["phi mean"], n = pm if isinstance(pm, tuple) else (pm, m.n_sampled)
+            s["phi mean samples"] = np.array([n], np.int64)
     assert int(s["phi mean samples"][0]) == 1 if has_mean(row.scheme) else True
     _authority[row.id] = s
     return s

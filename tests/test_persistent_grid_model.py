@@ -33,3 +33,11 @@ def test_trip_arithmetic():
             PG.assert_trips(r.V, 1, PG.CAP_WORDLIST, r.id, waves=PG.WORDLIST_WAVES)
         if "alias" in r.phases:
             PG.assert_trips(PG.alias_items(r.V, r.K), 1, PG.CAP_ALIAS, r.id)
+        if "vsbits" in r.phases:
+            PG.assert_trips(PG.vs_bits_items(r.V, r.K), 1, PG.CAP_VSBITS, r.id)
+            assert PG.vs_bits_items(r.V, r.K) % PG.CAP_VSBITS != 0    # a ragged last trip
+        if "wordmask" in r.phases:
+            PG.assert_trips(r.V, 1, PG.CAP_WORDMASK, r.id, waves=PG.WORDLIST_WAVES)
+            assert -(-r.V // PG.WORDLIST_WAVES) % PG.CAP_WORDMASK != 0
+    assert PG.vs_bits_items(1030, 130) == 99 and PG.vs_bits_items(210, 8) == 7 and PG.min_trips(99, 1, PG.CAP_VSBITS) == 4
+    assert sum("vsbits" in r.phases and "wordmask" in r.phases for r in T.ROWS) == 1
