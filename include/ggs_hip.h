@@ -290,6 +290,34 @@ int ggs_init_phi(ggs_handle *h);
 /* currentIteration (UPLDA:646); enters the RNG counters */
 int ggs_set_iteration(ggs_handle *h, int32_t iteration);
 int ggs_get_iteration(const ggs_handle *h, int32_t *iteration);
+/* ---- a handle with a history: resume, rewind, reuse --------------------------------------------------------------------
+ * The streams are keyed by (seed, iteration, purpose, element), so a chain is continued exactly from its EXPORTED STATE:
+ * z (ggs_get_z), Phi (ggs_get_phi) and the iteration number -- on a fresh handle of the same configuration (flags, alpha, beta,
+ * seed, alias_poisson_threshold, the topic priors, the variable-selection prior) and corpus, on the handle itself, or on the
+ * ranks of an exchange (each rank its slice of z, every rank the whole Phi): ggs_set_z(z, 0), ggs_set_phi, ggs_set_iteration,
+ * in any order, then sweeps.  The count-form schemes (collapsed, lightcollapsed, adlda) have no Phi: their state is z and the
+ * iteration number, and ggs_init_phi (tokensPerTopic; with an exchange the merge of the ranks' counts) follows ggs_set_z.
+ * theta is not state: it is drawn from z for the iteration at hand; one drawn ahead, beside the previous sweep's Phi draw,
+ * is used only by a z step of the iteration it was drawn for and is dropped by ggs_set_z, ggs_init_z_java_lcg and
+ * ggs_set_corpus.  What each call does to the rest of a handle that has run before:
+ *   the iteration number  is the caller's: only the sweeps (+1 each) and ggs_set_iteration change it.  ggs_set_corpus, ggs_set_z
+ *       and ggs_set_phi leave it: a second corpus goes on counting where the first stopped unless ggs_set_iteration is called.
+ *   the phi mean and n_sampled (GGS_FLAG_SAVE_PHI_MEAN)  belong to one corpus' chain on one handle: ggs_set_corpus zeroes both;
+ *       ggs_set_phi restarts the running sum while n_sampled keeps counting (UPLDA:1897-1902), so the mean reported after it is
+ *       (the Phi accepted since) / (all Phi accepted since ggs_set_corpus); ggs_set_z and ggs_set_iteration leave both.  A Phi is
+ *       accepted when phi_burn_in > 0, iteration > phi_burn_in and iteration % phi_mean_thin == 0, whatever came before.
+ *   the topic priors and the variable-selection prior  are configuration: they survive ggs_set_corpus, ggs_set_z and
+ *       ggs_set_iteration; they can be set (again) whenever the handle has no Phi, which after ggs_set_corpus it has not.
+ *   the cumulative counters (ggs_get_mh_stats, ggs_get_sparse_stats)  start at 0 at ggs_set_corpus and only grow: none of
+ *       ggs_set_z, ggs_set_phi, ggs_set_iteration resets them.  (ggs_get_vs_stats describes the last draw, see there.)
+ *   alias tables and the words' lists  follow every Phi, a set one included; nzvsspalias' lists are the drawn cells after a
+ *       sweep and the cells with phi != 0.0 after ggs_set_phi: the resumed chain is the exporting handle's exactly when no drawn
+ *       cell holds 0.0 (a gamma draw that underflowed: beta of 0.5 does not, beta of 0.001 does), otherwise a token may walk
+ *       the other list and the chains may part.
+ *   ggs_set_corpus  besides: no Phi and no sweep in progress, the global token count back to the handle's own, the z form
+ *       timed again, every table, list and launch geometry the new corpus'.  A run on a reused handle is, bit for bit and in
+ *       everything the getters return, the run of a fresh handle that was given the same iteration number.
+ * tests/test_handle_lifecycle_gpu.py pins each of these for every scheme. */
 
 /* ---- the sweep ------------------------------------------------------------- */
 /* replaces one loop body of sample() (UPLDA:645-687) n_sweeps times:

@@ -2154,6 +2154,9 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   if (!pcgs) HIP_TRY(h, hipMemset(h->d_theta_next, 0, sizeof(double) * std::max<size_t>((size_t)D * h->K, 1)));
   if (h->d_mh) HIP_TRY(h, hipMemset(h->d_mh, 0, 3 * sizeof(unsigned long long)));
   if (h->d_ps_stats) HIP_TRY(h, hipMemset(h->d_ps_stats, 0, 4 * sizeof(unsigned long long)));
+  // the phi mean is the mean over ONE corpus' chain, like the counters above: a sum that ran on into the next corpus' Phi would be neither's
+  if (h->d_phi_mean) HIP_TRY(h, hipMemset(h->d_phi_mean, 0, sizeof(double) * (size_t)h->K * h->V));
+  h->n_sampled_phi = 0;
   HIP_TRY(h, hipDeviceSynchronize());   // the uploads and memsets above ran on the null stream; the handle's stream may not synchronise with it
 
   // 5. a new corpus: no Phi, no sweep in progress, the z form to be timed again

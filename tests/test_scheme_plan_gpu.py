@@ -3,7 +3,8 @@ score-register kernels take (8) and one they do not (200), launch_info() names t
 that launch's dynamic LDS and work items -- for the pcgs family written out here from the layout functions beside the
 kernels (ggs_z_pcgs.hpp, ggs_z_pcgs_wave.hpp, ggs_z_spalias.hpp, ggs_z_lightpc.hpp) -- before a corpus, with one, and
 with a second one on the same handle; the sweeps run with GGS_FLAG_PARANOID.  The bits of the results are pinned by the
-parity, posterior and knife-edge files."""
+parity, posterior and knife-edge files; the bits of a REUSED handle -- a second and a third corpus against a fresh handle and
+the oracle, for every scheme -- by tests/test_handle_lifecycle_gpu.py."""
 import numpy as np
 import pytest
 
