@@ -287,7 +287,11 @@ int ggs_java_lcg_next_ints(int32_t seed, int32_t bound, int64_t n, int32_t *out)
 int ggs_set_z(ggs_handle *h, const int32_t *z /*N*/, int32_t redraw_phi);
 /* replaces: initialSamplePhi (UPLDA:1287-1294 -> MarsagliaSparseDirichlet.java:31-55) */
 int ggs_init_phi(ggs_handle *h);
-/* currentIteration (UPLDA:646); enters the RNG counters */
+/* currentIteration (UPLDA:646); enters the RNG counters as their fourth word.  Iterations are 0 ... INT32_MAX:
+ * ggs_set_iteration with a negative number returns GGS_ERR_BAD_ARG and leaves the handle as it was.  Every call that steps
+ * the iteration (ggs_sweep, ggs_sweep_begin, ggs_sample_z_given_phi, ggs_collapsed_serial_sweep, ggs_group_sweep) returns
+ * GGS_ERR_STATE, launches nothing and changes nothing when iteration + its number of steps would pass INT32_MAX -- a call
+ * of several sweeps is refused as a whole, not after the sweeps that still fit. */
 int ggs_set_iteration(ggs_handle *h, int32_t iteration);
 int ggs_get_iteration(const ggs_handle *h, int32_t *iteration);
 /* ---- a handle with a history: resume, rewind, reuse --------------------------------------------------------------------

@@ -1643,7 +1643,7 @@ int z_phase(ggs_handle *h) {
   }
   if (!h->hot_fork_from) h->hot_fork_from = E.e[1];        // the event just recorded serves as the hot chunks' fork: one packet less
   h->theta_ahead_iter = INT64_MIN;
-  const bool ahead = h->overlap_theta && h->side && h->D > 0;
+  const bool ahead = h->overlap_theta && h->side && h->D > 0 && h->iteration < INT32_MAX;   // there is no iteration behind the last
   const int32_t P = (int32_t)h->part_doc.size() - 1;   // 1 for a small corpus
   if (ahead && P > 1 && h->plan.stream()) {
     // part by part: z of part p on the main stream, then -- beside z of part p + 1 -- theta of iteration t+1 for the
@@ -2215,7 +2215,18 @@ int ggs_init_phi(ggs_handle *h) {
   return check_status(h);
 }
 
-int ggs_set_iteration(ggs_handle *h, int32_t it) { if (!h) return GGS_ERR_BAD_ARG; h->iteration = it; return GGS_OK; }   // a theta drawn ahead for another iteration is simply not used
+int ggs_set_iteration(ggs_handle *h, int32_t it) {     // a theta drawn ahead for another iteration is simply not used
+  if (!h) return GGS_ERR_BAD_ARG;
+  if (it < 0) return set_err(h, GGS_ERR_BAD_ARG, "the iteration number is 0 ... INT32_MAX");
+  h->iteration = it;
+  return GGS_OK;
+}
+// iterations are 0 ... INT32_MAX: a call whose steps would count past the end is refused as a whole, before anything is launched
+static int iteration_room(ggs_handle *h, int32_t steps) {
+  if (steps > 0 && (int64_t)h->iteration + (int64_t)steps > (int64_t)INT32_MAX)
+    return set_err(h, GGS_ERR_STATE, "the iteration number would pass INT32_MAX");
+  return GGS_OK;
+}
 int ggs_get_iteration(const ggs_handle *h, int32_t *it) { if (!h || !it) return GGS_ERR_BAD_ARG; *it = h->iteration; return GGS_OK; }
 
 // see theta_main: only where the z step is one launch pair (no parts), theta is drawn at all, no collective is in the chain, and
@@ -2229,6 +2240,7 @@ int ggs_sweep_begin(ggs_handle *h) {
   int rc = require_ready(h, true);
   if (rc) return rc;
   if (h->in_sweep) return set_err(h, GGS_ERR_STATE, "ggs_sweep_begin called twice without ggs_sweep_end");
+  if ((rc = iteration_room(h, 1))) return rc;
   h->iteration += 1;                                   // currentIteration = iteration, UPLDA:646
   h->chain_on_side = chain_on_side_ok(h);              // kept until the sweep's end
   if ((rc = z_phase(h))) { h->chain_on_side = false; return rc; }
@@ -2257,6 +2269,10 @@ int ggs_sweep_end_async(ggs_handle *h) {
 }
 
 int ggs_sweep(ggs_handle *h, int32_t n_sweeps) {
+  if (h && n_sweeps > 0) {                             // all n_sweeps or none
+    int rc = require_ready(h, true);
+    if (rc || (rc = iteration_room(h, n_sweeps))) return rc;
+  }
   for (int32_t i = 0; i < n_sweeps; ++i) {
     if (h) h->whole_sweep = true;
     int rc = ggs_sweep_begin(h);
@@ -2277,6 +2293,7 @@ int ggs_collapsed_serial_sweep(ggs_handle *h, int32_t java_seed, int32_t n_sweep
   if (h->xg || h->tok_base != 0) return set_err(h, GGS_ERR_STATE, "the serial chain runs over ONE unsharded corpus");
   if (h->in_sweep) return set_err(h, GGS_ERR_STATE, "inside a split sweep");
   if ((size_t)h->K * 16 > (size_t)kMaxLdsBytes) return set_err(h, GGS_ERR_UNSUPPORTED, "num_topics too large for the serial kernel's LDS");
+  if ((rc = iteration_room(h, n_sweeps))) return rc;
   if ((rc = launch_magnitude(h))) return rc;           // tokensPerTopic in step with the counts
   if (!h->lcg_ready) {                                 // new java.util.Random(seed): the scrambled initial state
     const uint64_t st = ((uint64_t)(int64_t)java_seed ^ 0x5DEECE66DULL) & ((1ULL << 48) - 1);
@@ -2301,6 +2318,7 @@ int ggs_sample_z_given_phi(ggs_handle *h, int32_t n_sweeps) {
   if (rc) return rc;
   if (h->in_sweep) return set_err(h, GGS_ERR_STATE, "inside a split sweep");
   if (count_form(h->scheme)) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=collapsed, scheme=lightcollapsed and scheme=adlda have no Phi to condition on");
+  if ((rc = iteration_room(h, n_sweeps))) return rc;
   for (int32_t i = 0; i < n_sweeps; ++i) {
     h->iteration += 1;                                 // UPLDA:980
     h->force_detail = true;
@@ -2579,6 +2597,8 @@ int ggs_group_set_z(ggs_handle **hs, int32_t n, const int32_t *const *z, int32_t
 int ggs_group_sweep(ggs_handle **hs, int32_t n, int32_t n_sweeps) {
   if (!is_group(hs, n)) return GGS_ERR_BAD_ARG;
   int rc;
+  for (int32_t i = 0; i < n; ++i)
+    if ((rc = iteration_room(hs[i], n_sweeps))) return rc;
   for (int32_t s = 0; s < n_sweeps; ++s) {
     if (count_form(hs[0]->scheme) && (rc = group_gather_counts(hs, n))) return rc;   // the z step conditions on the corpus-wide sweep-start counts
     for (int32_t i = 0; i < n; ++i) {

@@ -212,15 +212,16 @@ def expected_phi_mean(row, phis, n_before=0, burn_in=BURN_IN, thin=THIN):
 # ---- the oracle over a script of calls ----------------------------------------------------------------------------------
 class Chain:
     """The oracle of a row over corpus c from z0, started at an iteration number: steps ("sweep", n), ("zgiven", n),
-    ("iteration", t), ("serial", java_seed, n), ("initz", java_seed: a new seeded z, ggs_init_z_java_lcg; the C oracle only).  state(): z, n_wk, n_k and whatever else the oracle restates."""
+    ("iteration", t), ("serial", java_seed, n), ("initz", java_seed: a new seeded z, ggs_init_z_java_lcg; the C oracle only).  state(): z, n_wk, n_k and whatever else the oracle restates.
+    seed, doc_base and tok_base are the handle's (ggs_config.seed, ggs_set_corpus): the key and the first elements of the streams."""
 
-    def __init__(self, row, K, c, z0, iteration=0):
+    def __init__(self, row, K, c, z0, iteration=0, seed=SEED, doc_base=0, tok_base=0):
         self.row, self.K, self.c = row, K, c
         if row.oracle == "c":
-            o = self.o = O.OracleSampler(K, V, ALPHA, row.beta, SEED, threads=4)
+            o = self.o = O.OracleSampler(K, V, ALPHA, row.beta, seed, threads=4)
             if row.scheme == "pcgs":
                 o.set_scheme("pcgs")
-            o.set_corpus(c.doc_ptr, c.tokens)
+            o.set_corpus(c.doc_ptr, c.tokens, doc_base, tok_base)
             o.set_iteration(iteration)
             o.set_z(z0, redraw_phi=False)
             if row.form != "count":
@@ -233,7 +234,7 @@ class Chain:
             kw["cells"] = prior_cells(K)
         if row.vs:
             kw["pi"] = VS_PI
-        m = self.m = R.Model(K, V, ALPHA, row.beta, SEED, c.doc_ptr, c.tokens, z0, **kw)
+        m = self.m = R.Model(K, V, ALPHA, row.beta, seed, c.doc_ptr, c.tokens, z0, tok_base=tok_base, **kw)   # no theta in these: no doc_base
         m.iteration = iteration
         if hasattr(m, "o"):
             m.o.set_iteration(iteration)
@@ -261,7 +262,7 @@ class Chain:
             m = self.m
             for _ in range(n):
                 m.iteration += 1
-                PR.z_step(m.doc_ptr, m.tokens, m.z, m.phi, m.alpha, m.seed, m.iteration)
+                PR.z_step(m.doc_ptr, m.tokens, m.z, m.phi, m.alpha, m.seed, m.iteration, m.tok_base)
             return None
         for _ in range(n):
             self.o.set_iteration(self.o.iteration + 1)
@@ -317,9 +318,9 @@ def oracle_state(name, K, corpus_name, script=CANON, iteration=0):
 
 
 # ---- handles ------------------------------------------------------------------------------------------------------------
-def create(native, row, K):
+def create(native, row, K, seed=SEED):
     """A handle of the row's scheme with its configuration (the priors, pi) and the phi mean's gating; no corpus yet."""
-    h = native.GGSHandle(K, V, ALPHA, row.beta, SEED, flags=native.SCHEME_FLAGS[row.scheme] | native.FLAG_SAVE_PHI_MEAN, phi_burn_in=BURN_IN,
+    h = native.GGSHandle(K, V, ALPHA, row.beta, seed, flags=native.SCHEME_FLAGS[row.scheme] | native.FLAG_SAVE_PHI_MEAN, phi_burn_in=BURN_IN,
                          phi_mean_thin=THIN)
     try:
         if row.priors:
@@ -481,28 +482,31 @@ def exchange_callbacks(tr, rank, world):
     return reduce_scatter_i32, all_gather("<f8"), all_gather("<i4"), all_to_all_v
 
 
-def shard_of(whole, rank, world):
-    """(sub-corpus, doc_base, tok_base) of a rank: documents split evenly and contiguously"""
+def shard_of(whole, rank, world, doc_off=0, tok_off=0):
+    """(sub-corpus, doc_base, tok_base) of a rank: documents split evenly and contiguously.  doc_off / tok_off: the global
+    indices of the first document / token of `whole` itself (a corpus that is a part of a larger one)."""
     bounds = even_split(whole.num_docs, world)
-    return whole.shard(bounds[rank], bounds[rank + 1])
+    sub, doc_base, tok_base = whole.shard(bounds[rank], bounds[rank + 1])
+    return sub, doc_base + doc_off, tok_base + tok_off
 
 
-def run_world(native, row, K, whole, world, mode, body):
+def run_world(native, row, K, whole, world, mode, body, seed=SEED, doc_off=0, tok_off=0):
     """`world` threads, each with one handle of the row's scheme joined to the others (the count exchange in `mode`, its shard
     of `whole` set as corpus); body(h, rank, sub, tok_base) runs on each and its return values come back in rank order.  Every
-    collective call of body must be made by every rank in the same order."""
+    collective call of body must be made by every rank in the same order.  With doc_off / tok_off (shard_of) the handles' bases
+    are offset; body's tok_base stays the shard's first token WITHIN `whole` (what slices a z of the whole corpus)."""
     tr, out, errs = Transport(world), [None] * world, []
 
     def rank_main(rank):
         h = None
         try:
-            sub, doc_base, tok_base = shard_of(whole, rank, world)
-            h = create(native, row, K)
+            sub, doc_base, tok_base = shard_of(whole, rank, world, doc_off, tok_off)
+            h = create(native, row, K, seed)
             h.attach_exchange(rank, world, *exchange_callbacks(tr, rank, world))
             h.set_count_exchange(mode)
             h.set_corpus(sub.doc_ptr, sub.tokens, doc_base, tok_base)
             h.set_global_token_count(whole.num_tokens)
-            out[rank] = body(h, rank, sub, tok_base)
+            out[rank] = body(h, rank, sub, tok_base - tok_off)
             assert h.count_exchange()["sparse"] == (mode == "sparse")
         except BaseException as e:                      # noqa: BLE001 -- re-raised by the caller
             errs.append(e)

@@ -273,8 +273,8 @@ class Model:
     """A whole nzvsspalias run.  The oracle's pcgs sampler keeps the counts and draws the initial Phi; the variable-selection
     Phi, the lists and the statistics live here."""
 
-    def __init__(self, K, V, alpha, beta, seed, doc_ptr, tokens, z0, pi=0.5):
-        self.K, self.V, self.alpha, self.beta, self.seed, self.pi = K, V, alpha, beta, seed, pi
+    def __init__(self, K, V, alpha, beta, seed, doc_ptr, tokens, z0, pi=0.5, tok_base=0):
+        self.K, self.V, self.alpha, self.beta, self.seed, self.pi, self.tok_base = K, V, alpha, beta, seed, pi, tok_base
         self.doc_ptr = np.asarray(doc_ptr, np.int64)
         self.tokens = np.asarray(tokens, np.int64)
         self.z = np.array(z0, np.int64)
@@ -309,7 +309,7 @@ class Model:
     def sample_z_given_phi(self, n=1):
         for _ in range(n):
             self.iteration += 1
-            z_step(self.doc_ptr, self.tokens, self.z, self.phi, self.tables, self.lists, self.seed, self.iteration, stats=self.stats)
+            z_step(self.doc_ptr, self.tokens, self.z, self.phi, self.tables, self.lists, self.seed, self.iteration, self.tok_base, stats=self.stats)
 
     def sweep(self, n=1):
         for _ in range(n):

@@ -128,8 +128,8 @@ def counts_of(tokens, z, K, V):
 class Model:
     """A whole polyaurn run: init_phi, then sweeps (iteration += 1, z step, counts, Phi draw, the phi mean's gating)."""
 
-    def __init__(self, K, V, alpha, beta, seed, doc_ptr, tokens, z0, L=0, save_phi_mean=False, phi_burn_in=0, phi_thin=1):
-        self.K, self.V, self.alpha, self.beta, self.seed = K, V, alpha, beta, seed
+    def __init__(self, K, V, alpha, beta, seed, doc_ptr, tokens, z0, L=0, save_phi_mean=False, phi_burn_in=0, phi_thin=1, tok_base=0):
+        self.K, self.V, self.alpha, self.beta, self.seed, self.tok_base = K, V, alpha, beta, seed, tok_base
         self.L = threshold_of(L)
         self.table = poisson_table(beta, self.L)
         self.doc_ptr = np.asarray(doc_ptr, np.int64)
@@ -150,7 +150,7 @@ class Model:
     def sweep(self, n=1):
         for _ in range(n):
             self.iteration += 1
-            z_step(self.doc_ptr, self.tokens, self.z, self.phi, self.alpha, self.seed, self.iteration)
+            z_step(self.doc_ptr, self.tokens, self.z, self.phi, self.alpha, self.seed, self.iteration, self.tok_base)
             self.phi, _, _ = phi_draw(self.counts(), self.beta, self.L, self.seed, self.iteration, False, self.table)
             if self.save_phi_mean and self.phi_burn_in > 0 and self.iteration > self.phi_burn_in and self.iteration % self.phi_thin == 0:
                 self.phi_sum += self.phi

@@ -98,8 +98,8 @@ class Model:
     """A whole polyaurn_sparse run: init_phi, then sweeps (iteration += 1, z step, counts, Poisson Phi draw, the phi mean's
     gating); set_phi / sample_z_given_phi as the handle's.  The tables and the words' lists follow every Phi."""
 
-    def __init__(self, K, V, alpha, beta, seed, doc_ptr, tokens, z0, L=0, save_phi_mean=False, phi_burn_in=0, phi_thin=1):
-        self.K, self.V, self.alpha, self.beta, self.seed = K, V, alpha, beta, seed
+    def __init__(self, K, V, alpha, beta, seed, doc_ptr, tokens, z0, L=0, save_phi_mean=False, phi_burn_in=0, phi_thin=1, tok_base=0):
+        self.K, self.V, self.alpha, self.beta, self.seed, self.tok_base = K, V, alpha, beta, seed, tok_base
         self.L = threshold_of(L)
         self.table = poisson_table(beta, self.L)
         self.doc_ptr = np.asarray(doc_ptr, np.int64)
@@ -131,7 +131,7 @@ class Model:
     def sample_z_given_phi(self, n=1):
         for _ in range(n):
             self.iteration += 1
-            z_step(self.doc_ptr, self.tokens, self.z, self.phi, self.tables, self.lists, self.seed, self.iteration, stats=self.stats,
+            z_step(self.doc_ptr, self.tokens, self.z, self.phi, self.tables, self.lists, self.seed, self.iteration, self.tok_base, stats=self.stats,
                    over64=self.over64)
 
     def sweep(self, n=1):

@@ -109,8 +109,8 @@ def conditional_phi(phi_old, gam, P):
 class Model(R.Model):
     """A whole spalias_priors run.  The oracle keeps the counts and draws the gammas; Phi and the running phi mean live here."""
 
-    def __init__(self, K, V, alpha, beta, seed, doc_ptr, tokens, z0, cells=None, save_phi_mean=False, phi_burn_in=0, phi_thin=1):
-        super().__init__(K, V, alpha, beta, seed, doc_ptr, tokens, z0, save_phi_mean=save_phi_mean, phi_burn_in=phi_burn_in, phi_thin=phi_thin)
+    def __init__(self, K, V, alpha, beta, seed, doc_ptr, tokens, z0, cells=None, save_phi_mean=False, phi_burn_in=0, phi_thin=1, tok_base=0):
+        super().__init__(K, V, alpha, beta, seed, doc_ptr, tokens, z0, save_phi_mean=save_phi_mean, phi_burn_in=phi_burn_in, phi_thin=phi_thin, tok_base=tok_base)
         self.P = None if cells is None else priors_matrix(K, V, cells)
         self._gating = (bool(save_phi_mean), int(phi_burn_in), int(phi_thin))
         self._mean_sum, self._mean_n = np.zeros((K, V), np.float64), 0
@@ -138,7 +138,7 @@ class Model(R.Model):
             return super().sample_z_given_phi(n)
         for _ in range(n):
             self.iteration += 1
-            self.n_prior += z_step(self.doc_ptr, self.tokens, self.z, self.phi, self.P, self.tables, self.seed, self.iteration)
+            self.n_prior += z_step(self.doc_ptr, self.tokens, self.z, self.phi, self.P, self.tables, self.seed, self.iteration, self.tok_base)
 
     def sweep(self, n=1):
         if self.P is None:

@@ -163,8 +163,8 @@ class Model:
     """A whole spalias run: init_phi, then sweeps (iteration += 1, z step, counts, Phi draw, the phi mean's gating).  Phi and
     the phi mean are the oracle's pcgs ones; the tables follow every Phi."""
 
-    def __init__(self, K, V, alpha, beta, seed, doc_ptr, tokens, z0, save_phi_mean=False, phi_burn_in=0, phi_thin=1):
-        self.K, self.V, self.alpha, self.seed = K, V, alpha, seed
+    def __init__(self, K, V, alpha, beta, seed, doc_ptr, tokens, z0, save_phi_mean=False, phi_burn_in=0, phi_thin=1, tok_base=0):
+        self.K, self.V, self.alpha, self.seed, self.tok_base = K, V, alpha, seed, tok_base
         self.doc_ptr = np.asarray(doc_ptr, np.int64)
         self.tokens = np.asarray(tokens, np.int64)
         self.z = np.array(z0, np.int64)
@@ -192,7 +192,7 @@ class Model:
     def sample_z_given_phi(self, n=1):
         for _ in range(n):
             self.iteration += 1
-            p, s = z_step(self.doc_ptr, self.tokens, self.z, self.phi, self.tables, self.seed, self.iteration)
+            p, s = z_step(self.doc_ptr, self.tokens, self.z, self.phi, self.tables, self.seed, self.iteration, self.tok_base)
             self.n_prior += p
             self.nnz_sum += s
 
