@@ -20,9 +20,9 @@ import pytest
 
 from tests import adlda_knife_edge as KE
 from tests import adlda_restatement as R
+from tests.ranks import assert_bit_equal, force_form
 from tests.test_adlda_knife_edge_model import assert_survey, print_survey
-from tests.test_native_exchange_gpu import assert_bit_equal
-from tests.test_polyaurn_sparse_knife_edge_gpu import FORMS, force_form
+from tests.test_polyaurn_sparse_knife_edge_gpu import FORMS
 
 pytestmark = pytest.mark.gpu
 

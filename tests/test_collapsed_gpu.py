@@ -9,13 +9,12 @@ the in-tree twin of what SerialCollapsedLDA runs), SURVEY.md 8(a) row 9 / 8(f) i
                       serial chain that schedule is a different, approximate sampler: the north_star's "otherwise"
                       clause applies, held-out log likelihood within +-1 %.
 Parity against a JVM run: unpinned, as for every path (no JVM, no fixture in the reference; tests/test_oracle_cpu.py)."""
-import threading
 
 import numpy as np
 import pytest
 
-from ldagroupedgibbssampler_amd.corpus import even_split, random_corpus, synthetic_lda_corpus
-from tests.test_native_exchange_gpu import ThreadTransport, assert_bit_equal
+from ldagroupedgibbssampler_amd.corpus import random_corpus, synthetic_lda_corpus
+from tests.ranks import assert_bit_equal, run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -140,45 +139,19 @@ def test_parallel_schedule_wide_topic_rows(native, oracle, monkeypatch, K, force
         same_counts(g, o, "parallel wide K=%d sweep %d" % (K, it + 1))
 
 
-def _shard_rank(native, tr, rank, world, whole, K, zseed, sweeps, out, errs):
-    import torch
-    from ldagroupedgibbssampler_amd.sharded import _DevPtr, java_lcg_initial_z
-    try:
-        dev = torch.device("cuda", 0)
+def _shard_rank(native, whole, K, zseed, sweeps):
+    """(make_handle, body) of a rank for tests/ranks.py's run_ranks"""
+    from ldagroupedgibbssampler_amd.sharded import java_lcg_initial_z
 
-        def view(ptr, n, typestr):
-            return torch.as_tensor(_DevPtr(ptr, n, typestr), device=dev)
+    def make_handle(rank):
+        return native.GGSHandle(K, whole.num_types, 0.1, 0.01, 5, flags=native.FLAG_COLLAPSED)
 
-        def reduce_scatter_i32(send, recv, count, stream):
-            torch.cuda.synchronize()
-            parts = tr.exchange(rank, view(send, count * world, "<i4").cpu().numpy().reshape(world, count))
-            view(recv, count, "<i4").copy_(torch.from_numpy(np.sum([p[rank] for p in parts], axis=0, dtype=np.int32)))
-            torch.cuda.synchronize()
-            return 0
-
-        def all_gather(typestr):
-            def cb(send, recv, count, stream):
-                torch.cuda.synchronize()
-                parts = tr.exchange(rank, view(send, count, typestr).cpu().numpy())
-                view(recv, count * world, typestr).copy_(torch.from_numpy(np.concatenate(parts)))
-                torch.cuda.synchronize()
-                return 0
-            return cb
-
-        b = even_split(whole.num_docs, world)
-        sub, doc_base, tok_base = whole.shard(b[rank], b[rank + 1])
-        h = native.GGSHandle(K, whole.num_types, 0.1, 0.01, 5, flags=native.FLAG_COLLAPSED)
-        h.attach_exchange(rank, world, reduce_scatter_i32, all_gather("<f8"), all_gather("<i4"))
-        h.set_corpus(sub.doc_ptr, sub.tokens, doc_base, tok_base)
-        h.set_global_token_count(whole.num_tokens)
+    def body(h, rank, sub, tok_base):
         h.set_z(java_lcg_initial_z(whole.num_tokens, K, zseed)[tok_base:tok_base + sub.num_tokens], redraw_phi=True)
         h.sweep(sweeps)
         h.check_invariants()
-        out[rank] = dict(z=h.get_z(), nwk=h.get_type_topic_counts(), nk=h.get_topic_totals())
-        h.close()
-    except BaseException as e:  # noqa: BLE001
-        errs.append(e)
-        tr.bar.abort()
+        return dict(z=h.get_z(), nwk=h.get_type_topic_counts(), nk=h.get_topic_totals())
+    return make_handle, body
 
 
 def test_parallel_schedule_doc_sharded_is_ad_lda_with_a_merge_per_sweep(native, oracle):
@@ -187,14 +160,7 @@ def test_parallel_schedule_doc_sharded_is_ad_lda_with_a_merge_per_sweep(native, 
     from ldagroupedgibbssampler_amd.sharded import java_lcg_initial_z
     whole = random_corpus(260, 400, 120, seed=9, empty_every=8)
     K, world, sweeps = 24, 2, 3
-    tr, out, errs = ThreadTransport(world), [None] * world, []
-    ts = [threading.Thread(target=_shard_rank, args=(native, tr, r, world, whole, K, 3, sweeps, out, errs)) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
-    if errs:
-        raise errs[0]
+    out = run_ranks(world, whole, *_shard_rank(native, whole, K, 3, sweeps), all_to_all=False)
     o = oracle.OracleSampler(K, whole.num_types, 0.1, 0.01, 5, threads=4)
     o.set_corpus(whole.doc_ptr, whole.tokens)
     o.set_z(java_lcg_initial_z(whole.num_tokens, K, 3), redraw_phi=True)

@@ -8,14 +8,13 @@
 The oracle legs use orc_sweep_tuned where a whole-corpus sweep is needed: tests/test_oracle_cpu.py proves it the same
 sampler as the Java-layout orc_sweep, and it is what fits the time budget at K=1024."""
 import os
-import threading
 
 import numpy as np
 import pytest
 
-from ldagroupedgibbssampler_amd.corpus import even_split, synthetic_lda_corpus, zipf_unigram_corpus
+from ldagroupedgibbssampler_amd.corpus import synthetic_lda_corpus, zipf_unigram_corpus
 from ldagroupedgibbssampler_amd.sharded import java_lcg_initial_z
-from tests.test_native_exchange_gpu import ThreadTransport, assert_bit_equal
+from tests.ranks import assert_bit_equal, run_ranks
 
 pytestmark = pytest.mark.gpu
 CORES = min(64, os.cpu_count() or 4)
@@ -44,45 +43,17 @@ def test_config3_full_size_k1024(native, oracle):
     assert_bit_equal(th, o.get_theta()[:1000], "K=1024 full size theta (first 1000 documents)")
 
 
-def _c4_rank(native, tr, rank, world, whole, K, z0, sweeps, out, errs):
-    import torch
-    from ldagroupedgibbssampler_amd.sharded import _DevPtr
-    try:
-        dev = torch.device("cuda", 0)
+def _c4_rank(native, whole, K, z0, sweeps):
+    """(make_handle, body) of a rank for tests/ranks.py's run_ranks"""
+    def make_handle(rank):
+        return native.GGSHandle(K, whole.num_types, 0.1, 0.01, 2019)
 
-        def view(ptr, n, typestr):
-            return torch.as_tensor(_DevPtr(ptr, n, typestr), device=dev)
-
-        def reduce_scatter_i32(send, recv, count, stream):
-            torch.cuda.synchronize()
-            parts = tr.exchange(rank, view(send, count * world, "<i4").cpu().numpy().reshape(world, count))
-            view(recv, count, "<i4").copy_(torch.from_numpy(np.sum([p[rank] for p in parts], axis=0, dtype=np.int32)))
-            torch.cuda.synchronize()
-            return 0
-
-        def all_gather(typestr):
-            def cb(send, recv, count, stream):
-                torch.cuda.synchronize()
-                parts = tr.exchange(rank, view(send, count, typestr).cpu().numpy())
-                view(recv, count * world, typestr).copy_(torch.from_numpy(np.concatenate(parts)))
-                torch.cuda.synchronize()
-                return 0
-            return cb
-
-        b = even_split(whole.num_docs, world)
-        sub, doc_base, tok_base = whole.shard(b[rank], b[rank + 1])
-        h = native.GGSHandle(K, whole.num_types, 0.1, 0.01, 2019)
-        h.attach_exchange(rank, world, reduce_scatter_i32, all_gather("<f8"), all_gather("<i4"))
-        h.set_corpus(sub.doc_ptr, sub.tokens, doc_base, tok_base)
-        h.set_global_token_count(whole.num_tokens)
+    def body(h, rank, sub, tok_base):
         h.set_z(z0[tok_base:tok_base + sub.num_tokens], redraw_phi=True)
         h.sweep(sweeps)
         h.check_invariants()
-        out[rank] = dict(z=h.get_z(), theta=h.get_theta(), phi=h.get_phi(), nwk=h.get_type_topic_counts())
-        h.close()
-    except BaseException as e:  # noqa: BLE001
-        errs.append(e)
-        tr.bar.abort()
+        return dict(z=h.get_z(), theta=h.get_theta(), phi=h.get_phi(), nwk=h.get_type_topic_counts())
+    return make_handle, body
 
 
 def test_config4_standin_three_shards_one_handle_oracle(native, oracle):
@@ -95,14 +66,7 @@ def test_config4_standin_three_shards_one_handle_oracle(native, oracle):
     one.sweep(sweeps)
     ref = dict(z=one.get_z(), theta=one.get_theta(), phi=one.get_phi(), nwk=one.get_type_topic_counts())
     one.close()
-    tr, out, errs = ThreadTransport(world), [None] * world, []
-    ts = [threading.Thread(target=_c4_rank, args=(native, tr, r, world, whole, K, z0, sweeps, out, errs)) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
-    if errs:
-        raise errs[0]
+    out = run_ranks(world, whole, *_c4_rank(native, whole, K, z0, sweeps), all_to_all=False)
     assert_bit_equal(np.concatenate([p["z"] for p in out]), ref["z"], "3 shards vs one handle: z")
     assert_bit_equal(np.concatenate([p["theta"] for p in out]), ref["theta"], "3 shards vs one handle: theta")
     for p in out:

@@ -9,7 +9,6 @@ polyaurn): the diagnostics leave the chain alone.
 
 Every check prints its ratio |device - exact| / (2^-53 * sum|t|) beside the c it had to stay under (pytest -s shows them)."""
 import math
-import threading
 
 import numpy as np
 import pytest
@@ -17,8 +16,8 @@ import pytest
 from tests import diagnostics_cases as DC
 from tests import polyaurn_restatement as PR
 from tests import spalias_restatement as SR
-from tests.test_native_exchange_gpu import ThreadTransport
-from tests.test_parity_gpu import assert_bit_equal, compare_state
+from tests.ranks import assert_bit_equal, run_ranks
+from tests.test_parity_gpu import compare_state
 
 pytestmark = pytest.mark.gpu
 
@@ -191,37 +190,12 @@ def test_huge_count(native, oracle, scheme):
 
 
 # ---- shards ----------------------------------------------------------------------------------------------------------
-def _shard_rank(native, tr, rank, cuts, whole, K, alpha, beta, scheme, z0, out, errs):
-    import torch
-    from ldagroupedgibbssampler_amd.sharded import _DevPtr
-    world = len(cuts) - 1
-    try:
-        dev = torch.device("cuda", 0)
+def _shard_rank(native, whole, K, alpha, beta, scheme, z0):
+    """(make_handle, body) of a rank for tests/ranks.py's run_ranks"""
+    def make_handle(rank):
+        return native.GGSHandle(K, whole.num_types, alpha, beta, SEED, flags=flags_of(native, scheme))
 
-        def view(ptr, n, typestr):
-            return torch.as_tensor(_DevPtr(ptr, n, typestr), device=dev)
-
-        def reduce_scatter_i32(send, recv, count, stream):
-            torch.cuda.synchronize()
-            parts = tr.exchange(rank, view(send, count * world, "<i4").cpu().numpy().reshape(world, count))
-            view(recv, count, "<i4").copy_(torch.from_numpy(np.sum([p[rank] for p in parts], axis=0, dtype=np.int32)))
-            torch.cuda.synchronize()
-            return 0
-
-        def all_gather(typestr):
-            def cb(send, recv, count, stream):
-                torch.cuda.synchronize()
-                parts = tr.exchange(rank, view(send, count, typestr).cpu().numpy())
-                view(recv, count * world, typestr).copy_(torch.from_numpy(np.concatenate(parts)))
-                torch.cuda.synchronize()
-                return 0
-            return cb
-
-        sub, doc_base, tok_base = whole.shard(cuts[rank], cuts[rank + 1])
-        h = native.GGSHandle(K, whole.num_types, alpha, beta, SEED, flags=flags_of(native, scheme))
-        h.attach_exchange(rank, world, reduce_scatter_i32, all_gather("<f8"), all_gather("<i4"))
-        h.set_corpus(sub.doc_ptr, sub.tokens, doc_base, tok_base)
-        h.set_global_token_count(whole.num_tokens)
+    def body(h, rank, sub, tok_base):
         h.set_z(z0[tok_base:tok_base + sub.num_tokens], redraw_phi=True)
         h.sweep(1)
         h.check_invariants()                       # collective: gathers the corpus-wide counts
@@ -230,11 +204,8 @@ def _shard_rank(native, tr, rank, cuts, whole, K, alpha, beta, scheme, z0, out, 
         r["theta"] = h.get_theta()
         h.sweep(1)
         r["z"], r["phi"] = h.get_z(), h.get_phi()
-        out[rank] = r
-        h.close()
-    except BaseException as e:                      # noqa: BLE001 -- re-raised by the test body
-        errs.append(e)
-        tr.bar.abort()
+        return r
+    return make_handle, body
 
 
 @pytest.mark.parametrize("scheme", ["ggs", "pcgs"])
@@ -249,14 +220,7 @@ def test_document_shards(native, oracle, cuts, scheme):
     K, alpha, beta = 33, DC.asymmetric_alpha(33), 0.01
     world = len(cuts) - 1
     z0 = java_lcg_initial_z(whole.num_tokens, K, ZSEED)
-    tr, out, errs = ThreadTransport(world), [None] * world, []
-    ts = [threading.Thread(target=_shard_rank, args=(native, tr, r, cuts, whole, K, alpha, beta, scheme, z0, out, errs)) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
-    if errs:
-        raise errs[0]
+    out = run_ranks(world, whole, *_shard_rank(native, whole, K, alpha, beta, scheme, z0), all_to_all=False, cuts=cuts)
     o = oracle.OracleSampler(K, whole.num_types, alpha, beta, SEED, threads=4)
     o.set_scheme(scheme)
     o.set_corpus(whole.doc_ptr, whole.tokens)

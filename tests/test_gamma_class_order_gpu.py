@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from ldagroupedgibbssampler_amd.corpus import Corpus, random_corpus
-from tests.test_parity_gpu import assert_bit_equal
+from tests.ranks import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
 

@@ -14,9 +14,9 @@ import pytest
 
 from tests import lightcollapsed_knife_edge as KE
 from tests import lightcollapsed_restatement as R
+from tests.ranks import assert_bit_equal
 from tests.test_lightcollapsed_knife_edge_model import assert_survey, print_survey
 from tests.test_lightpclda_knife_edge_gpu import compare, report
-from tests.test_native_exchange_gpu import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
 

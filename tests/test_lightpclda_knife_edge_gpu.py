@@ -15,7 +15,7 @@ import pytest
 
 from tests import lightpclda_knife_edge as KE
 from tests import spalias_restatement as SR
-from tests.test_native_exchange_gpu import assert_bit_equal
+from tests.ranks import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
 

@@ -11,24 +11,16 @@ Every case must reproduce the one-handle run / the oracle bit for bit."""
 import os
 import socket
 import sys
-import threading
 
 import numpy as np
 import pytest
 
 from ldagroupedgibbssampler_amd.corpus import Corpus, even_split, random_corpus
 from ldagroupedgibbssampler_amd.sharded import TopicSliceLayout, java_lcg_initial_z
+from tests.ranks import assert_bit_equal, run_ranks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-
-
-def assert_bit_equal(a, b, what):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape, what
-    if a.dtype == np.float64:
-        a, b = a.view(np.int64), b.view(np.int64)
-    assert np.array_equal(a, b), "%s differs in %d of %d places" % (what, int((a != b).sum()), a.size)
 
 
 def reference_run(oracle, corpus, K, alpha, beta, seed, zseed, sweeps, scheme="ggs", save_mean=False):
@@ -112,54 +104,8 @@ def test_callers_own_communicator(native, oracle):
     assert rccl.ncclCommDestroy(comm) == 0           # still alive: the library did not destroy what it does not own
 
 
-class ThreadTransport:
-    """In-memory collectives between handles driven by threads of one process."""
-
-    def __init__(self, n):
-        self.n, self.bar, self.box = n, threading.Barrier(n, timeout=300), [None] * n
-
-    def exchange(self, rank, payload):
-        self.box[rank] = payload
-        self.bar.wait()
-        got = list(self.box)
-        self.bar.wait()
-        return got
-
-
-def _thread_rank(native, tr, rank, world, whole, K, scheme, zseed, sweeps, out, errs):
-    import torch
-    from ldagroupedgibbssampler_amd.sharded import _DevPtr
-    try:
-        dev = torch.device("cuda", 0)
-
-        def view(ptr, n, typestr):
-            return torch.as_tensor(_DevPtr(ptr, n, typestr), device=dev)
-
-        def reduce_scatter_i32(send, recv, count, stream):
-            torch.cuda.synchronize()
-            mine = view(send, count * world, "<i4").cpu().numpy().reshape(world, count)
-            parts = tr.exchange(rank, mine)
-            own = np.sum([p[rank] for p in parts], axis=0, dtype=np.int32)
-            view(recv, count, "<i4").copy_(torch.from_numpy(own))
-            torch.cuda.synchronize()
-            return 0
-
-        def all_gather(typestr):
-            def cb(send, recv, count, stream):
-                torch.cuda.synchronize()
-                parts = tr.exchange(rank, view(send, count, typestr).cpu().numpy())
-                view(recv, count * world, typestr).copy_(torch.from_numpy(np.concatenate(parts)))
-                torch.cuda.synchronize()
-                return 0
-            return cb
-
-        bounds = even_split(whole.num_docs, world)
-        sub, doc_base, tok_base = whole.shard(bounds[rank], bounds[rank + 1])
-        flags = (native.FLAG_PCGS if scheme == "pcgs" else 0) | native.FLAG_SAVE_PHI_MEAN
-        h = native.GGSHandle(K, whole.num_types, 0.1, 0.01, 4242, flags=flags, phi_burn_in=1, phi_mean_thin=2)
-        h.attach_exchange(rank, world, reduce_scatter_i32, all_gather("<f8"), all_gather("<i4"))
-        h.set_corpus(sub.doc_ptr, sub.tokens, doc_base, tok_base)
-        h.set_global_token_count(whole.num_tokens)
+def _thread_body(whole, K, scheme, zseed, sweeps):
+    def body(h, rank, sub, tok_base):
         z0 = java_lcg_initial_z(whole.num_tokens, K, zseed)
         h.set_z(z0[tok_base:tok_base + sub.num_tokens], redraw_phi=True)
         h.sweep(sweeps - 1)
@@ -167,13 +113,10 @@ def _thread_rank(native, tr, rank, world, whole, K, scheme, zseed, sweeps, out, 
         h.sweep_end()
         h.check_invariants()                       # collective: gathers the corpus-wide counts
         doc_side, topic_side = h.model_log_likelihood()
-        out[rank] = dict(z=h.get_z(), nwk=h.get_type_topic_counts(), nk=h.get_topic_totals(), phi=h.get_phi(),
-                         theta=h.get_theta() if scheme == "ggs" else None, mean=h.get_phi_mean(), info=h.exchange_info(),
-                         ll=(doc_side, topic_side))
-        h.close()
-    except BaseException as e:                      # noqa: BLE001 -- re-raised by the test body
-        errs.append(e)
-        tr.bar.abort()
+        return dict(z=h.get_z(), nwk=h.get_type_topic_counts(), nk=h.get_topic_totals(), phi=h.get_phi(),
+                    theta=h.get_theta() if scheme == "ggs" else None, mean=h.get_phi_mean(), info=h.exchange_info(),
+                    ll=(doc_side, topic_side))
+    return body
 
 
 @pytest.mark.parametrize("scheme,K,world,docs,V", [("ggs", 100, 3, 310, 900), ("ggs", 7, 4, 310, 900), ("pcgs", 24, 2, 310, 900), ("ggs", 200, 3, 310, 900),
@@ -187,14 +130,9 @@ def test_topic_sliced_exchange_between_handles(native, oracle, scheme, K, world,
     gammas in two halves (the first on the communication stream under the draw of the second)."""
     whole = random_corpus(docs, V, 120 if docs > 10 else 25, seed=5 + K, empty_every=9 if docs > 10 else 0)
     sweeps = 4
-    tr, out, errs = ThreadTransport(world), [None] * world, []
-    ts = [threading.Thread(target=_thread_rank, args=(native, tr, r, world, whole, K, scheme, 17, sweeps, out, errs)) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
-    if errs:
-        raise errs[0]
+    flags = (native.FLAG_PCGS if scheme == "pcgs" else 0) | native.FLAG_SAVE_PHI_MEAN
+    out = run_ranks(world, whole, lambda rank: native.GGSHandle(K, whole.num_types, 0.1, 0.01, 4242, flags=flags, phi_burn_in=1, phi_mean_thin=2),
+                    _thread_body(whole, K, scheme, 17, sweeps), all_to_all=False)
     o = reference_run(oracle, whole, K, 0.1, 0.01, 4242, 17, sweeps, scheme, save_mean=False)
     o2 = oracle.OracleSampler(K, whole.num_types, 0.1, 0.01, 4242, threads=4)
     o2.set_scheme(scheme)
@@ -432,67 +370,16 @@ def test_forced_split_point_of_the_all_gather(native, oracle, monkeypatch, split
     h.close()
 
 
-def _sparse_rank(native, tr, rank, world, whole, K, scheme, mode, sweeps, out, errs):
-    import torch
-    from ldagroupedgibbssampler_amd.sharded import _DevPtr
-    try:
-        dev = torch.device("cuda", 0)
-
-        def view(ptr, n, typestr):
-            return torch.as_tensor(_DevPtr(ptr, n, typestr), device=dev)
-
-        def reduce_scatter_i32(send, recv, count, stream):
-            torch.cuda.synchronize()
-            parts = tr.exchange(rank, view(send, count * world, "<i4").cpu().numpy().reshape(world, count))
-            view(recv, count, "<i4").copy_(torch.from_numpy(np.sum([p[rank] for p in parts], axis=0, dtype=np.int32)))
-            torch.cuda.synchronize()
-            out[rank]["dense_calls"] += 1
-            return 0
-
-        def all_gather(typestr):
-            def cb(send, recv, count, stream):
-                torch.cuda.synchronize()
-                parts = tr.exchange(rank, view(send, count, typestr).cpu().numpy())
-                view(recv, count * world, typestr).copy_(torch.from_numpy(np.concatenate(parts)))
-                torch.cuda.synchronize()
-                return 0
-            return cb
-
-        def all_to_all_v(send, soff, scnt, recv, roff, rcnt, stream):
-            torch.cuda.synchronize()
-            total = max(soff[i] + scnt[i] for i in range(world))
-            mine = view(send, max(total, 1), "<i4").cpu().numpy()
-            blocks = [mine[soff[d]:soff[d] + scnt[d]].copy() for d in range(world)]
-            everyone = tr.exchange(rank, blocks)                   # everyone[s][d] = what rank s addresses to rank d
-            for s_ in range(world):
-                got = everyone[s_][rank]
-                assert got.size == rcnt[s_], "rank %d expected %d elements from rank %d, got %d" % (rank, rcnt[s_], s_, got.size)
-                if got.size:
-                    view(recv + 4 * roff[s_], got.size, "<i4").copy_(torch.from_numpy(got))
-            torch.cuda.synchronize()
-            out[rank]["sparse_calls"] += 1
-            out[rank]["pairs_sent"] += sum(scnt) // 2
-            return 0
-
-        bounds = even_split(whole.num_docs, world)
-        sub, doc_base, tok_base = whole.shard(bounds[rank], bounds[rank + 1])
-        flags = native.FLAG_PCGS if scheme == "pcgs" else 0
-        h = native.GGSHandle(K, whole.num_types, 0.1, 0.01, 515, flags=flags)
-        h.attach_exchange(rank, world, reduce_scatter_i32, all_gather("<f8"), all_gather("<i4"), all_to_all_v)
-        h.set_count_exchange(mode)
-        h.set_corpus(sub.doc_ptr, sub.tokens, doc_base, tok_base)
-        h.set_global_token_count(whole.num_tokens)
+def _sparse_body(whole, K, sweeps):
+    def body(h, rank, sub, tok_base):
         z0 = java_lcg_initial_z(whole.num_tokens, K, 23)
         h.set_z(z0[tok_base:tok_base + sub.num_tokens], redraw_phi=True)
         h.sweep(sweeps - 1)
         h.sweep_begin()
         h.sweep_end()
         h.check_invariants()
-        out[rank].update(z=h.get_z(), nwk=h.get_type_topic_counts(), nk=h.get_topic_totals(), phi=h.get_phi(), how=h.count_exchange())
-        h.close()
-    except BaseException as e:                      # noqa: BLE001
-        errs.append(e)
-        tr.bar.abort()
+        return dict(z=h.get_z(), nwk=h.get_type_topic_counts(), nk=h.get_topic_totals(), phi=h.get_phi(), how=h.count_exchange())
+    return body
 
 
 @pytest.mark.parametrize("scheme,K,world,V", [("ggs", 100, 3, 900), ("ggs", 200, 3, 1500), ("pcgs", 24, 2, 700), ("ggs", 2, 3, 300), ("ggs", 37, 4, 1100)])
@@ -503,18 +390,11 @@ def test_sparse_count_exchange_equals_the_dense_one(native, oracle, scheme, K, w
     score-register and the streaming z kernels."""
     whole = random_corpus(240, V, 110, seed=3 + K, empty_every=9)
     sweeps = 3
-    res = {}
+    res, flags = {}, native.FLAG_PCGS if scheme == "pcgs" else 0
     for mode in ("sparse", "dense"):
-        tr, errs = ThreadTransport(world), []
-        out = [dict(dense_calls=0, sparse_calls=0, pairs_sent=0) for _ in range(world)]
-        ts = [threading.Thread(target=_sparse_rank, args=(native, tr, r, world, whole, K, scheme, mode, sweeps, out, errs)) for r in range(world)]
-        for t in ts:
-            t.start()
-        for t in ts:
-            t.join()
-        if errs:
-            raise errs[0]
-        res[mode] = out
+        out, counters = run_ranks(world, whole, lambda rank: native.GGSHandle(K, whole.num_types, 0.1, 0.01, 515, flags=flags), _sparse_body(whole, K, sweeps),
+                                  mode=mode, counters=True)
+        res[mode] = [dict(p, **n) for p, n in zip(out, counters)]
     o = reference_run(oracle, whole, K, 0.1, 0.01, 515, 23, sweeps, scheme)
     for mode, out in res.items():
         assert_bit_equal(np.concatenate([p["z"] for p in out]), o.get_z(), mode + " z")

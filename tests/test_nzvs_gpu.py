@@ -6,16 +6,15 @@ mean, misuse, the launch plan.
 The z kernel is nzvs_wave_kernel (sparse_wave_body with the alias draw for a token without a candidate): the wave scans'
 proposal, and the exact chain that replays what it leaves open.  GGS_DEBUG_MARGIN=1e30 (FORMS) sends every token with
 candidates through the replay; both ways give the same bits."""
-import threading
 
 import numpy as np
 import pytest
 
-from ldagroupedgibbssampler_amd.corpus import Corpus, even_split, random_corpus
+from ldagroupedgibbssampler_amd.corpus import Corpus, random_corpus
 from ldagroupedgibbssampler_amd.sharded import java_lcg_initial_z
 from tests import nzvs_restatement as R
 from tests import polyaurn_sparse_restatement as PS
-from tests.test_native_exchange_gpu import ThreadTransport, assert_bit_equal
+from tests.ranks import assert_bit_equal, force_form, run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -24,14 +23,6 @@ BETA = 0.01
 KERNEL = "nzvs_wave_kernel (wave per document)"
 FORMS = [None, "1e30"]                  # GGS_DEBUG_MARGIN: the proposal with its margins / every token replayed exactly
 PATHS = ["lds", "global"]               # the chain's rows in LDS / in global scratch (GGS_DEBUG_VS_GLOBAL=1)
-
-
-def force_form(monkeypatch, margin):
-    monkeypatch.setenv("GGS_DEBUG", "1")
-    if margin is None:
-        monkeypatch.delenv("GGS_DEBUG_MARGIN", raising=False)
-    else:
-        monkeypatch.setenv("GGS_DEBUG_MARGIN", margin)
 
 
 def force_path(monkeypatch, path):
@@ -236,74 +227,27 @@ def test_the_phi_mean_stays_zero_and_n_sampled_counts(native, oracle, cats):
 # ---- sharded: bit-identical to one handle ---------------------------------------------------------------------------
 # Each rank runs the indicator chain of its own topic slice; the drawn sets travel as the sign of zero of the gathered gammas.
 # A drawn cell whose gamma underflowed holds +0.0 and stays listed: every case asserts that it has one.
-def _rank(native, tr, rank, world, whole, K, mode, sweeps, out, errs):
-    import torch
-    from ldagroupedgibbssampler_amd.sharded import _DevPtr
-    try:
-        dev = torch.device("cuda", 0)
-
-        def view(ptr, n, typestr):
-            return torch.as_tensor(_DevPtr(ptr, n, typestr), device=dev)
-
-        def reduce_scatter_i32(send, recv, count, stream):
-            torch.cuda.synchronize()
-            parts = tr.exchange(rank, view(send, count * world, "<i4").cpu().numpy().reshape(world, count))
-            view(recv, count, "<i4").copy_(torch.from_numpy(np.sum([p[rank] for p in parts], axis=0, dtype=np.int32)))
-            torch.cuda.synchronize()
-            return 0
-
-        def all_gather(typestr):
-            def cb(send, recv, count, stream):
-                torch.cuda.synchronize()
-                parts = tr.exchange(rank, view(send, count, typestr).cpu().numpy())
-                view(recv, count * world, typestr).copy_(torch.from_numpy(np.concatenate(parts)))
-                torch.cuda.synchronize()
-                return 0
-            return cb
-
-        def all_to_all_v(send, soff, scnt, recv, roff, rcnt, stream):
-            torch.cuda.synchronize()
-            total = max(soff[i] + scnt[i] for i in range(world))
-            mine = view(send, max(total, 1), "<i4").cpu().numpy()
-            everyone = tr.exchange(rank, [mine[soff[d]:soff[d] + scnt[d]].copy() for d in range(world)])
-            for s_ in range(world):
-                got = everyone[s_][rank]
-                if got.size:
-                    view(recv + 4 * roff[s_], got.size, "<i4").copy_(torch.from_numpy(got))
-            torch.cuda.synchronize()
-            return 0
-
-        bounds = even_split(whole.num_docs, world)
-        sub, doc_base, tok_base = whole.shard(bounds[rank], bounds[rank + 1])
+def _rank(native, whole, K, sweeps):
+    """(make_handle, body) of a rank for tests/ranks.py's run_ranks"""
+    def make_handle(rank):
         h = native.GGSHandle(K, whole.num_types, 0.1, 0.01, SEED, flags=native.FLAG_NZVSSPALIAS)
         h.set_variable_selection_prior(0.4)
-        h.attach_exchange(rank, world, reduce_scatter_i32, all_gather("<f8"), all_gather("<i4"), all_to_all_v)
-        h.set_count_exchange(mode)
-        h.set_corpus(sub.doc_ptr, sub.tokens, doc_base, tok_base)
-        h.set_global_token_count(whole.num_tokens)
+        return h
+
+    def body(h, rank, sub, tok_base):
         z0 = java_lcg_initial_z(whole.num_tokens, K, 17)
         h.set_z(z0[tok_base:tok_base + sub.num_tokens], redraw_phi=True)
         h.sweep(sweeps)
         h.check_invariants()
-        out[rank] = dict(z=h.get_z(), nwk=h.get_type_topic_counts(), phi=h.get_phi(), how=h.count_exchange(), tables=h.alias_tables(),
-                         lists=h.word_topic_lists(), stats=h.sparse_stats(), vs=h.vs_stats(), kernel=h.launch_info()["z_kernel"])
-        h.close()
-    except BaseException as e:                      # noqa: BLE001 -- re-raised by the test body
-        errs.append(e)
-        tr.bar.abort()
+        return dict(z=h.get_z(), nwk=h.get_type_topic_counts(), phi=h.get_phi(), how=h.count_exchange(), tables=h.alias_tables(),
+                    lists=h.word_topic_lists(), stats=h.sparse_stats(), vs=h.vs_stats(), kernel=h.launch_info()["z_kernel"])
+    return make_handle, body
 
 
 def ranks_equal_one_handle(native, world, K, mode):
     sweeps, V = 3, 900
     whole = random_corpus(310, V, 90, seed=K + V, empty_every=9)
-    tr, out, errs = ThreadTransport(world), [None] * world, []
-    ts = [threading.Thread(target=_rank, args=(native, tr, r, world, whole, K, mode, sweeps, out, errs)) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
-    if errs:
-        raise errs[0]
+    out = run_ranks(world, whole, *_rank(native, whole, K, sweeps), mode=mode)
     h = native.GGSHandle(K, V, 0.1, 0.01, SEED, flags=native.FLAG_NZVSSPALIAS)
     h.set_variable_selection_prior(0.4)
     h.set_corpus(whole.doc_ptr, whole.tokens)

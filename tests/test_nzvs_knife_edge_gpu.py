@@ -16,7 +16,7 @@ import pytest
 from tests import nzvs_knife_edge as NE
 from tests import nzvs_restatement as R
 from tests import polyaurn_sparse_knife_edge as KE
-from tests.test_native_exchange_gpu import assert_bit_equal
+from tests.ranks import assert_bit_equal, force_form
 
 pytestmark = pytest.mark.gpu
 
@@ -25,14 +25,6 @@ BETA = NE.BETA
 KERNEL = "nzvs_wave_kernel (wave per document)"
 FORMS = [None, "1e30"]                  # GGS_DEBUG_MARGIN: the proposal with its margins / every token replayed exactly
 PATHS = ["lds", "global"]               # the chain's rows in LDS / in global scratch (GGS_DEBUG_VS_GLOBAL=1)
-
-
-def force_form(monkeypatch, margin):
-    monkeypatch.setenv("GGS_DEBUG", "1")
-    if margin is None:
-        monkeypatch.delenv("GGS_DEBUG_MARGIN", raising=False)
-    else:
-        monkeypatch.setenv("GGS_DEBUG_MARGIN", margin)
 
 
 def force_path(monkeypatch, path):

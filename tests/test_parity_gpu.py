@@ -8,24 +8,9 @@ import numpy as np
 import pytest
 
 from ldagroupedgibbssampler_amd.corpus import even_split, random_corpus, synthetic_lda_corpus
+from tests.ranks import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.int64)
-
-
-def assert_bit_equal(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape, what
-    if a.dtype.kind == "f":
-        bad = bits(a) != bits(b)
-        # NaN payloads aside, every bit must match
-        assert not bad.any(), "%s: %d of %d differ, first at %s: %r vs %r" % (
-            what, bad.sum(), bad.size, np.argwhere(bad)[0], a[bad][0], b[bad][0])
-    else:
-        assert np.array_equal(a, b), "%s differs in %d places" % (what, (a != b).sum())
 
 
 # ---------------------------------------------------------------- primitives

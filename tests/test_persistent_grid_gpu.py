@@ -24,13 +24,11 @@ CU count like its z kernel (ggs_api.hip: launch_vs_chain and the list build behi
 each of the three at least three trips on one CU, the last one ragged (the z kernel's 200 documents come as the padded
 two-round order of 384 entries there: its last round is ragged by the entries that hold no document)."""
 import os
-import threading
 
 import numpy as np
 import pytest
 
 from ldagroupedgibbssampler_amd import priors
-from ldagroupedgibbssampler_amd.corpus import even_split
 from ldagroupedgibbssampler_amd.sharded import java_lcg_initial_z
 from tests import lightpclda_restatement as LR
 from tests import nzvs_restatement as NR
@@ -39,7 +37,7 @@ from tests import polyaurn_restatement as PR
 from tests import polyaurn_sparse_restatement as PSR
 from tests import spalias_priors_restatement as SPR
 from tests import spalias_restatement as SR
-from tests.test_native_exchange_gpu import ThreadTransport, assert_bit_equal
+from tests.ranks import assert_bit_equal, run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -346,82 +344,35 @@ def test_the_knob_reaches_the_corpus_lists(native, oracle, monkeypatch):
 
 
 # ---- an exchange: two ranks of one CU each against one handle -----------------------------------------------------------
-def _rank(native, tr, rank, world, whole, K, flags, kw, out, errs):
-    import torch
-    from ldagroupedgibbssampler_amd.sharded import _DevPtr
-    try:
-        dev = torch.device("cuda", 0)
-
-        def view(ptr, n, typestr):
-            return torch.as_tensor(_DevPtr(ptr, n, typestr), device=dev)
-
-        def reduce_scatter_i32(send, recv, count, stream):
-            torch.cuda.synchronize()
-            parts = tr.exchange(rank, view(send, count * world, "<i4").cpu().numpy().reshape(world, count))
-            view(recv, count, "<i4").copy_(torch.from_numpy(np.sum([p[rank] for p in parts], axis=0, dtype=np.int32)))
-            torch.cuda.synchronize()
-            return 0
-
-        def all_gather(typestr):
-            def cb(send, recv, count, stream):
-                torch.cuda.synchronize()
-                parts = tr.exchange(rank, view(send, count, typestr).cpu().numpy())
-                view(recv, count * world, typestr).copy_(torch.from_numpy(np.concatenate(parts)))
-                torch.cuda.synchronize()
-                return 0
-            return cb
-
-        def all_to_all_v(send, soff, scnt, recv, roff, rcnt, stream):
-            torch.cuda.synchronize()
-            total = max(soff[i] + scnt[i] for i in range(world))
-            mine = view(send, max(total, 1), "<i4").cpu().numpy()
-            everyone = tr.exchange(rank, [mine[soff[d]:soff[d] + scnt[d]].copy() for d in range(world)])
-            for s_ in range(world):
-                got = everyone[s_][rank]
-                if got.size:
-                    view(recv + 4 * roff[s_], got.size, "<i4").copy_(torch.from_numpy(got))
-            torch.cuda.synchronize()
-            return 0
-
-        bounds = even_split(whole.num_docs, world)
-        sub, doc_base, tok_base = whole.shard(bounds[rank], bounds[rank + 1])
+def _rank(native, whole, K, flags, kw):
+    """(make_handle, body) of a rank for tests/ranks.py's run_ranks"""
+    def make_handle(rank):
         assert os.environ.get(PG.KNOB) == "1"                       # set by the test body around both ranks' ggs_create
         h = native.GGSHandle(K, whole.num_types, ALPHA, BETA, SEED, flags=flags, **kw)
-        h.attach_exchange(rank, world, reduce_scatter_i32, all_gather("<f8"), all_gather("<i4"), all_to_all_v)
-        h.set_count_exchange("dense")
-        h.set_corpus(sub.doc_ptr, sub.tokens, doc_base, tok_base)
-        h.set_global_token_count(whole.num_tokens)
+        return h
+
+    def body(h, rank, sub, tok_base):
         z0 = java_lcg_initial_z(whole.num_tokens, K, 17)
         h.set_z(z0[tok_base:tok_base + sub.num_tokens], redraw_phi=True)
         info = h.launch_info()
         h.sweep(SWEEPS)
         h.check_invariants()
-        out[rank] = dict(z=h.get_z(), n_wk=h.get_type_topic_counts(), n_k=h.get_topic_totals(), phi=h.get_phi(), mean=h.get_phi_mean(), info=info,
-                         docs=sub.num_docs, tables=h.alias_tables() if flags & native.FLAG_SPALIAS else None)
-        h.close()
-    except BaseException as e:                      # noqa: BLE001 -- re-raised by the test body
-        errs.append(e)
-        tr.bar.abort()
+        return dict(z=h.get_z(), n_wk=h.get_type_topic_counts(), n_k=h.get_topic_totals(), phi=h.get_phi(), mean=h.get_phi_mean(), info=info,
+                    docs=sub.num_docs, tables=h.alias_tables() if flags & native.FLAG_SPALIAS else None)
+    return make_handle, body
 
 
 @pytest.mark.parametrize("scheme,K,kernel", [("spalias", 40, "spalias_wave_kernel"), ("polyaurn", 200, "pcgs_wave_kernel")])
 def test_two_ranks_of_one_cu_equal_one_handle(native, oracle, monkeypatch, scheme, K, kernel):
-    """Over the ThreadTransport: each rank's z kernel walks its 100 documents on one CU's grid, its Poisson draw (polyaurn) the
+    """Over the thread transport of tests/ranks.py: each rank's z kernel walks its 100 documents on one CU's grid, its Poisson draw (polyaurn) the
     100 topics of its slice in 8 tiles on two workgroups; the reference is one handle on the real grid."""
     world, V = 2, 900
     whole = corpus_of("wave", V)
     flags = flags_of(native, scheme) | native.FLAG_SAVE_PHI_MEAN
     kw = dict(phi_burn_in=1, phi_mean_thin=1)
-    tr, out, errs = ThreadTransport(world), [None] * world, []
     monkeypatch.setenv(PG.KNOB, "1")
-    ts = [threading.Thread(target=_rank, args=(native, tr, r, world, whole, K, flags, kw, out, errs)) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
+    out = run_ranks(world, whole, *_rank(native, whole, K, flags, kw), mode="dense")
     monkeypatch.delenv(PG.KNOB)
-    if errs:
-        raise errs[0]
     for r in range(world):
         assert kernel in out[r]["info"]["z_kernel"], out[r]["info"]
         assert out[r]["docs"] >= 3 * PG.CAP_WAVE

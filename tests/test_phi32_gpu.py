@@ -9,20 +9,9 @@ import numpy as np
 import pytest
 
 from ldagroupedgibbssampler_amd.corpus import random_corpus
+from tests.ranks import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def assert_bit_equal(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    bad = np.flatnonzero(bits(a).ravel() != bits(b).ravel())
-    assert bad.size == 0, "%s: %d of %d differ, first at %d" % (what, bad.size, a.size, bad[0])
 
 
 def make_pair(native, oracle, corpus, K, seed, zseed):

@@ -4,7 +4,6 @@ likelihood against pcgs; the host mirror end to end; misuse."""
 import os
 import subprocess
 import sys
-import threading
 
 import numpy as np
 import pytest
@@ -12,7 +11,7 @@ import pytest
 from ldagroupedgibbssampler_amd.corpus import Corpus, even_split, random_corpus, synthetic_lda_corpus
 from ldagroupedgibbssampler_amd.sharded import java_lcg_initial_z
 from tests import polyaurn_restatement as R
-from tests.test_native_exchange_gpu import ThreadTransport, assert_bit_equal
+from tests.ranks import assert_bit_equal, run_ranks, z_kernel
 
 pytestmark = pytest.mark.gpu
 
@@ -51,10 +50,6 @@ def run_pair(native, oracle, c, K, alpha, beta, sweeps, zseed=5, flags=0, burn_i
     assert_bit_equal(g.get_topic_totals(), n_kw.sum(axis=1).astype(np.int32), "n_k")
     assert_bit_equal(g.get_phi(), m.phi, "phi")
     return g, m
-
-
-def z_kernel(g):
-    return g.launch_info()["z_kernel"]
 
 
 @pytest.mark.parametrize("K,alpha,beta", [(3, 5.0, 7.0), (20, 0.1, 0.01)])
@@ -152,61 +147,20 @@ def test_topic_without_tokens_gives_a_zero_row(native, oracle):
 
 
 # ---- sharded: bit-identical to one handle -------------------------------------------------------------------------
-def _rank(native, tr, rank, world, whole, K, mode, sweeps, out, errs):
-    import torch
-    from ldagroupedgibbssampler_amd.sharded import _DevPtr
-    try:
-        dev = torch.device("cuda", 0)
+def _rank(native, whole, K, sweeps):
+    """(make_handle, body) of a rank for tests/ranks.py's run_ranks"""
+    def make_handle(rank):
+        return native.GGSHandle(K, whole.num_types, 0.1, 0.01, SEED, flags=native.FLAG_POLYAURN | native.FLAG_SAVE_PHI_MEAN, phi_burn_in=1,
+                                phi_mean_thin=2, alias_poisson_threshold=20)
 
-        def view(ptr, n, typestr):
-            return torch.as_tensor(_DevPtr(ptr, n, typestr), device=dev)
-
-        def reduce_scatter_i32(send, recv, count, stream):
-            torch.cuda.synchronize()
-            parts = tr.exchange(rank, view(send, count * world, "<i4").cpu().numpy().reshape(world, count))
-            view(recv, count, "<i4").copy_(torch.from_numpy(np.sum([p[rank] for p in parts], axis=0, dtype=np.int32)))
-            torch.cuda.synchronize()
-            return 0
-
-        def all_gather(typestr):
-            def cb(send, recv, count, stream):
-                torch.cuda.synchronize()
-                parts = tr.exchange(rank, view(send, count, typestr).cpu().numpy())
-                view(recv, count * world, typestr).copy_(torch.from_numpy(np.concatenate(parts)))
-                torch.cuda.synchronize()
-                return 0
-            return cb
-
-        def all_to_all_v(send, soff, scnt, recv, roff, rcnt, stream):
-            torch.cuda.synchronize()
-            total = max(soff[i] + scnt[i] for i in range(world))
-            mine = view(send, max(total, 1), "<i4").cpu().numpy()
-            everyone = tr.exchange(rank, [mine[soff[d]:soff[d] + scnt[d]].copy() for d in range(world)])
-            for s_ in range(world):
-                got = everyone[s_][rank]
-                if got.size:
-                    view(recv + 4 * roff[s_], got.size, "<i4").copy_(torch.from_numpy(got))
-            torch.cuda.synchronize()
-            return 0
-
-        bounds = even_split(whole.num_docs, world)
-        sub, doc_base, tok_base = whole.shard(bounds[rank], bounds[rank + 1])
-        h = native.GGSHandle(K, whole.num_types, 0.1, 0.01, SEED, flags=native.FLAG_POLYAURN | native.FLAG_SAVE_PHI_MEAN, phi_burn_in=1,
-                             phi_mean_thin=2, alias_poisson_threshold=20)
-        h.attach_exchange(rank, world, reduce_scatter_i32, all_gather("<f8"), all_gather("<i4"), all_to_all_v)
-        h.set_count_exchange(mode)
-        h.set_corpus(sub.doc_ptr, sub.tokens, doc_base, tok_base)
-        h.set_global_token_count(whole.num_tokens)
+    def body(h, rank, sub, tok_base):
         z0 = java_lcg_initial_z(whole.num_tokens, K, 17)
         h.set_z(z0[tok_base:tok_base + sub.num_tokens], redraw_phi=True)
         h.sweep(sweeps)
         h.check_invariants()
-        out[rank] = dict(z=h.get_z(), nwk=h.get_type_topic_counts(), nk=h.get_topic_totals(), phi=h.get_phi(), mean=h.get_phi_mean(),
-                         how=h.count_exchange())
-        h.close()
-    except BaseException as e:                      # noqa: BLE001 -- re-raised by the test body
-        errs.append(e)
-        tr.bar.abort()
+        return dict(z=h.get_z(), nwk=h.get_type_topic_counts(), nk=h.get_topic_totals(), phi=h.get_phi(), mean=h.get_phi_mean(),
+                    how=h.count_exchange())
+    return make_handle, body
 
 
 def one_handle(native, whole, K, sweeps):
@@ -224,14 +178,7 @@ def one_handle(native, whole, K, sweeps):
 def test_sharded_runs_equal_one_handle(native, oracle, world, mode, K, V):
     whole = random_corpus(310, V, 90, seed=K + V, empty_every=9)
     sweeps = 5
-    tr, out, errs = ThreadTransport(world), [None] * world, []
-    ts = [threading.Thread(target=_rank, args=(native, tr, r, world, whole, K, mode, sweeps, out, errs)) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
-    if errs:
-        raise errs[0]
+    out = run_ranks(world, whole, *_rank(native, whole, K, sweeps), mode=mode)
     ref = one_handle(native, whole, K, sweeps)
     bounds = even_split(whole.num_docs, world)
     z = np.concatenate([out[r]["z"] for r in range(world)])

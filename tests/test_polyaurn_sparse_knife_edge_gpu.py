@@ -8,19 +8,12 @@ import numpy as np
 import pytest
 
 from tests import polyaurn_sparse_knife_edge as KE
+from tests.ranks import force_form
 
 pytestmark = pytest.mark.gpu
 
 KERNEL = "polyaurn_sparse_wave_kernel (wave per document)"
 FORMS = [None, "1e30"]
-
-
-def force_form(monkeypatch, margin):
-    monkeypatch.setenv("GGS_DEBUG", "1")
-    if margin is None:
-        monkeypatch.delenv("GGS_DEBUG_MARGIN", raising=False)
-    else:
-        monkeypatch.setenv("GGS_DEBUG_MARGIN", margin)
 
 
 def row_key(ke, sv, r, j):

@@ -5,7 +5,6 @@ through ggs_set_phi, sharded over an exchange, and the misuse the C-ABI refuses.
 import os
 import subprocess
 import sys
-import threading
 
 import numpy as np
 import pytest
@@ -14,7 +13,7 @@ from ldagroupedgibbssampler_amd import priors
 from ldagroupedgibbssampler_amd.corpus import random_corpus
 from ldagroupedgibbssampler_amd.sharded import NativeExchange, ShardedGGS, java_lcg_initial_z
 from tests import spalias_priors_restatement as PR
-from tests.test_native_exchange_gpu import ThreadTransport, assert_bit_equal
+from tests.ranks import assert_bit_equal, run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -216,59 +215,28 @@ def test_sample_z_given_phi_after_set_phi(native, oracle):
 FLAGS_SHARDED = dict(phi_burn_in=1, phi_mean_thin=2)
 
 
-def _rank(native, tr, rank, world, whole, K, mode, sweeps, cells, out, errs):
-    import torch
-    from ldagroupedgibbssampler_amd.sharded import _DevPtr
-    try:
-        dev = torch.device("cuda", 0)
+def _rank(native, world, whole, K, sweeps, cells):
+    """(make_handle, through, body) of a rank for tests/ranks.py's run_ranks: ShardedGGS cuts the shard, attaches through the
+    engine it is handed and sets the corpus"""
+    sharded = {}
 
-        def view(ptr, n, typestr):
-            return torch.as_tensor(_DevPtr(ptr, n, typestr), device=dev)
+    def make_handle(rank):
+        return native.GGSHandle(K, whole.num_types, 0.1, 0.01, SEED, flags=native.FLAG_SPALIAS | native.FLAG_SAVE_PHI_MEAN, **FLAGS_SHARDED)
 
-        def reduce_scatter_i32(send, recv, count, stream):
-            torch.cuda.synchronize()
-            parts = tr.exchange(rank, view(send, count * world, "<i4").cpu().numpy().reshape(world, count))
-            view(recv, count, "<i4").copy_(torch.from_numpy(np.sum([p[rank] for p in parts], axis=0, dtype=np.int32)))
-            torch.cuda.synchronize()
-            return 0
-
-        def all_gather(typestr):
-            def cb(send, recv, count, stream):
-                torch.cuda.synchronize()
-                parts = tr.exchange(rank, view(send, count, typestr).cpu().numpy())
-                view(recv, count * world, typestr).copy_(torch.from_numpy(np.concatenate(parts)))
-                torch.cuda.synchronize()
-                return 0
-            return cb
-
-        def all_to_all_v(send, soff, scnt, recv, roff, rcnt, stream):
-            torch.cuda.synchronize()
-            total = max(soff[i] + scnt[i] for i in range(world))
-            mine = view(send, max(total, 1), "<i4").cpu().numpy()
-            everyone = tr.exchange(rank, [mine[soff[d]:soff[d] + scnt[d]].copy() for d in range(world)])
-            for s_ in range(world):
-                got = everyone[s_][rank]
-                if got.size:
-                    view(recv + 4 * roff[s_], got.size, "<i4").copy_(torch.from_numpy(got))
-            torch.cuda.synchronize()
-            return 0
-
-        def attach(engine):
-            engine.attach_exchange(rank, world, reduce_scatter_i32, all_gather("<f8"), all_gather("<i4"), all_to_all_v)
-            engine.set_count_exchange(mode)
+    def through(h, attach, rank):
+        def exchange_factory(engine):
+            attach(engine)
             return NativeExchange()
+        sharded[rank] = ShardedGGS(h, exchange_factory, whole, rank, world, topic_priors=cells)     # sharded.py hands every rank the same cells
 
-        h = native.GGSHandle(K, whole.num_types, 0.1, 0.01, SEED, flags=native.FLAG_SPALIAS | native.FLAG_SAVE_PHI_MEAN, **FLAGS_SHARDED)
-        sh = ShardedGGS(h, attach, whole, rank, world, topic_priors=cells)         # sharded.py hands every rank the same cells
+    def body(h, rank, sub, tok_base):
+        sh = sharded[rank]
         sh.set_z_global(java_lcg_initial_z(whole.num_tokens, K, 17))
         sh.sweep(sweeps)
         h.check_invariants()
-        out[rank] = dict(z=h.get_z(), nwk=h.get_type_topic_counts(), nk=h.get_topic_totals(), phi=h.get_phi(), mean=h.get_phi_mean(),
-                         how=h.count_exchange(), tables=h.alias_tables(), priors=h.get_topic_priors(), info=h.exchange_info())
-        h.close()
-    except BaseException as e:                      # noqa: BLE001 -- re-raised by the test body
-        errs.append(e)
-        tr.bar.abort()
+        return dict(z=h.get_z(), nwk=h.get_type_topic_counts(), nk=h.get_topic_totals(), phi=h.get_phi(), mean=h.get_phi_mean(),
+                    how=h.count_exchange(), tables=h.alias_tables(), priors=h.get_topic_priors(), info=h.exchange_info())
+    return make_handle, through, body
 
 
 def one_handle(native, whole, K, sweeps, cells):
@@ -295,14 +263,8 @@ def sharded_case(K, V):
 def test_sharded_runs_equal_one_handle(native, oracle, world, mode, K, V):
     whole, cells = sharded_case(K, V)
     sweeps = 4
-    tr, out, errs = ThreadTransport(world), [None] * world, []
-    ts = [threading.Thread(target=_rank, args=(native, tr, r, world, whole, K, mode, sweeps, cells, out, errs)) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
-    if errs:
-        raise errs[0]
+    make_handle, through, body = _rank(native, world, whole, K, sweeps, cells)
+    out = run_ranks(world, whole, make_handle, body, mode=mode, through=through)
     ref = one_handle(native, whole, K, sweeps, cells)
     masked = ref["priors"] == 0.0
     assert masked.any() and (ref["phi"][masked] == 0.0).all() and ref["phi"][~masked].any()
