@@ -23,7 +23,7 @@ def main():
     ap.add_argument("dataset")
     ap.add_argument("--stoplist", default=None, help="one stop word per line (LDAConfiguration: stoplist.txt)")
     ap.add_argument("--rare-threshold", type=int, default=0)
-    ap.add_argument("--scheme", default="ggs", choices=list(SCHEME_FLAGS) + ["spalias_priors"])   # spalias_priors: spalias's flag and --topic-priors
+    ap.add_argument("--scheme", default="ggs", choices=list(SCHEME_FLAGS) + ["spalias_priors", "lightpcldaw2"])   # spalias_priors: spalias's flag and --topic-priors; lightpcldaw2: its class, below
     ap.add_argument("--topic-priors", default=None, metavar="FILE",
                     help="scheme spalias_priors: lines `topic,word,word,...`; those words may only belong to that topic (topic_prior_filename)")
     ap.add_argument("--vs-prior", type=float, default=0.5, metavar="X",
@@ -69,6 +69,9 @@ def main():
     elif args.scheme == "adlda":
         from ldagroupedgibbssampler_amd.sampler import ADLDA
         model = ADLDA(cfg)
+    elif args.scheme == "lightpcldaw2":
+        from ldagroupedgibbssampler_amd.sampler import LightPCLDAtypeTopicProposal
+        model = LightPCLDAtypeTopicProposal(cfg)
     else:
         model = create_model(cfg)
     model.setRandomSeed(cfg.get_seed())

@@ -183,7 +183,7 @@ enum {
                                      Results are bit-identical to one handle.  K up to 4096, any document length.  With any of GGS_FLAG_COLLAPSED,
                                      GGS_FLAG_POLYAURN, GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE,
                                      GGS_FLAG_LIGHTCOLLAPSED: GGS_ERR_BAD_ARG.  A new bit, not a new ABI version. */
-  GGS_FLAG_ADLDA = 1 << 10        /* scheme=adlda (ADLDA, ParallelLDA.java:409-412; MyWorkerRunnable.sampleTopicsForOneDoc,
+  GGS_FLAG_ADLDA = 1 << 10,       /* scheme=adlda (ADLDA, ParallelLDA.java:409-412; MyWorkerRunnable.sampleTopicsForOneDoc,
                                      MyWorkerRunnable.java:32-409): the collapsed model -- no theta, no Phi; ggs_get_phi, the exchange,
                                      the likelihoods and ggs_check_invariants exactly as under GGS_FLAG_COLLAPSED -- under the SparseLDA
                                      bucket z step of Yao, Mimno and McCallum: the exact conditional of GGS_FLAG_COLLAPSED's parallel
@@ -208,6 +208,29 @@ enum {
                                      length.  With any of GGS_FLAG_COLLAPSED, GGS_FLAG_PCGS, GGS_FLAG_POLYAURN, GGS_FLAG_SPALIAS,
                                      GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE, GGS_FLAG_LIGHTCOLLAPSED, GGS_FLAG_NZVSSPALIAS:
                                      GGS_ERR_BAD_ARG.  A new bit, not a new ABI version. */
+  GGS_FLAG_LIGHTPCLDAW2 = 1 << 11 /* scheme=lightpcldaw2 (LightPCLDAtypeTopicProposal, ParallelLDA.createModel's "lightpcldaw2";
+                                     LightPCLDAtypeTopicProposal.java:101-274): the pcgs model (implied: GGS_FLAG_PCGS is set
+                                     internally; Phi, counts, merge, phi mean and exchange exactly as pcgs) under the LightLDA z step
+                                     with GGS_FLAG_LIGHTCOLLAPSED's word proposal.  At the head of every z step, on the corpus-wide
+                                     sweep-start counts (with an exchange: gathered there), per word w: the ascending list of its
+                                     topics with n_wk > 0 (ggs_get_word_topic_lists), p_i = n_wk / ((double)n_k + betaSum),
+                                     type_norm[w] their i-order sum, the alias table of the nw[w] values p_i / type_norm[w]
+                                     (ggs_get_alias_tables) and tokensPerType[w] -- the tables the class declares
+                                     (TypeTopicTableBuilderFactory, :72-77; a JVM run never installs them).  Per
+                                     token, G = the sweep-start counts, nothing moved for the token in flight, bhat[k] =
+                                     (double)n_k + betaSum: the word proposal t as under GGS_FLAG_LIGHTCOLLAPSED; if t != s,
+                                     pi_w = (phi[t][w] * (alpha[s] + ni[t]) * (beta + G[w][s]) * bhat[t]) /
+                                     (phi[s][w] * (alpha[s] + ni[s]) * (beta + G[w][t]) * bhat[s]), each product left to right
+                                     (:270-272); then GGS_FLAG_LIGHTPCLDA's document proposal, word for word, the token returning
+                                     to its OLD topic when the proposal equals the current one.  The uniforms are
+                                     GGS_FLAG_LIGHTPCLDA's four; ggs_get_mh_stats keeps the same three counters.  A table draw with
+                                     i == nw[w] and a beta- or alpha-branch topic == K: GGS_ERR_INVALID_TOPIC.
+                                     ggs_sample_z_given_phi as under GGS_FLAG_LIGHTPCLDA, the tables rebuilt from the merged counts
+                                     at the head of each iteration.  ggs_get_theta: GGS_ERR_UNSUPPORTED (no theta is kept; the
+                                     diagnostics that draw one allocate it when first asked).  The chain is approximate as the
+                                     reference writes it and is not repaired.  Sharded runs are bit-identical to one handle.
+                                     K up to 4096, any document length.  With any other scheme flag but GGS_FLAG_PCGS:
+                                     GGS_ERR_BAD_ARG, answered before a device is asked for.  A new bit, not a new ABI version. */
 };
 
 /* RNG stream addressing.  The reference draws from ThreadLocalRandom and a
@@ -506,7 +529,7 @@ int ggs_get_z_parts(ggs_handle *h, int32_t *parts);
  * assuming it: *kernel = 0 whole-row tile kernel, 1 score-register kernels (K <= 160), 2 one-pass streaming kernel,
  * 3 its two-pass cross-check, 4 pcgs lane-per-document, 5 pcgs wave-per-document, 6 spalias wave-per-document,
  * 7 lightpclda wave-per-document, 8 polyaurn_sparse wave-per-document, 9 lightcollapsed wave-per-document,
- * 10 nzvsspalias wave-per-document; *form (kernel 1 only, else 0) =
+ * 10 nzvsspalias wave-per-document, 11 adlda wave-per-document, 12 lightpcldaw2 wave-per-document; *form (kernel 1 only, else 0) =
  * 1 split (cold chunks and hot chunks as two kernels side by side), 2 fused (one kernel takes both in turn);
  * *calibrated = 1 once the first z step of the corpus has timed both forms and kept the faster (0 before that, and
  * when a form is forced or there is nothing to split).  ABI version 4. */
@@ -526,7 +549,7 @@ int ggs_debug_poisson(int32_t device_id, double beta, int32_t threshold, uint64_
  * A draw x in [0, 1) from word w's table: ups = x * K, i = (int)ups, topic = (ups - i) > ps[w][i] ? a[w][i] : i.  K up to 4096. */
 int ggs_debug_alias(int32_t device_id, int32_t V, int32_t K, const double *phi, const double *alpha, double *ps, int32_t *a, double *type_norm);
 /* the tables of the handle's current Phi (GGS_FLAG_SPALIAS, GGS_FLAG_LIGHTPCLDA, GGS_FLAG_POLYAURN_SPARSE or GGS_FLAG_NZVSSPALIAS; GGS_ERR_STATE
- * otherwise or before the first Phi); any of the three outputs may be null.  GGS_FLAG_LIGHTCOLLAPSED: the tables of the handle's
+ * otherwise or before the first Phi); any of the three outputs may be null.  GGS_FLAG_LIGHTCOLLAPSED and GGS_FLAG_LIGHTPCLDAW2: the tables of the handle's
  * current counts, which the next sweep builds at its head (after ggs_set_corpus, outside a split sweep): the call itself
  * rebuilds all V lists and tables from the corpus-wide counts, overwriting those the last z step used, and with an exchange
  * attached gathering the counts is a collective -- every rank makes the call, in the same order.  The first nw[w] entries of row w are
@@ -560,11 +583,11 @@ int ggs_get_topic_priors(ggs_handle *h, double *priors /*[K][V]*/);
 /* scheme=lightpclda's Metropolis-Hastings counters, cumulative since ggs_set_corpus (the three the reference keeps
  * commented out, LightPCLDA.java:28-44), every token in exactly one: out[0] tokens whose word proposal was accepted and
  * kept, out[1] tokens whose document proposal was accepted, out[2] tokens left on their old topic.  The same three classes
- * under GGS_FLAG_LIGHTCOLLAPSED.  GGS_ERR_STATE without either flag. */
+ * under GGS_FLAG_LIGHTCOLLAPSED and GGS_FLAG_LIGHTPCLDAW2.  GGS_ERR_STATE without one of these flags. */
 int ggs_get_mh_stats(ggs_handle *h, int64_t out[3]);
 /* scheme=polyaurn_sparse's word lists of the handle's current Phi: nw[w] = the number of topics with phi[k][w] != 0.0,
  * topics[w][0 .. nw[w]) those topics in ascending order, -1 behind them.  Either output may be null.  GGS_ERR_STATE without
- * GGS_FLAG_POLYAURN_SPARSE or before the first Phi.  GGS_FLAG_LIGHTCOLLAPSED: the lists of the handle's current counts, nw[w] = the
+ * GGS_FLAG_POLYAURN_SPARSE or before the first Phi.  GGS_FLAG_LIGHTCOLLAPSED and GGS_FLAG_LIGHTPCLDAW2: the lists of the handle's current counts, nw[w] = the
  * number of topics with n_wk > 0 (0 for a word without tokens); the same rebuild and, with an exchange, the same collective as
  * ggs_get_alias_tables under that flag.  GGS_FLAG_ADLDA: the same lists of the current counts.  GGS_FLAG_NZVSSPALIAS: the lists
  * as that flag defines them (the drawn cells). */

@@ -15,7 +15,7 @@ final class GGSNative {
 	static { System.loadLibrary("ggs_jni"); }          // libggs_jni.so -> libggs_hip.so
 	private GGSNative() { }
 
-	static final int FLAG_PARANOID = 1, FLAG_SAVE_PHI_MEAN = 2, FLAG_PCGS = 4, FLAG_COLLAPSED = 8, FLAG_POLYAURN = 16, FLAG_SPALIAS = 32, FLAG_LIGHTPCLDA = 64, FLAG_POLYAURN_SPARSE = 128, FLAG_LIGHTCOLLAPSED = 256, FLAG_ADLDA = 1024;   // GGS_FLAG_*
+	static final int FLAG_PARANOID = 1, FLAG_SAVE_PHI_MEAN = 2, FLAG_PCGS = 4, FLAG_COLLAPSED = 8, FLAG_POLYAURN = 16, FLAG_SPALIAS = 32, FLAG_LIGHTPCLDA = 64, FLAG_POLYAURN_SPARSE = 128, FLAG_LIGHTCOLLAPSED = 256, FLAG_ADLDA = 1024, FLAG_LIGHTPCLDAW2 = 2048;   // GGS_FLAG_*
 
 	// ---- one handle = one GPU ------------------------------------------------------------------------------------
 	static native long nCreate(int numTopics, int numTypes, double[] alpha, double beta, long seed, int deviceId,

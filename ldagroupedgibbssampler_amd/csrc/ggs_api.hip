@@ -27,6 +27,7 @@
 #include "ggs_phi_vs.hpp"
 #include "ggs_z_lightpc.hpp"
 #include "ggs_z_lightcollapsed.hpp"
+#include "ggs_z_lightpcw2.hpp"
 #include "ggs_z_adlda.hpp"
 #include "ggs_loglik.hpp"
 #include "ggs_heldout.hpp"
@@ -84,7 +85,7 @@ constexpr int kThetaBlock = 256;
 // What a handle samples and how: derived once from ggs_config::flags (scheme_of).  Every scheme but ggs runs the pcgs
 // machinery: no theta in the chain, a document order instead of chunk lists, the plan's lane / wave / ... entries.  What a
 // scheme is stands in its row of kSchemes, below the launch plan.
-enum class Scheme { ggs, pcgs, collapsed, polyaurn, spalias, lightpclda, polyaurn_sparse, lightcollapsed, nzvsspalias, adlda };
+enum class Scheme { ggs, pcgs, collapsed, polyaurn, spalias, lightpclda, polyaurn_sparse, lightcollapsed, nzvsspalias, adlda, lightpcldaw2 };
 
 // One kernel as a handle launches it: the function, its workgroup, its dynamic LDS and the workgroups per CU of its
 // persistent grid.  The table kernels' LDS is given without table rows (they differ by corpus).
@@ -121,8 +122,9 @@ struct LaunchPlan {
   int32_t theta_docs_main = 0, theta_lds_main = 0;   // ... where the theta draw is the critical leg (theta_main)
   // scheme pcgs / collapsed / polyaurn: a lane or a wave per document; spalias: the table build and the sparse walk (LDS per corpus);
   // lightpclda: the same table build and the Metropolis-Hastings step; polyaurn_sparse: the table build, the words' lists and
-  // the doubly sparse walk (LDS per corpus); lightcollapsed: the lists and tables over the counts and its Metropolis-Hastings step
-  KernelLaunch lane, wave, alias, spalias, lightpc, serial, wordlist, pusparse, countalias, lightcol;
+  // the doubly sparse walk (LDS per corpus); lightcollapsed: the lists and tables over the counts and its Metropolis-Hastings step;
+  // lightpcldaw2: the same build and its own Metropolis-Hastings step over Phi
+  KernelLaunch lane, wave, alias, spalias, lightpc, serial, wordlist, pusparse, countalias, lightcol, lightpcw2;
   // nzvsspalias (ggs_phi_vs.hpp): the indicator chain's three kernels (its LDS comes with V), the list build from the drawn
   // cells (wordlist stays the build from phi != 0.0, after ggs_set_phi) and the z step
   KernelLaunch vsbits, vschain, wordmask, nzvs;
@@ -130,13 +132,13 @@ struct LaunchPlan {
   KernelLaunch adhead, adlists, adlda;
   bool wave_forced = false;            // ... because of K; otherwise per corpus (a document of 32 768 tokens or more)
   int32_t alias_wpb = 0;
-  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse, &countalias, &lightcol, &vsbits, &wordmask, &nzvs, &adlda}; }   // not vschain: it has static LDS, and its dynamic LDS stays below the default cap
+  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse, &countalias, &lightcol, &lightpcw2, &vsbits, &wordmask, &nzvs, &adlda}; }   // not vschain: it has static LDS, and its dynamic LDS stays below the default cap
 };
 
 // One row per scheme, indexed by the enum: everything the host code asks about a scheme that is not its own buffers or its own
 // launches.  A new scheme is a row here, its kernel header, its plan entry (plan_launches) and its own buffers (ggs_create).
 enum : uint32_t { kHasAlias = 1, kHasTables = 2, kCountForm = 4, kCountsOnly = 8, kHasWordLists = 16, kDoublySparse = 32, kSparseWalk = 64, kHasMh = 128,
-                  kPoissonPhi = 256, kSparseStats = 512 };   // SchemeRow::caps: what the predicates below the table ask
+                  kPoissonPhi = 256, kSparseStats = 512, kCountTables = 1024, kNoTheta = 2048 };   // SchemeRow::caps: what the predicates below the table ask
 struct SchemeRow {
   const char *name;                       // as the documentation spells it; the flag is GGS_FLAG_<NAME>
   int32_t flag, refused;                  // its own bit of ggs_config::flags (ggs: none), the bits that are GGS_ERR_BAD_ARG beside it
@@ -161,14 +163,17 @@ constexpr SchemeRow kSchemes[] = {
     {"polyaurn_sparse", GGS_FLAG_POLYAURN_SPARSE, kModelFlags | GGS_FLAG_SPALIAS | GGS_FLAG_LIGHTPCLDA, 8, &LaunchPlan::pusparse, spalias_lds_bytes, kGgsInvalidTopic,
      kHasAlias | kHasTables | kHasWordLists | kDoublySparse | kSparseWalk | kPoissonPhi | kSparseStats},
     {"lightcollapsed", GGS_FLAG_LIGHTCOLLAPSED, kLightFlags | GGS_FLAG_PCGS, 9, &LaunchPlan::lightcol, nullptr, "Collapsed Light-LDA: Sampled invalid topic." /* CollapsedLightLDA.java:957-959 */,
-     kHasTables | kCountForm | kCountsOnly | kHasWordLists | kHasMh},
+     kHasTables | kCountForm | kCountsOnly | kHasWordLists | kHasMh | kCountTables},
     {"nzvsspalias", GGS_FLAG_NZVSSPALIAS, kLightFlags | GGS_FLAG_LIGHTCOLLAPSED, 10, &LaunchPlan::nzvs, spalias_lds_bytes, kGgsInvalidTopic,
      kHasAlias | kHasTables | kHasWordLists | kDoublySparse | kSparseWalk | kSparseStats},
     {"adlda", GGS_FLAG_ADLDA, kLightFlags | GGS_FLAG_PCGS | GGS_FLAG_LIGHTCOLLAPSED | GGS_FLAG_NZVSSPALIAS, 11, &LaunchPlan::adlda, adlda_lds_bytes, "ADLDA: New topic not sampled." /* MyWorkerRunnable.java:332-336 */,
      kCountForm | kCountsOnly | kHasWordLists | kSparseStats},
+    // the pcgs model (GGS_FLAG_PCGS beside it is accepted) under lightcollapsed's tables and a z step of its own: no other scheme's flag beside it
+    {"lightpcldaw2", GGS_FLAG_LIGHTPCLDAW2, kLightFlags | GGS_FLAG_LIGHTCOLLAPSED | GGS_FLAG_NZVSSPALIAS | GGS_FLAG_ADLDA, 12, &LaunchPlan::lightpcw2, nullptr,
+     "Light PC-LDA (Type topic proposal): Sampled invalid topic." /* LightPCLDAtypeTopicProposal.java:159-161 */, kHasTables | kHasWordLists | kHasMh | kCountTables | kNoTheta},
 };
 constexpr int kNumSchemes = (int)(sizeof(kSchemes) / sizeof(kSchemes[0]));
-static_assert(kNumSchemes == (int)Scheme::adlda + 1, "one row per Scheme, in the enum's order");
+static_assert(kNumSchemes == (int)Scheme::lightpcldaw2 + 1, "one row per Scheme, in the enum's order");
 constexpr const SchemeRow &row_of(Scheme s) { return kSchemes[(int)s]; }
 constexpr bool has(Scheme s, uint32_t cap) { return (row_of(s).caps & cap) != 0; }
 constexpr bool pcgs_family(Scheme s) { return row_of(s).flag != 0; }
@@ -182,6 +187,8 @@ constexpr bool sparse_walk(Scheme s) { return has(s, kSparseWalk); }         // 
 constexpr bool has_mh(Scheme s) { return has(s, kHasMh); }                   // d_mh: a Metropolis-Hastings z step
 constexpr bool poisson_phi(Scheme s) { return has(s, kPoissonPhi); }         // Phi drawn as polyaurn draws it
 constexpr bool has_sparse_stats(Scheme s) { return has(s, kSparseStats); }   // d_ps_stats: ggs_get_sparse_stats
+constexpr bool count_tables(Scheme s) { return has(s, kCountTables); }       // count_alias_build_kernel at the head of the z step: lists, tables, d_tpt over the sweep-start counts
+constexpr bool no_theta(Scheme s) { return has(s, kNoTheta); }               // a Phi scheme that keeps no theta: the diagnostics that draw one allocate it (ensure_diag_theta)
 constexpr bool wave_only(Scheme s) { return row_of(s).entry != nullptr; }   // no lane-per-document form: K <= kPcgsWaveMaxTopics, a wave per order entry
 // "F needs GGS_FLAG_A, GGS_FLAG_B or GGS_FLAG_C": the flags of the schemes with `cap`, for the getters that only they answer
 std::string needs_flag(const char *fn, uint32_t cap) {
@@ -261,7 +268,7 @@ struct ggs_handle {
   bool alpha_symmetric = false;                        // every alpha[k] has the bits of alpha[0]: the theta draw's count-0 cells share their gamma constants per document
   unsigned long long *d_mh = nullptr;                  // [3]: ggs_get_mh_stats, zeroed by ggs_set_corpus
   double *d_ad_den0 = nullptr, *d_ad_s0 = nullptr;     // scheme=adlda (ggs_z_adlda.hpp): [K] den0 and [1] S0 of the sweep-start counts
-  int32_t *d_tpt = nullptr;                            // scheme=lightcollapsed (ggs_z_lightcollapsed.hpp): [V] tokensPerType of the sweep-start counts
+  int32_t *d_tpt = nullptr;                            // scheme=lightcollapsed, lightpcldaw2 (count_alias_build_kernel): [V] tokensPerType of the sweep-start counts
   // scheme=polyaurn_sparse (ggs_z_polyaurn_sparse.hpp): polyaurn's Phi, spalias's tables and document lists, and per word the
   // ascending list of its topics with phi != 0, rebuilt with the tables
   uint16_t *d_nzw = nullptr;                           // [V][K]
@@ -1043,7 +1050,7 @@ int launch_adlda_head(ggs_handle *h) {
 int launch_sweep_head(ggs_handle *h) {
   const int rc = launch_magnitude(h);                  // the counts gathered, tokensPerTopic in step with them
   if (rc) return rc;
-  if (h->scheme == Scheme::lightcollapsed) return launch_count_alias_build(h);
+  if (count_tables(h->scheme)) return launch_count_alias_build(h);   // lightpcldaw2 too: Phi is not touched
   if (h->scheme == Scheme::adlda) return launch_adlda_head(h);
   // collapsed: the ratios (beta + n_wk)/(betaSum + n_k) into phiT, for the pcgs loop over them
   hipLaunchKernelGGL(psi_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, h->d_n_wk, h->d_n_k, h->beta, h->beta * (double)h->V, h->d_phiT,
@@ -1352,11 +1359,17 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
     pl.lightpc = {reinterpret_cast<const void *>(lightpc_wave_kernel), 64, (int)lightpc_lds_bytes(K), 0};
     pl.lightpc.per_cu = resident_waves_per_cu(pl.lightpc.fn, pl.lightpc.lds);
   }
-  if (scheme == Scheme::lightcollapsed) {
+  if (count_tables(scheme)) {
     // the tables over the counts: alias_build_kernel's words per workgroup and residency; the z step: lightpc's rule
     pl.alias_wpb = alias_words_per_block(K);
     pl.countalias = {reinterpret_cast<const void *>(count_alias_build_kernel), 64, (int)count_alias_lds_bytes(K, pl.alias_wpb), 0};
     pl.countalias.per_cu = lds_workgroups_per_cu(pl.countalias.lds, 16);
+  }
+  if (scheme == Scheme::lightpcldaw2) {
+    pl.lightpcw2 = {reinterpret_cast<const void *>(lightpcw2_wave_kernel), 64, (int)lightpcw2_lds_bytes(K), 0};
+    pl.lightpcw2.per_cu = resident_waves_per_cu(pl.lightpcw2.fn, pl.lightpcw2.lds);
+  }
+  if (scheme == Scheme::lightcollapsed) {
     pl.lightcol = {reinterpret_cast<const void *>(lightcollapsed_wave_kernel), 64, (int)lightcollapsed_lds_bytes(K), 0};
     pl.lightcol.per_cu = resident_waves_per_cu(pl.lightcol.fn, pl.lightcol.lds);
   }
@@ -1383,9 +1396,12 @@ int launch_pcgs_z(ggs_handle *h) {
   if (count_form(h->scheme)) {
     if ((rc = launch_sweep_head(h))) return rc;
     pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;   // betaSum = beta * numTypes, MSLDA:136
+  } else if (count_tables(h->scheme)) {                // lightpcldaw2: Phi as it stands, the lists and tables of the corpus-wide sweep-start counts
+    if ((rc = launch_sweep_head(h))) return rc;
+    pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;
   }
   PolyaurnSparseParams sp{};                           // spalias's kernel takes its base, SpaliasParams
-  LightpcParams lp{}; LightCollapsedParams lc{}; AdldaParams ad{};
+  LightpcParams lp{}; LightCollapsedParams lc{}; AdldaParams ad{}; LightpcW2Params lw{};
   void *args[] = {&pp, &h->margin_scale};              // the wave-per-document kernel takes both, the lane-per-document kernels the first
   if (sparse_walk(h->scheme)) {
     // one wave per document over its non-zero topics (ggs_z_spalias.hpp), or over the word's where they are fewer
@@ -1399,6 +1415,9 @@ int launch_pcgs_z(ggs_handle *h) {
   } else if (h->scheme == Scheme::lightcollapsed) {    // one wave per document over the tables of the sweep-start counts
     lc.b = pp; lc.ps = h->d_alias_ps; lc.a = h->d_alias_a; lc.nzw = h->d_nzw; lc.nw = h->d_nw; lc.tpt = h->d_tpt; lc.mh = h->d_mh; lc.alpha_sum = h->alpha_sum;
     args[0] = &lc;
+  } else if (h->scheme == Scheme::lightpcldaw2) {      // one wave per document over Phi and the tables of the sweep-start counts (ggs_z_lightpcw2.hpp)
+    lw.b = pp; lw.ps = h->d_alias_ps; lw.a = h->d_alias_a; lw.nzw = h->d_nzw; lw.nw = h->d_nw; lw.tpt = h->d_tpt; lw.mh = h->d_mh; lw.alpha_sum = h->alpha_sum;
+    args[0] = &lw;
   } else if (h->scheme == Scheme::adlda) {             // one wave per document over den0, S0 and the lists of the sweep-start counts
     ad.b = pp; ad.den0 = h->d_ad_den0; ad.s0 = h->d_ad_s0; ad.nzw = h->d_nzw; ad.nw = h->d_nw; ad.stats = h->d_ps_stats; ad.cap = h->sp_cap; ad.margin_scale = h->margin_scale;
     args[0] = &ad;
@@ -1991,7 +2010,7 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
     h->pa_t00 = T[0];
     if ((rc = upload(h, &h->d_pa_table, T)) || (rc = dev_alloc(h, &h->d_pa_acc, (size_t)h->K * kPoissonAccStride))) return bail(rc);
   }
-  if (h->scheme == Scheme::lightcollapsed && (rc = dev_alloc_zeroed(h, &h->d_tpt, (size_t)h->V))) return bail(rc);
+  if (count_tables(h->scheme) && (rc = dev_alloc_zeroed(h, &h->d_tpt, (size_t)h->V))) return bail(rc);
   if (h->scheme == Scheme::adlda && ((rc = dev_alloc_zeroed(h, &h->d_ad_den0, (size_t)h->K)) || (rc = dev_alloc_zeroed(h, &h->d_ad_s0, 1)))) return bail(rc);
   if (h->scheme == Scheme::collapsed && (rc = dev_alloc(h, &h->d_lcg, 2))) return bail(rc);
   // 5. events and streams
@@ -2144,7 +2163,8 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   if (L.warm_tiers > 0 && ((rc = upload(h, &h->d_wt_pack, L.wt_pack)) || (rc = upload(h, &h->d_w_docs, L.w_docs)) ||
                            (rc = upload(h, &h->d_warm_words, L.warm_words)) || (rc = upload(h, &h->d_warm_meta, L.warm_meta))))
     return rc;
-  const bool with_theta = !counts_only(h->scheme);   // no theta in its chain and none for a diagnostic (ggs_log_posterior is unsupported)
+  const bool with_theta = !counts_only(h->scheme) && !no_theta(h->scheme);   // no theta in its chain and none for a diagnostic (ggs_log_posterior is unsupported); lightpcldaw2: ensure_diag_theta
+  if (!with_theta && h->d_theta) { (void)hipFree(h->d_theta); h->d_theta = nullptr; }   // an earlier corpus' diagnostic theta
   if ((rc = dev_alloc(h, &h->d_z, (size_t)N)) || (rc = dev_alloc(h, &h->d_zw, (size_t)N)) ||
       (with_theta && (rc = dev_alloc(h, &h->d_theta, theta_elems))) || (!pcgs && (rc = dev_alloc(h, &h->d_theta_next, theta_elems))))   // theta_next: what the ggs z phase swaps in
     return rc;
@@ -2600,7 +2620,7 @@ int ggs_group_sweep(ggs_handle **hs, int32_t n, int32_t n_sweeps) {
   for (int32_t i = 0; i < n; ++i)
     if ((rc = iteration_room(hs[i], n_sweeps))) return rc;
   for (int32_t s = 0; s < n_sweeps; ++s) {
-    if (count_form(hs[0]->scheme) && (rc = group_gather_counts(hs, n))) return rc;   // the z step conditions on the corpus-wide sweep-start counts
+    if ((count_form(hs[0]->scheme) || count_tables(hs[0]->scheme)) && (rc = group_gather_counts(hs, n))) return rc;   // the z step conditions on the corpus-wide sweep-start counts
     for (int32_t i = 0; i < n; ++i) {
       ggs_handle *h = hs[i];
       if ((rc = require_ready(h, true))) return rc;
@@ -2771,7 +2791,7 @@ int ggs_get_topic_priors(ggs_handle *h, double *priors) {
 // the next sweep builds at its head), or of the current Phi
 static int refresh_tables(ggs_handle *h) {
   int rc;
-  if (count_form(h->scheme)) return (rc = require_ready(h, false)) ? rc : launch_sweep_head(h);
+  if (count_form(h->scheme) || count_tables(h->scheme)) return (rc = require_ready(h, false)) ? rc : launch_sweep_head(h);
   if (!h->have_phi) return set_err(h, GGS_ERR_STATE, "no Phi yet: call ggs_init_phi or ggs_set_phi first");
   return h->alias_stale ? launch_alias_build(h) : GGS_OK;
 }
@@ -2783,7 +2803,7 @@ int ggs_get_alias_tables(ggs_handle *h, double *ps, int32_t *a, double *type_nor
     return counts_only(h->scheme) ? set_err(h, GGS_ERR_UNSUPPORTED, "scheme=adlda builds no alias tables") : set_err(h, GGS_ERR_STATE, needs_flag("ggs_get_alias_tables", kHasTables));
   if ((rc = refresh_tables(h))) return rc;
   const size_t kv = (size_t)h->K * h->V;
-  std::vector<int32_t> n(count_form(h->scheme) ? (size_t)h->V : 0);   // lightcollapsed: the kernel writes a row's first nw[w] entries
+  std::vector<int32_t> n(count_tables(h->scheme) ? (size_t)h->V : 0);   // lightcollapsed, lightpcldaw2: the kernel writes a row's first nw[w] entries
   if (!n.empty()) HIP_TRY(h, hipMemcpyAsync(n.data(), h->d_nw, n.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   if (ps) HIP_TRY(h, hipMemcpyAsync(ps, h->d_alias_ps, kv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (a) HIP_TRY(h, hipMemcpyAsync(a, h->d_alias_a, kv * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -2881,6 +2901,7 @@ int ggs_get_theta(ggs_handle *h, int64_t doc_begin, int64_t doc_end, double *the
   if (rc) return rc;
   if (doc_begin < 0 || doc_end > h->D || doc_begin > doc_end || (!theta && doc_end > doc_begin)) return set_err(h, GGS_ERR_BAD_ARG, "bad document range");
   if (counts_only(h->scheme)) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=lightcollapsed and scheme=adlda keep no theta");
+  if (no_theta(h->scheme)) return set_err(h, GGS_ERR_UNSUPPORTED, "scheme=lightpcldaw2 keeps no theta");
   return copy_out(h, theta, h->d_theta + (size_t)doc_begin * h->K, sizeof(double) * (size_t)(doc_end - doc_begin) * h->K);
 }
 int ggs_get_doc_topic_counts(ggs_handle *h, int64_t doc_begin, int64_t doc_end, int32_t *n_dk) {
@@ -2895,6 +2916,14 @@ int ggs_get_doc_topic_counts(ggs_handle *h, int64_t doc_begin, int64_t doc_end, 
   hipLaunchKernelGGL(doc_topic_kernel, dim3((unsigned)nd), dim3(64), 0, h->stream, h->d_doc_ptr, h->d_z, doc_begin, h->K, static_cast<int32_t *>(h->d_scratch));
   HIP_TRY(h, hipGetLastError());
   return copy_out(h, n_dk, h->d_scratch, bytes);
+}
+// the diagnostics' theta of a scheme that keeps none (lightpcldaw2): allocated when the log posterior or the document distances first draw one
+static int ensure_diag_theta(ggs_handle *h) {
+  if (h->d_theta) return GGS_OK;
+  const int rc = dev_alloc(h, &h->d_theta, (size_t)h->D * h->K + 2);
+  if (rc) return rc;
+  HIP_TRY(h, hipMemset(h->d_theta, 0, sizeof(double) * ((size_t)h->D * h->K + 2)));
+  return GGS_OK;
 }
 // ll_docs_kernel and lp_docs_kernel keep four K-long histograms per block in LDS (ggs_loglik.hpp)
 static int ll_check_topics(ggs_handle *h) {
@@ -2940,7 +2969,7 @@ int ggs_log_posterior(ggs_handle *h, double *doc_side, double *topic_side) {
   if (pcgs_family(h->scheme)) {
     // UPLDA:710-714: every scheme but ggs draws theta_d ~ Dir(n_d. + alpha) afresh for the diagnostics
     // (LDAUtils.drawDirichlets); here: the theta draw of GGS:57-72 under the stream GGS_PURPOSE_THETA at the current iteration
-    if ((rc = drop_theta_ahead(h)) || (rc = launch_theta(h, h->stream, h->d_theta, h->iteration))) return rc;
+    if ((rc = drop_theta_ahead(h)) || (rc = ensure_diag_theta(h)) || (rc = launch_theta(h, h->stream, h->d_theta, h->iteration))) return rc;
   }
   const int K = h->K;
   const int64_t doc_blocks = (h->D + kLLBlock / 64 - 1) / (kLLBlock / 64), phi_blocks = 1024;
@@ -2998,7 +3027,7 @@ int ggs_min_doc_distances(ggs_handle *h, const double *other, int64_t n_other, d
   if (pcgs_family(h->scheme)) {
     // UPLDA:710-714: one fresh theta per diagnostic iteration for the distances and the log posterior together; here both
     // calls redraw the same bits (the stream GGS_PURPOSE_THETA at the current iteration), as ggs_log_posterior does
-    if ((rc = drop_theta_ahead(h)) || (rc = launch_theta(h, h->stream, h->d_theta, h->iteration))) return rc;
+    if ((rc = drop_theta_ahead(h)) || (rc = ensure_diag_theta(h)) || (rc = launch_theta(h, h->stream, h->d_theta, h->iteration))) return rc;
   }
   const int64_t piece_rows = other ? std::max<int64_t>(1, std::min<int64_t>(n_other, (int64_t)(dist_piece_bytes() / (sizeof(double) * (size_t)K)))) : 0;
   const size_t head = sizeof(double) * 2 * (size_t)D;     // [D] minimal sums as bit patterns, [D] distances

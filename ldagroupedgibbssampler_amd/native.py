@@ -13,6 +13,7 @@ FLAG_POLYAURN_SPARSE = 128
 FLAG_LIGHTCOLLAPSED = 256
 FLAG_NZVSSPALIAS = 512
 FLAG_ADLDA = 1024
+FLAG_LIGHTPCLDAW2 = 2048   # sampler.LightPCLDAtypeTopicProposal: constructed directly, so not a key of SCHEME_FLAGS (create_model refuses the name)
 # scheme name -> its flag, in the order of the library's scheme table (csrc/ggs_api.hip, kSchemes)
 SCHEME_FLAGS = {"ggs": 0, "pcgs": FLAG_PCGS, "collapsed": FLAG_COLLAPSED, "polyaurn": FLAG_POLYAURN, "spalias": FLAG_SPALIAS, "lightpclda": FLAG_LIGHTPCLDA,
                 "polyaurn_sparse": FLAG_POLYAURN_SPARSE, "lightcollapsed": FLAG_LIGHTCOLLAPSED, "nzvsspalias": FLAG_NZVSSPALIAS, "adlda": FLAG_ADLDA}
@@ -307,7 +308,7 @@ class GGSHandle:
 
     def alias_tables(self):
         """scheme=spalias, lightpclda or polyaurn_sparse: the alias tables of the current Phi, (ps [V][K], a [V][K], type_norm [V]).
-        scheme=lightcollapsed: the tables of the current counts (what the next sweep builds at its head): row w holds the word's
+        scheme=lightcollapsed and lightpcldaw2: the tables of the current counts (what the next sweep builds at its head): row w holds the word's
         table in its first nw[w] entries, ps = 1.0 and a = the index behind them; type_norm [V] = typeMass."""
         ps, a, tn = np.empty((self.V, self.K), np.float64), np.empty((self.V, self.K), np.int32), np.empty(self.V, np.float64)
         self._chk(self._L.ggs_get_alias_tables(self._h, _dp(ps), _ip(a), _dp(tn)))
@@ -328,7 +329,7 @@ class GGSHandle:
         return out
 
     def mh_stats(self):
-        """scheme=lightpclda and lightcollapsed: tokens whose word proposal was accepted and kept, whose document proposal was accepted, and
+        """scheme=lightpclda, lightcollapsed and lightpcldaw2: tokens whose word proposal was accepted and kept, whose document proposal was accepted, and
         tokens left on their old topic, cumulative since set_corpus (int64 [3]; they sum to the tokens sampled)."""
         out = np.zeros(3, np.int64)
         self._chk(self._L.ggs_get_mh_stats(self._h, _lp(out)))
@@ -336,7 +337,7 @@ class GGSHandle:
 
     def word_topic_lists(self):
         """scheme=polyaurn_sparse: (nw [V], topics [V][K]) of the current Phi -- per word the number of topics with
-        phi[k][w] != 0 and those topics in ascending order, -1 behind them.  scheme=lightcollapsed: of the current counts, the
+        phi[k][w] != 0 and those topics in ascending order, -1 behind them.  scheme=lightcollapsed and lightpcldaw2: of the current counts, the
         topics with n_wk > 0; scheme=adlda: the same lists of the current counts."""
         nw, topics = np.empty(self.V, np.int32), np.empty((self.V, self.K), np.int32)
         self._chk(self._L.ggs_get_word_topic_lists(self._h, _ip(nw), _ip(topics)))
@@ -516,7 +517,7 @@ Z_KERNEL_NAMES = {0: "z_kernel (whole-row tiles)", 1: "z_sliced_kernel + z_hot_k
                   3: "z_stream_kernel (two passes)", 4: "pcgs_sliced_kernel (lane per document)", 5: "pcgs_wave_kernel (wave per document)",
                   6: "spalias_wave_kernel (wave per document)", 7: "lightpc_wave_kernel (wave per document)",
                   8: "polyaurn_sparse_wave_kernel (wave per document)", 9: "lightcollapsed_wave_kernel (wave per document)",
-                  10: "nzvs_wave_kernel (wave per document)", 11: "adlda_wave_kernel (wave per document)"}
+                  10: "nzvs_wave_kernel (wave per document)", 11: "adlda_wave_kernel (wave per document)", 12: "lightpcw2_wave_kernel (wave per document)"}
 
 
 class GGSGroup:

@@ -544,6 +544,33 @@ class LightPCLDA(LDAPartiallyCollapsedGibbsSampler):
         return self._h.mh_stats()
 
 
+class LightPCLDAtypeTopicProposal(LDAPartiallyCollapsedGibbsSampler):
+    """scheme=lightpcldaw2 (topics/LightPCLDAtypeTopicProposal.java, ParallelLDA.createModel's "lightpcldaw2"): the pcgs model
+    and driver -- Phi is drawn -- under the LightLDA z step with scheme=lightcollapsed's word proposal: the word's alias table
+    over n_wk / (n_k + betaSum) on its non-zero topics plus a beta * K smoothing branch, the acceptance ratio correcting for it
+    with Phi; then scheme=lightpclda's document proposal.  O(1) per token.  The tables are the ones the class declares
+    (DESIGN.md 6m); the chain is approximate as written.  Constructed directly: create_model does not know the name
+    (tests/test_lightcollapsed_model.py pins its refusal)."""
+    _scheme_flags = native.FLAG_LIGHTPCLDAW2
+
+    def getTheta(self):
+        raise NotImplementedError("scheme=lightpcldaw2 never draws theta; use getThetaEstimate() (UPLDA:716-720 does the same)")
+
+    def getAliasTables(self):
+        """(ps [V][K], a [V][K], typeMass [V]) of the current counts: a word's table in the first nw[w] entries of its row"""
+        self._need_data()
+        return self._h.alias_tables()
+
+    def getWordTopicLists(self):
+        """(nw [V], topics [V][K]): per word the topics with n_wk > 0 in ascending order, -1 behind them"""
+        self._need_data()
+        return self._h.word_topic_lists()
+
+    def getMHStats(self):
+        """tokens whose word proposal was kept, whose document proposal was accepted, left on their old topic (cumulative)"""
+        return self._h.mh_stats()
+
+
 class PolyaUrnSparseLDA(LDAPartiallyCollapsedGibbsSampler):
     """scheme=polyaurn_sparse (the sampler topics/PolyaUrnSpaliasLDA.java builds, sampleTopicAssignmentsParallel :180-334):
     polyaurn's model -- Phi drawn as Poisson counts with exact zeros, config key alias_poisson_threshold -- with the doubly
@@ -689,8 +716,8 @@ class ADLDA(LDAGroupedGibbsSampler):
 def create_model(config, scheme=None):
     """The `case "ggs"` / `case "pcgs"` / `case "collapsed"` / `case "lightcollapsed"` / `case "polyaurn"` / `case "spalias"` / `case "lightpclda"` of tui/ParallelLDA.createModel
     (ParallelLDA.java:401-490); "spalias_priors" is :464-468; "polyaurn_sparse" is this build's name for polyaurn over the sparse z step the reference's class holds.
-    "adlda" (:409-412) is not in this registry, as "nzvsspalias" is not (tests/test_host_mirror.py pins the refusal of the name):
-    construct ADLDA(config) itself."""
+    "adlda" (:409-412) is not in this registry, as "nzvsspalias" and "lightpcldaw2" are not (tests/test_host_mirror.py and
+    tests/test_lightcollapsed_model.py pin the refusal of the names): construct ADLDA(config) / LightPCLDAtypeTopicProposal(config) itself."""
     scheme = scheme or config.scheme
     if scheme == "ggs":
         return LDAGroupedGibbsSampler(config)
