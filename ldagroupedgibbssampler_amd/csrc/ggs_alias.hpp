@@ -41,7 +41,7 @@ inline size_t alias_lds_bytes(int K, int wpb) { return (size_t)wpb * K * 12 + 64
 
 // One word's pairing chain over n entries, on one lane, out of LDS: b [n] holds bs and takes ps[l] in the slot of every paired
 // l, aw [n] the alias (preset to the index), s [n] both stacks.  n = K for the tables over Phi (alias_build_kernel), n = the
-// word's number of non-zero topics for the tables over the counts (count_alias_build_kernel, ggs_z_lightcollapsed.hpp).
+// word's number of non-zero topics for the tables over the counts (count_alias_build_kernel, at the end of this file).
 __device__ __forceinline__ void alias_pairing_chain(double *b, uint16_t *s, uint16_t *aw, const int n) {
   int nl = 0, hp = n;                                                              // lows: s[0, nl), top s[nl - 1]; highs: s[hp, n), top s[hp]
   for (int k = 0; k < n; ++k) {
@@ -107,6 +107,93 @@ __global__ __launch_bounds__(64) void alias_build_kernel(AliasParams p) {
       const size_t o = (size_t)w0 * K + idx;
       p.ps[o] = av == k ? 1.0 : bs[idx];
       p.a[o] = av;
+    }
+  }
+}
+
+// ---- the words' lists and tables over the counts (scheme=lightcollapsed, lightpcldaw2) -------------------------------------
+// TypeTopicParallelTableBuilder.java:38-51 over the ascending list L of the word's topics with n_wk > 0:
+// p_i = n_w,L[i] / topicCountBetaHat[L[i]], typeMass = the i-order sum from 0.0, then reGenerateAliasTable
+// (OptimizedGentleAliasMethodDynamicSize.java:55-82) with k = nnz: bs[i] = p_i / typeMass - 1.0 / nnz and the lows / highs
+// pairing chain above.  A single-wave workgroup takes `wpb` words at a time, as alias_build_kernel does: the
+// whole wave makes each word's list (a ballot and a prefix popcount per block of 64 topics, as word_list_build_kernel) and
+// fills p into LDS, lanes 0..wpb-1 each sum their word's p in i order and run its chain out of LDS, all lanes write out.
+// Only the first nnz entries of a row of ps / a / nzw are written; a word without tokens writes nw = 0 and nothing else.
+struct CountAliasParams {
+  const int32_t *n_wk;         // [V][K] corpus-wide sweep-start counts
+  const int32_t *n_k;          // [K]
+  double *ps;                  // [V][K]
+  int32_t *a;                  // [V][K]
+  double *type_norm;           // [V] typeMass
+  uint16_t *nzw;               // [V][K]
+  int32_t *nw;                 // [V]
+  int32_t *tpt;                // [V] tokensPerType
+  double beta_sum;
+  int32_t V, K, wpb;
+};
+
+inline size_t count_alias_lds_bytes(int K, int wpb) { return alias_lds_bytes(K, wpb) + 64 * sizeof(int32_t); }
+
+__global__ __launch_bounds__(64) void count_alias_build_kernel(CountAliasParams p) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int K = p.K, wpb = p.wpb, lane = threadIdx.x;
+  double *bs = reinterpret_cast<double *>(smem);                                   // [wpb][K]
+  double *tnl = bs + (size_t)wpb * K;                                              // [64]
+  int32_t *nnzl = reinterpret_cast<int32_t *>(tnl + 64);                           // [64]
+  uint16_t *al = reinterpret_cast<uint16_t *>(nnzl + 64);                          // [wpb][K]
+  uint16_t *st = al + (size_t)wpb * K;                                             // [wpb][K]
+
+  for (int w0 = blockIdx.x * wpb; w0 < p.V; w0 += gridDim.x * wpb) {
+    const int nwd = min(wpb, p.V - w0);
+    __syncthreads();
+    for (int wi = 0; wi < nwd; ++wi) {                                             // the list, p and the identity alias of word w0 + wi
+      const int32_t *row = p.n_wk + (size_t)(w0 + wi) * K;
+      uint16_t *out = p.nzw + (size_t)(w0 + wi) * K;
+      int n = 0, tot = 0;
+      for (int k0 = 0; k0 < K; k0 += 64) {
+        const int k = k0 + lane;
+        const int c = k < K ? row[k] : 0;
+        const bool nz = c > 0;
+        const unsigned long long m = __ballot(nz);
+        const int slot = n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (nz) {                                                                  // slot < number of non-zeros <= K
+          out[slot] = (uint16_t)k;
+          bs[(size_t)wi * K + slot] = (double)c / ((double)p.n_k[k] + p.beta_sum);
+          al[(size_t)wi * K + slot] = (uint16_t)slot;
+          tot += c;
+        }
+        n += __popcll(m);
+      }
+      for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
+      if (lane == 0) { nnzl[wi] = n; p.nw[w0 + wi] = n; p.tpt[w0 + wi] = tot; }
+    }
+    __syncthreads();
+    if (lane < nwd) {
+      const int n = nnzl[lane];
+      const double *b = bs + (size_t)lane * K;
+      double tn = 0.0;
+      for (int i = 0; i < n; ++i) tn += b[i];
+      tnl[lane] = tn;
+      p.type_norm[w0 + lane] = tn;
+    }
+    __syncthreads();
+    for (int wi = 0; wi < nwd; ++wi) {
+      const int n = nnzl[wi];
+      const double tn = tnl[wi], inv_n = 1.0 / (double)n;
+      for (int i = lane; i < n; i += 64) bs[(size_t)wi * K + i] = bs[(size_t)wi * K + i] / tn - inv_n;
+    }
+    __syncthreads();
+    if (lane < nwd && nnzl[lane] > 0)                                              // the chain above with k = nnz
+      alias_pairing_chain(bs + (size_t)lane * K, st + (size_t)lane * K, al + (size_t)lane * K, nnzl[lane]);
+    __syncthreads();
+    for (int wi = 0; wi < nwd; ++wi) {
+      const int n = nnzl[wi];
+      for (int i = lane; i < n; i += 64) {
+        const int av = al[(size_t)wi * K + i];
+        const size_t o = (size_t)(w0 + wi) * K + i;
+        p.ps[o] = av == i ? 1.0 : bs[(size_t)wi * K + i];
+        p.a[o] = av;
+      }
     }
   }
 }

@@ -1356,7 +1356,7 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
   }
   if (scheme == Scheme::lightpclda) {
     // as many resident waves as fit: a lone wave issues at a fraction of a SIMD's rate, and the step is a chain of dependent operations
-    pl.lightpc = {reinterpret_cast<const void *>(lightpc_wave_kernel), 64, (int)lightpc_lds_bytes(K), 0};
+    pl.lightpc = {reinterpret_cast<const void *>(lightpc_wave_kernel), 64, (int)light_lds_bytes(K), 0};
     pl.lightpc.per_cu = resident_waves_per_cu(pl.lightpc.fn, pl.lightpc.lds);
   }
   if (count_tables(scheme)) {
@@ -1366,11 +1366,11 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
     pl.countalias.per_cu = lds_workgroups_per_cu(pl.countalias.lds, 16);
   }
   if (scheme == Scheme::lightpcldaw2) {
-    pl.lightpcw2 = {reinterpret_cast<const void *>(lightpcw2_wave_kernel), 64, (int)lightpcw2_lds_bytes(K), 0};
+    pl.lightpcw2 = {reinterpret_cast<const void *>(lightpcw2_wave_kernel), 64, (int)light_lds_bytes(K), 0};
     pl.lightpcw2.per_cu = resident_waves_per_cu(pl.lightpcw2.fn, pl.lightpcw2.lds);
   }
   if (scheme == Scheme::lightcollapsed) {
-    pl.lightcol = {reinterpret_cast<const void *>(lightcollapsed_wave_kernel), 64, (int)lightcollapsed_lds_bytes(K), 0};
+    pl.lightcol = {reinterpret_cast<const void *>(lightcollapsed_wave_kernel), 64, (int)light_lds_bytes(K), 0};
     pl.lightcol.per_cu = resident_waves_per_cu(pl.lightcol.fn, pl.lightcol.lds);
   }
   if (scheme == Scheme::adlda) {                       // one wave for the head, a wave per word for the lists; the z kernel's LDS comes with the corpus
@@ -1401,7 +1401,8 @@ int launch_pcgs_z(ggs_handle *h) {
     pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;
   }
   PolyaurnSparseParams sp{};                           // spalias's kernel takes its base, SpaliasParams
-  LightpcParams lp{}; LightCollapsedParams lc{}; AdldaParams ad{}; LightpcW2Params lw{};
+  LightCountParams lp{};                               // lightpclda's kernel takes its base, LightpcParams
+  AdldaParams ad{};
   void *args[] = {&pp, &h->margin_scale};              // the wave-per-document kernel takes both, the lane-per-document kernels the first
   if (sparse_walk(h->scheme)) {
     // one wave per document over its non-zero topics (ggs_z_spalias.hpp), or over the word's where they are fewer
@@ -1409,15 +1410,12 @@ int launch_pcgs_z(ggs_handle *h) {
     sp.b = pp; sp.ps = h->d_alias_ps; sp.a = h->d_alias_a; sp.type_norm = h->d_alias_tn; sp.cap = h->sp_cap; sp.margin_scale = h->margin_scale;
     sp.nzw = h->d_nzw; sp.nw = h->d_nw; sp.stats = h->d_ps_stats;
     args[0] = static_cast<SpaliasParams *>(&sp);
-  } else if (h->scheme == Scheme::lightpclda) {        // one wave per document, two proposals per token (ggs_z_lightpc.hpp)
+  } else if (has_mh(h->scheme)) {
+    // one wave per document, two proposals per token (ggs_z_light.hpp): over spalias's tables (lightpclda), or over the lists and
+    // tables of the sweep-start counts (lightcollapsed, lightpcldaw2; null in a lightpclda handle)
     lp.b = pp; lp.ps = h->d_alias_ps; lp.a = h->d_alias_a; lp.mh = h->d_mh; lp.alpha_sum = h->alpha_sum;
-    args[0] = &lp;
-  } else if (h->scheme == Scheme::lightcollapsed) {    // one wave per document over the tables of the sweep-start counts
-    lc.b = pp; lc.ps = h->d_alias_ps; lc.a = h->d_alias_a; lc.nzw = h->d_nzw; lc.nw = h->d_nw; lc.tpt = h->d_tpt; lc.mh = h->d_mh; lc.alpha_sum = h->alpha_sum;
-    args[0] = &lc;
-  } else if (h->scheme == Scheme::lightpcldaw2) {      // one wave per document over Phi and the tables of the sweep-start counts (ggs_z_lightpcw2.hpp)
-    lw.b = pp; lw.ps = h->d_alias_ps; lw.a = h->d_alias_a; lw.nzw = h->d_nzw; lw.nw = h->d_nw; lw.tpt = h->d_tpt; lw.mh = h->d_mh; lw.alpha_sum = h->alpha_sum;
-    args[0] = &lw;
+    lp.nzw = h->d_nzw; lp.nw = h->d_nw; lp.tpt = h->d_tpt;
+    args[0] = static_cast<LightpcParams *>(&lp);
   } else if (h->scheme == Scheme::adlda) {             // one wave per document over den0, S0 and the lists of the sweep-start counts
     ad.b = pp; ad.den0 = h->d_ad_den0; ad.s0 = h->d_ad_s0; ad.nzw = h->d_nzw; ad.nw = h->d_nw; ad.stats = h->d_ps_stats; ad.cap = h->sp_cap; ad.margin_scale = h->margin_scale;
     args[0] = &ad;
