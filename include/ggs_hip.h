@@ -536,7 +536,7 @@ int ggs_get_z_parts(ggs_handle *h, int32_t *parts);
 int ggs_get_z_form(ggs_handle *h, int32_t *kernel, int32_t *form, int32_t *calibrated);
 /* ---- primitives, exported so the parity tests can pin each layer ----------- */
 int ggs_debug_philox(int32_t device_id, int64_t n, const uint32_t *ctr /*n*4*/, const uint32_t *key /*n*2*/, uint32_t *out /*n*4*/);
-int ggs_debug_math(int32_t device_id, int32_t op /*0 log,1 pow,2 sqrt,3 div,4 exp*/, int64_t n, const double *x, const double *y, double *out);
+int ggs_debug_math(int32_t device_id, int32_t op /*0 log,1 pow,2 sqrt,3 div,4 exp,5 pow as the gamma draws call it,6 u53 of the words x,y*/, int64_t n, const double *x, const double *y, double *out);
 int ggs_debug_draw(int32_t device_id, int32_t kind /*0 uniform,1 gaussian,2 gamma (general loops),3 gamma as the kernels draw it: first try then general,4 as 3 with first-try results negated*/, uint64_t seed, uint32_t iteration,
                    uint32_t purpose, uint64_t elem0, int64_t n, const double *shape, double *out, int32_t *status);
 /* scheme=polyaurn's Poisson draw (PoissonFixedCoeffSampler.java:31-50, PolyaUrnDirichlet.java:102-107; GGS_FLAG_POLYAURN):

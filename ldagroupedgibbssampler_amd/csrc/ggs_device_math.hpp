@@ -9,6 +9,7 @@
 //                      (JDK 8: 26+27 bit doubles, polar Gaussian with caching)
 //                      fed from the Philox blocks of one (purpose, iteration, elem)
 //   strict_log/pow/exp fdlibm 5.3 e_log.c / e_pow.c / e_exp.c == java.lang.StrictMath
+//   boost_pow          the same pow where the gamma draws call it: e_pow.c's main path straight-line, strict_pow elsewhere
 //   rgamma             cc/mallet/util/ParallelRandoms.java:60-70,148-159
 #pragma once
 #include <hip/hip_runtime.h>
@@ -38,9 +39,11 @@ __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c
 }
 
 // ((next(26) << 27) + next(27)) * 2^-53 with next(n) = top n bits of a 32-bit word
+// Two 32-bit conversions instead of one 64-bit one (6 VALU instructions against 12), and exact: a >> 6 < 2^26 and
+// b >> 5 < 2^27 convert exactly, both scalings are by powers of two, and the sum is an integer below 2^53 times 2^-53,
+// so the fma -- explicit: this file is compiled with -ffp-contract=off -- rounds nothing.
 __device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
-  const uint64_t m = ((uint64_t)(a >> 6) << 27) + (uint64_t)(b >> 5);
-  return (double)m * 0x1.0p-53;
+  return __builtin_fma((double)(b >> 5), 0x1.0p-53, (double)(a >> 6) * 0x1.0p-26);
 }
 // the z step's uniform of global token gtok: the first double of block 0 of (gtok, GGS_PURPOSE_Z, iteration, seed)
 __device__ __forceinline__ double z_uniform(uint64_t gtok, uint32_t iteration, uint64_t seed) {
@@ -289,6 +292,107 @@ __device__ __noinline__ double strict_pow(double x, double y) {
   return set_hi(z, j);
 }
 
+// ---- the boost's pow: e_pow.c's main path as straight-line code ----------------
+// The boost of a gamma draw (ParallelRandoms.java:66) raises the element's first uniform, a multiple of 2^-53 in [0, 1),
+// to 1/shape with shape < 1.  On
+//   x normal with 0 < x < 1,
+//   the high word of y in (0x3ff00000, 0x41e00000]   (1 + 2^-20 <= y < 2^31 + 2^11),
+//   the high word of |y log2 x| as e_pow.c forms it below 0x40900000   (|y log2 x| < 1024), and a normal result
+// strict_pow takes none of its early returns, neither of its rescalings (subnormal x, scalbn) and not the |y| > 2^31
+// branch: what is left is the sequence of IEEE operations below, the same operations in the same order, with fdlibm's
+// three-way choice of k and its `i > 0x3fe00000` block turned into selects (a lane outside that block subtracts +0.0
+// from p_h, which changes no bit of it).  Where any of the four conditions fails -- x = 0, subnormal or >= 1,
+// y <= 1 + 2^-20 or >= 2^31 + 2^11 or not finite, a result that underflows or is subnormal -- the function returns NaN,
+// which no result inside the domain is, and the caller goes to strict_pow.  The shift counts are masked to five bits,
+// which is what the hardware does and changes nothing inside the domain (there they are 0..20), and the integer sums
+// that can wrap outside the domain are unsigned: outside it the arithmetic stays defined.
+// __noinline__ like strict_pow: inlined at its three call sites it cost theta_kernel a wave per SIMD (67 -> 75 VGPRs).
+__device__ __noinline__ double strict_pow_unit(double x, double y) {
+  constexpr double
+      L1 = 5.99999999999994648725e-01, L2 = 4.28571428578550184252e-01,
+      L3 = 3.33333329818377432918e-01, L4 = 2.72728123808534006489e-01,
+      L5 = 2.30660745775561754067e-01, L6 = 2.06975017800338417784e-01,
+      P1 = 1.66666666666666019037e-01, P2 = -2.77777777770155933842e-03,
+      P3 = 6.61375632143793436117e-05, P4 = -1.65339022054652515390e-06,
+      P5 = 4.13813679705723846039e-08,
+      lg2 = 6.93147180559945286227e-01, lg2_h = 6.93147182464599609375e-01,
+      lg2_l = -1.90465429995776804525e-09,
+      cp = 9.61796693925975554329e-01, cp_h = 9.61796700954437255859e-01,
+      cp_l = -7.02846165095275826516e-09;
+  const int32_t hx = hi32(x), hy = hi32(y);
+  bool in_domain = (uint32_t)hx - 0x00100000u < 0x3ff00000u - 0x00100000u && (uint32_t)hy - 0x3ff00001u <= 0x41e00000u - 0x3ff00001u;
+  // log2(x) = t1 + t2
+  const int32_t jx = hx & 0x000fffff;
+  const bool k = jx > 0x3988E && jx < 0xBB67A, up = jx >= 0xBB67A;
+  const int32_t ix = jx | (up ? 0x3fe00000 : 0x3ff00000);
+  const double t = (double)((hx >> 20) - 0x3ff + (up ? 1 : 0));
+  const double ax = set_hi(x, ix);
+  const double bpk = k ? 1.5 : 1.0;
+  const double dp_hk = k ? 5.84962487220764160156e-01 : 0.0;
+  const double dp_lk = k ? 1.35003920212974897128e-08 : 0.0;
+  double u = ax - bpk;
+  double v = 1.0 / (ax + bpk);
+  const double ss = u * v;
+  const double s_h = clr_lo(ss);
+  double t_h = mk(((ix >> 1) | 0x20000000) + 0x00080000 + (k ? 0x00040000 : 0), 0u);
+  double t_l = ax - (t_h - bpk);
+  const double s_l = v * ((u - s_h * t_h) - s_h * t_l);
+  double s2 = ss * ss;
+  double r = s2 * s2 * (L1 + s2 * (L2 + s2 * (L3 + s2 * (L4 + s2 * (L5 + s2 * L6)))));
+  r += s_l * (s_h + ss);
+  s2 = s_h * s_h;
+  t_h = clr_lo(3.0 + s2 + r);
+  t_l = r - ((t_h - 3.0) - s2);
+  u = s_h * t_h;
+  v = s_l * t_h + t_l * ss;
+  double p_h = clr_lo(u + v);
+  double p_l = v - (p_h - u);
+  const double z_h = cp_h * p_h;
+  const double z_l = cp_l * p_h + p_l * cp + dp_lk;
+  const double t1 = clr_lo(((z_h + z_l) + dp_hk) + t);
+  const double t2 = z_l - (((t1 - t) - dp_hk) - z_h);
+  // y * log2(x) = p_h + p_l, split into the integer n and the rest
+  const double y1 = clr_lo(y);
+  p_l = (y - y1) * t1 + y * t2;
+  p_h = y1 * t1;
+  double z = p_l + p_h;
+  int32_t j = hi32(z);
+  const int32_t i = j & 0x7fffffff;
+  in_domain = in_domain && i < 0x40900000;
+  const bool split = i > 0x3fe00000;
+  int32_t n = (int32_t)((uint32_t)j + (0x00100000u >> (((i >> 20) - 0x3ff + 1) & 31)));
+  const int32_t kn = ((n & 0x7fffffff) >> 20) - 0x3ff;
+  const int32_t th = n & ~(0x000fffff >> (kn & 31));
+  n = ((n & 0x000fffff) | 0x00100000) >> ((20 - kn) & 31);
+  if (j < 0) n = -n;
+  n = split ? n : 0;
+  p_h -= mk(split ? th : 0, 0u);
+  // 2^(p_h + p_l)
+  const double tt = clr_lo(p_l + p_h);
+  u = tt * lg2_h;
+  v = (p_l - (tt - p_h)) * lg2 + tt * lg2_l;
+  z = u + v;
+  const double w = v - (z - u);
+  const double zz = z * z;
+  const double e1 = z - zz * (P1 + zz * (P2 + zz * (P3 + zz * (P4 + zz * P5))));
+  r = (z * e1) / (e1 - 2.0) - (w + z * w);
+  z = 1.0 - (r - z);
+  j = (int32_t)((uint32_t)hi32(z) + ((uint32_t)n << 20));
+  in_domain = in_domain && (j >> 20) > 0;
+  return in_domain ? set_hi(z, j) : __builtin_nan("");
+}
+// pow as the gamma draws call it: the straight-line form, and strict_pow for the lanes it does not cover.  The test is
+// one scalar branch per wave, so a wave whose lanes are all inside the domain (every wave of the theta draw at
+// alpha = 0.1; 95 % of the Phi draw's at beta = 0.01, where u < 2^-10.22 leaves the normal range) runs no call.
+__device__ __forceinline__ double boost_pow(double u, double inv_alpha) {
+  double r = strict_pow_unit(u, inv_alpha);
+  const bool outside = r != r;
+  if (__ballot(outside) != 0) {
+    if (outside) r = strict_pow(u, inv_alpha);
+  }
+  return r;
+}
+
 // ---- per-draw stream ----------------------------------------------------------
 struct DrawStream {
   uint32_t k0, k1, c0, c1, c2base, c3;
@@ -380,7 +484,7 @@ __device__ __forceinline__ double prgamma(DrawStream &r, const double d, const d
 __device__ __forceinline__ double rgamma(DrawStream &r, const GammaConsts &k) {
   const double u = r.next_double();                  // drawn BEFORE the Marsaglia-Tsang loop, as at ParallelRandoms.java:62
   const double g = prgamma(r, k.d, k.c);
-  return k.boost ? g * strict_pow(u, k.inv_alpha) : g;
+  return k.boost ? g * boost_pow(u, k.inv_alpha) : g;
 }
 __device__ __forceinline__ double rgamma(DrawStream &r, double alpha) { return rgamma(r, gamma_consts(alpha)); }
 
@@ -411,7 +515,7 @@ __device__ __forceinline__ bool rgamma_first_try(uint64_t seed, uint32_t iter, u
   v = v * v * v;
   if (!(u < (1.0 - 0.0331 * (x * x) * (x * x)))) return false;        // rgamma: the log test, perhaps another round
   const double r = k.d * v;
-  g = k.boost ? r * strict_pow(u0, k.inv_alpha) : r;
+  g = k.boost ? r * boost_pow(u0, k.inv_alpha) : r;
   return true;
 }
 __device__ __forceinline__ bool rgamma_first_try(uint64_t seed, uint32_t iter, uint32_t purpose, uint64_t elem, double alpha, double &g) {

@@ -854,6 +854,8 @@ __global__ void debug_math_kernel(int op, int64_t n, const double *x, const doub
     case 1: r = strict_pow(x[i], y[i]); break;
     case 2: r = sqrt(x[i]); break;
     case 4: r = strict_exp(x[i]); break;
+    case 5: r = boost_pow(x[i], y[i]); break;                        // pow as the gamma draws call it: the exited lanes of a ragged last wave take no part in its ballot
+    case 6: r = u53((uint32_t)x[i], (uint32_t)y[i]); break;          // the two 32-bit words, passed as doubles
     default: r = x[i] / y[i]; break;
   }
   out[i] = r;

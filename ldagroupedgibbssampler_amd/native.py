@@ -599,7 +599,7 @@ def debug_math(op, x, y=None, device_id=0):
     x = np.ascontiguousarray(x, np.float64)
     y = x if y is None else np.ascontiguousarray(y, np.float64)
     out = np.empty_like(x)
-    rc = L.ggs_debug_math(device_id, {"log": 0, "pow": 1, "sqrt": 2, "div": 3, "exp": 4}[op], x.size, _dp(x), _dp(y), _dp(out))
+    rc = L.ggs_debug_math(device_id, {"log": 0, "pow": 1, "sqrt": 2, "div": 3, "exp": 4, "boost_pow": 5, "u53": 6}[op], x.size, _dp(x), _dp(y), _dp(out))
     if rc:
         raise GGSError(rc, "ggs_debug_math")
     return out
