@@ -9,7 +9,7 @@
 // by length, longest first, so the 64 of a group are equally long) and walks their tokens in
 // lockstep -- step t handles token t of each of the 64 documents, which is exactly the access
 // pattern of a GGS chunk (64 tokens, 64 different phiT rows).  The rows stream through the
-// slice ring of ggs_z_stream.hpp (3 slots here) twice per step (pass 1 sums, pass 2 re-multiplies and
+// slice ring of ggs_slice_ring.hpp (3 slots here) twice per step (pass 1 sums, pass 2 re-multiplies and
 // walks; the product (n + alpha) * phi is the same two roundings in both passes: int + double,
 // then the multiply), the next step's first slices are in flight while this step ends.
 // Per-lane state: the document's K topic counts, int16, in LDS as [k][lane] (lane-contiguous,
@@ -46,7 +46,7 @@ constexpr int kPcgsRingSlots = 3;      // two slices ahead: 24 KiB of ring, so t
 constexpr int pcgs_z_alpha_offset() { return kPcgsRingSlots * kSliceBytes; }
 constexpr int pcgs_z_slices(const int K) { return imax(kPcgsRingSlots - 1, (K + kSliceTopics - 1) / kSliceTopics); }
 constexpr int pcgs_z_lds_bytes(const int K) { return pcgs_z_alpha_offset() + pcgs_z_slices(K) * kSliceTopics * (8 + 128); }
-// LDS of the score-register kernels (ggs_z_pcgs_sliced_body.hpp): the alpha row and the counts, then the ring
+// LDS of the score-register kernels (pcgs_sliced_body, below): the alpha row and the counts, then the ring
 constexpr int pcgs_sliced_head_bytes(const int kmax) { return (kmax * 8 + kmax * 128 + 255) / 256 * 256; }
 constexpr int pcgs_sliced_lds_bytes(const int K) { return pcgs_sliced_head_bytes((K + 7) / 8 * 8) + kPcgsRingSlots * kSliceBytes; }
 
@@ -67,24 +67,8 @@ __device__ __forceinline__ void pcgs_z_body(PcgsParams &p) {
   int16_t *cnt = reinterpret_cast<int16_t *>(alb + KT);                              // [KT][64]
   const unsigned char *phib = reinterpret_cast<const unsigned char *>(p.phiT);
   const size_t rowbytes = (size_t)p.Kp * 8;
-  const int lrow = lane >> 3, lslot = lane & 7;
-  const unsigned char *my_row = smem + lane * 128;
-  const int rot = lane >> 1;
-
-  auto row_addresses = [&](const int w, const unsigned char *(&ra)[8]) {
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const int row = 8 * m + lrow;
-      const int wm = __shfl(w, row);
-      ra[m] = phib + (size_t)wm * rowbytes + (size_t)(((lslot - (row >> 1)) & 7) << 4);
-    }
-  };
-  auto issue_slice = [&](const int s, const int slot, const unsigned char *const (&ra)[8]) {
-    const size_t off = (size_t)s * 128;
-#pragma unroll
-    for (int m = 0; m < 8; ++m)
-      __builtin_amdgcn_global_load_lds((glb_cvoid_t *)(ra[m] + off), (lds_void_t *)(smem + slot * kSliceBytes + m * 1024), 16, 0, 0);
-  };
+  const unsigned char *my_row = ring_lane_row(smem, lane);        // the ring (ggs_slice_ring.hpp) starts the workgroup's LDS
+  const int rot = ring_lane_rotation(lane);
 
   for (int k = lane; k < KT; k += 64) alb[k] = k < K ? p.alpha[k] : 0.0;
 
@@ -102,10 +86,10 @@ __device__ __forceinline__ void pcgs_z_body(PcgsParams &p) {
 
     int w = len > 0 ? p.tok[beg] : 0;
     const unsigned char *ra[8], *ran[8];
-    row_addresses(w, ra);
-    int gs = 0;                                                    // ring slot of this step's first slice
+    ring_row_addresses(phib, rowbytes, w, lane, ra);
+    int gs = 0;                                                   // ring slot of this step's first slice
 #pragma unroll
-    for (int s = 0; s < kAhead; ++s) issue_slice(s, s, ra);
+    for (int s = 0; s < kAhead; ++s) ring_issue(smem, s, s, ra);
     // the token's old topic and (COLLAPSED) psi of that topic with the token itself removed (MSLDA:185-190), both
     // fetched one step ahead: z[beg + t + 1] is not written before step t + 1, the counts are the sweep-start ones
     int znext = len > 0 ? p.z[beg] : 0;
@@ -122,7 +106,7 @@ __device__ __forceinline__ void pcgs_z_body(PcgsParams &p) {
       const int w1 = (t + 1 < len) ? p.tok[beg + t + 1] : 0;
       znext = (t + 1 < len) ? p.z[beg + t + 1] : 0;
       if (COLLAPSED && t + 1 < len) own_next = own_of(w1, znext);
-      if (has1) row_addresses(w1, ran);
+      if (has1) ring_row_addresses(phib, rowbytes, w1, lane, ran);
       if (active) cnt[zold * 64 + lane] -= 1;                      // UPLDA:1494 (a count below zero cannot arise: it was built from z above)
       asm volatile("" ::: "memory");
 
@@ -133,12 +117,11 @@ __device__ __forceinline__ void pcgs_z_body(PcgsParams &p) {
         const int cur = (gs + j) % kPcgsRingSlots;
         const int nxt = (gs + j + kAhead) % kPcgsRingSlots;
         const int ja = j + kAhead;
-        if (ja < 2 * NS) issue_slice(ja < NS ? ja : ja - NS, nxt, ra);
-        else if (has1) issue_slice(ja - 2 * NS, nxt, ran);
-        // all but the youngest 8*kAhead DMAs done => slice j has landed; at the tail of the last step fewer follow
-        if (has1 || ja < 2 * NS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * kAhead) : "memory");
-        else if (2 * NS - 1 - j == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (ja < 2 * NS) ring_issue(smem, ja < NS ? ja : ja - NS, nxt, ra);
+        else if (has1) ring_issue(smem, ja - 2 * NS, nxt, ran);
+        // kAhead slices follow slice j; at the tail of the last step fewer
+        if (has1 || ja < 2 * NS) ring_wait_all_but<kAhead>();
+        else ring_wait_all_but<kAhead - 1>(2 * NS - 1 - j);
         if (active) {
           const unsigned char *rb = my_row + cur * kSliceBytes;
           const unsigned char *ab = reinterpret_cast<const unsigned char *>(alb) + s * kSliceTopics * 8;
@@ -147,7 +130,7 @@ __device__ __forceinline__ void pcgs_z_body(PcgsParams &p) {
           int n[kSliceTopics];
 #pragma unroll
           for (int u = 0; u < kSliceUnits; ++u) {
-            ph[u] = lds_d2(rb + (((u + rot) & 7) << 4));
+            ph[u] = lds_d2(rb + ring_unit_offset(u, rot));
             al[u] = lds_d2(ab + u * 16);
             n[2 * u] = cb[(2 * u) * 64];
             n[2 * u + 1] = cb[(2 * u + 1) * 64];
@@ -183,7 +166,7 @@ __device__ __forceinline__ void pcgs_z_body(PcgsParams &p) {
             newc += __popc(bits);
           }
         }
-        asm volatile("" ::: "memory");
+        ring_release_issued();
       }
       gs = (gs + 2 * NS) % kPcgsRingSlots;
 
@@ -218,17 +201,153 @@ __global__ __launch_bounds__(64) void polyaurn_z_kernel(PcgsParams p) { pcgs_z_b
 // ONCE per step: half the LDS-DMA instructions of pcgs_z_kernel, and those are what a step costs.
 // Same lane-per-document groups, same int16 [k][lane] counts in LDS, same 3-slot ring with the slice
 // offset as the DMA immediate (the ring therefore starts above the alpha row and the counts).
+// One body, pcgs_sliced_body<KMAX, COLLAPSED, POLYAURN>, for pcgs_sliced_kernel and polyaurn_sliced_kernel, as pcgs_z_body
+// is for the streaming pair.
 namespace ggs {
 
+template <int KMAX, bool COLLAPSED, bool POLYAURN>
+__device__ __forceinline__ void pcgs_sliced_body(PcgsParams &p) {
+  constexpr int NS = (KMAX + kSliceTopics - 1) / kSliceTopics;
+  constexpr int kAhead = NS < kPcgsRingSlots - 1 ? NS : kPcgsRingSlots - 1;
+  constexpr int kHead = pcgs_sliced_head_bytes(KMAX);              // alpha row + counts, below the ring (>= NS*128)
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int lane = threadIdx.x;
+  const int K = p.K;
+  double *alb = reinterpret_cast<double *>(smem);                  // alpha, zero padded to KMAX
+  int16_t *cnt = reinterpret_cast<int16_t *>(smem + KMAX * 8);     // [KMAX][64]
+  unsigned char *ring = smem + kHead;
+  const unsigned char *phib = reinterpret_cast<const unsigned char *>(p.phiT);
+  const size_t rowbytes = (size_t)p.Kp * 8;
+  const unsigned char *my_row = ring_lane_row(ring, lane);
+  const int rot = ring_lane_rotation(lane);
+  const int16_t *my_cnt = cnt + lane;
+
+  for (int k = lane; k < KMAX; k += 64) alb[k] = k < K ? p.alpha[k] : 0.0;
+
+  const int64_t groups = (p.num_docs + 63) / 64;
+  for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+    const int64_t di = g * 64 + lane;
+    const int d = di < p.num_docs ? p.order[di] : -1;
+    const int64_t beg = d >= 0 ? p.doc_ptr[d] : 0;
+    const int len = d >= 0 ? (int)(p.doc_ptr[d + 1] - beg) : 0;
+    const int steps = __shfl(len, 0);                              // lane 0 holds the group's longest document
+    if (steps == 0) break;                                         // sorted: every later group is empty too
+    for (int k = 0; k < KMAX; ++k) cnt[k * 64 + lane] = 0;         // UPLDA:1482-1485 localTopicCounts
+    for (int t = 0; t < len; ++t) cnt[p.z[beg + t] * 64 + lane] += 1;
+
+    int w = len > 0 ? p.tok[beg] : 0;
+    const unsigned char *ra[8], *ran[8];
+    ring_row_addresses(phib, rowbytes, w, lane, ra);
+    int gs = 0;
+    static_for<0, kAhead>([&](auto sc) { ring_issue<decltype(sc)::value>(ring, decltype(sc)::value % kPcgsRingSlots, ra); });
+    int znext = len > 0 ? p.z[beg] : 0;                            // old topic and (COLLAPSED) its own-token psi, one step ahead (see pcgs_z_kernel)
+    auto own_of = [&](const int word, const int topic) {
+      return (p.beta + (double)(p.n_wk[(size_t)word * K + topic] - 1)) / (p.beta_sum + (double)(p.n_k[topic] - 1));
+    };
+    double own_next = (COLLAPSED && len > 0) ? own_of(w, znext) : 0.0;
+
+    for (int t = 0; t < steps; ++t) {
+      const bool active = t < len, has1 = t + 1 < steps;
+      gs = __builtin_amdgcn_readfirstlane(gs);
+      const int zold = znext;
+      const double own = own_next;
+      const int ip = active ? p.inv_perm[beg + t] : 0;
+      const int w1 = (t + 1 < len) ? p.tok[beg + t + 1] : 0;
+      znext = (t + 1 < len) ? p.z[beg + t + 1] : 0;
+      if (COLLAPSED && t + 1 < len) own_next = own_of(w1, znext);
+      if (has1) ring_row_addresses(phib, rowbytes, w1, lane, ran);
+      if (active) cnt[zold * 64 + lane] -= 1;                      // UPLDA:1494
+      asm volatile("" ::: "memory");
+
+      double sc[KMAX];
+      double sum = 0.0;
+      static_for<0, NS>([&](auto sidx) {                           // UPLDA:1509-1513
+        constexpr int s = decltype(sidx)::value;
+        const int cur = (gs + s) % kPcgsRingSlots;
+        const int nxt = (gs + s + kAhead) % kPcgsRingSlots;
+        if constexpr (s + kAhead < NS) ring_issue<s + kAhead>(ring, nxt, ra);
+        else if (has1) ring_issue<s + kAhead - NS>(ring, nxt, ran);
+        ring_wait<kAhead, NS, s>(has1);
+        if (active) {
+          const unsigned char *rb = my_row + cur * kSliceBytes;
+          D2 ph[kSliceUnits], al[kSliceUnits];
+          int n[kSliceTopics];
+#pragma unroll
+          for (int u = 0; u < kSliceUnits; ++u)
+            if (s * kSliceTopics + 2 * u + 1 < KMAX) {
+              ph[u] = lds_d2(rb + ring_unit_offset(u, rot));
+              al[u] = lds_d2(reinterpret_cast<const unsigned char *>(alb) + (s * kSliceTopics + 2 * u) * 8);
+              n[2 * u] = my_cnt[(s * kSliceTopics + 2 * u) * 64];
+              n[2 * u + 1] = my_cnt[(s * kSliceTopics + 2 * u + 1) * 64];
+            }
+          if constexpr (COLLAPSED) {
+            const int rel = zold - s * kSliceTopics;               // position of the old topic inside this slice, if any
+#pragma unroll
+            for (int u = 0; u < kSliceUnits; ++u) {
+              if (rel == 2 * u) ph[u].a = own;
+              if (rel == 2 * u + 1) ph[u].b = own;
+            }
+          }
+#pragma unroll
+          for (int u = 0; u < kSliceUnits; ++u) {
+            constexpr int k0 = s * kSliceTopics;
+            const int k = k0 + 2 * u;
+            if (k + 1 < KMAX) {
+              sc[k] = ((double)n[2 * u] + al[u].a) * ph[u].a;
+              sum += sc[k];
+              sc[k + 1] = ((double)n[2 * u + 1] + al[u].b) * ph[u].b;
+              sum += sc[k + 1];
+            }
+          }
+        }
+        ring_release_issued();
+      });
+      gs = (gs + NS) % kPcgsRingSlots;
+
+      if (active) {
+        const uint64_t gtok = (uint64_t)(p.tok_base + beg + t);
+        const U4 o = philox4x32_10((uint32_t)gtok, (uint32_t)(gtok >> 32), (uint32_t)GGS_PURPOSE_Z << 24, p.iteration,
+                                   (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
+        double tt = 0.0 - u53(o.x, o.y) * sum;                     // UPLDA:1519-1526, negated walk (see ggs_z_sliced.hpp)
+        if constexpr (POLYAURN)                                    // decided before the walk (pcgs_z_body): a walk from +0 stops at once
+          if (len == 1 || sum == 0.0) tt = 0.0;
+        int newc = 0;
+        bool live = true;
+#pragma unroll
+        for (int kb = 0; kb < KMAX; kb += 16) {
+          if (live) {
+            uint32_t bits = 0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+              if (kb + j < KMAX) {
+                bits = __builtin_amdgcn_alignbit(bits, (uint32_t)hi32(tt), 31);
+                tt += sc[kb + j];
+              }
+            newc += __popc(bits);
+            live = __any(hi32(tt) < 0);
+          }
+        }
+        int new_topic = newc - 1;
+        if (POLYAURN && (len == 1 || sum == 0.0)) {
+          new_topic = polyaurn_uniform_topic(u53(o.x, o.y), K);
+        } else if (new_topic < 0 || hi32(tt) < 0) {                // UPLDA:1529-1531
+          atomicOr(p.status, ST_INVALID_TOPIC);
+          new_topic = new_topic < 0 ? 0 : K - 1;
+        }
+        cnt[new_topic * 64 + lane] += 1;                           // UPLDA:1535
+        p.z[beg + t] = new_topic;
+        p.zw[ip] = new_topic;
+      }
+      asm volatile("" ::: "memory");
+      w = w1;
+#pragma unroll
+      for (int m = 0; m < 8; ++m) ra[m] = ran[m];
+    }
+  }
+}
 template <int KMAX, bool COLLAPSED = false>
-__global__ __launch_bounds__(64) void pcgs_sliced_kernel(PcgsParams p) {
-  constexpr bool POLYAURN = false;
-#include "ggs_z_pcgs_sliced_body.hpp"
-}
+__global__ __launch_bounds__(64) void pcgs_sliced_kernel(PcgsParams p) { pcgs_sliced_body<KMAX, COLLAPSED, false>(p); }
 template <int KMAX>
-__global__ __launch_bounds__(64) void polyaurn_sliced_kernel(PcgsParams p) {
-  constexpr bool COLLAPSED = false, POLYAURN = true;
-#include "ggs_z_pcgs_sliced_body.hpp"
-}
+__global__ __launch_bounds__(64) void polyaurn_sliced_kernel(PcgsParams p) { pcgs_sliced_body<KMAX, false, true>(p); }
 
 }  // namespace ggs

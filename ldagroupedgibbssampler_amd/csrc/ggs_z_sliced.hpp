@@ -32,21 +32,11 @@
 // The two fp64 chains per token (sum, then walk) are the reference's sequential chains; the
 // products are computed once and kept, as in the reference.
 //
-// DMA shape: one global_load_lds_dwordx4 wave-instruction fills 1 KiB = 8 rows x 128 B, lane l
-// -> row 8m + l/8, LDS slot l%8.  Slot j of row r holds source unit (j - r/2) mod 8 (a per-row
-// rotation chosen through the per-lane SOURCE address), so lane t's 16-byte read of unit u, at
-// slot (u + t/2) mod 8 of row t, is bank-conflict free across the wave.  Per chunk every lane
-// computes its 8 source row addresses once; the slice offset is the DMA instruction's immediate
-// -- which the hardware adds to the LDS destination as well as to the global source, hence the
-// "- s*128" on the destination and a ring that does not start at LDS address 0.  The ring slot
-// is wave-uniform and reaches M0 through scalar registers.
-// Lanes with nothing useful to fetch (rows past the chunk, units past the row) read whatever
-// finite bytes sit there (word 0's row; the next row's first entries; the zeroed tail pad of
-// phiT): those scores are multiplied by theta = 0 or belong to lanes that store nothing.
+// The ring (DMA shape, the per-row rotation, completion and release of a slot): ggs_slice_ring.hpp.
 #pragma once
 #include <type_traits>
 
-#include "ggs_z_kernel.hpp"
+#include "ggs_slice_ring.hpp"
 
 // timing-only experiments, compile time (results are wrong on purpose): 1 no DMA, 8 DMA issued but never waited for
 #ifndef GGS_ABL
@@ -55,10 +45,8 @@
 
 namespace ggs {
 
-constexpr int kSliceTopics = 16;
-constexpr int kSliceUnits = 8;            // 16-byte units per row per slice
+constexpr int kSliceTopics = 16;          // fp64 topics in a slice's 128 bytes per row (kSliceUnits, kSliceBytes: ggs_slice_ring.hpp)
 constexpr int kSlice32Topics = 32;        // ... a slice of phiT32 (z_sliced32_kernel): 32 float32 topics in the same 128 bytes
-constexpr int kSliceBytes = 64 * 128;     // 64 rows x 16 topics x 8 B
 // Two slots (one slice in flight beyond the one being scored) since round 4: the LDS a third slot takes is worth more as
 // hot-word table -- measured at BASELINE config 2, sweep / z step in ms: 2 slots 1.496 / 0.922 (96 hot rows), 3 slots
 // 1.548 / 0.968 (57 rows), 4 slots 1.622 / 1.048 (19 rows).  (Round 1 chose 3 when the hot chunks still cost twice as much.)
@@ -179,9 +167,8 @@ __device__ __forceinline__ void cold_chunks32(const ZParams &p, unsigned char *t
   const size_t rowbytes = (size_t)p.Kp32 * 4;
   const const_i32_t *cdocs = (const const_i32_t *)p.c_docs;
   double *prod = reinterpret_cast<double *>(thb + kChunkDocs * kThetaRow);   // the replay's products (KMAX doubles)
-  const int lrow = lane >> 3, lslot = lane & 7;
-  const unsigned char *my_row = ring + lane * 128;
-  const int rot = lane >> 1;
+  const unsigned char *my_row = ring_lane_row(ring, lane);
+  const int rot = ring_lane_rotation(lane);
   const float mscale = (float)p.margin_scale32;
 
   auto load_theta = [&](const int d0, const int d1, double (&tv)[kChunkDocs][NT]) {
@@ -200,18 +187,7 @@ __device__ __forceinline__ void cold_chunks32(const ZParams &p, unsigned char *t
         if (t * 64 + lane < KMAX) reinterpret_cast<float *>(thb + r * kThetaRow)[t * 64 + lane] = phi32_of(tv[r][t]);
   };
   auto row_addresses = [&](const int w, const unsigned char *(&ra)[8]) {
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const int row = 8 * m + lrow;
-      const int wm = __shfl(w, row) & ((1 << kSlotShift) - 1);     // 0 for rows past the chunk
-      ra[m] = phib + (size_t)wm * rowbytes + (size_t)(((lslot - (row >> 1)) & 7) << 4);
-    }
-  };
-  auto issue_slice = [&](auto sc, const int slot, const unsigned char *const (&ra)[8]) {
-    constexpr int s = decltype(sc)::value;
-#pragma unroll
-    for (int m = 0; m < 8; ++m)
-      __builtin_amdgcn_global_load_lds((glb_cvoid_t *)ra[m], (lds_void_t *)(ring + slot * kSliceBytes + m * 1024 - s * 128), 16, s * 128, 0);
+    ring_row_addresses(phib, rowbytes, w, (1 << kSlotShift) - 1, lane, ra);   // word 0 for rows past the chunk
   };
   // U, the decision, the replay and the stores of one chunk c
   auto finish = [&](const float (&a)[KMAX], const int64_t c, const int idx, const int ip, const int w) {
@@ -304,7 +280,7 @@ __device__ __forceinline__ void cold_chunks32(const ZParams &p, unsigned char *t
   row_addresses(w0, ra);
   row_addresses(w1, ran);
   int g = 0;
-  static_for<0, kAhead>([&](auto sc) { issue_slice(sc, decltype(sc)::value % kRingSlots, ra); });
+  static_for<0, kAhead>([&](auto sc) { ring_issue<decltype(sc)::value>(ring, decltype(sc)::value % kRingSlots, ra); });
 
   for (;;) {
     const bool has1 = c + stride < C, has2 = c + 2 * stride < C;
@@ -318,18 +294,16 @@ __device__ __forceinline__ void cold_chunks32(const ZParams &p, unsigned char *t
       constexpr int s = decltype(sidx)::value;
       const int cur = (g + s) % kRingSlots;
       const int nxt = (g + s + kAhead) % kRingSlots;
-      if constexpr (s + kAhead < NS) issue_slice(std::integral_constant<int, s + kAhead>{}, nxt, ra);
-      else if (has1) issue_slice(std::integral_constant<int, s + kAhead - NS>{}, nxt, ran);
-      // as in cold_chunks: 8 DMAs per slice, issued in order
-      if (has1 || s + kAhead < NS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * kAhead) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * (NS - 1 - s)) : "memory");
+      if constexpr (s + kAhead < NS) ring_issue<s + kAhead>(ring, nxt, ra);
+      else if (has1) ring_issue<s + kAhead - NS>(ring, nxt, ran);
+      ring_wait<kAhead, NS, s>(has1);
       {                                                            // every lane (an idle one reads finite bytes: it stores nothing)
         const unsigned char *rb = my_row + cur * kSliceBytes;
         f4_t ph[kSliceUnits], th[kSliceUnits];                     // unit u = topics 4u .. 4u + 3 of the slice
 #pragma unroll
         for (int u = 0; u < kSliceUnits; ++u)
           if (s * kSlice32Topics + 4 * u < KMAX) {                 // compile time (KMAX is a multiple of 8)
-            ph[u] = *reinterpret_cast<const f4_t *>(rb + (((u + rot) & 7) << 4));
+            ph[u] = *reinterpret_cast<const f4_t *>(rb + ring_unit_offset(u, rot));
             th[u] = *reinterpret_cast<const f4_t *>(trow + s * (kSlice32Topics * 4) + u * 16);
           }
 #pragma unroll
@@ -346,11 +320,7 @@ __device__ __forceinline__ void cold_chunks32(const ZParams &p, unsigned char *t
           }
         }
       }
-      // every read of this ring slot has RETURNED before the next step's DMA may refill it: issued is not enough -- the
-      // scheduler may sink the arithmetic (and the compiler's wait for these reads) behind that DMA, and beside the table
-      // waves of the fused form the reads queue long enough for an L2 hit to overwrite the slot first (measured: wrong
-      // draws in the fused form only, without this wait)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      ring_release_returned();                                     // "issued" gave wrong draws in the fused form (ggs_slice_ring.hpp)
     });
     g = (g + NS) % kRingSlots;
 
@@ -408,10 +378,8 @@ __device__ __forceinline__ void z_sliced_body(const ZParams &p) {
   }
   __syncthreads();                                                 // the only barrier; no DMA is in flight yet
 
-  const int lrow = lane >> 3, lslot = lane & 7;
-  // byte offset of unit u of this lane's row inside a ring slot: lane*128 + ((u + lane/2) & 7)*16
-  const unsigned char *my_row = ring + lane * 128;
-  const int rot = lane >> 1;
+  const unsigned char *my_row = ring_lane_row(ring, lane);
+  const int rot = ring_lane_rotation(lane);
 
   // theta rows of a chunk's two documents: lane l holds entries l, l + 64, ... of each (0.0 beyond K)
   auto load_theta = [&](const int d0, const int d1, double (&tv)[kChunkDocs][NT]) {
@@ -475,22 +443,11 @@ __device__ __forceinline__ void z_sliced_body(const ZParams &p) {
   // ------------------------------------------------------------------ cold chunks
   auto cold_chunks = [&]() {
     const int64_t C = p.num_cold;
-    // Source addresses of this lane's 8 DMA rows (m = 0..7): row 8m + lrow of the chunk, unit
-    // (lslot - row/2) mod 8 of slice 0.
     auto row_addresses = [&](const int w, const unsigned char *(&ra)[8]) {
-#pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        const int row = 8 * m + lrow;
-        const int wm = __shfl(w, row) & ((1 << kSlotShift) - 1);   // 0 for rows past the chunk
-        ra[m] = phib + (size_t)wm * rowbytes + (size_t)(((lslot - (row >> 1)) & 7) << 4);
-      }
+      ring_row_addresses(phib, rowbytes, w, (1 << kSlotShift) - 1, lane, ra);   // word 0 for rows past the chunk
     };
     auto issue_slice = [&](auto sc, const int slot, const unsigned char *const (&ra)[8]) {
-      constexpr int s = decltype(sc)::value;
-      if (GGS_ABL & 1) return;
-#pragma unroll
-      for (int m = 0; m < 8; ++m)
-        __builtin_amdgcn_global_load_lds((glb_cvoid_t *)ra[m], (lds_void_t *)(ring + slot * kSliceBytes + m * 1024 - s * 128), 16, s * 128, 0);
+      if (!(GGS_ABL & 1)) ring_issue<decltype(sc)::value>(ring, slot, ra);
     };
 
     // ---- prologue.  Suffix 0 = this chunk, 1 = next, 2 = the one after.
@@ -532,13 +489,7 @@ __device__ __forceinline__ void z_sliced_body(const ZParams &p) {
         // keep kAhead slices in flight: slice s + kAhead of this chunk, or of the next one
         if constexpr (s + kAhead < NS) issue_slice(std::integral_constant<int, s + kAhead>{}, nxt, ra);
         else if (has1) issue_slice(std::integral_constant<int, s + kAhead - NS>{}, nxt, ran);
-        // LDS-DMA completion is tracked by vmcnt in issue order.  With kAhead slices (8 DMAs each)
-        // issued after slice s, "at most 8*kAhead outstanding" means slice s has landed; at the tail
-        // of the last chunk fewer slices follow.  The waves of the workgroup never meet in the
-        // chunk loop: no hardware barrier, only a compiler fence so that no LDS read moves above the wait.
-        if (GGS_ABL & (1 | 8)) {}
-        else if (has1 || s + kAhead < NS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * kAhead) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * (NS - 1 - s)) : "memory");
+        if (!(GGS_ABL & (1 | 8))) ring_wait<kAhead, NS, s>(has1);
         if (id0 >= 0) {
           const unsigned char *rb = my_row + cur * kSliceBytes;
           // unit u = topics (k, k+1).  All 16 LDS reads of the slice are issued up front (they return
@@ -547,7 +498,7 @@ __device__ __forceinline__ void z_sliced_body(const ZParams &p) {
 #pragma unroll
           for (int u = 0; u < kSliceUnits; ++u)
             if (s * kSliceTopics + 2 * u + 1 < KMAX) {             // compile time (KMAX is even)
-              ph[u] = lds_d2(rb + (((u + rot) & 7) << 4));
+              ph[u] = lds_d2(rb + ring_unit_offset(u, rot));
               th[u] = lds_d2(trow + s * (kSliceTopics * 8) + u * 16);
             }
 #pragma unroll
@@ -562,7 +513,7 @@ __device__ __forceinline__ void z_sliced_body(const ZParams &p) {
             }
           }
         }
-        asm volatile("" ::: "memory");                             // every read of this ring slot is issued before it is refilled
+        ring_release_issued();
       });
       g = (g + NS) % kRingSlots;                             // ring slot of the next chunk's slice 0
 

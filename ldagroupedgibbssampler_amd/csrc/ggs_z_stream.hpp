@@ -46,24 +46,8 @@ __global__ __launch_bounds__(64) void z_stream_kernel(ZParams p) {
   const const_i32_t *cdoc = (const const_i32_t *)p.chunk_doc;
   const int64_t C = p.num_chunks;
 
-  const int lrow = lane >> 3, lslot = lane & 7;
-  const unsigned char *my_row = smem + lane * 128;
-  const int rot = lane >> 1;
-
-  auto row_addresses = [&](const int w, const unsigned char *(&ra)[8]) {
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const int row = 8 * m + lrow;
-      const int wm = __shfl(w, row);                               // 0 for rows past the chunk
-      ra[m] = phib + (size_t)wm * rowbytes + (size_t)(((lslot - (row >> 1)) & 7) << 4);
-    }
-  };
-  auto issue_slice = [&](const int s, const int slot, const unsigned char *const (&ra)[8]) {
-    const size_t off = (size_t)s * 128;
-#pragma unroll
-    for (int m = 0; m < 8; ++m)
-      __builtin_amdgcn_global_load_lds((glb_cvoid_t *)(ra[m] + off), (lds_void_t *)(smem + slot * kSliceBytes + m * 1024), 16, 0, 0);
-  };
+  const unsigned char *my_row = ring_lane_row(smem, lane);        // the ring (ggs_slice_ring.hpp) starts the workgroup's LDS
+  const int rot = ring_lane_rotation(lane);
 
   // a contiguous range of chunks per wave (every chunk costs the same whatever its length), so
   // the chunks of one document follow each other and its theta row is staged once
@@ -77,10 +61,10 @@ __global__ __launch_bounds__(64) void z_stream_kernel(ZParams p) {
   int w0 = (lane < len0) ? p.tok[start0 + lane] : 0;
   int ip0 = (lane < len0) ? p.inv_perm[start0 + lane] : 0;
   const unsigned char *ra[8], *ran[8];
-  row_addresses(w0, ra);
+  ring_row_addresses(phib, rowbytes, w0, lane, ra);                // word 0 for rows past the chunk
   int g = 0;                                                       // ring slot of this chunk's first slice
 #pragma unroll
-  for (int s = 0; s < kAhead; ++s) issue_slice(s, (g + s) % kStreamRingSlots, ra);
+  for (int s = 0; s < kAhead; ++s) ring_issue(smem, s, (g + s) % kStreamRingSlots, ra);
 
   for (;;) {
     const bool has1 = c + 1 < cend;
@@ -111,7 +95,7 @@ __global__ __launch_bounds__(64) void z_stream_kernel(ZParams p) {
       w1 = (lane < len1) ? p.tok[start1 + lane] : 0;
       ip1 = (lane < len1) ? p.inv_perm[start1 + lane] : 0;
       if (c + 2 < cend) { start2 = cstart[c + 2]; len2 = clen[c + 2]; doc2 = cdoc[c + 2]; }
-      row_addresses(w1, ran);
+      ring_row_addresses(phib, rowbytes, w1, lane, ran);
     }
     asm volatile("" ::: "memory");
 
@@ -122,24 +106,18 @@ __global__ __launch_bounds__(64) void z_stream_kernel(ZParams p) {
       const int cur = (g + j) % kStreamRingSlots;
       const int nxt = (g + j + kAhead) % kStreamRingSlots;
       const int ja = j + kAhead;
-      if (ja < 2 * NS) issue_slice(ja < NS ? ja : ja - NS, nxt, ra);
-      else if (has1) issue_slice(ja - 2 * NS, nxt, ran);
-      // all but the youngest 8*kAhead DMAs done => slice j has landed; at the tail of the last
-      // chunk fewer slices follow it
-      if (has1 || ja < 2 * NS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * kAhead) : "memory");
-      else {
-        const int rem = 2 * NS - 1 - j;                            // slices still behind this one: fewer than kAhead
-        if (rem >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if (rem == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
+      if (ja < 2 * NS) ring_issue(smem, ja < NS ? ja : ja - NS, nxt, ra);
+      else if (has1) ring_issue(smem, ja - 2 * NS, nxt, ran);
+      // kAhead slices follow slice j; at the tail of the last chunk fewer
+      if (has1 || ja < 2 * NS) ring_wait_all_but<kAhead>();
+      else ring_wait_all_but<kAhead - 1>(2 * NS - 1 - j);
       if (lane < len0) {
         const unsigned char *rb = my_row + cur * kSliceBytes;
         const unsigned char *tb = reinterpret_cast<const unsigned char *>(thb) + s * kSliceTopics * 8;
         D2 ph[kSliceUnits], th[kSliceUnits];
 #pragma unroll
         for (int u = 0; u < kSliceUnits; ++u) {
-          ph[u] = lds_d2(rb + (((u + rot) & 7) << 4));
+          ph[u] = lds_d2(rb + ring_unit_offset(u, rot));
           th[u] = lds_d2(tb + u * 16);
         }
         if (j < NS) {
@@ -161,7 +139,7 @@ __global__ __launch_bounds__(64) void z_stream_kernel(ZParams p) {
           }
         }
       }
-      asm volatile("" ::: "memory");                               // every read of this ring slot is issued before it is refilled
+      ring_release_issued();
     }
     g = (g + 2 * NS) % kStreamRingSlots;
 
@@ -231,7 +209,7 @@ template <bool REGCK, int kGroupSlices>
 __global__ __launch_bounds__(64) void z_stream1_kernel(ZParams p) {
   constexpr int R = kStream1RingSlots, kAhead = R - 1;
   static_assert(kGroupSlices == 1 || kGroupSlices == 2 || kGroupSlices == 4, "the checkpoint test masks with G - 1");
-  static_assert(kAhead >= 1 && kAhead <= 3, "wait_younger covers up to 3 slices in flight behind the current one");
+  static_assert(kAhead >= 1, "at least one slice in flight behind the current one");
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = threadIdx.x;
   const int K = p.K, Kp = p.Kp;
@@ -249,24 +227,9 @@ __global__ __launch_bounds__(64) void z_stream1_kernel(ZParams p) {
   const const_i32_t *cdoc1 = (const const_i32_t *)p.chunk_doc1;
   const int64_t C = p.num_chunks;
 
-  const int lrow = lane >> 3, lslot = lane & 7;
-  const unsigned char *my_row = smem + lane * 128;
-  const int rot = lane >> 1;
-
-  auto row_addresses = [&](const int w, const unsigned char *(&ra)[8]) {
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const int row = 8 * m + lrow;
-      const int wm = __shfl(w, row);                               // 0 for rows past the chunk
-      ra[m] = phib + (size_t)wm * rowbytes + (size_t)(((lslot - (row >> 1)) & 7) << 4);
-    }
-  };
-  auto issue_slice = [&](const int s, const int slot, const unsigned char *const (&ra)[8]) {
-    const size_t off = (size_t)s * 128;
-#pragma unroll
-    for (int m = 0; m < 8; ++m)
-      __builtin_amdgcn_global_load_lds((glb_cvoid_t *)(ra[m] + off), (lds_void_t *)(smem + slot * kSliceBytes + m * 1024), 16, 0, 0);
-  };
+  const int lrow = lane >> 3;
+  const unsigned char *my_row = ring_lane_row(smem, lane);
+  const int rot = ring_lane_rotation(lane);
 
   const int64_t cend = C * (int64_t)(blockIdx.x + 1) / (int64_t)gridDim.x;
   int64_t c = C * (int64_t)blockIdx.x / (int64_t)gridDim.x;
@@ -282,17 +245,10 @@ __global__ __launch_bounds__(64) void z_stream1_kernel(ZParams p) {
   int w0 = (lane < tokens_of(len0)) ? p.tok[start0 + lane] : 0;
   int ip0 = (lane < tokens_of(len0)) ? p.inv_perm[start0 + lane] : 0;
   const unsigned char *ra[8], *ran[8], *rr[8];
-  row_addresses(w0, ra);
-  // all but the youngest n slices (8 DMA instructions each) have landed
-  auto wait_younger = [](const int n) {
-    if (n >= 3) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    else if (n == 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if (n == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
+  ring_row_addresses(phib, rowbytes, w0, lane, ra);                // word 0 for rows past the chunk
   int g = 0;                                                       // ring slot of this chunk's first slice
 #pragma unroll
-  for (int s = 0; s < kAhead; ++s) issue_slice(s, (g + s) % R, ra);
+  for (int s = 0; s < kAhead; ++s) ring_issue(smem, s, (g + s) % R, ra);
 
   for (;;) {
     const bool has1 = c + 1 < cend;
@@ -330,7 +286,7 @@ __global__ __launch_bounds__(64) void z_stream1_kernel(ZParams p) {
       w1 = (lane < tokens_of(len1)) ? p.tok[start1 + lane] : 0;
       ip1 = (lane < tokens_of(len1)) ? p.inv_perm[start1 + lane] : 0;
       if (c + 2 < cend) { start2 = cstart[c + 2]; len2 = clen[c + 2]; doc2 = cdoc[c + 2]; docb2 = p.two_rows ? cdoc1[c + 2] : doc2; }
-      row_addresses(w1, ran);
+      ring_row_addresses(phib, rowbytes, w1, lane, ran);
     }
     asm volatile("" ::: "memory");
 
@@ -338,15 +294,15 @@ __global__ __launch_bounds__(64) void z_stream1_kernel(ZParams p) {
     double sum = 0.0;
     auto pass1_slice = [&](const int j) {
       const int cur = (g + j) % R;
-      if (j + kAhead < NS) issue_slice(j + kAhead, (g + j + kAhead) % R, ra);
-      wait_younger(min(kAhead, NS - 1 - j));                       // the pipeline drains at the end: which group to stream next is not known yet
+      if (j + kAhead < NS) ring_issue(smem, j + kAhead, (g + j + kAhead) % R, ra);
+      ring_wait_all_but<kAhead>(min(kAhead, NS - 1 - j));          // the pipeline drains at the end: which group to stream next is not known yet
       if (lane < n0) {
         const unsigned char *rb = my_row + cur * kSliceBytes;
         const unsigned char *tb = reinterpret_cast<const unsigned char *>(thl) + j * kSliceTopics * 8;
         D2 ph[kSliceUnits], th[kSliceUnits];
 #pragma unroll
         for (int u = 0; u < kSliceUnits; ++u) {
-          ph[u] = lds_d2(rb + (((u + rot) & 7) << 4));
+          ph[u] = lds_d2(rb + ring_unit_offset(u, rot));
           th[u] = lds_d2(tb + u * 16);
         }
 #pragma unroll
@@ -355,7 +311,7 @@ __global__ __launch_bounds__(64) void z_stream1_kernel(ZParams p) {
           sum += th[u].b * ph[u].b;
         }
       }
-      asm volatile("" ::: "memory");                               // every read of this ring slot is issued before it is refilled
+      ring_release_issued();
     };
     if constexpr (REGCK) {
 #pragma unroll
@@ -407,8 +363,8 @@ __global__ __launch_bounds__(64) void z_stream1_kernel(ZParams p) {
     const int gr = (g + NS) % R;                                   // ring slot of the first refinement slice
 #pragma unroll
     for (int i = 0; i < kAhead; ++i) {
-      if (i < kGroupSlices) issue_slice(i, (gr + i) % R, rr);
-      else if (has1) issue_slice(i - kGroupSlices, (gr + i) % R, ran);
+      if (i < kGroupSlices) ring_issue(smem, i, (gr + i) % R, rr);
+      else if (has1) ring_issue(smem, i - kGroupSlices, (gr + i) % R, ran);
     }
     int found = -1;
     double dprev = 0.0;
@@ -416,16 +372,16 @@ __global__ __launch_bounds__(64) void z_stream1_kernel(ZParams p) {
     for (int i = 0; i < kGroupSlices; ++i) {
       const int cur = (gr + i) % R;
       const int ia = i + kAhead;
-      if (ia < kGroupSlices) issue_slice(ia, (gr + ia) % R, rr);
-      else if (has1) issue_slice(ia - kGroupSlices, (gr + ia) % R, ran);   // the next chunk's first slices
-      wait_younger(has1 ? kAhead : min(kAhead, kGroupSlices - 1 - i));
+      if (ia < kGroupSlices) ring_issue(smem, ia, (gr + ia) % R, rr);
+      else if (has1) ring_issue(smem, ia - kGroupSlices, (gr + ia) % R, ran);   // the next chunk's first slices
+      ring_wait_all_but<kAhead>(has1 ? kAhead : min(kAhead, kGroupSlices - 1 - i));
       if (lane < n0) {
         const unsigned char *rb = my_row + cur * kSliceBytes;
         const unsigned char *tb = reinterpret_cast<const unsigned char *>(thl) + ((size_t)gsel * kGroupSlices + i) * kSliceTopics * 8;
         D2 ph[kSliceUnits], th[kSliceUnits];
 #pragma unroll
         for (int u = 0; u < kSliceUnits; ++u) {
-          ph[u] = lds_d2(rb + (((u + rot) & 7) << 4));
+          ph[u] = lds_d2(rb + ring_unit_offset(u, rot));
           th[u] = lds_d2(tb + u * 16);
         }
 #pragma unroll
@@ -439,7 +395,7 @@ __global__ __launch_bounds__(64) void z_stream1_kernel(ZParams p) {
           if (found < 0 && t0 - s < -delta) { found = kk + 1; dprev = t0 - sp; }
         }
       }
-      asm volatile("" ::: "memory");
+      ring_release_issued();
     }
     g = (g + NS + kGroupSlices) % R;
 
