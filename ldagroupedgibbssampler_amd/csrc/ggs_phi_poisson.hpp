@@ -6,7 +6,7 @@
 //
 // Per cell, with c = n_kv, lambda = beta + c (fp64), element e = k * V + v and the purpose of ggs_hip.h:
 //   c <  L  X = the smallest j with u < T_c[j]; u = the element's first uniform; T_c = row c of the host-built table
-//           (ggs_api.hip, build_poisson_table): the pmf of Poisson(lambda) truncated to 2L entries, renormalised, as a
+//           (build_poisson_table, ggs_host_phi.hpp): the pmf of Poisson(lambda) truncated to 2L entries, renormalised, as a
 //           cumulative table with T_c[2L - 1] = 1.  The reference samples the same truncated pmf with a Walker alias
 //           table; inverse CDF makes X a pure function of (u, table), so the search order cannot change a bit.
 //   c >= L  X = max(0, floor(sqrt(lambda) * g + lambda + 0.5)); g = the element's first Gaussian (java.util.Random's

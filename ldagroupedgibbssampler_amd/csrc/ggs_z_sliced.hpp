@@ -55,7 +55,7 @@ constexpr int kSlice32Topics = 32;        // ... a slice of phiT32 (z_sliced32_k
 #endif
 constexpr int kRingSlots = GGS_RING_SLOTS;
 constexpr int kSlicedMaxTopics = 192;     // 384 score registers (VGPR + AGPR) + working set < 512
-constexpr int kSlicedDefaultTopics = 160; // ... and the largest K the host gives to these kernels unasked (ggs_api.hip: measured break-even)
+constexpr int kSlicedDefaultTopics = 160; // ... and the largest K the host gives to these kernels unasked (plan_launches, ggs_host_plan.hpp: measured break-even)
 constexpr int kPhiTailPadBytes = 1024;    // zeroed bytes after the last phiT row (see above; the pcgs kernel pads K to 48, the one-pass stream kernel to a multiple of 64)
 constexpr int kHotTailBytes = 64;          // zeroed bytes after z_hot_kernel's table: what a lane refining the last slice reads past the last row
 

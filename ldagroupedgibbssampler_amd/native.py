@@ -14,7 +14,7 @@ FLAG_LIGHTCOLLAPSED = 256
 FLAG_NZVSSPALIAS = 512
 FLAG_ADLDA = 1024
 FLAG_LIGHTPCLDAW2 = 2048   # sampler.LightPCLDAtypeTopicProposal: constructed directly, so not a key of SCHEME_FLAGS (create_model refuses the name)
-# scheme name -> its flag, in the order of the library's scheme table (csrc/ggs_api.hip, kSchemes)
+# scheme name -> its flag, in the order of the library's scheme table (csrc/ggs_host_state.hpp, kSchemes)
 SCHEME_FLAGS = {"ggs": 0, "pcgs": FLAG_PCGS, "collapsed": FLAG_COLLAPSED, "polyaurn": FLAG_POLYAURN, "spalias": FLAG_SPALIAS, "lightpclda": FLAG_LIGHTPCLDA,
                 "polyaurn_sparse": FLAG_POLYAURN_SPARSE, "lightcollapsed": FLAG_LIGHTCOLLAPSED, "nzvsspalias": FLAG_NZVSSPALIAS, "adlda": FLAG_ADLDA}
 PURPOSE_Z, PURPOSE_THETA, PURPOSE_PHI, PURPOSE_INIT_PHI = 1, 2, 3, 4

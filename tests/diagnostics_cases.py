@@ -14,7 +14,7 @@ from ldagroupedgibbssampler_amd.corpus import Corpus, random_corpus
 
 U = 2.0 ** -53                                   # unit roundoff of a double
 
-# ---- the launch shapes of csrc/ggs_loglik.hpp and their launchers in ggs_api.hip, restated ---------------------------
+# ---- the launch shapes of csrc/ggs_loglik.hpp and their launchers (the entry points of ggs_api.hip), restated ----
 LL_BLOCK = 256                                   # kLLBlock: threads of every block of these kernels
 LL_GRID = 1024                                   # blocks of the grid-stride kernels over n_wk and over Phi
 MAX_LDS = 160 * 1024                             # kMaxLdsBytes

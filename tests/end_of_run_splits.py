@@ -1,5 +1,5 @@
 """What tests/test_end_of_run_splits_gpu.py and tests/test_end_of_run_splits_model.py share: how the host side of the end-of-run
-features (ggs_api.hip: the min distances, the topic diagnostics) cuts its work -- pieces of documents, groups of topics, bands
+features (ggs_host_end_of_run.hpp: the min distances, the topic diagnostics) cuts its work -- pieces of documents, groups of topics, bands
 of tiles, pieces of a foreign block, grids that are capped so that a workgroup loops -- restated with the caps named, and the
 inputs whose second piece, group, band and third trip the GPU cases compare.
 

@@ -1,6 +1,6 @@
 """A handle with a history: what tests/test_handle_lifecycle_gpu.py needs to resume a chain on a fresh handle, rewind a
 handle to an earlier state of itself, reuse it for a second and a third corpus and continue across shards -- for all
-eleven schemes from ONE table (ROWS, in the order of kSchemes in csrc/ggs_api.hip plus spalias_priors), the way
+eleven schemes from ONE table (ROWS, in the order of kSchemes in csrc/ggs_host_state.hpp plus spalias_priors), the way
 tests/scheme_table_cases.py keeps the capabilities in one place.  Everything here runs without a device; the pure parts
 are pinned by tests/test_handle_lifecycle_model.py.
 
@@ -185,7 +185,7 @@ def point_estimate(n_wk, beta):
 
 # ---- the phi mean's rule ------------------------------------------------------------------------------------------------
 def accepted(iteration, burn_in=BURN_IN, thin=THIN):
-    """UPLDA:1350-1352, sample_phi_this_iteration in csrc/ggs_api.hip"""
+    """UPLDA:1350-1352, sample_phi_this_iteration in csrc/ggs_host_sweep.hpp"""
     return burn_in > 0 and iteration > burn_in and iteration % thin == 0
 
 

@@ -2,17 +2,18 @@
 then a short one, then a one-token one, then an empty one; and the arithmetic that says how many work items a workgroup
 of a persistent grid takes (its loop trips) under a given CU count -- restated from the host code, with the caps named.
 
-Every persistent launch goes through launch() (ggs_api.hip:340): grid = min(ceil(items / waves), CUs x per_cu) workgroups
-of `waves` waves, an item per wave and trip.  per_cu is what the plan allows at most:
+Every persistent launch goes through launch() (ggs_host_state.hpp): grid = min(ceil(items / waves), CUs x per_cu) workgroups
+of `waves` waves, an item per wave and trip.  per_cu is what the plan allows at most (plan_launches, ggs_host_plan.hpp, but where
+another function is named):
 
-  CAP_WAVE      32   the single-wave document kernels: pcgs_wave (ggs_api.hip:1115), lightpc (:1142), spalias and
-                     polyaurn_sparse (:1893) -- min(what LDS and registers allow, 32)
-  CAP_LANE       8   the lane-per-document kernels, one wave of 64 documents per workgroup (:1123); the ggs tile and
-                     streaming kernels (:1058)
-  CAP_WORDLIST   8   word_list_build_kernel, workgroups of WORDLIST_WAVES = 4 waves, a word per wave (:1133)
-  CAP_ALIAS     16   alias_build_kernel, alias_words_per_block(K) words per workgroup and trip (:1129, ggs_alias.hpp:39)
-  CAP_POISSON    2   phi_poisson_kernel: tiles of rows_per_tile rows, two workgroups per CU (:738-741)
-  CAP_SLICED     1   the ggs score-register kernels: one workgroup of SLICED_WAVES = 4 waves per CU (:1036-1039)
+  CAP_WAVE      32   the single-wave document kernels: pcgs_wave (pl.wave), lightpc (pl.lightpc), spalias and
+                     polyaurn_sparse (ggs_set_corpus, ggs_api.hip) -- min(what LDS and registers allow, 32)
+  CAP_LANE       8   the lane-per-document kernels, one wave of 64 documents per workgroup (pl.lane); the ggs tile and
+                     streaming kernels (pl.z)
+  CAP_WORDLIST   8   word_list_build_kernel, workgroups of WORDLIST_WAVES = 4 waves, a word per wave (pl.wordlist)
+  CAP_ALIAS     16   alias_build_kernel, alias_words_per_block(K) words per workgroup and trip (pl.alias, ggs_alias.hpp:39)
+  CAP_POISSON    2   phi_poisson_kernel: tiles of rows_per_tile rows, two workgroups per CU (phi_slice_poisson, ggs_host_phi.hpp)
+  CAP_SLICED     1   the ggs score-register kernels: one workgroup of SLICED_WAVES = 4 waves per CU (pl.cold, pl.hot, pl.warm)
   CAP_VSBITS    32   vs_bits_kernel (nzvsspalias): a wave per 32-cell word of 64 topics (plan_launches, pl.vsbits)
   CAP_WORDMASK   8   word_list_mask_kernel (nzvsspalias): as word_list_build_kernel, a word per wave (pl.wordmask)
 nzvs_wave_kernel takes CAP_WAVE like the other sparse walks (resident_waves_per_cu: 32 at most).
@@ -46,15 +47,15 @@ def alias_words_per_block(K):
 
 
 def alias_items(V, K):
-    return -(-V // alias_words_per_block(K))                      # launch_alias_build, ggs_api.hip:859
+    return -(-V // alias_words_per_block(K))                      # launch_alias_build, ggs_host_phi.hpp
 
 
 def vs_bits_items(V, K):
-    return -(-V // 32) * -(-K // 64)                               # launch_vs_chain: vs_W words x ceil(Ks / 64) (ggs_api.hip)
+    return -(-V // 32) * -(-K // 64)                               # launch_vs_chain: vs_W words x ceil(Ks / 64) (ggs_host_phi.hpp)
 
 
 def poisson_tiles(V, K, cus):
-    """phi_slice_poisson (ggs_api.hip:737-741) for the whole vocabulary and all K topics"""
+    """phi_slice_poisson (ggs_host_phi.hpp) for the whole vocabulary and all K topics"""
     cells = V * K
     want = max(POISSON_THREADS, cells // (cus * 8))
     rows_per_tile = max(1, min(V, -(-want // K)))

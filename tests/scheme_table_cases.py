@@ -1,4 +1,4 @@
-"""What the scheme table (csrc/ggs_api.hip, kSchemes) must leave as it was: how ggs_create classes every combination of the
+"""What the scheme table (csrc/ggs_host_state.hpp, kSchemes) must leave as it was: how ggs_create classes every combination of the
 scheme flags, and what every scheme's handle answers to the getters that only some schemes have.  The two functions here
 observe a library; the goldens beside them (tests/golden/scheme_flag_codes.json, scheme_capabilities.json) were recorded
 with them from the library of the commit before the table."""

@@ -109,7 +109,7 @@ def test_parallel_schedule_matches_its_restatement(native, oracle, cats, K, alph
 
 @pytest.mark.parametrize("K,wave", [(96, None), (97, None), (130, "0"), (192, "0")])
 def test_parallel_schedule_either_kernel_around_the_switch_point(native, oracle, monkeypatch, K, wave):
-    """scheme=collapsed takes the wave-per-document kernel from 97 topics on (ggs_api.hip: the measured break-even); the
+    """scheme=collapsed takes the wave-per-document kernel from 97 topics on (kCollapsedWaveFromTopics, ggs_host_plan.hpp: the measured break-even); the
     lane-per-document variants above stay reachable (GGS_DEBUG_PCGS_WAVE=0) and give the same counts."""
     if wave is not None:
         monkeypatch.setenv("GGS_DEBUG_PCGS_WAVE", wave)

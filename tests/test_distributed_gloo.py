@@ -261,7 +261,7 @@ class OracleSlicedEngine:
     def _exchange_phi(self, initial):
         """What travels since round 3: the rank's UNNORMALISED gammas [V][Ksm] in two halves of the vocabulary (whole 64-row
         segments), the Ksm column sums behind the second; the receiver divides (ParallelDirichlet.java:60-66: the same
-        IEEE division, the clamp to Double.MIN_VALUE) -- csrc/ggs_api.hip phi_step_b1 .. phi_step_c, phi_repack_kernel."""
+        IEEE division, the clamp to Double.MIN_VALUE) -- csrc/ggs_host_phi.hpp phi_step_b1 .. phi_step_c, phi_repack_kernel."""
         n = self.k1 - self.k0
         gam, sums = self.o.phi_gammas_range(self.k0, self.k1, initial)
         mine = np.zeros((self.V, self.lay.Ksm))

@@ -1,7 +1,7 @@
 """The end-of-run kernels on their second piece, group, band and trip.
 
 The min distances (csrc/ggs_distances.hpp), the top words and the topic diagnostics (csrc/ggs_topic_diagnostics.hpp) split
-their work on the host side of ggs_api.hip: documents in pieces, topics in groups, tiles in bands, a foreign block in pieces,
+their work on the host side, in ggs_host_end_of_run.hpp: documents in pieces, topics in groups, tiles in bands, a foreign block in pieces,
 and grids that are capped so that a workgroup loops.  The constants are sized for the benchmark corpus; at test shapes none of
 these loops runs twice.  Here each of them does, either at a shape that reaches the built-in constant (the document pass on
 8 492 documents, td_wtc_kernel on 16 389 words, td_mirror_kernel on 540 672 cells, two groups of topics at V = 70 000) or under
@@ -10,7 +10,7 @@ GGS_DEBUG_DIST_BAND_TILES).  tests/end_of_run_splits.py hol
 tests/test_end_of_run_splits_model.py proves without a device that every case reaches what it claims; every case here
 asserts the same counts before it compares anything.
 
-  loop of ggs_api.hip                                   its second round is reached by
+  loop of ggs_host_end_of_run.hpp                          its second round is reached by
   td_docs_kernel, grid min(nd, 4096)                    test_document_pass_second_and_third_trip
   TdDocPlan::piece                                      test_document_pieces_of_256, test_document_pieces_through_a_handle
   TdScorePlan::group, td_sorted_kernel with k0 > 0      test_topic_groups_of_g, test_topic_groups_through_a_handle,

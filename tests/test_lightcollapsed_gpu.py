@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 777
 KERNEL = "lightcollapsed_wave_kernel"
-# the plan's caps of the two kernels (ggs_api.hip, plan_launches), beside persistent_grid's CAP_* constants: the z kernel is a
+# the plan's caps of the two kernels (plan_launches, ggs_host_plan.hpp), beside persistent_grid's CAP_* constants: the z kernel is a
 # single-wave document kernel planned by lightpc's rule, min(what LDS and registers allow, 32) -- at its 173 VGPRs the registers
 # allow 2 waves per SIMD, 8 workgroups per CU, so 32 is an upper bound of the real grid and a trip count computed with it holds;
 # the build takes alias_build_kernel's words per workgroup and its cap of 16

@@ -38,7 +38,7 @@ def test_class_flag_header_and_java_constant_agree():
     java = open(os.path.join(ROOT, "integration", "java", "cc", "mallet", "topics", "GGSNative.java")).read()
     assert "FLAG_LIGHTPCLDAW2 = 2048" in java
     assert native.Z_KERNEL_NAMES[12] == "lightpcw2_wave_kernel (wave per document)"
-    api = open(os.path.join(ROOT, "ldagroupedgibbssampler_amd", "csrc", "ggs_api.hip")).read()
+    api = open(os.path.join(ROOT, "ldagroupedgibbssampler_amd", "csrc", "ggs_host_state.hpp")).read()
     assert re.search(r'\{"lightpcldaw2", GGS_FLAG_LIGHTPCLDAW2, [^}]*?, 12, &LaunchPlan::lightpcw2,', api)   # its row of the scheme table
 
 

@@ -710,7 +710,7 @@ def test_pcgs_wave_kernel_forced_and_its_exact_replay(native, oracle, monkeypatc
 @pytest.mark.parametrize("K,wave", [(176, None), (177, None), (192, "0"), (184, "0"), (150, "1")])
 def test_pcgs_either_kernel_around_the_switch_point(native, oracle, monkeypatch, K, wave):
     """The lane-per-document score-register kernels serve up to 176 topics by default and the wave-per-document kernel
-    from 177 (ggs_api.hip: the measured break-even); both stay reachable on either side (GGS_DEBUG_PCGS_WAVE) and give the
+    from 177 (kPcgsWaveFromTopics, ggs_host_plan.hpp: the measured break-even); both stay reachable on either side (GGS_DEBUG_PCGS_WAVE) and give the
     oracle's bits -- including the 176..192 lane variants that spill."""
     if wave is not None:
         monkeypatch.setenv("GGS_DEBUG_PCGS_WAVE", wave)

@@ -1,6 +1,6 @@
 """Every persistent kernel on its second and later work items.
 
-launch() (ggs_api.hip:340) starts min(items, CUs x per_cu) workgroups and each strides its share; between two items a
+launch() (ggs_host_state.hpp) starts min(items, CUs x per_cu) workgroups and each strides its share; between two items a
 workgroup has to bring its private state back to fresh -- LDS counts, the non-zero list with its back-map and nnz, cuml[],
 the chunks loaded ahead, polyaurn_sparse's entries and Phi values of the next two tokens, lightpclda's proposal state, the
 Poisson kernel's LDS totals, the alias builder's stacks.  On 256 CUs no bit-exact test of the per-document kernels is large
@@ -20,7 +20,7 @@ runs debug_poisson_kernel, a thread per draw): alias_build_kernel by the K = 102
 V = 210: 53 trips over at most 16 workgroups, the last one of 2 words), word_list_build_kernel by the polyaurn_sparse rows,
 phi_poisson_kernel by the polyaurn and polyaurn_sparse rows; each of those rows writes the inequality out from V and K.
 nzvsspalias' two persistent Phi-phase kernels, vs_bits_kernel and word_list_mask_kernel, go through launch() with the handle's
-CU count like its z kernel (ggs_api.hip: launch_vs_chain and the list build behind the alias tables): the K = 130 row gives
+CU count like its z kernel (ggs_host_phi.hpp: launch_vs_chain and the list build behind the alias tables): the K = 130 row gives
 each of the three at least three trips on one CU, the last one ragged (the z kernel's 200 documents come as the padded
 two-round order of 384 entries there: its last round is ragged by the entries that hold no document)."""
 import os
