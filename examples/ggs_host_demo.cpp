@@ -2,9 +2,11 @@
 // tui/ParallelLDA.java:173-296 drives the Java sampler.  Reads an integer corpus
 //   line 1: D V      then D lines: len tok tok ...
 // runs `iterations` sweeps and prints z and tokensPerTopic so a test can compare it with the
-// ctypes path.   usage: ggs_host_demo corpus.txt K alpha beta seed iterations [log_dir [ggs|collapsed|lightpclda|lightcollapsed|adlda]]
-// With a log_dir the corpus doubles as the test set and the loop's diagnostics are on (compute_likelihood,
+// ctypes path.   usage: ggs_host_demo corpus.txt K alpha beta seed iterations [log_dir [ggs|pcgs|polyaurn|collapsed|lightpclda|lightcollapsed|adlda
+//                                      [hyperparam_optim_interval [symmetric_alpha: 0|1]]]]
+// With a log_dir (not "") the corpus doubles as the test set and the loop's diagnostics are on (compute_likelihood,
 // start_diagnostic = 1, log_topic_indicators): the files of the Java driver appear there (ggs_formats.hpp).
+// With an interval the learned hyperparameters are printed as hexadecimal floats (every bit): alphasum, alpha, beta, betasum.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -14,7 +16,7 @@
 #include "ggs_sampler.hpp"
 
 int main(int argc, char **argv) {
-  if (argc < 7 || argc > 9) { std::fprintf(stderr, "usage: %s corpus.txt K alpha beta seed iterations [log_dir [ggs|collapsed|lightpclda|lightcollapsed|adlda]]\n", argv[0]); return 2; }
+  if (argc < 7 || argc > 11) { std::fprintf(stderr, "usage: %s corpus.txt K alpha beta seed iterations [log_dir [ggs|pcgs|polyaurn|collapsed|lightpclda|lightcollapsed|adlda [hyperparam_optim_interval [symmetric_alpha]]]]\n", argv[0]); return 2; }
   std::ifstream in(argv[1]);
   ggs::InstanceList inst;
   int64_t D;
@@ -28,12 +30,17 @@ int main(int argc, char **argv) {
   ggs::LDAConfiguration cfg;
   cfg.topics = std::atoi(argv[2]); cfg.alpha = std::atof(argv[3]); cfg.beta = std::atof(argv[4]);
   cfg.seed = std::atoi(argv[5]); cfg.iterations = std::atoi(argv[6]); cfg.exec_time = 1800; cfg.paranoid = true;
-  const bool logging = argc >= 8;
+  const bool logging = argc >= 8 && argv[7][0] != '\0';
   if (logging) { cfg.log_dir = argv[7]; cfg.compute_likelihood = true; cfg.start_diagnostic = 1; cfg.log_topic_indicators = true; }
   cfg.collapsed = argc >= 9 && std::string(argv[8]) == "collapsed";
   cfg.lightpclda = argc >= 9 && std::string(argv[8]) == "lightpclda";
   cfg.lightcollapsed = argc >= 9 && std::string(argv[8]) == "lightcollapsed";
   cfg.adlda = argc >= 9 && std::string(argv[8]) == "adlda";
+  cfg.pcgs = argc >= 9 && std::string(argv[8]) == "pcgs";
+  cfg.polyaurn = argc >= 9 && std::string(argv[8]) == "polyaurn";
+  const bool optimizing = argc >= 10;
+  if (optimizing) cfg.hyperparam_optim_interval = std::atoi(argv[9]);
+  cfg.symmetric_alpha = argc >= 11 && std::atoi(argv[10]) != 0;
   struct Counting : ggs::LDAGroupedGibbsSampler {
     using LDAGroupedGibbsSampler::LDAGroupedGibbsSampler;
     int pre = 0, post = 0;
@@ -52,6 +59,11 @@ int main(int argc, char **argv) {
     std::printf("\nnk");
     for (int32_t n : model.getTopicTotals()) std::printf(" %d", n);
     std::printf("\n");
+    if (optimizing) {
+      std::printf("alphasum %a\nalpha", model.getAlphaSum());
+      for (double a : model.getAlpha()) std::printf(" %a", a);
+      std::printf("\nbeta %a\nbetasum %a\n", model.getBeta(), model.getBetaSum());
+    }
     const auto est = model.getThetaEstimate();
     double s = 0; for (int k = 0; k < cfg.topics; ++k) s += est[(size_t)k];
     std::printf("theta_estimate_doc0_sum %.17g\n", s);

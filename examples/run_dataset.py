@@ -32,6 +32,9 @@ def main():
     ap.add_argument("--alpha", type=float, default=0.1)
     ap.add_argument("--beta", type=float, default=0.01)
     ap.add_argument("--iterations", type=int, default=200)
+    ap.add_argument("--optimize-interval", type=int, default=-1, metavar="N",
+                    help="hyperparam_optim_interval (MALLET's --optimize-interval): alpha and beta are re-estimated every N iterations, N > 1")
+    ap.add_argument("--symmetric-alpha", action="store_true", help="symmetric_alpha: one concentration for all topics instead of an alpha per topic")
     ap.add_argument("--seed", type=int, default=4711)
     ap.add_argument("--top-words", type=int, default=8, help="nr_top_words: words per topic, printed and in TopWords.txt / RelevanceWords.txt (clamped to the vocabulary size, as the driver clamps)")
     ap.add_argument("--lambda", dest="lambda_", type=float, default=0.6, help="lambda: the relevance weight of RelevanceWords.txt")
@@ -60,6 +63,7 @@ def main():
     cfg = SimpleLDAConfiguration(scheme=args.scheme, topics=args.topics, alpha=args.alpha, beta=args.beta, iterations=args.iterations,
                                  seed=args.seed, exec_time=None, compute_likelihood=bool(args.out), log_dir=args.out,
                                  topic_prior_filename=args.topic_priors, variable_selection_prior=args.vs_prior,
+                                 hyperparam_optim_interval=args.optimize_interval, symmetric_alpha=args.symmetric_alpha,
                                  compute_doc_topic_distances=args.doc_topic_distances, start_diagnostic=args.start_diagnostic,
                                  nr_top_words=args.top_words, save_doc_topic_diagnostics=bool(args.topic_diagnostics),
                                  doc_topic_diagnostics_filename=args.topic_diagnostics, **{"lambda": args.lambda_})
@@ -80,6 +84,8 @@ def main():
     print("%d iterations: z %.1f ms, Phi %.1f ms in all; model log likelihood %.2f" %
           (model.getCurrentIteration(), model.zSamplingTimeCum, model.phiSamplingTimeCum, model.modelLogLikelihood()))
 
+    print("alpha: %s (sum %.17g)\nbeta: %.17g" % (" ".join("%.6g" % a for a in model.getAlpha()), model.alphaSum, model.getBeta()))
+
     requested = min(cfg.nr_top_words, c.num_types)          # tui/ParallelLDA.java:272-274
     top = model.getTopWords(requested)                      # LDAUtils.getTopWords on the device-resident counts: ties by falling id
     for k in range(args.topics):
@@ -98,6 +104,9 @@ def main():
             F.write_binary_double_matrix(np.asarray(model.getPhi()), F.binary_matrix_name(os.path.join(args.out, "phi"), K, V, it))
         F.write_ascii_double_matrix(np.asarray(model.getThetaEstimate()), F.ascii_matrix_name(args.out, "Theta_DxK", D, K, it))
         F.write_ascii_int_matrix(n_wk.T, os.path.join(args.out, "type_topic_counts.csv"))
+        with open(os.path.join(args.out, "hyperparameters.txt"), "w") as f:       # the final values, every digit: alpha per topic, then beta and betaSum
+            f.write("".join("alpha\t%d\t%.17g\n" % (k, a) for k, a in enumerate(model.getAlpha())))
+            f.write("beta\t%.17g\nbetaSum\t%.17g\n" % (model.getBeta(), model.betaSum))
         print("wrote", ", ".join(sorted(os.listdir(args.out))))
 
 

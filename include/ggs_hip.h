@@ -344,6 +344,10 @@ int ggs_get_iteration(const ggs_handle *h, int32_t *iteration);
  *   ggs_set_corpus  besides: no Phi and no sweep in progress, the global token count back to the handle's own, the z form
  *       timed again, every table, list and launch geometry the new corpus'.  A run on a reused handle is, bit for bit and in
  *       everything the getters return, the run of a fresh handle that was given the same iteration number.
+ *   ggs_set_hyperparameters  changes the configuration itself: from the next z step on the handle is a fresh handle of the NEW alpha,
+ *       beta and betaSum that was given this handle's exported state.  It drops a theta drawn ahead (drawn under the old alpha), as
+ *       ggs_set_z does; tables over alpha * phi are rebuilt from the Phi that stands; the iteration, the phi mean, the priors and the
+ *       cumulative counters are left alone.
  * tests/test_handle_lifecycle_gpu.py pins each of these for every scheme. */
 
 /* ---- the sweep ------------------------------------------------------------- */
@@ -491,7 +495,9 @@ int ggs_get_exchange_info(const ggs_handle *h, int32_t *rank, int32_t *nranks, i
  * A benchmark line quotes these beside its number.  ABI version 4. */
 int ggs_get_exchange_provider(const ggs_handle *h, int32_t *provider, int32_t *comm_nranks, int32_t *comm_rank);
 
-/* ---- state copy-back (the Java getters) ------------------------------------ */
+/* ---- state copy-back (the Java getters) ------------------------------------
+ * Wherever a getter or a diagnostic below names alpha, alphaSum, beta or betaSum it means the handle's CURRENT values
+ * (ggs_get_hyperparameters): the configuration's until ggs_set_hyperparameters gives others. */
 int ggs_get_z(ggs_handle *h, int32_t *z /*N*/);                         /* getZIndicators, MSLDA:464-477 */
 int ggs_get_type_topic_counts(ggs_handle *h, int32_t *n_wk /*[V][K]*/); /* getTypeTopicMatrix, UPLDA:226-234 */
 int ggs_get_topic_totals(ggs_handle *h, int32_t *n_k /*K*/);            /* getTopicTotals, MSLDA:976 */
@@ -501,6 +507,61 @@ int ggs_get_phi_mean(ggs_handle *h, double *phi_mean /*[K][V]*/, int32_t *n_samp
 int ggs_get_theta(ggs_handle *h, int64_t doc_begin, int64_t doc_end, double *theta /*[(end-begin)][K]*/); /* thetaMatrix, GGS:72, UPLDA:716-720 */
 int ggs_get_doc_topic_counts(ggs_handle *h, int64_t doc_begin, int64_t doc_end, int32_t *n_dk); /* getDocumentTopicMatrix, MSLDA:536-547 */
 int ggs_get_timings(ggs_handle *h, ggs_timings *out);                   /* zSamplingTimeCum / phiSamplingTimeCum, UPLDA:642-693 */
+
+/* ---- hyperparameter optimisation (hyperparam_optim_interval, symmetric_alpha; UPLDA:647-649, 891-902) -------------------------
+ * The step of MALLET's --optimize-interval: two histograms of the current state (from the device, a few KB of bins), the two
+ * estimators of MALLET's Dirichlet (host, no GPU), and the setter that hands the learned values back to the handle.
+ *
+ * Rules of both histograms:
+ *   bin range   n_bins must exceed every value that occurs: the caller passes longestDocLength + 1 and maxTypeCount + 1, as Java
+ *               sizes its arrays.  If a value is >= n_bins the call returns GGS_ERR_BAD_ARG and writes NOTHING to its outputs (the
+ *               device flags the value, it never indexes with it).
+ *   Java ints   every bin is a Java int.  Bin 0 of the symmetric document histogram counts D * K pairs and can pass 2^31: it wraps
+ *               modulo 2^32 as Java's would; neither estimator reads bin 0.  Every other bin is exact.
+ *   schemes     both calls work under every scheme flag: they read only z, doc_ptr and the counts.
+ *   empty documents count n_dk == 0 for every topic, and length 0.
+ *
+ * topicDocCounts of MSLDA:815-845 from the device-resident z of THIS handle's documents (a shard's own; the caller sums shards).
+ * rows = symmetric ? 1 : K; hist is int32 [rows][n_bins]. hist[k][c] = documents with n_dk == c. symmetric: all topics into row 0.
+ * doc_lengths (or NULL) is int32 [n_bins]: documents of that length (docLengthCounts, UPLDA:377-432); with it, a document of
+ * n_bins tokens or more is out of range too.  More than ~9000 topics (four rows of K counts pass the LDS): GGS_ERR_UNSUPPORTED. */
+int ggs_doc_topic_histogram(ggs_handle *h, int32_t symmetric, int64_t n_bins, int32_t *hist, int32_t *doc_lengths);
+/* countHistogram of MSLDA:867-880 over the corpus-wide int32 [V][K] counts: hist[c] = cells with n_wk == c, int32 [n_bins].
+ * With an exchange this is a COLLECTIVE call, as ggs_get_type_topic_counts is. The counts are gathered first and every rank returns
+ * the corpus histogram. */
+int ggs_type_topic_count_histogram(ggs_handle *h, int64_t n_bins, int32_t *hist);
+/* alpha: K values, or NULL to keep the current ones. beta > 0. beta_sum: the Java field betaSum, or 0.0 for beta * V.
+ * From the next z step on the handle is, bit for bit and in everything the getters return, a handle created with these values
+ * and given this handle's exported state (z, Phi, iteration).  (After optimizeBeta the Java field betaSum is the learned value and
+ * beta = betaSum / numTypes, MSLDA:897-901: not the bits of beta * V, hence the third argument.)
+ * A non-finite or non-positive alpha_k or beta, or a negative or non-finite beta_sum, returns GGS_ERR_BAD_ARG and leaves the handle
+ * untouched; a call between ggs_sweep_begin and ggs_sweep_end returns GGS_ERR_STATE.  With an exchange every rank makes the same
+ * call with the same values; this is NOT checked.
+ * One deviation, ours: the reference builds spalias's alias tables inside samplePhi with the old alpha and optimises afterwards, so
+ * its next z step runs on alpha_old * phi tables.  Here the tables follow the setter -- one rule for every scheme. */
+int ggs_set_hyperparameters(ggs_handle *h, const double *alpha, double beta, double beta_sum);
+/* the current values: alpha (K values, or NULL), beta, betaSum (each or NULL) */
+int ggs_get_hyperparameters(const ggs_handle *h, double *alpha /*K or NULL*/, double *beta, double *beta_sum);
+/* MALLET 2.0.8's Dirichlet.learnSymmetricConcentration and Dirichlet.learnParameters, on the host (no GPU, like
+ * ggs_java_lcg_next_ints).  The jar is not in the reference tree, so THIS TEXT is the specification (parity against a JVM is
+ * unpinned).  All arithmetic is fp64, left to right, in exactly this order; log is the host libm's.
+ *   digamma(z): if z < 1e-6 return -0.5772156649015328606065121 - 1/z.  psi = 0; while z < 9.5 { psi -= 1/z; z++ }; x = 1/z; y = x*x;
+ *     psi += log(z) - .5*x - y*(1/12. - y*(1/120. - y*(1/252. - y*(1/240. - y*(1/132. - y*(691/32760. - y*(1/12.))))))).
+ *   ggs_learn_symmetric_concentration: largest = the largest i with count_hist[i] > 0, or 0; nz = the ascending indices with
+ *     obs_lengths > 0.  200 iterations, always: cp = current / num_dimensions; dg = 0, num = 0; for i = 1 .. largest:
+ *     dg += 1.0 / (cp + i - 1), num += count_hist[i] * dg.  dg = 0, den = 0, prev = 0, cached = digamma(current); for each len in nz:
+ *     if len - prev > 20: dg = digamma(current + len) - cached, else for i = prev .. len-1: dg += 1.0 / (current + i); then
+ *     den += dg * obs_lengths[len], prev = len.  current = cp * num / den.  *out = current.
+ *   ggs_learn_parameters: parametersSum = the k-order sum of params; nonZeroLimit[k] = the largest i with obs[k][i] > 0, or -1.
+ *     Per iteration: denominator = 0, dg = 0; for i = 1 .. n_len-1: dg += 1 / (parametersSum + i - 1), denominator +=
+ *     obs_lengths[i] * dg; denominator -= 1 / scale; parametersSum = 0; for each k: old = params[k], p = 0, dg = 0; for i = 1 ..
+ *     nonZeroLimit[k]: dg += 1 / (old + i - 1), p += obs[k][i] * dg; params[k] = old * (p + shape) / denominator,
+ *     parametersSum += params[k].  *sum_out = parametersSum.
+ * A null pointer or a size < 1 returns GGS_ERR_BAD_ARG. */
+int ggs_learn_symmetric_concentration(const int32_t *count_hist, int64_t n_hist, const int32_t *obs_lengths, int64_t n_len,
+                                      int32_t num_dimensions, double current, double *out);
+int ggs_learn_parameters(double *params /*K, in/out*/, int32_t K, const int32_t *obs /*[K][n_bins]*/, int64_t n_bins,
+                         const int32_t *obs_lengths, int64_t n_len, double shape, double scale, int32_t iterations, double *sum_out);
 int ggs_reset_timings(ggs_handle *h);
 /* replaces: ensureConsistentTopicTypeCounts (UPLDA:299-338): counts >= 0, they sum to the
  * corpus size, column sums == tokensPerTopic.  (The reference's other paranoid assert, "all

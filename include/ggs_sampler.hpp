@@ -13,6 +13,7 @@
 // Errors: the Java code throws IllegalStateException / IllegalArgumentException; here a
 // non-zero C-ABI return becomes ggs::SamplerError carrying the code and ggs_last_error().
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <fstream>
 #include <cstdint>
@@ -46,6 +47,8 @@ struct LDAConfiguration {
   int phi_mean_burnin = 0;         // percent of iterations
   int phi_mean_thin = 1;
   bool paranoid = false;
+  int hyperparam_optim_interval = -1;   // HYPERPARAM_OPTIM_INTERVAL_DEFAULT (LDAConfiguration.java:46): optimised when > 1 and iteration % interval == 0 (UPLDA:647,891)
+  bool symmetric_alpha = false;         // SYMMETRIC_ALPHA_DEFAULT (LDAConfiguration.java:47)
   bool pcgs = false;              // scheme=pcgs instead of ggs (ParallelLDA.java:414-416): the z step of UPLDA:1466-1544
   bool collapsed = false;         // scheme=collapsed (ParallelLDA.java:424-428, SerialCollapsedLDA): the serial chain of MSLDA:158-226
   bool polyaurn = false;          // scheme=polyaurn (ParallelLDA.java:444-447, PolyaUrnSpaliasLDA): the pcgs z step over a Poisson-drawn Phi
@@ -102,6 +105,18 @@ class LDAGroupedGibbsSampler {
     if (rc) { h_ = nullptr; throw SamplerError(rc, "ggs_create failed"); }
     D_ = training.size(); N_ = training.doc_ptr.back(); V_ = training.num_types;
     doc_ptr_ = training.doc_ptr;
+    alpha_.assign((size_t)config_.topics, config_.alpha);
+    alphaSum_ = config_.alpha * config_.topics;
+    chk(ggs_get_hyperparameters(h_, nullptr, &beta_, &betaSum_));              // betaSum = beta * numTypes, UPLDA:372,435
+    // docLengthCounts (UPLDA:377-432) and maxTypeCount, once, from the corpus
+    int64_t longest = 0;
+    for (int64_t d = 0; d < D_; ++d) longest = std::max(longest, doc_ptr_[(size_t)d + 1] - doc_ptr_[(size_t)d]);
+    docLengthCounts_.assign((size_t)longest + 1, 0);
+    for (int64_t d = 0; d < D_; ++d) docLengthCounts_[(size_t)(doc_ptr_[(size_t)d + 1] - doc_ptr_[(size_t)d])] += 1;
+    std::vector<int32_t> typeCounts((size_t)V_, 0);
+    for (int32_t w : training.tokens) typeCounts[(size_t)w] += 1;
+    maxTypeCount_ = 0;
+    for (int32_t n : typeCounts) maxTypeCount_ = std::max(maxTypeCount_, n);
     chk(ggs_set_corpus(h_, D_, training.doc_ptr.data(), training.tokens.data(), 0, 0));
     chk(ggs_init_z_java_lcg(h_, startSeed_));                               // UPLDA:458-460
     chk(ggs_init_phi(h_));                                                  // UPLDA:1287-1294
@@ -128,6 +143,11 @@ class LDAGroupedGibbsSampler {
       zSamplingTimeCum += (t1.theta_ms - t0.theta_ms) + (t1.z_ms - t0.z_ms) + (t1.merge_ms - t0.merge_ms);
       phiSamplingTimeCum += t1.phi_ms - t0.phi_ms;
       diagnostics(iteration);
+      if (optimizesAt(iteration)) {                                         // UPLDA:891-894
+        optimizeAlpha();
+        optimizeBeta();
+        chk(ggs_set_hyperparameters(h_, alpha_.data(), beta_, betaSum_));
+      }
       postIteration();
       if (std::ifstream("abort").good()) abort();                           // the sentinel file of UPLDA:131,908-910
       if (zSamplingTimeCum + phiSamplingTimeCum >= maxExecMs) break;        // UPLDA:926-928
@@ -148,8 +168,43 @@ class LDAGroupedGibbsSampler {
   int getNoTypes() const { return V_; }
   int getCurrentIteration() const { return currentIteration_; }
   int64_t getCorpusSize() const { return N_; }
-  double getBeta() const { return config_.beta; }
-  std::vector<double> getAlpha() const { return std::vector<double>((size_t)config_.topics, config_.alpha); }
+  double getBeta() const { return h_ ? beta_ : config_.beta; }
+  double getBetaSum() const { return betaSum_; }
+  double getAlphaSum() const { return alphaSum_; }
+  std::vector<double> getAlpha() const { return h_ ? alpha_ : std::vector<double>((size_t)config_.topics, config_.alpha); }
+
+  // ---- the hyperparameter step (MALLET's --optimize-interval): the histograms from the device, the estimators in the library ----
+  // The count-form classes (SerialCollapsedLDA, CollapsedLightLDA, ADLDA) do not read the key, as in Java.
+  bool optimizesAt(int iteration) const {
+    return !config_.collapsed && !config_.lightcollapsed && !config_.adlda && config_.hyperparam_optim_interval > 1 &&
+           iteration % config_.hyperparam_optim_interval == 0;
+  }
+  void optimizeAlpha() {                                                    // MSLDA:812-861
+    need();
+    const int K = config_.topics;
+    const int64_t n_bins = (int64_t)docLengthCounts_.size();
+    std::vector<int32_t> hist((size_t)(config_.symmetric_alpha ? 1 : K) * (size_t)n_bins);
+    chk(ggs_doc_topic_histogram(h_, config_.symmetric_alpha ? 1 : 0, n_bins, hist.data(), nullptr));
+    if (config_.symmetric_alpha) {
+      chk(ggs_learn_symmetric_concentration(hist.data(), n_bins, docLengthCounts_.data(), n_bins, K, alphaSum_, &alphaSum_));
+      for (double &a : alpha_) a = alphaSum_ / K;
+    } else {
+      chk(ggs_learn_parameters(alpha_.data(), K, hist.data(), n_bins, docLengthCounts_.data(), n_bins, 1.001, 1.0, 1, &alphaSum_));
+    }
+  }
+  void optimizeBeta() {                                                     // MSLDA:863-905
+    need();
+    std::vector<int32_t> countHistogram((size_t)maxTypeCount_ + 1);
+    chk(ggs_type_topic_count_histogram(h_, (int64_t)countHistogram.size(), countHistogram.data()));
+    const std::vector<int32_t> tokensPerTopic = getTopicTotals();
+    int32_t maxTopicSize = 0;
+    for (int32_t n : tokensPerTopic) maxTopicSize = std::max(maxTopicSize, n);
+    std::vector<int32_t> topicSizeHistogram((size_t)maxTopicSize + 1, 0);
+    for (int32_t n : tokensPerTopic) topicSizeHistogram[(size_t)n] += 1;
+    chk(ggs_learn_symmetric_concentration(countHistogram.data(), (int64_t)countHistogram.size(), topicSizeHistogram.data(), (int64_t)topicSizeHistogram.size(), V_,
+                                          betaSum_, &betaSum_));
+    beta_ = betaSum_ / V_;
+  }
 
   std::vector<std::vector<int32_t>> getZIndicators() {                      // MSLDA:464-477
     need();
@@ -203,8 +258,8 @@ class LDAGroupedGibbsSampler {
     std::vector<double> out((size_t)D_ * K);
     for (int64_t d = 0; d < D_; ++d) {
       double normalizer = 0.0;
-      for (int k = 0; k < K; ++k) normalizer += (double)ndk[(size_t)d * K + k] + config_.alpha;
-      for (int k = 0; k < K; ++k) out[(size_t)d * K + k] = ((double)ndk[(size_t)d * K + k] + config_.alpha) / normalizer;
+      for (int k = 0; k < K; ++k) normalizer += (double)ndk[(size_t)d * K + k] + alpha_[(size_t)k];
+      for (int k = 0; k < K; ++k) out[(size_t)d * K + k] = ((double)ndk[(size_t)d * K + k] + alpha_[(size_t)k]) / normalizer;
     }
     return out;
   }
@@ -361,6 +416,10 @@ class LDAGroupedGibbsSampler {
   int64_t D_ = 0, N_ = 0;
   int32_t V_ = 0;
   std::vector<int64_t> doc_ptr_;
+  std::vector<double> alpha_;                                                // the current hyperparameters: the configuration's until the step learns others
+  double alphaSum_ = 0, beta_ = 0, betaSum_ = 0;
+  std::vector<int32_t> docLengthCounts_;
+  int32_t maxTypeCount_ = 0;
   std::atomic<bool> abort_{false};
   bool haveTestSet_ = false;
 };

@@ -115,6 +115,44 @@ final class GGSDevice {
 		sweepsInFlight = false;
 	}
 
+	/** The sufficient statistics of optimizeAlpha (MSLDA:815-845) from the device: topicDocCounts, the handles' histograms summed
+	 *  (each handle counts its own documents; symmetric alpha: everything in row 0, as the reference fills it). */
+	void fillTopicDocCounts() {
+		settle();
+		boolean symmetric = model.usingSymmetricAlpha;
+		int rows = symmetric ? 1 : model.numTopics, nBins = model.docLengthCounts.length;
+		int[] part = new int[rows * nBins];
+		for (int[] row : model.topicDocCounts) java.util.Arrays.fill(row, 0);
+		for (long h : handles) {
+			GGSNative.nDocTopicHistogram(h, symmetric, nBins, part);
+			for (int k = 0; k < rows; k++)
+				for (int i = 0; i < nBins; i++) model.topicDocCounts[k][i] += part[k * nBins + i];
+		}
+	}
+
+	/** countHistogram of optimizeBeta (MSLDA:867-880) from the device-resident counts: maxTypeCount + 1 bins. */
+	int[] countHistogram() {
+		settle();
+		if (multi()) GGSNative.nGroupGatherCounts(handles);   // the per-handle call would start a collective one thread cannot complete
+		int[] hist = new int[model.maxTypeCount + 1];
+		GGSNative.nTypeTopicCountHistogram(handles[0], hist.length, hist);   // every handle holds the corpus' counts now
+		return hist;
+	}
+
+	/** tokensPerTopic for optimizeBeta's topicSizeHistogram (MSLDA:884-895), from the device */
+	int[] topicTotals() {
+		settle();
+		if (multi()) GGSNative.nGroupGatherCounts(handles);
+		int[] nk = new int[model.numTopics];
+		GGSNative.nGetTopicTotals(handles[0], nk);
+		return nk;
+	}
+
+	/** After Dirichlet.learn* moved alpha, beta and betaSum on the Java side: the same values to every handle. */
+	void pushHyperparameters() {
+		for (long h : handles) GGSNative.nSetHyperparameters(h, model.alpha, model.beta, model.betaSum);
+	}
+
 	/** setZIndicators (UPLDA:1797-1843) */
 	void setZ(int[][] zIndicators) {
 		int p = 0;

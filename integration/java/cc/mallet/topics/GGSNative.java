@@ -45,6 +45,9 @@ final class GGSNative {
 	static native void nSetTestCorpus(long h, long[] docPtr, int[] tokens);               // ggs_set_test_corpus
 	static native double nHeldOutLogLikelihood(long h, int numParticles);                 // ggs_heldout_log_likelihood
 	static native void nSetGlobalTokenCount(long h, long n);                              // ggs_set_global_token_count
+	static native void nDocTopicHistogram(long h, boolean symmetric, long nBins, int[] hist);   // ggs_doc_topic_histogram; hist [symmetric ? 1 : K][nBins] flat, this handle's documents
+	static native void nTypeTopicCountHistogram(long h, long nBins, int[] hist);          // ggs_type_topic_count_histogram; hist [nBins], the corpus' (collective over a group's handles)
+	static native void nSetHyperparameters(long h, double[] alpha, double beta, double betaSum);   // ggs_set_hyperparameters
 
 	// ---- one JVM, n GPUs: the handles travel as a long[] in rank order ---------------------------------------------
 	static native long[] nGroupCreate(int numTopics, int numTypes, double[] alpha, double beta, long seed,

@@ -71,6 +71,32 @@ public class LDAPartiallyCollapsedGibbsSamplerHIP extends LDAPartiallyCollapsedG
 	@Override
 	public void postSample() { device.syncToJava(); super.postSample(); }
 
+	// hyperparam_optim_interval (UPLDA:891-894): the histograms from the device, MALLET's own estimators (a JVM has the jar), the
+	// learned values back to the device
+	@Override
+	public void optimizeAlpha() {                       // MSLDA:812-861
+		device.fillTopicDocCounts();
+		if (usingSymmetricAlpha) {
+			alphaSum = cc.mallet.types.Dirichlet.learnSymmetricConcentration(topicDocCounts[0], docLengthCounts, numTopics, alphaSum);
+			for (int topic = 0; topic < numTopics; topic++) alpha[topic] = alphaSum / numTopics;
+		} else {
+			alphaSum = cc.mallet.types.Dirichlet.learnParameters(alpha, topicDocCounts, docLengthCounts, 1.001, 1.0, 1);
+		}
+	}
+
+	@Override
+	public void optimizeBeta() {                        // MSLDA:863-905; runs after optimizeAlpha (UPLDA:892-893) and pushes both
+		int[] countHistogram = device.countHistogram();
+		int[] perTopic = device.topicTotals();
+		int maxTopicSize = 0;
+		for (int n : perTopic) if (n > maxTopicSize) maxTopicSize = n;
+		int[] topicSizeHistogram = new int[maxTopicSize + 1];
+		for (int n : perTopic) topicSizeHistogram[n]++;
+		betaSum = cc.mallet.types.Dirichlet.learnSymmetricConcentration(countHistogram, topicSizeHistogram, numTypes, betaSum);
+		beta = betaSum / numTypes;
+		device.pushHyperparameters();
+	}
+
 	@Override
 	public void setZIndicators(int[][] zIndicators) {   // UPLDA:1797-1843
 		device.setZ(zIndicators);

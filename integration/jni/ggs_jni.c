@@ -94,6 +94,19 @@ JNIEXPORT void JNICALL Java_cc_mallet_topics_GGSNative_nGetTheta(JNIEnv *env, jc
   jdouble *p = (*env)->GetDoubleArrayElements(env, out, 0); int rc = ggs_get_theta(H(h), b, e, p);
   (*env)->ReleaseDoubleArrayElements(env, out, p, 0); if (rc) throw_for(env, H(h), rc);
 }
+/* the hyperparameter step (MSLDA:812-905): the two histograms come back as Java ints, the learned values go down */
+JNIEXPORT void JNICALL Java_cc_mallet_topics_GGSNative_nDocTopicHistogram(JNIEnv *env, jclass c, jlong h, jboolean symmetric, jlong nBins, jintArray out) {
+  jint *p = (*env)->GetIntArrayElements(env, out, 0); int rc = ggs_doc_topic_histogram(H(h), symmetric ? 1 : 0, nBins, (int32_t *)p, 0);
+  (*env)->ReleaseIntArrayElements(env, out, p, 0); if (rc) throw_for(env, H(h), rc);
+}
+JNIEXPORT void JNICALL Java_cc_mallet_topics_GGSNative_nTypeTopicCountHistogram(JNIEnv *env, jclass c, jlong h, jlong nBins, jintArray out) {
+  jint *p = (*env)->GetIntArrayElements(env, out, 0); int rc = ggs_type_topic_count_histogram(H(h), nBins, (int32_t *)p);
+  (*env)->ReleaseIntArrayElements(env, out, p, 0); if (rc) throw_for(env, H(h), rc);
+}
+JNIEXPORT void JNICALL Java_cc_mallet_topics_GGSNative_nSetHyperparameters(JNIEnv *env, jclass c, jlong h, jdoubleArray alpha, jdouble beta, jdouble betaSum) {
+  jdouble *a = (*env)->GetDoubleArrayElements(env, alpha, 0); int rc = ggs_set_hyperparameters(H(h), a, beta, betaSum);
+  (*env)->ReleaseDoubleArrayElements(env, alpha, a, JNI_ABORT); if (rc) throw_for(env, H(h), rc);
+}
 JNIEXPORT jdoubleArray JNICALL Java_cc_mallet_topics_GGSNative_nGetTimings(JNIEnv *env, jclass c, jlong h) {
   ggs_timings t; jdouble v[5]; jdoubleArray out = (*env)->NewDoubleArray(env, 5);
   if (ggs_get_timings(H(h), &t)) return out;

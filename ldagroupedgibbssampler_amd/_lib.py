@@ -146,6 +146,12 @@ SIGNATURES = {
     "ggs_get_vs_stats": (C.c_int, [_vp, _lp]),
     "ggs_debug_vs_indicators": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _ip, _dp, C.c_double, C.c_double, C.c_uint64, C.c_uint32, _dp,
                                           C.POINTER(C.c_uint8), _ip, _ip]),
+    "ggs_doc_topic_histogram": (C.c_int, [_vp, C.c_int32, C.c_int64, _ip, _ip]),
+    "ggs_type_topic_count_histogram": (C.c_int, [_vp, C.c_int64, _ip]),
+    "ggs_set_hyperparameters": (C.c_int, [_vp, _dp, C.c_double, C.c_double]),
+    "ggs_get_hyperparameters": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "ggs_learn_symmetric_concentration": (C.c_int, [_ip, C.c_int64, _ip, C.c_int64, C.c_int32, C.c_double, _dp]),
+    "ggs_learn_parameters": (C.c_int, [_dp, C.c_int32, _ip, C.c_int64, _ip, C.c_int64, C.c_double, C.c_double, C.c_int32, _dp]),
     "ggs_model_log_likelihood": (C.c_int, [_vp, _dp, _dp]),
     "ggs_log_posterior": (C.c_int, [_vp, _dp, _dp]),
     "ggs_min_doc_distances": (C.c_int, [_vp, _dp, C.c_int64, _dp]),

@@ -9,6 +9,7 @@
 #include "ggs_host_sweep.hpp"
 #include "ggs_host_exchange.hpp"
 #include "ggs_host_end_of_run.hpp"
+#include "ggs_host_hyper.hpp"
 #include "ggs_host_debug.hpp"
 
 extern "C" {
@@ -34,7 +35,7 @@ int ggs_create(const ggs_config *cfg, ggs_handle **out) {
   h->Ks = h->Ksm = h->K; h->k0 = 0;
   h->Kp = (h->K + 1) & ~1;
   h->pitch16 = (h->Kp / 2) | 1;             // odd number of 16-byte units per LDS row
-  h->beta = cfg->beta; h->seed = cfg->seed; h->flags = cfg->flags;
+  h->beta = cfg->beta; h->beta_sum = cfg->beta * (double)cfg->num_types; h->seed = cfg->seed; h->flags = cfg->flags;
   h->scheme = scheme; h->pa_L = poisson_L;
   h->phi_burn_in = cfg->phi_burn_in; h->phi_thin = cfg->phi_mean_thin > 0 ? cfg->phi_mean_thin : 1;
   h->alpha.assign(h->K, cfg->alpha_scalar);
@@ -400,7 +401,7 @@ int ggs_collapsed_serial_sweep(ggs_handle *h, int32_t java_seed, int32_t n_sweep
   }
   CollapsedSerialParams cp{};
   cp.doc_ptr = h->d_doc_ptr; cp.tok = h->d_tok; cp.inv_perm = h->d_inv_perm; cp.z = h->d_z; cp.zw = h->d_zw; cp.n_wk = h->d_n_wk; cp.n_k = h->d_n_k;
-  cp.alpha = h->d_alpha; cp.lcg = h->d_lcg; cp.status = h->d_status; cp.num_docs = h->D; cp.beta = h->beta; cp.beta_sum = h->beta * (double)h->V; cp.K = h->K;
+  cp.alpha = h->d_alpha; cp.lcg = h->d_lcg; cp.status = h->d_status; cp.num_docs = h->D; cp.beta = h->beta; cp.beta_sum = h->beta_sum; cp.K = h->K;
   for (int32_t i = 0; i < n_sweeps; ++i) {
     h->iteration += 1;
     hipLaunchKernelGGL(collapsed_serial_kernel, dim3(1), dim3(64), (size_t)h->K * 16, h->stream, cp);
@@ -693,7 +694,7 @@ int ggs_get_phi(ggs_handle *h, double *phi) {
   if (count_form(h->scheme)) {   // the point estimate from the current counts
     if (!h->d_phiT && (rc = dev_alloc(h, &h->d_phiT, (size_t)h->V * h->Kp + kPhiTailPadBytes / 8))) return rc;   // lightcollapsed: only now
     if ((rc = launch_magnitude(h))) return rc;
-    hipLaunchKernelGGL(psi_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, h->d_n_wk, h->d_n_k, h->beta, h->beta * (double)h->V,
+    hipLaunchKernelGGL(psi_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, h->d_n_wk, h->d_n_k, h->beta, h->beta_sum,
                        h->d_phiT, h->K, h->Kp, h->V);
     HIP_TRY(h, hipGetLastError());
   }
@@ -901,6 +902,30 @@ int ggs_get_doc_topic_counts(ggs_handle *h, int64_t doc_begin, int64_t doc_end, 
   HIP_TRY(h, hipGetLastError());
   return copy_out(h, n_dk, h->d_scratch, bytes);
 }
+int ggs_doc_topic_histogram(ggs_handle *h, int32_t symmetric, int64_t n_bins, int32_t *hist, int32_t *doc_lengths) {
+  return doc_topic_histogram(h, symmetric, n_bins, hist, doc_lengths);
+}
+int ggs_type_topic_count_histogram(ggs_handle *h, int64_t n_bins, int32_t *hist) { return type_topic_count_histogram(h, n_bins, hist); }
+int ggs_set_hyperparameters(ggs_handle *h, const double *alpha, double beta, double beta_sum) { return set_hyperparameters(h, alpha, beta, beta_sum); }
+int ggs_get_hyperparameters(const ggs_handle *h, double *alpha, double *beta, double *beta_sum) {
+  if (!h) return GGS_ERR_BAD_ARG;
+  if (alpha) std::copy(h->alpha.begin(), h->alpha.end(), alpha);
+  if (beta) *beta = h->beta;
+  if (beta_sum) *beta_sum = h->beta_sum;
+  return GGS_OK;
+}
+int ggs_learn_symmetric_concentration(const int32_t *count_hist, int64_t n_hist, const int32_t *obs_lengths, int64_t n_len, int32_t num_dimensions,
+                                      double current, double *out) {
+  if (!count_hist || n_hist < 1 || !obs_lengths || n_len < 1 || num_dimensions < 1 || !out) return GGS_ERR_BAD_ARG;
+  *out = mallet_learn_symmetric_concentration(count_hist, n_hist, obs_lengths, n_len, num_dimensions, current);
+  return GGS_OK;
+}
+int ggs_learn_parameters(double *params, int32_t K, const int32_t *obs, int64_t n_bins, const int32_t *obs_lengths, int64_t n_len, double shape, double scale,
+                         int32_t iterations, double *sum_out) {
+  if (!params || K < 1 || !obs || n_bins < 1 || !obs_lengths || n_len < 1 || iterations < 0 || !sum_out) return GGS_ERR_BAD_ARG;
+  *sum_out = mallet_learn_parameters(params, K, obs, n_bins, obs_lengths, n_len, shape, scale, iterations);
+  return GGS_OK;
+}
 int ggs_model_log_likelihood(ggs_handle *h, double *doc_side, double *topic_side) {
   int rc = require_ready(h, false);
   if (rc) return rc;
@@ -920,7 +945,7 @@ int ggs_model_log_likelihood(ggs_handle *h, double *doc_side, double *topic_side
     hipLaunchKernelGGL(ll_docs_kernel, dim3((unsigned)doc_blocks), dim3(kLLBlock), ll_docs_lds_bytes(K), h->stream, h->d_doc_ptr,
                        h->d_z, h->d_alpha, alpha_sum, h->D, K, d_doc);
   hipLaunchKernelGGL(ll_types_kernel, dim3((unsigned)type_blocks), dim3(kLLBlock), 0, h->stream, h->d_n_wk, (int64_t)K * h->V, h->beta, d_type, d_nz);
-  hipLaunchKernelGGL(ll_finish_kernel, dim3(1), dim3(kLLBlock), 0, h->stream, d_doc, doc_blocks, d_type, type_blocks, h->d_n_k, K, h->beta * h->V,
+  hipLaunchKernelGGL(ll_finish_kernel, dim3(1), dim3(kLLBlock), 0, h->stream, d_doc, doc_blocks, d_type, type_blocks, h->d_n_k, K, h->beta_sum,
                      alpha_sum, h->beta, h->D, d_nz, d_out);
   HIP_TRY(h, hipGetLastError());
   double out[2];

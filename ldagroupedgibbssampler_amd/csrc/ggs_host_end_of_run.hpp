@@ -398,7 +398,7 @@ int heldout_evaluate(ggs_handle *h, int32_t num_particles, double *doc_ll, doubl
   hp.alpha_sum = h->alpha_sum;                         // the k-order sum
   hp.seed = h->seed; hp.iteration = (uint32_t)h->iteration; hp.doc_base = h->test_doc_base;
   hp.K = K; hp.V = h->V; hp.P = num_particles; hp.blocks_per_doc = (num_particles + 63) / 64;
-  hipLaunchKernelGGL(heldout_setup_kernel, dim3(1), dim3(64), 0, h->stream, h->d_alpha, h->d_n_k, h->beta, h->beta * h->V, K, tab);
+  hipLaunchKernelGGL(heldout_setup_kernel, dim3(1), dim3(64), 0, h->stream, h->d_alpha, h->d_n_k, h->beta, h->beta_sum, K, tab);
   for (size_t b = 0; b + 1 < cuts.size(); ++b) {
     hp.d0 = cuts[b]; hp.d1 = cuts[b + 1];
     if (hp.d1 == hp.d0) continue;

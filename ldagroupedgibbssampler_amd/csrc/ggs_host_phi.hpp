@@ -304,7 +304,7 @@ int launch_alias_build(ggs_handle *h) {
 int launch_count_alias_build(ggs_handle *h) {
   CountAliasParams cp{};
   cp.n_wk = h->d_n_wk; cp.n_k = h->d_n_k; cp.ps = h->d_alias_ps; cp.a = h->d_alias_a; cp.type_norm = h->d_alias_tn;
-  cp.nzw = h->d_nzw; cp.nw = h->d_nw; cp.tpt = h->d_tpt; cp.beta_sum = h->beta * (double)h->V;
+  cp.nzw = h->d_nzw; cp.nw = h->d_nw; cp.tpt = h->d_tpt; cp.beta_sum = h->beta_sum;
   cp.V = h->V; cp.K = h->K; cp.wpb = h->plan.alias_wpb;
   void *args[] = {&cp};
   HIP_TRY(h, launch(h, h->plan.countalias, ((int64_t)h->V + cp.wpb - 1) / cp.wpb, args, h->stream));
@@ -314,7 +314,7 @@ int launch_count_alias_build(ggs_handle *h) {
 // scheme=adlda: den0, S0 and the words' lists
 int launch_adlda_head(ggs_handle *h) {
   AdldaHeadParams hp{};
-  hp.n_k = h->d_n_k; hp.alpha = h->d_alpha; hp.den0 = h->d_ad_den0; hp.s0 = h->d_ad_s0; hp.beta = h->beta; hp.beta_sum = h->beta * (double)h->V; hp.K = h->K;
+  hp.n_k = h->d_n_k; hp.alpha = h->d_alpha; hp.den0 = h->d_ad_den0; hp.s0 = h->d_ad_s0; hp.beta = h->beta; hp.beta_sum = h->beta_sum; hp.K = h->K;
   void *hargs[] = {&hp};
   HIP_TRY(h, launch(h, h->plan.adhead, 1, hargs, h->stream));
   WordListParams wp{};
@@ -330,7 +330,7 @@ int launch_sweep_head(ggs_handle *h) {
   if (count_tables(h->scheme)) return launch_count_alias_build(h);   // lightpcldaw2 too: Phi is not touched
   if (h->scheme == Scheme::adlda) return launch_adlda_head(h);
   // collapsed: the ratios (beta + n_wk)/(betaSum + n_k) into phiT, for the pcgs loop over them
-  hipLaunchKernelGGL(psi_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, h->d_n_wk, h->d_n_k, h->beta, h->beta * (double)h->V, h->d_phiT,
+  hipLaunchKernelGGL(psi_kernel, dim3(grid_for((int64_t)h->K * h->V, 256, 2)), dim3(256), 0, h->stream, h->d_n_wk, h->d_n_k, h->beta, h->beta_sum, h->d_phiT,
                      h->K, h->Kp, h->V);
   HIP_TRY(h, hipGetLastError());
   return GGS_OK;

@@ -89,6 +89,12 @@ int resident_waves_per_cu(const void *fn, int lds) {
 // two wave-per-document kernels.
 int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn, LaunchPlan &pl) {
   const int Kp = (K + 1) & ~1, pitch16 = (Kp / 2) | 1;
+  // ---- the histograms of the hyperparameter step, whatever the scheme: four waves per workgroup, a document or a run of cells per wave and trip
+  if (doc_hist_lds_bytes(K) <= (size_t)kMaxLdsBytes) {
+    pl.dochist = {reinterpret_cast<const void *>(doc_topic_hist_kernel), kHistBlock, (int)doc_hist_lds_bytes(K), 0};
+    pl.dochist.per_cu = lds_workgroups_per_cu(pl.dochist.lds, kHistPerCu);
+  }
+  pl.cellhist = {reinterpret_cast<const void *>(cell_hist_kernel), kHistBlock, kCellHistLdsBytes, kHistPerCu};
   if (scheme == Scheme::ggs) {                        // ---- the ggs z step
     // score-register kernels up to K = 160: measured on the benchmark corpus (sweep, ms; round 3) K=136: 2.13 sliced / 2.40
     // streaming, 152: 2.33 / 2.56, 160: 2.40 / 2.50, 164: 3.06 / 2.83, 168: 3.06 / 2.75, 184: 3.24 / 2.94 (round 2: 184: 3.55 /

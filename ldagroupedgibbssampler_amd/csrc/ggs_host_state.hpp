@@ -38,6 +38,7 @@
 #include "ggs_distances.hpp"
 #include "ggs_topic_summaries.hpp"
 #include "ggs_topic_diagnostics.hpp"
+#include "ggs_hyper_hist.hpp"
 
 using namespace ggs;
 
@@ -131,9 +132,11 @@ struct LaunchPlan {
   KernelLaunch vsbits, vschain, wordmask, nzvs;
   // adlda (ggs_z_adlda.hpp): the sweep head (den0 and S0; the words' lists of the counts) and the bucket z step (LDS per corpus)
   KernelLaunch adhead, adlists, adlda;
+  // every scheme (ggs_hyper_hist.hpp): the two histograms of the hyperparameter step; dochist.fn is null where K counts per wave pass the LDS
+  KernelLaunch dochist, cellhist;
   bool wave_forced = false;            // ... because of K; otherwise per corpus (a document of 32 768 tokens or more)
   int32_t alias_wpb = 0;
-  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse, &countalias, &lightcol, &lightpcw2, &vsbits, &wordmask, &nzvs, &adlda}; }   // not vschain: it has static LDS, and its dynamic LDS stays below the default cap
+  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse, &countalias, &lightcol, &lightpcw2, &vsbits, &wordmask, &nzvs, &adlda, &dochist, &cellhist}; }   // not vschain: it has static LDS, and its dynamic LDS stays below the default cap
 };
 
 // One row per scheme, indexed by the enum: everything the host code asks about a scheme that is not its own buffers or its own
@@ -218,6 +221,7 @@ struct Events {
 struct ggs_handle {
   int32_t K = 0, V = 0, Kp = 0, pitch16 = 0, device = 0;
   double beta = 0;
+  double beta_sum = 0;                                 // the Java field betaSum: beta * V until ggs_set_hyperparameters gives the learned value (MSLDA:897-901)
   std::vector<double> alpha;
   uint64_t seed = 0;
   int32_t flags = 0, phi_burn_in = 0, phi_thin = 1;   // flags: as the caller passed them

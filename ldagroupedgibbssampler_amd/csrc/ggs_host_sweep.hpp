@@ -31,7 +31,7 @@ int launch_pcgs_z(ggs_handle *h) {
   if (h->alias_stale && (rc = launch_alias_build(h))) return rc;   // the schemes with tables over Phi
   if (count_form(h->scheme) || count_tables(h->scheme)) {   // lightpcldaw2 too: Phi as it stands, the lists and tables of the corpus-wide sweep-start counts
     if ((rc = launch_sweep_head(h))) return rc;
-    pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta * (double)h->V;   // betaSum = beta * numTypes, MSLDA:136
+    pp.n_wk = h->d_n_wk; pp.n_k = h->d_n_k; pp.beta = h->beta; pp.beta_sum = h->beta_sum;   // betaSum: beta * numTypes (MSLDA:136) until ggs_set_hyperparameters gives another
   }
   PolyaurnSparseParams sp{};                           // spalias's kernel takes its base, SpaliasParams
   LightCountParams lp{};                               // lightpclda's kernel takes its base, LightpcParams

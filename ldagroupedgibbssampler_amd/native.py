@@ -375,6 +375,37 @@ class GGSHandle:
         self._chk(self._L.ggs_get_doc_topic_counts(self._h, doc_begin, doc_end, _ip(out)))
         return out
 
+    # ---- the hyperparameter step (optimizeAlpha / optimizeBeta, MSLDA:812-905) ----
+    def doc_topic_histogram(self, symmetric, n_bins, lengths=True, out=None, lengths_out=None):
+        """(topicDocCounts, docLengthCounts) of this handle's documents from the device: int32 [K][n_bins] (symmetric: [1][n_bins]) and
+        int32 [n_bins] (None with lengths=False).  n_bins must exceed every n_dk (and length): ERR_BAD_ARG otherwise, outputs untouched."""
+        rows = 1 if symmetric else self.K
+        hist = np.empty((rows, int(n_bins)), np.int32) if out is None else out
+        lens = (np.empty(int(n_bins), np.int32) if lengths_out is None else lengths_out) if lengths else None
+        self._chk(self._L.ggs_doc_topic_histogram(self._h, 1 if symmetric else 0, int(n_bins), _ip(hist), _ip(lens) if lengths else None))
+        return hist, lens
+
+    def type_topic_count_histogram(self, n_bins, out=None):
+        """countHistogram over the corpus-wide counts: int32 [n_bins], hist[c] = cells with n_wk == c (collective with an exchange)."""
+        hist = np.empty(int(n_bins), np.int32) if out is None else out
+        self._chk(self._L.ggs_type_topic_count_histogram(self._h, int(n_bins), _ip(hist)))
+        return hist
+
+    def set_hyperparameters(self, alpha, beta, beta_sum=0.0):
+        """alpha: K values or None (keep); beta_sum: the Java field betaSum, 0.0 for beta * V.  From the next z step on the handle is
+        a handle created with these values and given this one's state."""
+        a = None if alpha is None else np.ascontiguousarray(alpha, np.float64)
+        if a is not None and a.shape != (self.K,):
+            raise ValueError("alpha must have num_topics entries")
+        self._chk(self._L.ggs_set_hyperparameters(self._h, None if a is None else _dp(a), float(beta), float(beta_sum)))
+
+    def hyperparameters(self):
+        """(alpha [K], beta, betaSum): the current values"""
+        a = np.empty(self.K, np.float64)
+        b, bs = C.c_double(), C.c_double()
+        self._chk(self._L.ggs_get_hyperparameters(self._h, _dp(a), C.byref(b), C.byref(bs)))
+        return a, b.value, bs.value
+
     def get_timings(self):
         t = _lib.GGSTimings()
         self._chk(self._L.ggs_get_timings(self._h, C.byref(t)))
@@ -579,6 +610,33 @@ class GGSGroup:
             self.close()
         except Exception:
             pass
+
+
+# ---- the estimators of the hyperparameter step (host, no GPU) ----
+def learn_symmetric_concentration(count_hist, obs_lengths, num_dimensions, current):
+    """MALLET's Dirichlet.learnSymmetricConcentration as include/ggs_hip.h states it"""
+    ch, ol = np.ascontiguousarray(count_hist, np.int32), np.ascontiguousarray(obs_lengths, np.int32)
+    out = C.c_double()
+    rc = _lib.load().ggs_learn_symmetric_concentration(_ip(ch), ch.size, _ip(ol), ol.size, int(num_dimensions), float(current), C.byref(out))
+    if rc:
+        raise GGSError(rc, "ggs_learn_symmetric_concentration: bad argument")
+    return out.value
+
+
+def learn_parameters(params, obs, obs_lengths, shape=1.001, scale=1.0, iterations=1):
+    """MALLET's Dirichlet.learnParameters as include/ggs_hip.h states it: params (float64 [K]) is updated IN PLACE, the new
+    parameters' sum is returned.  obs: int32 [K][n_bins]."""
+    if not (isinstance(params, np.ndarray) and params.dtype == np.float64 and params.flags.c_contiguous and params.ndim == 1):
+        raise ValueError("params must be a contiguous float64 vector: it is updated in place")
+    ob, ol = np.ascontiguousarray(obs, np.int32), np.ascontiguousarray(obs_lengths, np.int32)
+    if ob.ndim != 2 or ob.shape[0] != params.size:
+        raise ValueError("obs must be [K][n_bins]")
+    out = C.c_double()
+    rc = _lib.load().ggs_learn_parameters(_dp(params), params.size, _ip(ob), ob.shape[1], _ip(ol), ol.size, float(shape), float(scale), int(iterations),
+                                          C.byref(out))
+    if rc:
+        raise GGSError(rc, "ggs_learn_parameters: bad argument")
+    return out.value
 
 
 # ---- primitives (parity tests) ----

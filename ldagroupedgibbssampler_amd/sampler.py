@@ -40,6 +40,8 @@ class SimpleLDAConfiguration:
         self.alias_poisson_threshold = int(kw.pop("alias_poisson_threshold", 100))   # ALIAS_POISSON_DEFAULT_THRESHOLD; scheme=polyaurn and polyaurn_sparse only
         self.topic_prior_filename = kw.pop("topic_prior_filename", None)   # TOPIC_PRIOR_FILENAME, default none; scheme=spalias_priors only
         self.variable_selection_prior = float(kw.pop("variable_selection_prior", 0.5))   # VARIABLE_SELECTION_PRIOR_DEFAULT; scheme=nzvsspalias only
+        self.hyperparam_optim_interval = int(kw.pop("hyperparam_optim_interval", -1))   # HYPERPARAM_OPTIM_INTERVAL_DEFAULT (LDAConfiguration.java:46): optimised when > 1 and iteration % interval == 0, UPLDA:647,891
+        self.symmetric_alpha = bool(kw.pop("symmetric_alpha", False))                   # SYMMETRIC_ALPHA_DEFAULT (LDAConfiguration.java:47)
         self.paranoid = bool(kw.pop("paranoid", False))              # run the UPLDA:299-338 invariants every sweep
         self.device_id = int(kw.pop("device_id", 0))                 # optional gpu_* key; default first visible GPU
         # the diagnostics of the sampling loop (UPLDA:695-905), computed on the device and written in the Java driver's formats
@@ -116,6 +118,7 @@ class LDAGroupedGibbsSampler:
     """scheme=ggs on MI355X.  One instance drives one GPU (doc-sharded runs wrap the same
     native handle with ldagroupedgibbssampler_amd.sharded.ShardedGGS)."""
     _scheme_flags = 0
+    _optimizes_hyperparameters = True    # the samplers on the UncollapsedParallelLDA base (UPLDA:891-894); the count-form classes do not
 
     def __init__(self, config):
         self.config = config
@@ -123,6 +126,7 @@ class LDAGroupedGibbsSampler:
         self.alpha = np.full(self.numTopics, config.alpha, np.float64)       # MSLDA:129-135
         self.alphaSum = config.alpha * self.numTopics
         self.beta = config.beta
+        self.betaSum = None                                                  # beta * numTypes at addInstances (UPLDA:372,435)
         self.startSeed = config.get_seed()
         self.currentIteration = 0
         self._abort = False
@@ -157,6 +161,8 @@ class LDAGroupedGibbsSampler:
                                    device_id=cfg.device_id, flags=flags, phi_burn_in=burn_in, phi_mean_thin=cfg.phi_mean_thin,
                                    alias_poisson_threshold=getattr(cfg, "alias_poisson_threshold", 100))
         self._corpus = training
+        self.betaSum = self._h.hyperparameters()[2]
+        self._doc_length_counts = None
         self._h.set_corpus(training.doc_ptr, training.tokens)
         self._before_initial_state(training)
         self._h.init_z_java_lcg(self.startSeed)          # initialDrawTopicIndicator, UPLDA:458-460
@@ -207,6 +213,10 @@ class LDAGroupedGibbsSampler:
             self.zSamplingTimeCum += (t1["theta_ms"] - t0["theta_ms"]) + (t1["z_ms"] - t0["z_ms"]) + (t1["merge_ms"] - t0["merge_ms"])
             self.phiSamplingTimeCum += t1["phi_ms"] - t0["phi_ms"]
             self._diagnostics(iteration)
+            if self.optimizes_at(iteration):             # UPLDA:891-894
+                self.optimizeAlpha()
+                self.optimizeBeta()
+                self._h.set_hyperparameters(self.alpha, self.beta, self.betaSum)
             self.postIteration()
             if os.path.exists("abort"):                  # the sentinel file of UPLDA:131,908-910 (relative to the working directory)
                 self.abort()
@@ -219,6 +229,42 @@ class LDAGroupedGibbsSampler:
 
     def _phi_half(self):
         self._h.sweep_end()
+
+    # ---- the hyperparameter step (hyperparam_optim_interval, MALLET's --optimize-interval) ----
+    def optimizes_at(self, iteration):
+        """UPLDA:647,891: hyperparameterOptimizationInterval > 1 && iteration % hyperparameterOptimizationInterval == 0"""
+        interval = int(getattr(self.config, "hyperparam_optim_interval", -1))
+        return self._optimizes_hyperparameters and interval > 1 and iteration % interval == 0
+
+    def optimizeAlpha(self):
+        """MSLDA:812-861: topicDocCounts from the device-resident z (ggs_doc_topic_histogram), docLengthCounts from the corpus (once,
+        UPLDA:377-432), then Dirichlet.learnSymmetricConcentration or learnParameters(alpha, ..., 1.001, 1.0, 1).  The new values
+        reach the device with the set_hyperparameters call of the step."""
+        self._need_data()
+        if self._doc_length_counts is None:
+            lens = np.diff(self._corpus.doc_ptr)
+            self._doc_length_counts = np.bincount(lens, minlength=int(lens.max()) + 1 if lens.size else 1).astype(np.int32)
+        lengths = self._doc_length_counts
+        symmetric = bool(getattr(self.config, "symmetric_alpha", False))
+        hist, _ = self._h.doc_topic_histogram(symmetric, lengths.size, lengths=False)
+        if symmetric:
+            self.alphaSum = native.learn_symmetric_concentration(hist[0], lengths, self.numTopics, self.alphaSum)
+            self.alpha[:] = self.alphaSum / self.numTopics
+        else:
+            self.alphaSum = native.learn_parameters(self.alpha, hist, lengths, 1.001, 1.0, 1)
+
+    def optimizeBeta(self):
+        """MSLDA:863-905: countHistogram from the device-resident counts (ggs_type_topic_count_histogram, maxTypeCount + 1 bins),
+        topicSizeHistogram from tokensPerTopic, betaSum = Dirichlet.learnSymmetricConcentration(...), beta = betaSum / numTypes."""
+        self._need_data()
+        V = self._corpus.num_types
+        tokens = self._corpus.tokens
+        max_type_count = int(np.bincount(tokens, minlength=V).max()) if len(tokens) else 0
+        count_hist = self._h.type_topic_count_histogram(max_type_count + 1)
+        n_k = self._h.get_topic_totals()
+        topic_size_hist = np.bincount(n_k, minlength=int(n_k.max()) + 1).astype(np.int32)
+        self.betaSum = native.learn_symmetric_concentration(count_hist, topic_size_hist, V, self.betaSum)
+        self.beta = self.betaSum / V
 
     def _diagnostics(self, iteration):
         """The per-iteration diagnostics of UPLDA:695-905 that have a device implementation, in the Java order: document and
@@ -635,6 +681,7 @@ class SerialCollapsedLDA(LDAGroupedGibbsSampler):
                   the device-speed variant, approximate as ADLDA is
     No theta and no Phi are drawn: getPhi() is the point estimate (beta + n_wk)/(betaSum + n_k)."""
     _scheme_flags = native.FLAG_COLLAPSED
+    _optimizes_hyperparameters = False   # as the Java class: hyperparam_optim_interval is ignored (ADLDA.java:387-391 optimises through MALLET internals that are not in the tree)
 
     def __init__(self, config, schedule="serial"):
         super().__init__(config)
@@ -667,6 +714,7 @@ class CollapsedLightLDA(LDAGroupedGibbsSampler):
     sweep-start counts and merged after the sweep (the AD-LDA decomposition of scheme=collapsed's parallel schedule); the chain
     is approximate as the reference writes it."""
     _scheme_flags = native.FLAG_LIGHTCOLLAPSED
+    _optimizes_hyperparameters = False   # as the Java class: hyperparam_optim_interval is ignored (ADLDA.java:387-391 optimises through MALLET internals that are not in the tree)
 
     def getTheta(self):
         raise NotImplementedError("scheme=lightcollapsed never draws theta; use getThetaEstimate()")
@@ -696,6 +744,7 @@ class ADLDA(LDAGroupedGibbsSampler):
     non-zero topics only.  The exact conditional and the schedule of scheme=collapsed's parallel (AD-LDA) schedule, at
     O(nnz_d + nnz_w) per token.  Constructed directly: create_model does not know the name."""
     _scheme_flags = native.FLAG_ADLDA
+    _optimizes_hyperparameters = False   # as the Java class: hyperparam_optim_interval is ignored (ADLDA.java:387-391 optimises through MALLET internals that are not in the tree)
 
     def getTheta(self):
         raise NotImplementedError("scheme=adlda never draws theta; use getThetaEstimate()")

@@ -181,6 +181,49 @@ class ShardedGGS:
         ts, ws = self.engine.topic_scores(n, idx, codoc, stats, chain, word_scores=True)
         return TopicDiagnostics(idx, codoc, stats, chain, ts, ws, alphabet)
 
+    def optimize_hyperparameters(self, symmetric, gather=None):
+        """optimizeAlpha + optimizeBeta (MSLDA:812-905) of a doc-sharded run, on every rank (a collective call).  The ranks' document
+        and length histograms are summed (``gather`` as for heldout_log_likelihood; integers, exact in any order), with n_bins from
+        the corpus-wide longest document; the cell histogram is the collective getter's, the corpus' on every rank.  Every rank
+        then computes the same estimate from the same integers and makes the same ggs_set_hyperparameters call: bit-identical
+        to one handle over the whole corpus.  alphaSum is kept on this object between calls (the Java field), from the k-order
+        sum of the engine's alpha.  Returns (alpha, beta, betaSum)."""
+        from . import native
+        if gather is None:
+            import torch.distributed as dist
+
+            def gather(a):
+                res = [None] * self.world
+                dist.all_gather_object(res, a)
+                return res
+        eng = self.engine
+        alpha, beta, beta_sum = eng.hyperparameters()
+        K, V = alpha.size, self.local.num_types
+        if getattr(self, "alphaSum", None) is None:
+            self.alphaSum = 0.0
+            for a in alpha.tolist():
+                self.alphaSum += a
+        lens = np.diff(self.local.doc_ptr)
+        shape = gather((int(lens.max()) if lens.size else 0, np.bincount(self.local.tokens, minlength=V).astype(np.int64)))
+        n_bins = max(s[0] for s in shape) + 1
+        max_type_count = int(np.sum([s[1] for s in shape], axis=0).max())
+        parts = gather(eng.doc_topic_histogram(symmetric, n_bins))
+        hist = (np.sum([np.asarray(p[0], np.int64) for p in parts], axis=0) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)   # bins are Java ints
+        lengths = np.sum([np.asarray(p[1], np.int64) for p in parts], axis=0).astype(np.int32)
+        if symmetric:
+            self.alphaSum = native.learn_symmetric_concentration(hist[0], lengths, K, self.alphaSum)
+            alpha = np.full(K, self.alphaSum / K)
+        else:
+            alpha = np.ascontiguousarray(alpha, np.float64)
+            self.alphaSum = native.learn_parameters(alpha, hist, lengths, 1.001, 1.0, 1)
+        count_hist = eng.type_topic_count_histogram(max_type_count + 1)
+        n_k = eng.get_topic_totals()
+        topic_size_hist = np.bincount(n_k, minlength=int(n_k.max()) + 1).astype(np.int32)
+        beta_sum = native.learn_symmetric_concentration(count_hist, topic_size_hist, V, beta_sum)
+        beta = beta_sum / V
+        eng.set_hyperparameters(alpha, beta, beta_sum)
+        return alpha, beta, beta_sum
+
     def sweep(self, n=1):
         """n sweeps, one count exchange each; only the last one is waited for (device-side error flags are sticky)."""
         end_async = getattr(self.engine, "sweep_end_async", self.engine.sweep_end)
