@@ -595,6 +595,11 @@ int ggs_get_z_parts(ggs_handle *h, int32_t *parts);
  * *calibrated = 1 once the first z step of the corpus has timed both forms and kept the faster (0 before that, and
  * when a form is forced or there is nothing to split).  ABI version 4. */
 int ggs_get_z_form(ggs_handle *h, int32_t *kernel, int32_t *form, int32_t *calibrated);
+/* The hot words of the current corpus as pair-chunks (z_pairs_kernel: each (document, hot word) pair scored once, its tokens
+ * drawn from that): *enabled = 1 where the split form launches z_pairs_kernel in z_hot_kernel's place (0 with
+ * GGS_DEBUG_HOT_PAIRS=0, in the fused form and where the score-register kernels do not run), and the pair-chunks, pairs and
+ * hot tokens of the lists (0 where they are not built). */
+int ggs_get_hot_pairs(ggs_handle *h, int32_t *enabled, int64_t *pair_chunks, int64_t *pairs, int64_t *tokens);
 /* ---- primitives, exported so the parity tests can pin each layer ----------- */
 int ggs_debug_philox(int32_t device_id, int64_t n, const uint32_t *ctr /*n*4*/, const uint32_t *key /*n*2*/, uint32_t *out /*n*4*/);
 int ggs_debug_math(int32_t device_id, int32_t op /*0 log,1 pow,2 sqrt,3 div,4 exp,5 pow as the gamma draws call it,6 u53 of the words x,y*/, int64_t n, const double *x, const double *y, double *out);

@@ -115,6 +115,7 @@ SIGNATURES = {
     "ggs_get_z_parts": (C.c_int, [_vp, _ip]),
     "ggs_get_z_form": (C.c_int, [_vp, _ip, _ip, _ip]),
     "ggs_get_warm_tiers": (C.c_int, [_vp, _ip, _ip, _ip]),
+    "ggs_get_hot_pairs": (C.c_int, [_vp, _ip, _lp, _lp, _lp]),
     "ggs_attach_exchange": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(GGSExchangeOps)]),
     "ggs_rccl_unique_id": (C.c_int, [_vp]),
     "ggs_attach_rccl": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp]),

@@ -203,6 +203,7 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   shape.pcgs = pcgs; shape.sliced = pl.sliced(); shape.two_rows = pl.two_rows;
   shape.hot_cap = pl.hot_cap; shape.warm_cap = pl.warm_cap; shape.warm_docs = pl.warm_docs;
   shape.warm_tiers_max = pl.warm_tiers_max; shape.warm_min_fill_pct = pl.warm_min_fill_pct; shape.warm_min_chunks_per_wave = pl.warm_min_chunks_per_wave;
+  shape.hot_pairs = pl.hot_pairs;
   shape.sliced_waves = (int64_t)h->num_cus * kSlicedWaves; shape.pcgs_waves = (int64_t)h->num_cus * pl.lane.per_cu;
   const CorpusLists L = build_corpus_lists(shape, D, doc_ptr, tokens);
   if (pcgs) {
@@ -226,7 +227,8 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   h->part_doc = L.part_doc; h->part_chunk = L.part_chunk;
   h->pcgs_order_len = (int64_t)L.order.size();
   h->num_hot = (int32_t)L.hot_words.size(); h->HS = (int64_t)L.hseg_word.size();
-  h->Cc = L.Cc; h->Cs = L.Cs;
+  h->Cc = L.Cc; h->Cs = L.Cs; h->Cp = L.Cp; h->hp_pairs = h->hp_tokens = 0;
+  for (int64_t c = 0; c < L.Cp; ++c) { h->hp_pairs += L.hp_docs[(size_t)(c * kWarmDocSlots + kHotPairCountSlot)]; h->hp_tokens += L.hp_docs[(size_t)(c * kWarmDocSlots + kHotPairTokSlot)]; }
   h->warm_tiers = L.warm_tiers; h->num_warm = L.num_warm; h->Cw = L.Cw; h->warm_chunks_max = L.warm_chunks_max; h->warm_rows_max = L.warm_rows_max;
 
   // 4. upload (on the null stream), the state of the corpus zeroed
@@ -244,6 +246,7 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   if (h->C && ((rc = upload(h, &h->d_chunk_start, L.cstart)) || (rc = upload(h, &h->d_chunk_doc, L.cdoc)) || (rc = upload(h, &h->d_chunk_len, L.clen)) ||
                (pl.two_rows && (rc = upload(h, &h->d_chunk_doc1, L.cdoc1)))))
     return rc;
+  if (L.Cp > 0 && ((rc = upload(h, &h->d_hp_pair, L.hp_pair)) || (rc = upload(h, &h->d_hp_docs, L.hp_docs)) || (rc = upload(h, &h->d_hp_tok, L.hp_tok)))) return rc;
   if (L.warm_tiers > 0 && ((rc = upload(h, &h->d_wt_pack, L.wt_pack)) || (rc = upload(h, &h->d_w_docs, L.w_docs)) ||
                            (rc = upload(h, &h->d_warm_words, L.warm_words)) || (rc = upload(h, &h->d_warm_meta, L.warm_meta))))
     return rc;
@@ -1196,6 +1199,16 @@ int ggs_get_warm_tiers(ggs_handle *h, int32_t *tiers, int32_t *warm_words, int32
   if (tiers) *tiers = on ? h->warm_tiers : 0;
   if (warm_words) *warm_words = on ? h->num_warm : 0;
   if (docs_per_chunk) *docs_per_chunk = on && h->warm_tiers ? h->plan.warm_docs : 0;
+  return GGS_OK;
+}
+
+int ggs_get_hot_pairs(ggs_handle *h, int32_t *enabled, int64_t *pair_chunks, int64_t *pairs, int64_t *tokens) {
+  if (!h) return GGS_ERR_BAD_ARG;
+  const bool built = h->have_corpus && h->plan.sliced() && h->plan.hot_pairs;
+  if (enabled) *enabled = (built && h->Cp > 0 && h->z_split && h->Cs > h->Cc && h->Cc > 0) ? 1 : 0;
+  if (pair_chunks) *pair_chunks = built ? h->Cp : 0;
+  if (pairs) *pairs = built ? h->hp_pairs : 0;
+  if (tokens) *tokens = built ? h->hp_tokens : 0;
   return GGS_OK;
 }
 

@@ -25,6 +25,7 @@ const void *sliced32_kernel_for(int K) { GGS_KMAX_SWITCH(z_sliced32_kernel) }
 
 const void *hot_kernel_for(int K) { GGS_KMAX_SWITCH(z_hot_kernel) }
 const void *warm_kernel_for(int K) { GGS_KMAX_SWITCH(z_warm_kernel) }
+const void *pairs_kernel_for(int K) { GGS_KMAX_SWITCH(z_pairs_kernel) }
 const void *pcgs_kernel_for(int K) { GGS_KMAX_SWITCH(pcgs_sliced_kernel) }
 const void *polyaurn_kernel_for(int K) { GGS_KMAX_SWITCH(polyaurn_sliced_kernel) }
 const void *collapsed_kernel_for(int K) {
@@ -142,10 +143,17 @@ int plan_launches(const int K, const int V, const Scheme scheme, const Knobs &kn
       pl.hot_wave_lds = hot_wave_lds(K); pl.warm_wave_lds = warm_wave_lds(K);
       if (kn.split.set) { pl.split = kn.split.v != 0; pl.split_forced = kn.split.v == 2; }
       // split: the two workgroups must fit one CU together
-      pl.hot_cap = pl.split ? table_rows_beside_cold(K, pl.hot_wave_lds) : table_rows_fused(K);
+      // the hot words by pair-chunks wherever the split form can run; the pairs' records take LDS the table had (K = 100: 79 rows
+      // for 96), and the rows given up are the head of the first warm tier.  Set where the split form is merely possible: if the
+      // first z step's timed comparison then keeps the fused form, the run has the smaller table and the pair lists were built
+      // and uploaded for the comparison's split steps alone (the benchmark keeps the split form)
+      pl.hot_pairs = pl.split && !kn.hot_pairs.is(0);
+      pl.pairs_wave_lds = pairs_wave_lds(K);
+      pl.hot_cap = !pl.split ? table_rows_fused(K) : table_rows_beside_cold(K, pl.hot_pairs ? std::max(pl.hot_wave_lds, pl.pairs_wave_lds) : pl.hot_wave_lds);
       if (kn.hot.set) pl.hot_cap = std::max(0, std::min(pl.hot_cap, kn.hot.v));
       pl.cold = {pl.f32 ? sliced32_kernel_for(K) : sliced_kernel_for(K), kSlicedWaves * 64, sliced_cold_lds(K), 1};
       pl.hot = {hot_kernel_for(K), kSlicedWaves * 64, table_lds(K, pl.hot_wave_lds, 0), 1};
+      if (pl.hot_pairs) pl.pairs = {pairs_kernel_for(K), kSlicedWaves * 64, table_lds(K, pl.pairs_wave_lds, 0), 1};
       // the warm tiers: the same LDS beside the cold kernel's workgroup, more of it for theta rows (warm_docs per wave), the rest a table
       pl.warm = {warm_kernel_for(K), kSlicedWaves * 64, table_lds(K, pl.warm_wave_lds, 0), 1};
       pl.warm_docs = warm_docs_for(sliced_kmax(K));

@@ -73,7 +73,7 @@ struct Knobs {
   // the planner's
   Knob zkernel{"GGS_DEBUG_ZKERNEL"}, group{"GGS_DEBUG_GROUP"}, regck{"GGS_DEBUG_REGCK"}, tworows{"GGS_DEBUG_TWOROWS"}, wpc{"GGS_DEBUG_WPC"};
   Knob phi64{"GGS_DEBUG_PHI64"}, split{"GGS_DEBUG_SPLIT"}, hot{"GGS_DEBUG_HOT"}, tile{"GGS_DEBUG_TILE"};
-  Knob warm{"GGS_DEBUG_WARM"}, warm_rows{"GGS_DEBUG_WARM_ROWS"}, warm_fill{"GGS_DEBUG_WARM_FILL"}, warm_cpw{"GGS_DEBUG_WARM_CPW"};
+  Knob hot_pairs{"GGS_DEBUG_HOT_PAIRS"}, warm{"GGS_DEBUG_WARM"}, warm_rows{"GGS_DEBUG_WARM_ROWS"}, warm_fill{"GGS_DEBUG_WARM_FILL"}, warm_cpw{"GGS_DEBUG_WARM_CPW"};
   Knob theta_b{"GGS_DEBUG_THETA_B"}, theta_wgs{"GGS_DEBUG_THETA_WGS"}, zparts{"GGS_DEBUG_ZPARTS"}, beside{"GGS_DEBUG_BESIDE"};
   Knob pcgs_wave{"GGS_DEBUG_PCGS_WAVE"}, pcgs_stream{"GGS_DEBUG_PCGS_STREAM"};
   // the handle's
@@ -108,6 +108,10 @@ struct LaunchPlan {
   // sliced: the cold chunks' kernel (from phiT32 unless GGS_DEBUG_PHI64=1; in the fused form it takes the hot chunks too, the
   // table behind its rings), the hot chunks' and the warm tiers' table kernels
   KernelLaunch cold, hot, warm;
+  // the split form's hot words by pair-chunks (z_pairs_kernel) in z_hot_kernel's place; GGS_DEBUG_HOT_PAIRS=0: z_hot_kernel, as the fused form's cold kernel takes them
+  KernelLaunch pairs;
+  bool hot_pairs = false;
+  int32_t pairs_wave_lds = 0;
   bool f32 = false;
   bool split = true, split_forced = false;   // GGS_DEBUG_SPLIT=0: the fused form only; 2: the split form without the timed comparison
   int32_t wave_lds = 0, ring_base = 0, hot_wave_lds = 0, warm_wave_lds = 0, hot_pitch = 0, Kp32 = 0;   // ZParams of the three
@@ -136,7 +140,7 @@ struct LaunchPlan {
   KernelLaunch dochist, cellhist;
   bool wave_forced = false;            // ... because of K; otherwise per corpus (a document of 32 768 tokens or more)
   int32_t alias_wpb = 0;
-  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse, &countalias, &lightcol, &lightpcw2, &vsbits, &wordmask, &nzvs, &adlda, &dochist, &cellhist}; }   // not vschain: it has static LDS, and its dynamic LDS stays below the default cap
+  std::vector<const KernelLaunch *> all() const { return {&z, &cold, &hot, &pairs, &warm, &theta, &lane, &wave, &alias, &spalias, &lightpc, &serial, &wordlist, &pusparse, &countalias, &lightcol, &lightpcw2, &vsbits, &wordmask, &nzvs, &adlda, &dochist, &cellhist}; }   // not vschain: it has static LDS, and its dynamic LDS stays below the default cap
 };
 
 // One row per scheme, indexed by the enum: everything the host code asks about a scheme that is not its own buffers or its own
@@ -314,6 +318,8 @@ struct ggs_handle {
   int32_t *d_wt_pack = nullptr, *d_w_docs = nullptr, *d_warm_words = nullptr;   // d_wt_pack: four int32 per lane (ZParams::wt_pack)
   int32_t *d_ht_pack = nullptr, *d_h_docs = nullptr;        // the hot chunks in the same packed form (z_hot_kernel)
   int64_t *d_warm_meta = nullptr;
+  int32_t *d_hp_pair = nullptr, *d_hp_docs = nullptr, *d_hp_tok = nullptr;   // the hot words' pair-chunks (plan.hot_pairs; ZParams::hp_*)
+  int64_t Cp = 0, hp_pairs = 0, hp_tokens = 0;              // ... of the current corpus: chunks, pairs, tokens
   bool overlap_theta = true;
   int32_t gamma_queue_cap = 1 << 20;   // GGS_DEBUG_GAMMA_QUEUE: a tiny queue sends the leftovers of the first try down the on-the-spot path
   std::vector<int64_t> part_doc, part_chunk;           // [parts + 1] boundaries of the z step's parts (plan.cfg_parts; the last part's theta runs beside the Phi phase)

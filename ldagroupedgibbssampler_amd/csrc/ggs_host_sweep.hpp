@@ -122,7 +122,13 @@ int launch_z(ggs_handle *h, bool force_fused = false, int64_t c0 = 0, int64_t c1
     }
     zp.num_chunks = h->Cc; zp.num_hot = 0;
     HIP_TRY(h, launch(h, pl.cold, h->Cc, args, h->stream));
-    HIP_TRY(h, launch(h, pl.hot, h->Cs - h->Cc, hargs, h->side_hot, hot_rows_lds));
+    if (pl.hot_pairs && h->Cp > 0) {                     // the same tokens as pair-chunks (z_pairs_kernel): the same z
+      hp.wave_lds = pl.pairs_wave_lds; hp.hot_off = kSlicedWaves * pl.pairs_wave_lds;
+      hp.hp_pair = h->d_hp_pair; hp.hp_docs = h->d_hp_docs; hp.hp_tok = reinterpret_cast<const int4 *>(h->d_hp_tok); hp.num_pair_chunks = h->Cp;
+      HIP_TRY(h, launch(h, pl.pairs, h->Cp, hargs, h->side_hot, hot_rows_lds));
+    } else {
+      HIP_TRY(h, launch(h, pl.hot, h->Cs - h->Cc, hargs, h->side_hot, hot_rows_lds));
+    }
     HIP_TRY(h, launch_warm(h->side_hot));
     if (defer_join && zp.cnt_send) {
       hipStream_t main_stream = h->stream;

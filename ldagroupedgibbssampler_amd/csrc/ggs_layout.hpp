@@ -27,6 +27,13 @@ constexpr int kSlotShift = 30;            // chunk token word: value | (which of
 constexpr int kWarmMaxTiers = 8;
 constexpr int kWarmSlotShift = 16;        // warm chunk token word: table row | (which of the chunk's documents) << 16
 constexpr int kWarmDocSlots = 8;          // document ids stored per warm chunk (one 32-byte scalar load), whatever warm_docs_for() says
+// the hot words' pair-chunks (z_pairs_kernel): up to 64 distinct (document, table row) pairs of at most kHotPairDocs consecutive
+// documents, and the tokens of exactly those pairs in rounds of 64 lanes
+constexpr int kHotPairDocs = 2;           // 2 keeps the theta rows of the next chunk in 8 registers (16 at KMAX > 128): 55.7 pairs per chunk on the benchmark corpus.  4 would fill the 64 pairs, but takes twice the registers (z_pairs_kernel<160> then spills) and two theta rows more of LDS per wave; profiles/hot_pairs_ab.txt has the comparison
+constexpr int kHotPairRounds = 4;         // token rounds of a pair-chunk at most: the token entries of the next chunk travel through registers
+constexpr int kHotPairTokenCap = 64 * kHotPairRounds;
+constexpr int kHotPairLaneShift = 24;     // pair-chunk token word: table row | (document slot) << kWarmSlotShift | (lane of its pair) << 24
+constexpr int kHotPairTokSlot = 4, kHotPairCountSlot = 5, kHotPairRoundSlot = 6;   // a pair-chunk's kWarmDocSlots words: its documents, then tokens, pairs, first token round
 constexpr int kPcgsMaxDocLen = 32767;     // the lane-per-document pcgs kernels count in int16
 constexpr int64_t kSegTokens = 4096;      // count kernel: a word's run of the word-sorted tokens is cut into segments of at most this
 

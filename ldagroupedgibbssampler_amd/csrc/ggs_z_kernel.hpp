@@ -101,6 +101,11 @@ struct ZParams {
   unsigned long long *replays; // null, or += the tokens replayed (GGS_DEBUG_REPLAYS)
   double margin_scale32;       // its margin's scale: 1.0; tests scale it up to force the replay, or down to [0, 1) to decide
                                // tokens the proof leaves undecided (a decided draw is always a topic < K: no walk to leave the row)
+  // z_pairs_kernel (ggs_z_sliced.hpp): the hot words as pair-chunks (CorpusLists::hp_*, ggs_corpus_lists.hpp)
+  const int32_t *hp_pair;      // [pair-chunks][64] a distinct (document, table row) pair per lane: row | (document slot) << kWarmSlotShift
+  const int32_t *hp_docs;      // [pair-chunks][kWarmDocSlots] its kHotPairDocs documents, then its tokens, pairs and first token round
+  const int4 *hp_tok;          // [token rounds][64] {the pair's word | (lane of the pair) << kHotPairLaneShift, local token index or -1, its word-sorted position, 0}
+  int64_t num_pair_chunks;
 };
 
 struct alignas(16) D2 { double a, b; };

@@ -99,6 +99,10 @@ constexpr int sliced_fused_lds(const int K, const int rows) { return sliced_cold
 // z_warm_kernel: warm_docs_for(KMAX) rows, kWarmThetaPad apart); behind the waves the table and its zeroed tail
 constexpr int hot_wave_lds(const int K) { return round_up(kChunkDocs * sliced_slices(K) * kSliceTopics * 8, 256); }
 constexpr int warm_wave_lds(const int K) { return round_up(warm_docs_for(sliced_kmax(K)) * (sliced_slices(K) * kSliceTopics * 8 + kWarmThetaPad), 256); }
+// z_pairs_kernel, per wave: the theta rows of a pair-chunk's kHotPairDocs documents, then a record of the slices' checkpoints per
+// pair (an odd number of doubles apart: the 32 lanes of a half wave reading 8 bytes of 32 different records touch 32 different bank pairs)
+constexpr int pairs_record_pitch(const int K) { return (sliced_slices(K) | 1) * 8; }
+constexpr int pairs_wave_lds(const int K) { return round_up(kHotPairDocs * sliced_slices(K) * kSliceTopics * 8 + 64 * pairs_record_pitch(K), 256); }
 constexpr int table_lds(const int K, const int wave_lds, const int rows) { return kSlicedWaves * wave_lds + rows * table_row_pitch(K) + kHotTailBytes; }
 // rows a table may have: beside the cold kernel's workgroup on the same CU (both requests rounded up to the allocation
 // granule), or in the fused form; a row index is 8 bits of the chunk token word
@@ -653,10 +657,13 @@ __device__ __forceinline__ void load_phi_table(unsigned char *table, const int p
 // from the LDS row `trow` (both zero-padded to whole slices).  Returns the new topic.
 // UB = 16-byte units of a slice read ahead of the chain at a time: 8 (a whole slice: 64 registers of operands) in z_hot_kernel,
 // 4 in z_warm_kernel, whose next chunk's theta rows take 32 registers of the same 128.
+// In two halves, so that z_pairs_kernel runs the first once per (document, word) pair and the second once per token:
+// hot_pass1 = pass 1 (depends on the two rows only: ck[s] = the chain at the end of slice s, ck[NS - 1] the sum),
+// hot_decide = everything behind it.
 template <int KMAX, int UB = kSliceUnits>
-__device__ __forceinline__ int hot_token(const ZParams &p, const int K, const unsigned char *hrow, const unsigned char *trow, const int id0) {
+__device__ __forceinline__ void hot_pass1(const unsigned char *hrow, const unsigned char *trow, double (&ck)[(KMAX + kSliceTopics - 1) / kSliceTopics]) {
   constexpr int NS = (KMAX + kSliceTopics - 1) / kSliceTopics;
-  double sum = 0.0, ck[NS];
+  double sum = 0.0;
   static_for<0, NS>([&](auto sidx) {                           // GGS:96-101
     constexpr int s = decltype(sidx)::value;
 #pragma unroll
@@ -678,6 +685,12 @@ __device__ __forceinline__ int hot_token(const ZParams &p, const int K, const un
     }
     ck[s] = sum;
   });
+}
+template <int KMAX>
+__device__ __forceinline__ int hot_decide(const ZParams &p, const int K, const unsigned char *hrow, const unsigned char *trow, const int id0,
+                                          const double (&ck)[(KMAX + kSliceTopics - 1) / kSliceTopics]) {
+  constexpr int NS = (KMAX + kSliceTopics - 1) / kSliceTopics;
+  const double sum = ck[NS - 1];
   const uint64_t gtok = (uint64_t)(p.tok_base + id0);
   const double t0 = z_uniform(gtok, p.iteration, p.seed) * sum;   // GGS:107-108
   const double delta = (sum * (double)K) * 0x1p-51 * p.margin_scale;
@@ -737,6 +750,12 @@ __device__ __forceinline__ int hot_token(const ZParams &p, const int K, const un
     }
   }
   return new_topic;
+}
+template <int KMAX, int UB = kSliceUnits>
+__device__ __forceinline__ int hot_token(const ZParams &p, const int K, const unsigned char *hrow, const unsigned char *trow, const int id0) {
+  double ck[(KMAX + kSliceTopics - 1) / kSliceTopics];
+  hot_pass1<KMAX, UB>(hrow, trow, ck);
+  return hot_decide<KMAX>(p, K, hrow, trow, id0, ck);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -919,6 +938,131 @@ __global__ __launch_bounds__(kSlicedWaves * 64) __attribute__((amdgpu_waves_per_
     table_chunks<KMAX, warm_docs_for(KMAX), kWarmThetaPad, GGS_WARM_UNITS>(p, smem, thb, p.wt_pack, p.w_docs, meta[tier] + wid, meta[tier + 1], stride, lane,
                                                                           p.cnt_send ? words : nullptr);
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// z_pairs_kernel: the hot words by PAIR-CHUNKS, in z_hot_kernel's place.  Pass 1 of hot_token (the K products, their sum chain,
+// the checkpoints: 7/8 of a token's LDS reads and 2/3 of its arithmetic) depends on the (document, word) pair alone, and a
+// document holds each of its hot words 2.7 times on average (benchmark corpus: 0.365 distinct pairs per hot token) -- in
+// z_hot_kernel's lane-per-token layout the repeats ride along for nothing.  Here a chunk is up to 64 distinct pairs of at most
+// kHotPairDocs documents and the tokens of exactly those pairs (CorpusLists::hp_*):
+//   phase A  lane = pair: hot_pass1, unchanged; the pair's NS checkpoints go to the wave's record in LDS;
+//   phase B  lane = token, a round of 64 at a time (kHotPairRounds at most): hot_decide, unchanged, on the checkpoints of
+//            the token's pair -- the same products, the same additions in the same order, so the same z bit for bit.
+// The wave's own LDS operations complete in order; an s_waitcnt stands between the records' writes and their reads.
+// Loads are the compiler's, software-pipelined by one chunk: at the head of a chunk its operands (requested a chunk ago) are
+// taken -- the theta rows are the youngest of those loads, so the one wait there is for everything, and everything in flight is
+// a chunk old --, THEN the z stores of the chunk before are issued, then the loads of the next chunk.  A store or a load is
+// never waited for sooner than a whole chunk after its issue, and nothing is counted by hand.
+template <int KMAX>
+__global__ __launch_bounds__(kSlicedWaves * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void z_pairs_kernel(ZParams p) {
+  constexpr int NS = (KMAX + kSliceTopics - 1) / kSliceTopics;
+  constexpr int kRowD = NS * kSliceTopics, kThetaRow = kRowD * 8, NQ = (kRowD + 127) / 128;
+  constexpr int kRec = (NS | 1) * 8;                               // pairs_record_pitch
+  constexpr int R = kHotPairRounds;
+  constexpr int UB = kSliceUnits / 2;                              // half a slice of operands read ahead, as z_warm_kernel: the next chunk's operands take ~30 of the 128 registers
+  extern __shared__ __align__(16) unsigned char smem[];
+  __builtin_amdgcn_s_setprio(3);                                   // a guest beside the cold kernel: see z_hot_kernel
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  unsigned char *thb = smem + wave * p.wave_lds;                   // this wave's kHotPairDocs theta rows ...
+  unsigned char *rec = thb + kHotPairDocs * kThetaRow;             // ... and its 64 records
+  load_phi_table<KMAX>(smem + p.hot_off, p.hot_pitch, reinterpret_cast<const unsigned char *>(p.phiT), (size_t)p.Kp * 8, p.hot_words, p.num_hot, wave, lane, threadIdx.x);
+  __syncthreads();
+  const int K = p.K;
+  const int64_t C = p.num_pair_chunks, stride = (int64_t)gridDim.x * kSlicedWaves;
+  int64_t c = (int64_t)blockIdx.x * kSlicedWaves + wave;
+  if (c >= C) return;
+  const const_i32_t *cdocs = (const const_i32_t *)p.hp_docs;
+  uint32_t toff[NQ];                                               // as table_chunks: topics 2l, 2l + 1 (+ 128q) of a row, a lane past the row re-reads its head
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) { const int k0 = 2 * (q * 64 + lane); toff[q] = (uint32_t)(k0 < K ? k0 : 0) * 8; }
+
+  typedef i4v_t i4v8_t __attribute__((aligned(8)));                  // a theta row starts at d * K * 8
+  struct Set { int pw, nt; i3v_t e[R]; i4v_t t[kHotPairDocs][NQ]; };   // e: {token word, token index, its word-sorted position}
+  auto fetch = [&](const int64_t cc, Set &S) {
+    typedef int docs8_t __attribute__((ext_vector_type(8)));
+    const docs8_t dd = *reinterpret_cast<const __attribute__((address_space(4))) docs8_t *>(cdocs + cc * kWarmDocSlots);   // one s_load_dwordx8
+    S.nt = dd[kHotPairTokSlot];
+    S.pw = p.hp_pair[cc * 64 + lane];
+    const int4 *tp = p.hp_tok + ((int64_t)dd[kHotPairRoundSlot] * 64 + lane);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (r * 64 < S.nt) S.e[r] = *reinterpret_cast<const i3v_t *>(tp + r * 64);   // wave-uniform
+      else S.e[r] = i3v_t{0, -1, 0};
+    }
+#pragma unroll
+    for (int r = 0; r < kHotPairDocs; ++r)                         // the youngest loads: see above
+#pragma unroll
+      for (int q = 0; q < NQ; ++q)
+        S.t[r][q] = *reinterpret_cast<const i4v8_t *>(reinterpret_cast<const unsigned char *>(p.theta + (size_t)dd[r] * K) + toff[q]);
+  };
+
+  Set N;
+  fetch(c, N);
+  i3v_t ce[R];                                                     // the chunk's token entries and draws; at the loop head: the chunk before's
+  int res[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) { ce[r] = i3v_t{0, -1, 0}; res[r] = 0; }
+  for (;;) {
+    // ---- this chunk's operands (handed over through empty asm statements: every wait for them stands in front of the stores
+    // below); the theta rows to LDS (0.0 beyond K: the table's filler there is multiplied by it)
+    asm volatile("" : "+v"(N.pw));
+#pragma unroll
+    for (int r = 0; r < R; ++r) asm volatile("" : "+v"(N.e[r]));
+#pragma unroll
+    for (int r = 0; r < kHotPairDocs; ++r)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) asm volatile("" : "+v"(N.t[r][q]));
+#pragma unroll
+    for (int r = 0; r < kHotPairDocs; ++r)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q)
+        if (2 * (q * 64 + lane) < kRowD) {
+          const int k0 = 2 * (q * 64 + lane);
+          const D2 v = __builtin_bit_cast(D2, N.t[r][q]);
+          *reinterpret_cast<D2 *>(thb + r * kThetaRow + k0 * 8) = D2{k0 < K ? v.a : 0.0, k0 + 1 < K ? v.b : 0.0};
+        }
+    asm volatile("" ::: "memory");                                 // the stores below stay behind the wait the lines above needed
+    // ---- the draws of the chunk before
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (ce[r].y >= 0) { p.z[ce[r].y] = res[r]; p.zw[ce[r].z] = res[r]; }
+    const int pw = N.pw, nt = N.nt;
+#pragma unroll
+    for (int r = 0; r < R; ++r) ce[r] = N.e[r];
+    const bool has1 = c + stride < C;
+    if (has1) fetch(c + stride, N);
+    asm volatile("" ::: "memory");
+    // ---- phase A: lane = pair (an idle lane scores row 0 against the first document's theta: finite, read by nobody)
+    {
+      const unsigned char *hrow = smem + p.hot_off + (pw & ((1 << kWarmSlotShift) - 1)) * p.hot_pitch;
+      const unsigned char *trow = thb + ((unsigned)pw >> kWarmSlotShift) * kThetaRow;
+      double ck[NS];
+      hot_pass1<KMAX, UB>(hrow, trow, ck);
+#pragma unroll
+      for (int s = 0; s < NS; ++s) reinterpret_cast<double *>(rec + lane * kRec)[s] = ck[s];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // the wave's LDS operations complete in order
+    // ---- phase B: lane = token
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (r * 64 < nt && ce[r].y >= 0) {                           // (the first wave-uniform)
+        const int w = ce[r].x;
+        const unsigned char *hrow = smem + p.hot_off + (w & ((1 << kWarmSlotShift) - 1)) * p.hot_pitch;
+        const unsigned char *trow = thb + (((unsigned)w >> kWarmSlotShift) & ((1 << (kHotPairLaneShift - kWarmSlotShift)) - 1)) * kThetaRow;
+        const double *rk = reinterpret_cast<const double *>(rec + ((unsigned)w >> kHotPairLaneShift) * kRec);
+        double ck[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) ck[s] = rk[s];
+        res[r] = hot_decide<KMAX>(p, K, hrow, trow, ce[r].y, ck);
+      }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // every read of the rows and records is done before the next chunk's writes
+    if (!has1) break;
+    c += stride;
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (ce[r].y >= 0) { p.z[ce[r].y] = res[r]; p.zw[ce[r].z] = res[r]; }
 }
 
 }  // namespace ggs
