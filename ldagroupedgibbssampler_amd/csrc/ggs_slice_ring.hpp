@@ -94,16 +94,16 @@ __device__ __forceinline__ void ring_wait(const bool has1) {
 
 // ---- release: what must hold of a slot's LDS reads before the next step's DMA may refill it.  Two rules are in use,
 // and each kernel keeps the one it was measured and tested with:
-//   ring_release_returned   z_sliced32_kernel
-//   ring_release_issued     z_sliced_kernel, pcgs_sliced_kernel, polyaurn_sliced_kernel, pcgs_z_kernel, polyaurn_z_kernel,
-//                           z_stream_kernel, z_stream1_kernel
+//   ring_release_returned   z_sliced32_kernel and z_sliced_kernel (one loop: cold_chunk_loop, ggs_z_sliced.hpp)
+//   ring_release_issued     pcgs_sliced_kernel, polyaurn_sliced_kernel, pcgs_z_kernel, polyaurn_z_kernel, z_stream_kernel,
+//                           z_stream1_kernel
 // DESIGN.md section 5 on the float32 kernel: "the ring slot's LDS reads must have *returned*, not only been issued, before
 // the next DMA may refill the slot -- beside the table waves of the fused form an L2 hit overwrote a slot under queued
 // reads (wrong draws in the fused form only); the float32 kernel waits `lgkmcnt(0)` at the end of every slice."  How it
 // comes about: issued is not enough because the scheduler may sink the arithmetic (and the compiler's wait for these
 // reads) behind that DMA, and beside the table waves the reads queue long enough for an L2 hit to land first.
-// No argument that "issued" suffices is on record for the fp64 forms: they pass their tests with it, and nothing says why
-// the float32 kernel's hazard cannot reach them (open question).
+// No argument that "issued" suffices is on record for the six fp64 kernels that keep it: they pass their tests with it, and
+// nothing says why the float32 kernel's hazard cannot reach them (open question).
 __device__ __forceinline__ void ring_release_returned() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void ring_release_issued() { asm volatile("" ::: "memory"); }
 

@@ -32,13 +32,17 @@
 // The two fp64 chains per token (sum, then walk) are the reference's sequential chains; the
 // products are computed once and kept, as in the reference.
 //
+// One chunk loop, cold_chunk_loop, walks a wave's cold chunks for both forms of the kernel; a form is a struct that says
+// what a slice holds, how it is scored and how the chunk is finished:
+//   ColdForm32  z_sliced32_kernel, the production form: phiT32, 32 float32 topics per slice, draws decided by margin;
+//   ColdForm64  z_sliced_kernel, its cross-check (GGS_DEBUG_PHI64=1): phiT, 16 fp64 topics per slice, the walk above.
 // The ring (DMA shape, the per-row rotation, completion and release of a slot): ggs_slice_ring.hpp.
 #pragma once
 #include <type_traits>
 
 #include "ggs_slice_ring.hpp"
 
-// timing-only experiments, compile time (results are wrong on purpose): 1 no DMA, 8 DMA issued but never waited for
+// timing-only experiments of cold_chunk_loop, compile time (results are wrong on purpose): 1 no DMA, 8 DMA issued but never waited for
 #ifndef GGS_ABL
 #define GGS_ABL 0
 #endif
@@ -122,7 +126,7 @@ __device__ __forceinline__ void static_for(F &&f) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// The cold chunks from the float32 shadow of phiT (z_sliced32_kernel, the default below K = kSlicedDefaultTopics).
+// ColdForm32: the cold chunks from the float32 shadow of phiT (z_sliced32_kernel, the default below K = kSlicedDefaultTopics).
 //
 // phiT32 [V][Kp32] (phi32_of, ggs_kernels.hpp): a row is Kp32 = K rounded up to 32 floats, a slice 32 topics in the same
 // 128 bytes per row, gathered by the same LDS-DMA ring (the per-lane rotation is by 16-byte units: unchanged).  K = 100:
@@ -161,40 +165,55 @@ __device__ __forceinline__ void static_for(F &&f) {
 typedef float f2_t __attribute__((ext_vector_type(2)));
 typedef float f4_t __attribute__((ext_vector_type(4)));
 template <int KMAX>
-__device__ __forceinline__ void cold_chunks32(const ZParams &p, unsigned char *thb, unsigned char *ring, const int64_t wid, const int64_t stride, const int lane) {
-  constexpr int NS = (KMAX + kSlice32Topics - 1) / kSlice32Topics;   // 32-topic slices per chunk
-  constexpr int kAhead = NS < kRingSlots - 1 ? NS : kRingSlots - 1;
-  constexpr int NT = (KMAX + 63) / 64;
-  constexpr int kThetaRow = KMAX * 4;                              // bytes of one float32 theta row in LDS
-  const int K = p.K;
-  const unsigned char *phib = reinterpret_cast<const unsigned char *>(p.phiT32);
-  const size_t rowbytes = (size_t)p.Kp32 * 4;
-  const const_i32_t *cdocs = (const const_i32_t *)p.c_docs;
-  double *prod = reinterpret_cast<double *>(thb + kChunkDocs * kThetaRow);   // the replay's products (KMAX doubles)
-  const unsigned char *my_row = ring_lane_row(ring, lane);
-  const int rot = ring_lane_rotation(lane);
-  const float mscale = (float)p.margin_scale32;
+struct ColdForm32 {
+  static constexpr int NS = (KMAX + kSlice32Topics - 1) / kSlice32Topics;   // 32-topic slices per chunk
+  static constexpr int NT = (KMAX + 63) / 64;
+  static constexpr int kThetaRow = KMAX * 4;                       // bytes of one float32 theta row in LDS
+  struct State { float a[KMAX]; float acc = 0.0f; };               // the prefix sums a_j and the chain
+  const ZParams &p;
+  unsigned char *thb;
+  const int lane;
+  const float mscale;                                              // (float)p.margin_scale32
 
-  auto load_theta = [&](const int d0, const int d1, double (&tv)[kChunkDocs][NT]) {
-    const double *t0 = p.theta + (size_t)d0 * K, *t1 = p.theta + (size_t)d1 * K;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      tv[0][t] = (t * 64 + lane < K) ? t0[t * 64 + lane] : 0.0;
-      tv[1][t] = (t * 64 + lane < K) ? t1[t * 64 + lane] : 0.0;
-    }
-  };
-  auto stage_theta = [&](const double (&tv)[kChunkDocs][NT]) {
+  __device__ __forceinline__ const unsigned char *phib() const { return reinterpret_cast<const unsigned char *>(p.phiT32); }
+  __device__ __forceinline__ size_t rowbytes() const { return (size_t)p.Kp32 * 4; }
+  __device__ __forceinline__ void stage_theta(const double (&tv)[kChunkDocs][NT]) const {
 #pragma unroll
     for (int r = 0; r < kChunkDocs; ++r)
 #pragma unroll
       for (int t = 0; t < NT; ++t)
         if (t * 64 + lane < KMAX) reinterpret_cast<float *>(thb + r * kThetaRow)[t * 64 + lane] = phi32_of(tv[r][t]);
-  };
-  auto row_addresses = [&](const int w, const unsigned char *(&ra)[8]) {
-    ring_row_addresses(phib, rowbytes, w, (1 << kSlotShift) - 1, lane, ra);   // word 0 for rows past the chunk
-  };
+  }
+  // slice s from the lane's ring row `rb`: every lane scores (an idle one reads finite bytes: it stores nothing)
+  template <int s>
+  __device__ __forceinline__ void score(State &st, const unsigned char *rb, const unsigned char *trow, const int rot, const int) const {
+    f4_t ph[kSliceUnits], th[kSliceUnits];                         // unit u = topics 4u .. 4u + 3 of the slice
+#pragma unroll
+    for (int u = 0; u < kSliceUnits; ++u)
+      if (s * kSlice32Topics + 4 * u < KMAX) {                     // compile time (KMAX is a multiple of 8)
+        ph[u] = *reinterpret_cast<const f4_t *>(rb + ring_unit_offset(u, rot));
+        th[u] = *reinterpret_cast<const f4_t *>(trow + s * (kSlice32Topics * 4) + u * 16);
+      }
+#pragma unroll
+    for (int u = 0; u < kSliceUnits; ++u) {
+      constexpr int k0 = s * kSlice32Topics;
+      const int k = k0 + 4 * u;
+      if (k < KMAX) {
+        const f2_t q0 = f2_t{th[u].x, th[u].y} * f2_t{ph[u].x, ph[u].y};
+        const f2_t q1 = f2_t{th[u].z, th[u].w} * f2_t{ph[u].z, ph[u].w};
+        st.acc += q0.x; st.a[k] = st.acc;
+        st.acc += q0.y; st.a[k + 1] = st.acc;
+        st.acc += q1.x; st.a[k + 2] = st.acc;
+        st.acc += q1.y; st.a[k + 3] = st.acc;
+      }
+    }
+  }
   // U, the decision, the replay and the stores of one chunk c
-  auto finish = [&](const float (&a)[KMAX], const int64_t c, const int idx, const int ip, const int w) {
+  __device__ __forceinline__ void finish(const State &st, const int64_t c, const int idx, const int ip, const int w) const {
+    const float (&a)[KMAX] = st.a;
+    const int K = p.K;
+    const const_i32_t *cdocs = (const const_i32_t *)p.c_docs;
+    double *prod = reinterpret_cast<double *>(thb + kChunkDocs * kThetaRow);   // the replay's products (KMAX doubles)
     const uint64_t gtok = (uint64_t)(p.tok_base + idx);
     const double U = z_uniform(gtok, p.iteration, p.seed);
     const float A = a[KMAX - 1];
@@ -259,150 +278,71 @@ __device__ __forceinline__ void cold_chunks32(const ZParams &p, unsigned char *t
     p.zw[ip] = new_topic;
     const int word = w & ((1 << kSlotShift) - 1);
     if (p.cnt_send) __hip_atomic_fetch_add(&p.cnt_send[slice_cell(p.smap, new_topic, word)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-
-  // ---- the chunk loop of cold_chunks (z_sliced_body), 32 topics per slice
-  const int64_t C = p.num_cold;
-  int64_t c = wid;
-  if (c >= C) return;
-  int w0 = p.ct_tok[c * 64 + lane], id0 = p.ct_idx[c * 64 + lane], ip0 = p.ct_ip[c * 64 + lane];
-  int w1 = 0, id1 = -1, ip1 = 0, w2 = 0, id2 = -1, ip2 = 0;
-  double tv0[kChunkDocs][NT], tv1[kChunkDocs][NT], tv2[kChunkDocs][NT];
-  load_theta(cdocs[2 * c], cdocs[2 * c + 1], tv0);
-  if (c + stride < C) {
-    const int64_t c1 = c + stride;
-    w1 = p.ct_tok[c1 * 64 + lane]; id1 = p.ct_idx[c1 * 64 + lane]; ip1 = p.ct_ip[c1 * 64 + lane];
-    load_theta(cdocs[2 * c1], cdocs[2 * c1 + 1], tv1);
-  } else {
-    load_theta(0, 0, tv1);
   }
-#pragma unroll
-  for (int r = 0; r < kChunkDocs; ++r)
-#pragma unroll
-    for (int t = 0; t < NT; ++t) tv2[r][t] = 0.0;
-  const unsigned char *ra[8], *ran[8];
-  row_addresses(w0, ra);
-  row_addresses(w1, ran);
-  int g = 0;
-  static_for<0, kAhead>([&](auto sc) { ring_issue<decltype(sc)::value>(ring, decltype(sc)::value % kRingSlots, ra); });
+};
 
-  for (;;) {
-    const bool has1 = c + stride < C, has2 = c + 2 * stride < C;
-    g = __builtin_amdgcn_readfirstlane(g);
-    stage_theta(tv0);
-    const unsigned char *trow = thb + ((unsigned)w0 >> kSlotShift) * kThetaRow;
+// ------------------------------------------------------------------------------------------------
+// The fp64 form (z_sliced_kernel): 16 topics per slice, the K products of a token in registers.  Since the float32 form it
+// runs under GGS_DEBUG_PHI64=1 only, as that form's cross-check; its walk also serves the fused form's hot chunks.
 
-    float a[KMAX];
-    float acc = 0.0f;
-    static_for<0, NS>([&](auto sidx) {
-      constexpr int s = decltype(sidx)::value;
-      const int cur = (g + s) % kRingSlots;
-      const int nxt = (g + s + kAhead) % kRingSlots;
-      if constexpr (s + kAhead < NS) ring_issue<s + kAhead>(ring, nxt, ra);
-      else if (has1) ring_issue<s + kAhead - NS>(ring, nxt, ran);
-      ring_wait<kAhead, NS, s>(has1);
-      {                                                            // every lane (an idle one reads finite bytes: it stores nothing)
-        const unsigned char *rb = my_row + cur * kSliceBytes;
-        f4_t ph[kSliceUnits], th[kSliceUnits];                     // unit u = topics 4u .. 4u + 3 of the slice
+// theta rows of a chunk's two documents: lane l holds entries l, l + 64, ... of each (0.0 beyond K)
+template <int NT>
+__device__ __forceinline__ void load_theta(const ZParams &p, const int lane, const int d0, const int d1, double (&tv)[kChunkDocs][NT]) {
+  const int K = p.K;
+  const double *t0 = p.theta + (size_t)d0 * K, *t1 = p.theta + (size_t)d1 * K;
 #pragma unroll
-        for (int u = 0; u < kSliceUnits; ++u)
-          if (s * kSlice32Topics + 4 * u < KMAX) {                 // compile time (KMAX is a multiple of 8)
-            ph[u] = *reinterpret_cast<const f4_t *>(rb + ring_unit_offset(u, rot));
-            th[u] = *reinterpret_cast<const f4_t *>(trow + s * (kSlice32Topics * 4) + u * 16);
-          }
-#pragma unroll
-        for (int u = 0; u < kSliceUnits; ++u) {
-          constexpr int k0 = s * kSlice32Topics;
-          const int k = k0 + 4 * u;
-          if (k < KMAX) {
-            const f2_t q0 = f2_t{th[u].x, th[u].y} * f2_t{ph[u].x, ph[u].y};
-            const f2_t q1 = f2_t{th[u].z, th[u].w} * f2_t{ph[u].z, ph[u].w};
-            acc += q0.x; a[k] = acc;
-            acc += q0.y; a[k + 1] = acc;
-            acc += q1.x; a[k + 2] = acc;
-            acc += q1.y; a[k + 3] = acc;
-          }
-        }
-      }
-      ring_release_returned();                                     // "issued" gave wrong draws in the fused form (ggs_slice_ring.hpp)
-    });
-    g = (g + NS) % kRingSlots;
-
-    if (has2) {
-      const int64_t c2 = c + 2 * stride;
-      w2 = p.ct_tok[c2 * 64 + lane]; id2 = p.ct_idx[c2 * 64 + lane]; ip2 = p.ct_ip[c2 * 64 + lane];
-      load_theta(cdocs[2 * c2], cdocs[2 * c2 + 1], tv2);
-    } else {
-      w2 = 0; id2 = -1; ip2 = 0;
-    }
-
-    finish(a, c, id0, ip0, w0);
-    if (!has1) break;
-    c += stride;
-    w0 = w1; id0 = id1; ip0 = ip1;
-    w1 = w2; id1 = id2; ip1 = ip2;
-#pragma unroll
-    for (int r = 0; r < kChunkDocs; ++r)
-#pragma unroll
-      for (int t = 0; t < NT; ++t) { tv0[r][t] = tv1[r][t]; tv1[r][t] = tv2[r][t]; }
-#pragma unroll
-    for (int m = 0; m < 8; ++m) ra[m] = ran[m];
-    row_addresses(w1, ran);
+  for (int t = 0; t < NT; ++t) {
+    tv[0][t] = (t * 64 + lane < K) ? t0[t * 64 + lane] : 0.0;
+    tv[1][t] = (t * 64 + lane < K) ? t1[t * 64 + lane] : 0.0;
   }
 }
 
-// KMAX = K rounded up to a multiple of 8: the size of the score register file.  Topics
-// K..KMAX-1 are scored too, with theta = 0 (the LDS theta rows are zero-padded) against finite
-// phi bytes, so they add +0.0 to the sum and subtract 0.0 in the walk: no per-topic guards.
-template <int KMAX, bool F32>
-__device__ __forceinline__ void z_sliced_body(const ZParams &p) {
-  constexpr int NS = (KMAX + kSliceTopics - 1) / kSliceTopics;     // slices per chunk
-  constexpr int kAhead = NS < kRingSlots - 1 ? NS : kRingSlots - 1;   // slices in flight beyond the one being scored
-  constexpr int NT = (KMAX + 63) / 64;                             // 64-topic pieces of a theta row
-  constexpr int kThetaRow = KMAX * 8;                              // bytes of one theta row in LDS
-  extern __shared__ __align__(16) unsigned char smem[];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int K = p.K;
-  unsigned char *thb = smem + wave * p.wave_lds;                   // the chunk's kChunkDocs theta rows
-  unsigned char *ring = thb + p.ring_base;
-  const unsigned char *phib = reinterpret_cast<const unsigned char *>(p.phiT);
-  const size_t rowbytes = (size_t)p.Kp * 8;
-  const const_i32_t *cdocs = (const const_i32_t *)p.c_docs;
-  const int64_t stride = (int64_t)gridDim.x * kSlicedWaves;
-  const int64_t wid = (int64_t)blockIdx.x * kSlicedWaves + wave;
+template <int KMAX>
+struct ColdForm64 {
+  static constexpr int NS = (KMAX + kSliceTopics - 1) / kSliceTopics;   // slices per chunk
+  static constexpr int NT = (KMAX + 63) / 64;                      // 64-topic pieces of a theta row
+  static constexpr int kThetaRow = KMAX * 8;                       // bytes of one theta row in LDS
+  struct State { double sc[KMAX]; double sum = 0.0; };
+  const ZParams &p;
+  unsigned char *thb;
+  const int lane;
+  const int K;                                                     // p.K
 
-  // the hot rows: KMAX doubles each (like the ring, the tail past K is finite filler scored with theta = 0)
-  {
-    constexpr int upr = KMAX / 2;                                  // 16-byte units per row
-    for (int i = threadIdx.x; i < p.num_hot * upr; i += kSlicedWaves * 64) {
-      const int r = i / upr, u = i - r * upr;
-      *reinterpret_cast<D2 *>(smem + p.hot_off + r * p.hot_pitch + u * 16) =
-          *reinterpret_cast<const D2 *>(phib + (size_t)p.hot_words[r] * rowbytes + (size_t)u * 16);
-    }
-  }
-  __syncthreads();                                                 // the only barrier; no DMA is in flight yet
-
-  const unsigned char *my_row = ring_lane_row(ring, lane);
-  const int rot = ring_lane_rotation(lane);
-
-  // theta rows of a chunk's two documents: lane l holds entries l, l + 64, ... of each (0.0 beyond K)
-  auto load_theta = [&](const int d0, const int d1, double (&tv)[kChunkDocs][NT]) {
-    const double *t0 = p.theta + (size_t)d0 * K, *t1 = p.theta + (size_t)d1 * K;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      tv[0][t] = (t * 64 + lane < K) ? t0[t * 64 + lane] : 0.0;
-      tv[1][t] = (t * 64 + lane < K) ? t1[t * 64 + lane] : 0.0;
-    }
-  };
-  auto stage_theta = [&](const double (&tv)[kChunkDocs][NT]) {
+  __device__ __forceinline__ const unsigned char *phib() const { return reinterpret_cast<const unsigned char *>(p.phiT); }
+  __device__ __forceinline__ size_t rowbytes() const { return (size_t)p.Kp * 8; }
+  __device__ __forceinline__ void stage_theta(const double (&tv)[kChunkDocs][NT]) const {
 #pragma unroll
     for (int r = 0; r < kChunkDocs; ++r)
 #pragma unroll
       for (int t = 0; t < NT; ++t)
         if (t * 64 + lane < KMAX) reinterpret_cast<double *>(thb + r * kThetaRow)[t * 64 + lane] = tv[r][t];
-  };
+  }
+  template <int s>
+  __device__ __forceinline__ void score(State &st, const unsigned char *rb, const unsigned char *trow, const int rot, const int id0) const {
+    if (id0 < 0) return;
+    // unit u = topics (k, k+1).  All 16 LDS reads of the slice are issued up front (they return
+    // in order), so the chain below starts after one LDS latency and never waits again.
+    D2 ph[kSliceUnits], th[kSliceUnits];
+#pragma unroll
+    for (int u = 0; u < kSliceUnits; ++u)
+      if (s * kSliceTopics + 2 * u + 1 < KMAX) {                   // compile time (KMAX is even)
+        ph[u] = lds_d2(rb + ring_unit_offset(u, rot));
+        th[u] = lds_d2(trow + s * (kSliceTopics * 8) + u * 16);
+      }
+#pragma unroll
+    for (int u = 0; u < kSliceUnits; ++u) {
+      constexpr int k0 = s * kSliceTopics;
+      const int k = k0 + 2 * u;
+      if (k + 1 < KMAX) {
+        st.sc[k] = th[u].a * ph[u].a;
+        st.sum += st.sc[k];
+        st.sc[k + 1] = th[u].b * ph[u].b;
+        st.sum += st.sc[k + 1];
+      }
+    }
+  }
   // U, the walk and the stores (GGS:107-130) of one chunk
-  auto finish = [&](const double (&sc)[KMAX], const double sum, const int idx, const int ip, const int word) {
+  __device__ __forceinline__ void walk(const double (&sc)[KMAX], const double sum, const int idx, const int ip, const int word) const {
     if (idx < 0) return;
     const uint64_t gtok = (uint64_t)(p.tok_base + idx);
     const double U = z_uniform(gtok, p.iteration, p.seed);
@@ -442,109 +382,130 @@ __device__ __forceinline__ void z_sliced_body(const ZParams &p) {
     // (measured with them: the z step of one rank in eight 0.41 ms instead of 0.14) -- the hot words' segments are counted
     // by count_sorted_kernel on their own
     if (p.cnt_send && word >= 0) __hip_atomic_fetch_add(&p.cnt_send[slice_cell(p.smap, new_topic, word)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ void finish(const State &st, const int64_t, const int idx, const int ip, const int w) const {
+    walk(st.sc, st.sum, idx, ip, w & ((1 << kSlotShift) - 1));
+  }
+};
+
+// ------------------------------------------------------------------------------------------------
+// The chunk loop of both forms: a wave's cold chunks wid, wid + stride, ... < p.num_cold, the ring kept kAhead slices
+// ahead of the arithmetic across chunk boundaries.  A form supplies what it is: NS, NT, kThetaRow, its score State,
+// phib() / rowbytes() of the rows it gathers, stage_theta, score<s> and finish.
+template <class Form>
+__device__ __forceinline__ void cold_chunk_loop(const ZParams &p, Form &f, unsigned char *thb, unsigned char *ring, const int64_t wid, const int64_t stride, const int lane) {
+  constexpr int NS = Form::NS, NT = Form::NT, kThetaRow = Form::kThetaRow;
+  constexpr int kAhead = NS < kRingSlots - 1 ? NS : kRingSlots - 1;   // slices in flight beyond the one being scored
+  const unsigned char *phib = f.phib();
+  const size_t rowbytes = f.rowbytes();
+  const const_i32_t *cdocs = (const const_i32_t *)p.c_docs;
+  const unsigned char *my_row = ring_lane_row(ring, lane);
+  const int rot = ring_lane_rotation(lane);
+  const int64_t C = p.num_cold;
+  auto row_addresses = [&](const int w, const unsigned char *(&ra)[8]) {
+    ring_row_addresses(phib, rowbytes, w, (1 << kSlotShift) - 1, lane, ra);   // word 0 for rows past the chunk
+  };
+  auto issue_slice = [&](auto sc, const int slot, const unsigned char *const (&ra)[8]) {
+    if (!(GGS_ABL & 1)) ring_issue<decltype(sc)::value>(ring, slot, ra);
   };
 
-  // ------------------------------------------------------------------ cold chunks
-  auto cold_chunks = [&]() {
-    const int64_t C = p.num_cold;
-    auto row_addresses = [&](const int w, const unsigned char *(&ra)[8]) {
-      ring_row_addresses(phib, rowbytes, w, (1 << kSlotShift) - 1, lane, ra);   // word 0 for rows past the chunk
-    };
-    auto issue_slice = [&](auto sc, const int slot, const unsigned char *const (&ra)[8]) {
-      if (!(GGS_ABL & 1)) ring_issue<decltype(sc)::value>(ring, slot, ra);
-    };
+  // ---- prologue.  Suffix 0 = this chunk, 1 = next, 2 = the one after.
+  int64_t c = wid;
+  if (c >= C) return;
+  int w0 = p.ct_tok[c * 64 + lane], id0 = p.ct_idx[c * 64 + lane], ip0 = p.ct_ip[c * 64 + lane];
+  int w1 = 0, id1 = -1, ip1 = 0, w2 = 0, id2 = -1, ip2 = 0;
+  double tv0[kChunkDocs][NT], tv1[kChunkDocs][NT], tv2[kChunkDocs][NT];
+  load_theta(p, lane, cdocs[2 * c], cdocs[2 * c + 1], tv0);
+  if (c + stride < C) {
+    const int64_t c1 = c + stride;
+    w1 = p.ct_tok[c1 * 64 + lane]; id1 = p.ct_idx[c1 * 64 + lane]; ip1 = p.ct_ip[c1 * 64 + lane];
+    load_theta(p, lane, cdocs[2 * c1], cdocs[2 * c1 + 1], tv1);
+  } else {
+    load_theta(p, lane, 0, 0, tv1);
+  }
+#pragma unroll
+  for (int r = 0; r < kChunkDocs; ++r)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) tv2[r][t] = 0.0;
+  const unsigned char *ra[8], *ran[8];                             // DMA row addresses: this chunk, next chunk
+  row_addresses(w0, ra);
+  row_addresses(w1, ran);
+  int g = 0;                                                       // ring slot of this chunk's slice 0
+  static_for<0, kAhead>([&](auto sc) { issue_slice(sc, decltype(sc)::value % kRingSlots, ra); });
 
-    // ---- prologue.  Suffix 0 = this chunk, 1 = next, 2 = the one after.
-    int64_t c = wid;
-    if (c >= C) return;
-    int w0 = p.ct_tok[c * 64 + lane], id0 = p.ct_idx[c * 64 + lane], ip0 = p.ct_ip[c * 64 + lane];
-    int w1 = 0, id1 = -1, ip1 = 0, w2 = 0, id2 = -1, ip2 = 0;
-    double tv0[kChunkDocs][NT], tv1[kChunkDocs][NT], tv2[kChunkDocs][NT];
-    load_theta(cdocs[2 * c], cdocs[2 * c + 1], tv0);
-    if (c + stride < C) {
-      const int64_t c1 = c + stride;
-      w1 = p.ct_tok[c1 * 64 + lane]; id1 = p.ct_idx[c1 * 64 + lane]; ip1 = p.ct_ip[c1 * 64 + lane];
-      load_theta(cdocs[2 * c1], cdocs[2 * c1 + 1], tv1);
+  for (;;) {
+    const bool has1 = c + stride < C, has2 = c + 2 * stride < C;
+    g = __builtin_amdgcn_readfirstlane(g);                         // wave-uniform by construction: keep it scalar
+    f.stage_theta(tv0);                                            // requested two chunks ago
+    const unsigned char *trow = thb + ((unsigned)w0 >> kSlotShift) * kThetaRow;   // this lane's document
+
+    typename Form::State st;
+    static_for<0, NS>([&](auto sidx) {
+      constexpr int s = decltype(sidx)::value;
+      const int cur = (g + s) % kRingSlots;
+      const int nxt = (g + s + kAhead) % kRingSlots;               // freed by the slice scored last step
+      // keep kAhead slices in flight: slice s + kAhead of this chunk, or of the next one
+      if constexpr (s + kAhead < NS) issue_slice(std::integral_constant<int, s + kAhead>{}, nxt, ra);
+      else if (has1) issue_slice(std::integral_constant<int, s + kAhead - NS>{}, nxt, ran);
+      if (!(GGS_ABL & (1 | 8))) ring_wait<kAhead, NS, s>(has1);
+      f.template score<s>(st, my_row + cur * kSliceBytes, trow, rot, id0);
+      ring_release_returned();                                     // "issued" gave wrong draws in the fused form (ggs_slice_ring.hpp)
+    });
+    g = (g + NS) % kRingSlots;                                     // ring slot of the next chunk's slice 0
+
+    // requests for two chunks ahead: younger than every DMA above, so they are only waited for
+    // at the next chunk's slices, after the walk below.
+    if (has2) {
+      const int64_t c2 = c + 2 * stride;
+      w2 = p.ct_tok[c2 * 64 + lane]; id2 = p.ct_idx[c2 * 64 + lane]; ip2 = p.ct_ip[c2 * 64 + lane];
+      load_theta(p, lane, cdocs[2 * c2], cdocs[2 * c2 + 1], tv2);
     } else {
-      load_theta(0, 0, tv1);
+      w2 = 0; id2 = -1; ip2 = 0;
     }
+
+    f.finish(st, c, id0, ip0, w0);
+    if (!has1) break;
+    c += stride;
+    w0 = w1; id0 = id1; ip0 = ip1;
+    w1 = w2; id1 = id2; ip1 = ip2;
 #pragma unroll
     for (int r = 0; r < kChunkDocs; ++r)
 #pragma unroll
-      for (int t = 0; t < NT; ++t) tv2[r][t] = 0.0;
-    const unsigned char *ra[8], *ran[8];                           // DMA row addresses: this chunk, next chunk
-    row_addresses(w0, ra);
-    row_addresses(w1, ran);
-    int g = 0;                                                     // ring slot of this chunk's slice 0
-    static_for<0, kAhead>([&](auto sc) { issue_slice(sc, decltype(sc)::value % kRingSlots, ra); });
+      for (int t = 0; t < NT; ++t) { tv0[r][t] = tv1[r][t]; tv1[r][t] = tv2[r][t]; }
+#pragma unroll
+    for (int m = 0; m < 8; ++m) ra[m] = ran[m];
+    row_addresses(w1, ran);                                        // w1 was requested a chunk ago
+  }
+}
 
-    for (;;) {
-      const bool has1 = c + stride < C, has2 = c + 2 * stride < C;
-      g = __builtin_amdgcn_readfirstlane(g);                       // wave-uniform by construction: keep it scalar
-      stage_theta(tv0);                                            // requested two chunks ago
-      const unsigned char *trow = thb + ((unsigned)w0 >> kSlotShift) * kThetaRow;   // this lane's document
+// KMAX = K rounded up to a multiple of 8: the size of the score register file.  Topics
+// K..KMAX-1 are scored too, with theta = 0 (the LDS theta rows are zero-padded) against finite
+// phi bytes, so they add +0.0 to the sum and subtract 0.0 in the walk: no per-topic guards.
+template <int KMAX, bool F32>
+__device__ __forceinline__ void z_sliced_body(const ZParams &p) {
+  using Form64 = ColdForm64<KMAX>;
+  constexpr int NS = Form64::NS, NT = Form64::NT, kThetaRow = Form64::kThetaRow;
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  unsigned char *thb = smem + wave * p.wave_lds;                   // the chunk's kChunkDocs theta rows
+  unsigned char *ring = thb + p.ring_base;
+  Form64 f64{p, thb, lane, p.K};
+  const unsigned char *phib = f64.phib();
+  const size_t rowbytes = f64.rowbytes();
+  const const_i32_t *cdocs = (const const_i32_t *)p.c_docs;
+  const int64_t stride = (int64_t)gridDim.x * kSlicedWaves;
+  const int64_t wid = (int64_t)blockIdx.x * kSlicedWaves + wave;
 
-      double sc[KMAX];
-      double sum = 0.0;
-      static_for<0, NS>([&](auto sidx) {
-        constexpr int s = decltype(sidx)::value;
-        const int cur = (g + s) % kRingSlots;
-        const int nxt = (g + s + kAhead) % kRingSlots;        // freed by the slice scored last step
-        // keep kAhead slices in flight: slice s + kAhead of this chunk, or of the next one
-        if constexpr (s + kAhead < NS) issue_slice(std::integral_constant<int, s + kAhead>{}, nxt, ra);
-        else if (has1) issue_slice(std::integral_constant<int, s + kAhead - NS>{}, nxt, ran);
-        if (!(GGS_ABL & (1 | 8))) ring_wait<kAhead, NS, s>(has1);
-        if (id0 >= 0) {
-          const unsigned char *rb = my_row + cur * kSliceBytes;
-          // unit u = topics (k, k+1).  All 16 LDS reads of the slice are issued up front (they return
-          // in order), so the chain below starts after one LDS latency and never waits again.
-          D2 ph[kSliceUnits], th[kSliceUnits];
-#pragma unroll
-          for (int u = 0; u < kSliceUnits; ++u)
-            if (s * kSliceTopics + 2 * u + 1 < KMAX) {             // compile time (KMAX is even)
-              ph[u] = lds_d2(rb + ring_unit_offset(u, rot));
-              th[u] = lds_d2(trow + s * (kSliceTopics * 8) + u * 16);
-            }
-#pragma unroll
-          for (int u = 0; u < kSliceUnits; ++u) {
-            constexpr int k0 = s * kSliceTopics;
-            const int k = k0 + 2 * u;
-            if (k + 1 < KMAX) {
-              sc[k] = th[u].a * ph[u].a;
-              sum += sc[k];
-              sc[k + 1] = th[u].b * ph[u].b;
-              sum += sc[k + 1];
-            }
-          }
-        }
-        ring_release_issued();
-      });
-      g = (g + NS) % kRingSlots;                             // ring slot of the next chunk's slice 0
-
-      // requests for two chunks ahead: younger than every DMA above, so they are only waited for
-      // at the next chunk's slices, after the walk below.
-      if (has2) {
-        const int64_t c2 = c + 2 * stride;
-        w2 = p.ct_tok[c2 * 64 + lane]; id2 = p.ct_idx[c2 * 64 + lane]; ip2 = p.ct_ip[c2 * 64 + lane];
-        load_theta(cdocs[2 * c2], cdocs[2 * c2 + 1], tv2);
-      } else {
-        w2 = 0; id2 = -1; ip2 = 0;
-      }
-
-      finish(sc, sum, id0, ip0, w0 & ((1 << kSlotShift) - 1));
-      if (!has1) break;
-      c += stride;
-      w0 = w1; id0 = id1; ip0 = ip1;
-      w1 = w2; id1 = id2; ip1 = ip2;
-#pragma unroll
-      for (int r = 0; r < kChunkDocs; ++r)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) { tv0[r][t] = tv1[r][t]; tv1[r][t] = tv2[r][t]; }
-#pragma unroll
-      for (int m = 0; m < 8; ++m) ra[m] = ran[m];
-      row_addresses(w1, ran);                                      // w1 was requested a chunk ago
+  // the hot rows: KMAX doubles each (like the ring, the tail past K is finite filler scored with theta = 0)
+  {
+    constexpr int upr = KMAX / 2;                                  // 16-byte units per row
+    for (int i = threadIdx.x; i < p.num_hot * upr; i += kSlicedWaves * 64) {
+      const int r = i / upr, u = i - r * upr;
+      *reinterpret_cast<D2 *>(smem + p.hot_off + r * p.hot_pitch + u * 16) =
+          *reinterpret_cast<const D2 *>(phib + (size_t)p.hot_words[r] * rowbytes + (size_t)u * 16);
     }
-  };
+  }
+  __syncthreads();                                                 // the only barrier; no DMA is in flight yet
 
   // ------------------------------------------------------------------ hot chunks: phi from the LDS table
   auto hot_chunks = [&]() {
@@ -553,7 +514,7 @@ __device__ __forceinline__ void z_sliced_body(const ZParams &p) {
     if (c >= C) return;
     int w0 = p.ct_tok[c * 64 + lane], id0 = p.ct_idx[c * 64 + lane], ip0 = p.ct_ip[c * 64 + lane];
     double tv0[kChunkDocs][NT];
-    load_theta(cdocs[2 * c], cdocs[2 * c + 1], tv0);
+    load_theta(p, lane, cdocs[2 * c], cdocs[2 * c + 1], tv0);
     for (;;) {
       const bool has1 = c + stride < C;
       int w1 = 0, id1 = -1, ip1 = 0;
@@ -561,11 +522,11 @@ __device__ __forceinline__ void z_sliced_body(const ZParams &p) {
       if (has1) {                                                  // the next chunk's operands land during this chunk's arithmetic
         const int64_t c1 = c + stride;
         w1 = p.ct_tok[c1 * 64 + lane]; id1 = p.ct_idx[c1 * 64 + lane]; ip1 = p.ct_ip[c1 * 64 + lane];
-        load_theta(cdocs[2 * c1], cdocs[2 * c1 + 1], tv1);
+        load_theta(p, lane, cdocs[2 * c1], cdocs[2 * c1 + 1], tv1);
       } else {
-        load_theta(0, 0, tv1);
+        load_theta(p, lane, 0, 0, tv1);
       }
-      stage_theta(tv0);
+      f64.stage_theta(tv0);
       const unsigned char *trow = thb + ((unsigned)w0 >> kSlotShift) * kThetaRow;
       const unsigned char *hrow = smem + p.hot_off + (w0 & ((1 << kSlotShift) - 1)) * p.hot_pitch;   // table row (plain unit order)
 
@@ -594,7 +555,7 @@ __device__ __forceinline__ void z_sliced_body(const ZParams &p) {
           }
         });
       }
-      finish(sc, sum, id0, ip0, -1);
+      f64.walk(sc, sum, id0, ip0, -1);
       if (!has1) break;
       c += stride;
       w0 = w1; id0 = id1; ip0 = ip1;
@@ -608,9 +569,14 @@ __device__ __forceinline__ void z_sliced_body(const ZParams &p) {
   // odd waves start with their hot chunks: fewer waves at the address unit at any time
 #pragma unroll 1
   for (int phase = 0; phase < 2; ++phase) {
-    if ((phase ^ wave) & 1) hot_chunks();
-    else if constexpr (F32) cold_chunks32<KMAX>(p, thb, ring, wid, stride, lane);
-    else cold_chunks();
+    if ((phase ^ wave) & 1) {
+      hot_chunks();
+    } else if constexpr (F32) {
+      ColdForm32<KMAX> f32{p, thb, lane, (float)p.margin_scale32};
+      cold_chunk_loop(p, f32, thb, ring, wid, stride, lane);
+    } else {
+      cold_chunk_loop(p, f64, thb, ring, wid, stride, lane);
+    }
   }
 }
 
@@ -801,6 +767,21 @@ __device__ __forceinline__ void wait_vmcnt_take(const i3v_t &e, int &w, int &id,
                : "=&v"(w), "=&v"(id), "=&v"(ip) : "v"(e.x), "v"(e.y), "v"(e.z), "n"(N) : "memory");
 }
 
+// ---- what table_chunks and z_pairs_kernel share of their theta rows.  Lane l holds topics 2l, 2l + 1 (+ 128q) of each of a
+// chunk's rows: one 16-byte load per row and lane from a scalar row base (the document ids stay in SGPRs), unconditional (a
+// lane past the row re-reads its head; the last lane of an odd K reads 8 bytes past its row -- the next row, or the slack
+// ggs_set_corpus leaves behind the theta buffers) and masked to 0.0 beyond K when it is staged.
+template <int NQ>
+__device__ __forceinline__ void theta_piece_offsets(const int K, const int lane, uint32_t (&toff)[NQ]) {
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) { const int k0 = 2 * (q * 64 + lane); toff[q] = (uint32_t)(k0 < K ? k0 : 0) * 8; }
+}
+// the kWarmDocSlots document slots of chunk c: one s_load_dwordx8
+typedef int docs8_t __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ docs8_t load_chunk_docs(const const_i32_t *cdocs, const int64_t c) {
+  return *reinterpret_cast<const __attribute__((address_space(4))) docs8_t *>(cdocs + c * kWarmDocSlots);
+}
+
 // pack: per lane {table row | (which of the chunk's documents) << kWarmSlotShift, local token index or -1, its word-sorted
 // position, 0}; docs: kWarmDocSlots local documents per chunk (the first DOCS in use); chunks first + wid, + stride, ... < C.
 // count_words: null, or the word ids of the table's rows -- then every token adds its cell into p.cnt_send.
@@ -816,17 +797,11 @@ __device__ __forceinline__ void table_chunks(const ZParams &p, unsigned char *sm
   const int K = p.K;
   const const_i32_t *cdocs = (const const_i32_t *)docs_g;
   const uint32_t loff = (uint32_t)lane * 16;
-  // Lane l holds topics 2l, 2l + 1 (+ 128q) of each of the chunk's DOCS rows: one 16-byte load per row and lane from a scalar
-  // row base (the document ids stay in SGPRs), unconditional (a lane past the row re-reads its head; the last lane of an odd K
-  // reads 8 bytes past its row -- the next row, or the slack ggs_set_corpus leaves behind the theta buffers) and masked to
-  // 0.0 beyond K when it is staged.
   uint32_t toff[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) { const int k0 = 2 * (q * 64 + lane); toff[q] = (uint32_t)(k0 < K ? k0 : 0) * 8; }
+  theta_piece_offsets(K, lane, toff);
   struct Set { i3v_t e; i4v_t t[DOCS][NQ]; };
   auto issue = [&](const int64_t c, Set &S) {
-    typedef int docs8_t __attribute__((ext_vector_type(8)));
-    const docs8_t dd = *reinterpret_cast<const __attribute__((address_space(4))) docs8_t *>(cdocs + c * kWarmDocSlots);   // one s_load_dwordx8
+    const docs8_t dd = load_chunk_docs(cdocs, c);
     const int4 *lp = pack + c * 64;
     asm volatile("global_load_dwordx3 %0, %1, %2" : "=v"(S.e) : "v"(loff), "s"(lp) : "memory");
 #pragma unroll
@@ -973,15 +948,13 @@ __global__ __launch_bounds__(kSlicedWaves * 64) __attribute__((amdgpu_waves_per_
   int64_t c = (int64_t)blockIdx.x * kSlicedWaves + wave;
   if (c >= C) return;
   const const_i32_t *cdocs = (const const_i32_t *)p.hp_docs;
-  uint32_t toff[NQ];                                               // as table_chunks: topics 2l, 2l + 1 (+ 128q) of a row, a lane past the row re-reads its head
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) { const int k0 = 2 * (q * 64 + lane); toff[q] = (uint32_t)(k0 < K ? k0 : 0) * 8; }
+  uint32_t toff[NQ];
+  theta_piece_offsets(K, lane, toff);
 
   typedef i4v_t i4v8_t __attribute__((aligned(8)));                  // a theta row starts at d * K * 8
   struct Set { int pw, nt; i3v_t e[R]; i4v_t t[kHotPairDocs][NQ]; };   // e: {token word, token index, its word-sorted position}
   auto fetch = [&](const int64_t cc, Set &S) {
-    typedef int docs8_t __attribute__((ext_vector_type(8)));
-    const docs8_t dd = *reinterpret_cast<const __attribute__((address_space(4))) docs8_t *>(cdocs + cc * kWarmDocSlots);   // one s_load_dwordx8
+    const docs8_t dd = load_chunk_docs(cdocs, cc);
     S.nt = dd[kHotPairTokSlot];
     S.pw = p.hp_pair[cc * 64 + lane];
     const int4 *tp = p.hp_tok + ((int64_t)dd[kHotPairRoundSlot] * 64 + lane);

@@ -1,4 +1,4 @@
-"""A numpy restatement of the float32 decision rule of z_sliced32_kernel (ggs_z_sliced.hpp, cold_chunks32): float32
+"""A numpy restatement of the float32 decision rule of z_sliced32_kernel (ggs_z_sliced.hpp, ColdForm32): float32
 operands (phi32_of), float32 products and prefix sums, t0' = fl32(fl64(U * A)), d_j = fl32(a_j - t0'), decided as
 cnt = #{d_j < 0} when 2^-60 <= A <= FLT_MAX, min(t0', |d_j|) > (2K + 8) 2^-24 A and cnt < K.  Checked against the
 Java walk (GGS:96-113 in fp64) on random and adversarial rows, with float32 denormals kept and flushed: a decided
