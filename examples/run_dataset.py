@@ -44,12 +44,25 @@ def main():
     ap.add_argument("--topic-diagnostics", default=None, metavar="FILE",
                     help="save_doc_topic_diagnostics / doc_topic_diagnostics_filename: TopicModelDiagnosticsPlain's CSV (eleven quality scores per topic) "
                          "as FILE in --out; the coherence column is printed")
+    ap.add_argument("--similarity", default=None, metavar="TESTFILE",
+                    help="tui/LDASimilarity: fold the documents of TESTFILE (read against the training alphabet) into the trained Phi and write "
+                         "nearest_documents.csv into --out: lines `query_name,rank,train_name,distance`, the --nearest nearest training documents "
+                         "of every test document (the reference only prints to stdout: the file format is this project's)")
+    ap.add_argument("--distance", default="KLDistance", help="the Java class name of the distance (cc/mallet/similarity), e.g. ManhattanDistance")
+    ap.add_argument("--nearest", type=int, default=1, help="training documents per test document, 1 .. 16")
+    ap.add_argument("--fold-in", type=int, default=2000,
+                    help="z-only sweeps of the test documents under the trained Phi (LDADistancer.java:62).  The fold-in sampler is built from the "
+                         "configuration, as in Java: with --optimize-interval the training rows use the learned alpha, the test rows --alpha")
     ap.add_argument("--out", default=None, help="directory for the driver's files (phi / theta / counts / likelihood / TopWords.txt / RelevanceWords.txt)")
     args = ap.parse_args()
     if args.topic_priors and args.scheme != "spalias_priors":
         ap.error("--topic-priors belongs to --scheme spalias_priors")
     if args.topic_diagnostics and not args.out:
         ap.error("--topic-diagnostics writes into --out")
+    if args.similarity and not args.out:
+        ap.error("--similarity writes into --out")
+    if args.similarity and args.scheme in ("collapsed", "lightcollapsed", "adlda"):
+        ap.error("--similarity folds the test documents into a drawn Phi: scheme %s has none" % args.scheme)
 
     from ldagroupedgibbssampler_amd import formats as F
     from ldagroupedgibbssampler_amd.frontend import load_dataset
@@ -107,6 +120,18 @@ def main():
         with open(os.path.join(args.out, "hyperparameters.txt"), "w") as f:       # the final values, every digit: alpha per topic, then beta and betaSum
             f.write("".join("alpha\t%d\t%.17g\n" % (k, a) for k, a in enumerate(model.getAlpha())))
             f.write("beta\t%.17g\nbetaSum\t%.17g\n" % (model.getBeta(), model.betaSum))
+        if args.similarity:
+            from ldagroupedgibbssampler_amd.similarity import LDADistancer
+            test = load_dataset(args.similarity, stoplist=args.stoplist, alphabet=tuple(c.vocab))   # a tuple: the alphabet does not grow (data_alphabet)
+            distancer = LDADistancer(cfg)
+            distancer.setDist(args.distance)
+            distancer.setTrainedSampler(model)              # the model just trained, whatever its scheme; the fold-in is spalias's
+            idx, dist = distancer.nearest(test.corpus, args.nearest, fold_in_sweeps=args.fold_in)
+            with open(os.path.join(args.out, "nearest_documents.csv"), "w") as f:
+                for q, name in enumerate(test.names):
+                    for r in range(args.nearest):
+                        if idx[q, r] >= 0:
+                            f.write("%s,%d,%s,%s\n" % (name, r, ds.names[idx[q, r]], F.java_double_to_string(dist[q, r])))
         print("wrote", ", ".join(sorted(os.listdir(args.out))))
 
 

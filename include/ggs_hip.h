@@ -724,6 +724,60 @@ int ggs_log_posterior(ggs_handle *h, double *doc_side, double *topic_side);
  * null output or a negative size. */
 int ggs_min_doc_distances(ggs_handle *h, const double *other /*[n_other][K] host, or NULL*/, int64_t n_other, double *min_dist /*[D]*/);
 int ggs_min_topic_distance(ggs_handle *h, double *min_dist);
+/* replaces: the loops of similarity/LDADistancer.distance (LDADistancer.java:79-99), tui/LDASimilarity.java:175-183 and
+ * classify/KLDivergenceClassifier.classify (:71-78): the distance classes of cc/mallet/similarity between training documents and
+ * unseen ones, and the n nearest training documents (csrc/ggs_similarity.hpp).  New symbols, not a new ABI version.
+ * Distance.calculate(v1, v2) is always called with v1 = the training row (or class centroid) and v2 = the query row.  Each class is
+ * restated in Java operation order: sums from 0.0 in index order, every product, quotient and sum rounded on its own,
+ * Math.pow(x, 2) = x * x, Math.log = StrictMath.log, sqrt and / correctly rounded.  Bit-identical to those loops restated
+ * (tests/similarity_restatement.py).  cc.mallet.util.Maths.klDivergence is MALLET's and not in the reference tree; it is taken as
+ *   klDiv = 0; for i: if p1[i] == 0 continue; if p2[i] == 0 return +Infinity; klDiv += p1[i] * Math.log(p1[i] / p2[i]);
+ *   return klDiv / Math.log(2)
+ * (DESIGN.md 2), which is as far as metrics 7, 8 and 9 are pinned against a JVM. */
+#define GGS_DISTANCE_MANHATTAN 0      /* ManhattanDistance */
+#define GGS_DISTANCE_EUCLIDIAN 1      /* EuclidianDistance */
+#define GGS_DISTANCE_HELLINGER 2      /* HellingerDistance: the sum of (sqrt(a) - sqrt(b))^2 itself, no root, no 1/2, as written */
+#define GGS_DISTANCE_COSINE 3         /* CosineDistance: 1 + (-(dot / (sqrt(normA) * sqrt(normB)))) */
+#define GGS_DISTANCE_CANBERRA 4       /* CanberraDistance: a term with denom == 0.0 is 0.0 */
+#define GGS_DISTANCE_CHEBYCHEV 5      /* ChebychevDistance: Math.max, a NaN element gives NaN */
+#define GGS_DISTANCE_JACCARD 6        /* JaccardDistance: intersection > 0.0 ? 1 - (i / u) : 0.0, a NaN intersection gives 0.0 */
+#define GGS_DISTANCE_KL 7             /* KLDistance: (kl(v1, v2) + kl(v2, v1)) / 2 */
+#define GGS_DISTANCE_JENSEN_SHANNON 8 /* JensenShannonDistance: (KLDistance(v1, avg) + KLDistance(v2, avg)) / 2 */
+#define GGS_DISTANCE_UBER 9           /* UberDistance: Canberra, Chebychev, Cosine, Euclidian, Jaccard, KL, Manhattan summed, / 7 */
+#define GGS_DISTANCE_STATISTICAL 10   /* StatisticalDistance: -(correlation - 1), the covariance a running mean */
+#define GGS_DISTANCE_BHATTACHARYYA 11 /* BhattacharyyaDistance, as written (var2 / var2) */
+#define GGS_DISTANCE_COUNT 12
+#define GGS_NEAREST_MAX 16
+/* The training side of the two calls below: per document of the handle, from its device-resident z.
+ * ggs_get_theta_estimate: ModifiedSimpleLDA.getThetaEstimate (MSLDA:709-753): (n_dk + alpha_k) / sum_k (n_dk + alpha_k), the
+ *   normaliser summed in k order, with the handle's CURRENT alpha (after ggs_set_hyperparameters: the new one).
+ * ggs_get_zbar: getZbar (MSLDA:647-668): n_dk / N_d, zeros for an empty document.
+ * out is [doc_end - doc_begin][K]; the rows are made on the device in pieces whose work space does not grow with D.  Every scheme.
+ * GGS_ERR_STATE before a corpus, and with a corpus that has tokens before ggs_init_z_java_lcg or ggs_set_z gave it a z (so
+ * that the all-zero z ggs_set_corpus leaves is never taken for a state); the same for the two calls below.  GGS_ERR_BAD_ARG for
+ * a bad range or a null output. */
+int ggs_get_theta_estimate(ggs_handle *h, int64_t doc_begin, int64_t doc_end, double *out);
+int ggs_get_zbar(ggs_handle *h, int64_t doc_begin, int64_t doc_end, double *out);
+/* The distances of the handle's documents (their theta estimate rows: v1) to Q query rows (v2).  The rule of LDADistancer.java:84-87
+ * is part of the distance: both documents empty 0.0, exactly one empty +Infinity; the training lengths are the handle's, query_len
+ * [Q] the queries' (NULL: none is empty).
+ * ggs_nearest_documents: idx / dist [Q][n_nearest], ordered by (distance rising, document index rising).  Distances compare by
+ *   value (-0.0 and 0.0 tie, the index decides); only a distance < +Infinity is a candidate (NaN and +Infinity never enter); unfilled
+ *   places hold index -1 and distance +Infinity.  n_nearest = 1 is the loop of LDASimilarity.java:175-183 (strict minDist > d: the
+ *   first minimum).  The indices are global: the handle's doc_base + the local document, so the lists of the shards of a corpus merge
+ *   by the same order into the list of the whole.  1 <= n_nearest <= GGS_NEAREST_MAX.
+ * ggs_document_distances: dist [Q][D], every value as calculate() returns it (NaN included).
+ * Every scheme.  Training rows, queries and the [Q][D] output travel in pieces of at most 64 MiB.  Nothing a sweep reads is written.
+ * GGS_ERR_STATE before a corpus and a z exist; GGS_ERR_BAD_ARG: an unknown metric, n_nearest outside its range, a negative size or length, a null
+ * output or query.  Q == 0 writes nothing; D == 0 writes the "nothing found" values. */
+int ggs_nearest_documents(ggs_handle *h, int32_t metric, const double *query /*[Q][K] host*/, const int64_t *query_len /*[Q], or NULL*/, int64_t Q,
+                          int32_t n_nearest, int64_t *idx /*[Q][n_nearest]*/, double *dist /*[Q][n_nearest]*/);
+int ggs_document_distances(ggs_handle *h, int32_t metric, const double *query, const int64_t *query_len, int64_t Q, double *dist /*[Q][D]*/);
+/* The handle-free primitive over the same kernels: out[j][i] = calculate(a[i], b[j]) for the rows of a [n][len] (v1) and b [m][len]
+ * (v2), no length rule.  KLDivergenceClassifier's Q x C step.  GGS_ERR_BAD_ARG: an unknown metric, a negative n or m, len < 1, a null
+ * pointer with work to do. */
+int ggs_row_distances(int32_t device_id, int32_t metric, const double *a /*[n][len]: v1*/, const double *b /*[m][len]: v2*/, int64_t n, int64_t m, int64_t len,
+                      double *out /*[m][n]*/);
 /* replaces: LDAUtils.getTopWords / getTopWordIndices (LDAUtils.java:874-911; TopWords.txt, tui/ParallelLDA.java:272-283),
  * getTopRelevanceWords (:566-590; RelevanceWords.txt, ParallelLDA.java:285-296), getTopDistinctiveWords (:592-617),
  * getTopSalientWords (:619-644) and getK1ReWeightedWords (:752-801) on the handle's CURRENT corpus-wide type-topic counts (with

@@ -157,6 +157,11 @@ SIGNATURES = {
     "ggs_log_posterior": (C.c_int, [_vp, _dp, _dp]),
     "ggs_min_doc_distances": (C.c_int, [_vp, _dp, C.c_int64, _dp]),
     "ggs_min_topic_distance": (C.c_int, [_vp, _dp]),
+    "ggs_get_theta_estimate": (C.c_int, [_vp, C.c_int64, C.c_int64, _dp]),
+    "ggs_get_zbar": (C.c_int, [_vp, C.c_int64, C.c_int64, _dp]),
+    "ggs_nearest_documents": (C.c_int, [_vp, C.c_int32, _dp, _lp, C.c_int64, C.c_int32, _lp, _dp]),
+    "ggs_document_distances": (C.c_int, [_vp, C.c_int32, _dp, _lp, C.c_int64, _dp]),
+    "ggs_row_distances": (C.c_int, [C.c_int32, C.c_int32, _dp, _dp, C.c_int64, C.c_int64, C.c_int64, _dp]),
     "ggs_top_words": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, _ip, _dp]),
     "ggs_topic_doc_statistics": (C.c_int, [_vp, C.c_int32, _ip, _dp, _ip, _ip, _dp]),
     "ggs_topic_scores": (C.c_int, [_vp, C.c_int32, _ip, _ip, _ip, _dp, _dp, _dp]),
@@ -171,6 +176,13 @@ SIGNATURES = {
     "ggs_debug_topic_diagnostics_phases": (C.c_int, [_vp, C.c_int32, _dp]),
     "ggs_debug_topic_summaries": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _ip, C.c_double, C.c_double, C.c_int32, C.c_int32, _ip, _dp, _dp, _dp, _dp, _dp]),
 }
+
+# GGS_DISTANCE_* of include/ggs_hip.h, by the name of the Java class (cc/mallet/similarity)
+DISTANCE_IDS = {
+    "ManhattanDistance": 0, "EuclidianDistance": 1, "HellingerDistance": 2, "CosineDistance": 3, "CanberraDistance": 4, "ChebychevDistance": 5,
+    "JaccardDistance": 6, "KLDistance": 7, "JensenShannonDistance": 8, "UberDistance": 9, "StatisticalDistance": 10, "BhattacharyyaDistance": 11,
+}
+NEAREST_MAX = 16
 
 
 def build(force=False):

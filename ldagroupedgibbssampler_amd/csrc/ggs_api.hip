@@ -11,6 +11,7 @@
 #include "ggs_host_end_of_run.hpp"
 #include "ggs_host_hyper.hpp"
 #include "ggs_host_debug.hpp"
+#include "ggs_host_similarity.hpp"
 
 extern "C" {
 
@@ -267,7 +268,7 @@ int ggs_set_corpus(ggs_handle *h, int64_t D, const int64_t *doc_ptr, const int32
   HIP_TRY(h, hipDeviceSynchronize());   // the uploads and memsets above ran on the null stream; the handle's stream may not synchronise with it
 
   // 5. a new corpus: no Phi, no sweep in progress, the z form to be timed again
-  h->have_corpus = true; h->have_phi = false; h->in_sweep = false; h->global_tokens = -1; h->lcg_ready = false;
+  h->have_corpus = true; h->have_z = false; h->have_phi = false; h->in_sweep = false; h->global_tokens = -1; h->lcg_ready = false;
   h->z_split = pl.split; h->z_split_tried = pl.split_forced;
   h->counts_global = h->xg == nullptr; h->cnt_own_valid = false; h->n_k_valid = false;
   return GGS_OK;
@@ -291,6 +292,7 @@ int ggs_init_z_java_lcg(ggs_handle *h, int32_t seed) {
   if ((rc = launch_permute_z(h))) return rc;
   if ((rc = launch_count_rebuild(h))) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  h->have_z = true;
   return GGS_OK;
 }
 
@@ -306,6 +308,7 @@ int ggs_set_z(ggs_handle *h, const int32_t *z, int32_t redraw_phi) {
   if ((rc = launch_permute_z(h))) return rc;
   if ((rc = launch_count_rebuild(h))) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  h->have_z = true;
   if (redraw_phi) return ggs_init_phi(h);
   return GGS_OK;
 }
@@ -1034,6 +1037,19 @@ int ggs_min_topic_distance(ggs_handle *h, double *min_dist) {
   hipLaunchKernelGGL(min_dist_reduce_kernel, dim3(1), dim3(kDistBlock), 0, h->stream, d_bits, K, d_out);
   HIP_TRY(h, hipGetLastError());
   return copy_out(h, min_dist, d_out, sizeof(double));
+}
+int ggs_get_theta_estimate(ggs_handle *h, int64_t doc_begin, int64_t doc_end, double *out) { return sim_get_doc_rows(h, doc_begin, doc_end, false, out); }
+int ggs_get_zbar(ggs_handle *h, int64_t doc_begin, int64_t doc_end, double *out) { return sim_get_doc_rows(h, doc_begin, doc_end, true, out); }
+int ggs_nearest_documents(ggs_handle *h, int32_t metric, const double *query, const int64_t *query_len, int64_t Q, int32_t n_nearest, int64_t *idx, double *dist) {
+  if (!h) return GGS_ERR_BAD_ARG;
+  if (n_nearest < 1 || n_nearest > kSimMaxNearest) return set_err(h, GGS_ERR_BAD_ARG, "n_nearest must be in [1, GGS_NEAREST_MAX]");
+  return sim_handle_distances(h, metric, query, query_len, Q, n_nearest, idx, dist);
+}
+int ggs_document_distances(ggs_handle *h, int32_t metric, const double *query, const int64_t *query_len, int64_t Q, double *dist) {
+  return sim_handle_distances(h, metric, query, query_len, Q, 0, nullptr, dist);
+}
+int ggs_row_distances(int32_t device_id, int32_t metric, const double *a, const double *b, int64_t n, int64_t m, int64_t len, double *out) {
+  return sim_row_distances(device_id, metric, a, b, n, m, len, out);
 }
 int ggs_top_words(ggs_handle *h, int32_t kind, int32_t n_words, double lambda, int32_t *idx, double *score) {
   int rc = require_ready(h, false);

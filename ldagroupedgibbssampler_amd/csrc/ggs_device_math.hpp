@@ -64,7 +64,8 @@ __device__ __forceinline__ double mk(int32_t hi, uint32_t lo) {
 }
 
 // ---- StrictMath.log ---------------------------------------------------------
-__device__ __noinline__ double strict_log(double x) {
+// the body; strict_log below is its one out-of-line copy, ggs_similarity.hpp's kl steps take it inline (no call in a tile body)
+__device__ __forceinline__ double strict_log_body(double x) {
   constexpr double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10,
                    two54 = 1.80143985094819840000e+16,
                    Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01,
@@ -110,6 +111,7 @@ __device__ __noinline__ double strict_log(double x) {
   if (k == 0) return f - s * (f - R);
   return dk * ln2_hi - ((s * (f - R) - dk * ln2_lo) - f);
 }
+__device__ __noinline__ double strict_log(double x) { return strict_log_body(x); }
 
 // ---- StrictMath.exp (fdlibm 5.3 e_exp.c) ------------------------------------
 __device__ __noinline__ double strict_exp(double x) {

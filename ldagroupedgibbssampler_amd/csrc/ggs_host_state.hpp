@@ -235,6 +235,7 @@ struct ggs_handle {
 
   int64_t D = 0, N = 0, C = 0, S = 0, doc_base = 0, tok_base = 0, global_tokens = -1;
   bool have_corpus = false, have_phi = false, in_sweep = false;
+  bool have_z = false;                                 // ggs_init_z_java_lcg or ggs_set_z since the last ggs_set_corpus (read by ggs_host_similarity.hpp only)
   int32_t num_cus = 0;
   LaunchPlan plan;                                     // every launch this handle can make (plan_launches, at ggs_create)
   const LaunchPlan::ZCfg *cfg = nullptr;               // of the current corpus: plan.cfg_parts or plan.cfg_plain

@@ -450,6 +450,50 @@ class GGSHandle:
         self._chk(self._L.ggs_min_topic_distance(self._h, C.byref(v)))
         return v.value
 
+    # ---- the nearest training documents (similarity/LDADistancer, tui/LDASimilarity; csrc/ggs_similarity.hpp) ----
+    def theta_estimate(self, doc_begin=0, doc_end=None):
+        """getThetaEstimate (MSLDA:709-753) of the handle's documents from the device-resident z and the current alpha: [n][K]"""
+        doc_end = self.D if doc_end is None else doc_end
+        out = np.empty((doc_end - doc_begin, self.K), np.float64)
+        self._chk(self._L.ggs_get_theta_estimate(self._h, doc_begin, doc_end, _dp(out)))
+        return out
+
+    def zbar(self, doc_begin=0, doc_end=None):
+        """getZbar (MSLDA:647-668) of the handle's documents from the device-resident z: [n][K], zeros for an empty document"""
+        doc_end = self.D if doc_end is None else doc_end
+        out = np.empty((doc_end - doc_begin, self.K), np.float64)
+        self._chk(self._L.ggs_get_zbar(self._h, doc_begin, doc_end, _dp(out)))
+        return out
+
+    def _queries(self, query, query_len):
+        query = np.ascontiguousarray(query, np.float64)
+        if query.ndim != 2 or query.shape[1] != self.K:
+            raise ValueError("query must be [Q][K]")
+        if query_len is not None:
+            query_len = np.ascontiguousarray(query_len, np.int64)
+            if query_len.shape != (query.shape[0],):
+                raise ValueError("query_len must have one entry per query")
+        return query, query_len
+
+    def nearest_documents(self, query, n=1, metric="KLDistance", query_len=None):
+        """(idx int64 [Q][n], dist [Q][n]): per query row the n training documents of this handle with the smallest distance of
+        the class `metric` (a Java class name of cc/mallet/similarity, or its id) between their theta estimate (v1) and the
+        query (v2), ordered by (distance, global document index); -1 and +inf where fewer have a finite distance.  query_len:
+        the queries' token counts for the empty-document rule of LDADistancer.java:84-87 (None: none is empty)."""
+        query, query_len = self._queries(query, query_len)
+        idx = np.empty((query.shape[0], int(n)), np.int64)
+        dist = np.empty((query.shape[0], int(n)), np.float64)
+        self._chk(self._L.ggs_nearest_documents(self._h, distance_id(metric), _dp(query), None if query_len is None else _lp(query_len), query.shape[0], int(n),
+                                                _lp(idx), _dp(dist)))
+        return idx, dist
+
+    def document_distances(self, query, metric="KLDistance", query_len=None):
+        """dist [Q][D]: what LDADistancer.distance returns per query row (LDADistancer.java:79-99), on the device"""
+        query, query_len = self._queries(query, query_len)
+        dist = np.empty((query.shape[0], self.D), np.float64)
+        self._chk(self._L.ggs_document_distances(self._h, distance_id(metric), _dp(query), None if query_len is None else _lp(query_len), query.shape[0], _dp(dist)))
+        return dist
+
     def top_words(self, kind, n, lam=0.6, scores=False):
         """The n best words of every topic (ggs_top_words) on the corpus-wide counts: idx [K][n] in IDSorter's order (falling
         score, ties by falling id); kind = "top" (LDAUtils.getTopWords, TopWords.txt), "relevance" (getTopRelevanceWords with
@@ -795,6 +839,29 @@ def debug_min_distances(a, b=None, element_major=False, device_id=0):
     if rc:
         raise GGSError(rc, "ggs_debug_min_distances")
     return dist, sq
+
+
+def distance_id(metric):
+    """GGS_DISTANCE_* of a Java class name (cc/mallet/similarity), or of the id itself"""
+    if isinstance(metric, str):
+        if metric not in _lib.DISTANCE_IDS:
+            raise ValueError("unknown distance %r: one of %s" % (metric, ", ".join(_lib.DISTANCE_IDS)))
+        return _lib.DISTANCE_IDS[metric]
+    return int(metric)
+
+
+def row_distances(a, b, metric, device_id=0):
+    """out [m][n]: out[j][i] = Distance.calculate(a[i], b[j]) of the class `metric` for the rows of a [n][len] (v1) and b [m][len]
+    (v2), on the device (ggs_row_distances): the distance kernels without a handle and without the empty-document rule."""
+    L = _lib.load()
+    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError("a must be [n][len] and b [m][len]")
+    out = np.empty((b.shape[0], a.shape[0]), np.float64)
+    rc = L.ggs_row_distances(device_id, distance_id(metric), _dp(a), _dp(b), a.shape[0], b.shape[0], a.shape[1], _dp(out))
+    if rc:
+        raise GGSError(rc, "ggs_row_distances")
+    return out
 
 
 def debug_topic_summaries(counts, beta, kind, n, lam=0.6, device_id=0):

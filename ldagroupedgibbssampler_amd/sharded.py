@@ -154,6 +154,22 @@ class ShardedGGS:
             out = np.minimum(out, self.engine.min_doc_distances(blk))
         return out
 
+    def nearest_documents(self, query, n=1, metric="KLDistance", query_len=None, gather=None):
+        """The n nearest training documents of a doc-sharded run: (idx [Q][n], dist [Q][n]) over the whole corpus on every
+        rank.  Each rank lists its own documents (engine.nearest_documents: the indices are global, doc_base + local), the ranks
+        gather the lists (``gather`` as for heldout_log_likelihood) and similarity.merge_nearest merges them by the kernels'
+        order, which is total: bit-identical to one handle over the whole corpus."""
+        from .similarity import merge_nearest
+        idx, dist = self.engine.nearest_documents(query, n, metric, query_len)
+        if gather is None:
+            import torch.distributed as dist_
+
+            def gather(a):
+                res = [None] * self.world
+                dist_.all_gather_object(res, a)
+                return res
+        return merge_nearest(gather((idx, dist)), n)
+
     def topic_diagnostics(self, n, alphabet=None, gather=None):
         """TopicModelDiagnosticsPlain of a doc-sharded run, on every rank (a collective call).  The top words come from the
         corpus-wide counts, the same on every rank.  The clogc chain is ONE rounding chain per topic over all documents in
